@@ -284,6 +284,44 @@ def reduced_precision_leg(rays, samples, device, steps=10, warmup=4):
     return res
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def step_outputs(pipe, out):
+    """What a caller of the timed step holds when it returns, copied to the host: the loss, the loss terms the step logged,
+    every trainable parameter after the optimiser update and its gradient of that step."""
+    arrays = {"loss": out["loss"]}
+    for k, v in pipe.logged.items():
+        if k.startswith("train/"):
+            arrays[k.replace("/", ".")] = v
+    for k, p in pipe.named_parameters():
+        if p.requires_grad:
+            arrays["param." + k] = p
+            if p.grad is not None:
+                arrays["grad." + k] = p.grad
+    res = {}
+    for k, v in arrays.items():
+        t = v.detach() if torch.is_tensor(v) else torch.tensor(float(v), dtype=torch.float64)
+        res[k] = t.to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32).numpy().copy()
+    return res
+
+
+def dump_outputs(dump_dir, arrays):
+    """DIR/<name>.npy for every array.  Past DUMP_LIMIT_BYTES in all, every array keeps the same fraction of its elements at
+    positions drawn by a fixed seed (flattened, in index order), so two runs with the same arguments store the same positions."""
+    import numpy as np
+    os.makedirs(dump_dir, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES - 4096 * len(arrays)      # room for the .npy headers and the one element every array keeps
+    total = sum(a.nbytes for a in arrays.values())
+    frac = min(1.0, budget / total) if total else 1.0
+    for k, a in sorted(arrays.items()):
+        if frac < 1.0 and a.size > 1:
+            keep = max(1, int(a.size * frac))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dump_dir, k + ".npy"), a)
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: start N fresh rank processes of this script (one GPU per LOCAL_RANK,
     rendezvous on 127.0.0.1), relay rank 0's JSON line, fail if any rank fails.  Runs BEFORE this process touches the GPU
@@ -350,6 +388,8 @@ def rehearsal(args):
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"loss_sums": sums.double().numpy(), "gradient_bucket": bucket.numpy().copy()})
         dt = float(tmax.item())
         print(json.dumps({
             "metric": f"train rays/sec ({args.rays} rays x {args.samples} samples)", "value": args.rays * world * args.steps / dt, "unit": "rays/s",
@@ -393,6 +433,9 @@ def main():
     ap.add_argument("--no-eager-gpu-baseline", action="store_true", help="skip the stock-PyTorch-on-GPU denominator (3 steps)")
     ap.add_argument("--no-inference", action="store_true", help="skip the forward-only (full-frame inference) leg")
     ap.add_argument("--rehearsal", action="store_true", help="multi-rank protocol only (collectives, no kernels): CPU rigs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (loss, loss terms, updated parameters, their "
+                         "gradients) as DIR/<name>.npy, float32 / float64, at most 64 MB in all (rank 0)")
     args = ap.parse_args()
     preset = PRESETS.get(args.config or "", None)
     if preset is not None:
@@ -470,6 +513,8 @@ def main():
     t_issued = time.perf_counter()
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:      # before the roofline phase: its extra steps move the parameters on
+        dump_outputs(args.dump_outputs, step_outputs(pipe, out))
     exchange_ms = None
     if loop.exchange_events:
         ev = loop.exchange_events[-args.steps:]          # the timed steps' events (the warm-up's come first)
