@@ -58,7 +58,8 @@ extern "C" {
                                   to the block's maximum, 2 bytes per element -- weights packed as one plane, one MFMA product per
                                   contraction step (a third of the default's matrix work, half its operand bytes), fp32 accumulate.
                                   Same kernels, templated on the plane count.  Judged on PSNR / mIoU, not on the 1e-4 parity bar.
-                                  Needs fc_units % 64 == 0 and feat_last % 32 == 0 on top of the default's shape rules */
+                                  Needs fc_units % 64 == 0, feat_last % 32 == 0 and n_freq > 0 on top of the default's shape rules
+                                  (raw xyz, n_freq = 0, would enter the w0 = 30 first layer rounded to 11 bits: SNERF_ERR_BAD_DESC) */
 
 /* Model + batch description.  Field names follow the reference config
  * (configs/pipelines/rs_semantic.toml:13-67, semantic/pipelines/rs_semantic.py:125-141). */

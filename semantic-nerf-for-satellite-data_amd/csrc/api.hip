@@ -100,7 +100,7 @@ static void plan_bsp(Plan& p) {
   p.nd_fin = !p.sc && p.siren && p.H == 256 && p.C <= ND_FIN;   // one 256-column tile per head block, at most ND_FIN outputs per block
   {  // bsp_trunk.hip: the shapes it is written for (launch_trunk checks them again)
     bool ok = p.pl == 1 && p.siren && p.nd_sig && p.W == 512 && p.Ep == 64 && p.L >= 3 && p.L <= bsp::TR_MAXL &&
-              !(p.skip_mask & 1u) && (p.skip_mask >> (p.L - 1)) == 0u;
+              !(p.skip_mask & 1u) && (p.skip_mask >> (p.L - 1)) == 0u && !bsp::trunk_dma_in_final_layer(p.L, p.skip_mask, /*feats_fused=*/!p.train);   // (bsp_pass.hip: fused_feats)
     for (int i = 0; ok && i < p.L; ++i) ok = p.k_tr[i] == (i == 0 ? 64 : (((p.skip_mask >> i) & 1u) ? 576 : 512));
     p.fuse_trunk = ok;
   }
@@ -148,6 +148,10 @@ int make_plan(const SnerfDesc* d, Plan* pl) {
     if (sel == (SNERF_FLAG_F16X2 | SNERF_FLAG_F16X1)) return bad("more than one arithmetic flag (SNERF_FLAG_F16X2 / SNERF_FLAG_F16X1)");
     p.pl = (sel & SNERF_FLAG_F16X1) ? 1 : 2;
   }
+  // raw xyz (n_freq = 0: SatNeRF) as ONE fp16 plane: the coordinates enter the w0 = 30 first layer rounded to 11 bits, which alone
+  // moves sigma by 4e-3 (fp64 oracle with fp16-rounded xyz) -- beyond the mode's 5e-3 output bar once the other layers' rounding adds
+  // in (measured 5.0e-3).  Refused rather than computed at that accuracy (tests/test_abi_cpu.py, tests/test_gpu_geometry.py).
+  if (p.pl == 1 && p.F == 0) return bad("SNERF_FLAG_F16X1 with raw xyz input (n_freq = 0) is not supported: one fp16 plane rounds the coordinates to 11 bits; use the default arithmetic");
   p.E = p.F > 0 ? 6 * p.F : 3; p.Ep = round_up(p.E, p.pl == 2 ? 32 : 64);  // LDS stages (128 bytes per row: 32 / 64 k) never straddle the [gamma | h] segments
   p.tau = d->t_dim; p.C = d->n_classes;
   p.siren = d->siren != 0; p.sem_sigmoid = d->sem_sigmoid != 0;

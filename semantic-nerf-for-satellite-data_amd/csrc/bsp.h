@@ -196,6 +196,20 @@ struct TrunkArgs {
   int* tile_ctr = nullptr;                                   // 8 zeroed ints
   int dbg = 0;                                               // diagnostic builds only (bsp_trunk.hip: TRUNK_DIAG_BUILD); ignored by the product kernels
 };
+// The layer whose epilogue requests the next tile's encoding (TrunkArgs::gamma_free_layer): the last layer that reads gamma, at least 2
+// (the next tile's index is known from layer 2 on), at most L - 1.
+inline int trunk_gamma_free_layer(int L, unsigned skip_mask) {
+  int g = 2;
+  for (int l = 2; l < L; ++l)
+    if ((skip_mask >> l) & 1u) g = l;
+  return g < L - 1 ? g : L - 1;
+}
+// A pass whose FINAL layer would issue that request is not fused: the final layer's closing barrier does not wait on the memory
+// counter, so nothing orders the other waves' DMA pieces before the next tile's layer 0 reads all 128 rows.  With the feats layer
+// riding behind the trunk (inference passes) the final layer is the feats layer, never the requesting one; without it, L = 3.
+inline bool trunk_dma_in_final_layer(int L, unsigned skip_mask, bool feats_fused) {
+  return !feats_fused && trunk_gamma_free_layer(L, skip_mask) == L - 1;
+}
 int launch_trunk(const TrunkArgs& a, bool train, hipStream_t st);
 void trunk_set_grid_override(int n);                       // test hook: persistent grid of n workgroups (0: one per CU)
 void trunk_set_fusion(int on);                             // test hook: 0 = the launch-per-layer path for every pass

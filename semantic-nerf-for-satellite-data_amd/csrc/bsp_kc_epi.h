@@ -12,8 +12,9 @@ constexpr float INV_2PI = 0.15915494309189533577f;
 // sin(2 pi x_c) in place for eight values x_c in REVOLUTIONS (the FMA that applies scale and bias forms them), by v_sin_f32 on the
 // unreduced argument: inside the instruction's domain (|x| <= 256 revolutions) its own range reduction is exact -- measured on
 // gfx950 against fp64, bit for bit the results of v_sin_f32(v_fract_f32(x)) (tools/ablate/vsin_range.hip) -- and a SIREN
-// pre-activation of |w0 z| <= 1,608 rad lies inside it; KcArgs::sin_wide (host: |w0| > 30) keeps the explicit v_fract_f32 for
-// layers that may leave it.
+// pre-activation of |w0 z| <= 1,608 rad lies inside it.  Beyond the documented domain there is no guard: every ACT_SIN launch (and the
+// fused trunk) relies on v_sin_f32 staying accurate there too, and tests/test_gpu_bsp.py (test_siren_sine_beyond_256_revolutions: up to
+// 4,000 revolutions, within 2 pi ulp(x) of the fp64 sine, cos signs exact) is what holds it to that.
 // SIGNS: bit "cos(2 pi x_c) < 0" (= parity of round(2 x_c), the low mantissa bit of 2 x_c + 1.5 * 2^23) enters `sw` from the top,
 // earlier bits move down (after 32 calls' worth the first element sits in bit 0).
 constexpr int SIN_FRACT = 0, SIN_DIRECT = 1;

@@ -391,7 +391,7 @@ int launch_trunk(const TrunkArgs& a0, bool train, hipStream_t st) {
   if (a.W != 512 || a.L < 3 || a.L > TR_MAXL) return bad_trunk("W = 512, 3 <= L <= 8");
   if ((a.skip_mask & 1u) || (a.skip_mask >> (a.L - 1)) != 0u) return bad_trunk("skip layers: 0 < i < L - 1");
   if (a.P > 0x7FFFFF00) return bad_trunk("P");      // (every descriptor is built per 128-point tile: no 4 GiB limit on the tensors)
-  int gfree = 0;
+  if (trunk_dma_in_final_layer(a.L, a.skip_mask, a.F != nullptr)) return bad_trunk("the next tile's encoding would be requested in the final layer (L = 3 without the feats layer)");
   for (int l = 0; l < a.L; ++l) {
     const bool skip = (a.skip_mask >> l) & 1u;
     const int want = l == 0 ? 64 : (skip ? 576 : 512);
@@ -401,10 +401,8 @@ int launch_trunk(const TrunkArgs& a0, bool train, hipStream_t st) {
     const bool leave = train || (l == a.L - 1 && a.F == nullptr);
     if (leave && (!a.H[l] || !a.EH[l] || ((uintptr_t)a.H[l] & 15))) return bad_trunk("output planes of a leaving layer");
     if (train && !a.Hsign[l]) return bad_trunk("sign words (training)");
-    if (skip) gfree = l;
   }
-  a.gamma_free_layer = gfree < 2 ? 2 : gfree;       // >= 2: the next tile's index is known from layer 2 on
-  if (a.gamma_free_layer > a.L - 1) a.gamma_free_layer = a.L - 1;
+  a.gamma_free_layer = trunk_gamma_free_layer(a.L, a.skip_mask);
   if (a.nd_out != nullptr && (!a.nd_w || a.nd_stride < (unsigned long long)a.P)) return bad_trunk("sigma projection");
   if (a.F != nullptr && train) return bad_trunk("the feats layer is fused in inference passes only");
   if (a.F != nullptr) {     // the feats layer rides as entry L

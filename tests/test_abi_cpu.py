@@ -105,6 +105,23 @@ def test_plan_builder_over_model_variants_and_null_arguments():
     assert L.snerf_grad_floats(C.byref(bad)) == 0 and L.snerf_workspace_bytes(C.byref(bad)) == 0
 
 
+def test_one_plane_mode_refuses_raw_xyz():
+    """SNERF_FLAG_F16X1 with n_freq = 0 (SatNeRF's raw xyz) is refused by name: one fp16 plane rounds the coordinates entering the
+    w0 = 30 first layer to 11 bits (sigma off by 5e-3 against the fp64 oracle).  The default arithmetic, and the one-plane mode with any
+    positional encoding, keep their plans."""
+    from snerf_amd import _lib
+    from snerf_amd.ops import ModelSpec
+    L = _lib.lib()
+    raw = ModelSpec(n_freq=0, n_classes=0)
+    for flags in (_lib.FLAG_F16X1, _lib.FLAG_F16X1 | _lib.FLAG_TRAIN, _lib.FLAG_F16X1 | _lib.FLAG_SC_PASS):
+        d = raw.desc(512, 32, flags)
+        assert L.snerf_packed_floats(C.byref(d)) == 0 and L.snerf_workspace_bytes(C.byref(d)) == 0
+        assert b"raw xyz" in L.snerf_last_error(), L.snerf_last_error()
+    for spec, flags in ((raw, 0), (raw, _lib.FLAG_TRAIN), (ModelSpec(n_freq=1), _lib.FLAG_F16X1), (ModelSpec(), _lib.FLAG_F16X1 | _lib.FLAG_TRAIN)):
+        d = spec.desc(512, 32, flags)
+        assert L.snerf_packed_floats(C.byref(d)) > 0 and L.snerf_workspace_bytes(C.byref(d)) > 0, (flags, L.snerf_last_error())
+
+
 def test_product_path_refuses_cpu_tensors():
     """No CPU fallback: the HIP path raises instead of computing on the host."""
     import torch

@@ -512,3 +512,53 @@ def test_one_plane_dw_column_offsets_and_narrow():
     assert _relerr(Cn, refn) <= 1e-3
     Cn2 = _dw(An, B, 9, 200, b_col0=192, narrow=True, planes=1)
     assert _relerr(Cn2, An[:, :9].double().T @ B[:, 192:392].double()) <= 1e-3
+
+
+SIN_WIDE_STATS = []   # worst error beyond 256 revolutions per plane count (printed with -s)
+
+
+@pytest.mark.parametrize("planes", [2, 1])
+def test_siren_sine_beyond_256_revolutions(planes):
+    """Every ACT_SIN epilogue hands v_sin_f32 its argument in revolutions WITHOUT range reduction (bsp_kc_epi.h: sin2pi8<SIN_DIRECT>); the
+    instruction documents |x| <= 256 revolutions.  Pre-activations here span 0 ... 4,000 revolutions, about half beyond 256, on an EXACT
+    GEMM: A and W are small integers / quarters that both plane layouts hold exactly and whose fp32 sums are exact, so the only rounding
+    left before the sine is the fp32 argument x = z (w0 / 2 pi).  Bar, the same inside and outside the domain: 2 pi ulp(|x|) + 2e-6
+    against the fp64 sin(2 pi x) (+ the fp16 storage of the value, 2^-12, with one plane).  The sign words of cos must match wherever
+    x is more than one ulp from a zero of cos."""
+    g = torch.Generator().manual_seed(17 + planes)
+    I, J, K, w0 = 256, 256, 64, 30.0
+    n_lo = torch.randint(-50, 51, (I // 2,), generator=g)                    # |x| <= ~240 revolutions
+    n_hi = torch.randint(60, 841, (I - I // 2,), generator=g) * (torch.randint(0, 2, (I - I // 2,), generator=g) * 2 - 1)
+    A = torch.randint(-2, 3, (I, K), generator=g).float()
+    A[:, 0] = torch.cat([n_lo, n_hi]).float()
+    W = torch.randint(-2, 3, (J, K), generator=g).float() / 4
+    W[:, 0] = (torch.randint(0, 2, (J,), generator=g) * 2 - 1).float()
+    z = A.double() @ W.double().T                                            # exact (and exact in fp32: multiples of 1/4 below 2^11)
+    assert float(z.abs().max()) < 2 ** 11
+    H, sign, _ = _kc(A.to(DEV), W.to(DEV), None, act=ACT_SIN, w0=w0, want_sign=True, planes=planes)
+    # the kernel's scale: 2^-e w0 (exact) times fp32(1 / 2 pi), rounded once; the FMA then rounds x once
+    su = float(np.float32(np.float32(w0) * np.float32(1.0 / (2 * np.pi))))
+    xk = z * su                                                              # exact in fp64 (13 + 24 bits)
+    x32 = xk.float().double()                                                # the argument v_sin_f32 receives
+    ulp = torch.from_numpy(np.spacing(np.abs(x32.numpy()).astype(np.float32)).astype(np.float64))
+    bar = 2 * np.pi * ulp + 2e-6 + (2.0 ** -12 if planes == 1 else 0.0)
+    err = (H.double().cpu() - torch.sin(2 * np.pi * xk)).abs()
+    wide = xk.abs() > 256
+    frac_wide = float(wide.double().mean())
+    assert 0.4 <= frac_wide <= 0.6 and float(xk.abs().max()) > 3500, (frac_wide, float(xk.abs().max()))
+    assert bool((err <= bar).all()), (int((err > bar).sum()), float((err - bar).max()), float(xk.abs()[err > bar].min()) if bool((err > bar).any()) else None)
+    # sign words: word (32-row block, 64-column group, lane = row % 32 + 32 ((col >> 3) & 1)), bit 8 ((col >> 4) & 3) + (col & 7)
+    words = sign.cpu().numpy().astype(np.uint32).reshape(I // 32, J // 64, 64)
+    rows = np.arange(I)[:, None]
+    cols = np.arange(J)[None, :]
+    lane = rows % 32 + 32 * ((cols >> 3) & 1)
+    bit = 8 * ((cols >> 4) & 3) + (cols & 7)
+    got_neg = (words[rows // 32, cols // 64, lane] >> bit.astype(np.uint32)) & 1
+    x2 = 2 * x32.numpy()
+    want_neg = (np.rint(x2).astype(np.int64) & 1)                           # cos(2 pi x) < 0  <=>  round(2 x) is odd
+    clear = np.abs(np.abs(x2 - np.floor(x2)) - 0.5) > 2 * ulp.numpy()        # more than one ulp of x away from a zero of cos
+    assert clear.mean() > 0.95
+    assert np.array_equal(got_neg[clear], want_neg[clear]), int((got_neg[clear] != want_neg[clear]).sum())
+    SIN_WIDE_STATS.append({"planes": planes, "worst_err_beyond_256": float(err[wide].max()), "worst_err_inside": float(err[~wide].max()),
+                           "max_revolutions": float(xk.abs().max())})
+    print("sine beyond 256 revolutions:", SIN_WIDE_STATS[-1])

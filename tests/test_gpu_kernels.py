@@ -117,7 +117,7 @@ def _compare_outputs(hip, ora, cfg):
 
 
 FIXTURES = ["sem_siren_small", "sem_relu_small", "sem_variants_small", "sem_tj_small", "sem_cartreg_small",
-            "satnerf_small", "satnerf_relu_small"]
+            "satnerf_small", "satnerf_relu_small", "sem_geom3_small", "sem_geom5_small", "sem_geom1_small"]
 
 
 @pytest.mark.parametrize("name", FIXTURES)

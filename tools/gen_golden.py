@@ -382,8 +382,27 @@ def convergence_case(name, cfg: O.OracleCfg, seed, n_bank, n_test, batch, steps,
 FULL_GRADS_SEM = ("fc_net.0.weight", "fc_net.8.weight", "sun_v_net.0.weight", "semantic_prediction.2.weight", "model_t.weight")
 
 
+SMALL = dict(fc_units=32, n_samples=16, render_chunk_size=200)
+# K: trunk geometries other than the default 8 layers / skip at 4 / 10 frequencies (depth 1 and 3, two skip layers, 16 frequencies).
+# Written one by one: `python tools/gen_golden.py sem_geom3_small ...` (every other fixture stays byte-identical).
+NAMED_CASES = {
+    "sem_geom3_small": lambda: make_case("sem_geom3_small", O.OracleCfg(fc_layers=3, fc_skips=(1,), mapping_pos_n_freq=6, **SMALL),
+                                         48, seed=15, epoch=2),
+    "sem_geom5_small": lambda: make_case("sem_geom5_small", O.OracleCfg(fc_layers=5, fc_skips=(2, 3), mapping_pos_n_freq=16,
+                                                                        use_car_reg_loss=True, **SMALL), 48, seed=16, epoch=3),
+    "sem_geom1_small": lambda: make_case("sem_geom1_small", O.OracleCfg(fc_layers=1, fc_skips=(), **SMALL), 48, seed=17, epoch=0),
+}
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
+    if len(sys.argv) > 1 and not sys.argv[1].startswith("--"):   # only the named cases
+        unknown = [n for n in sys.argv[1:] if n not in NAMED_CASES]
+        if unknown:
+            sys.exit(f"unknown case(s) {unknown}; known: {sorted(NAMED_CASES)}")
+        for n in sys.argv[1:]:
+            NAMED_CASES[n]()
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "--trajectories":   # only the round-5 additions (the other fixtures regenerate array-identically)
         # I: long optimiser trajectories of the whole composed step -- 25 steps at W = 32 with L_t on, 10 steps at the full width
         make_trajectories()
@@ -423,6 +442,8 @@ def main():
     # H: seam-3 inference on explicit xyz/z_vals
     inference_case("inference_sem_small", O.OracleCfg(**small), 24, seed=10)
     inference_case("inference_satnerf_small", O.OracleCfg(model="satnerf", fc_units=32, n_samples=8), 24, seed=11)
+    for make in NAMED_CASES.values():
+        make()
     make_trajectories()
     make_convergence()
 
