@@ -262,6 +262,45 @@ int snerf_loss_finish(const SnerfLossCfg* cfg, const SnerfLossIn* in, const floa
 int snerf_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, unsigned long long n,
                     float lr, float beta1, float beta2, float eps, int step, float grad_scale, void* stream);
 
+/* ---- DSM evaluation (altitude MAE of a digital surface model; eval/utils/dsm.py:112-266, eval/utils/dsmr.py) ----------------
+ * Rasterisation is plyflatten(radius, sigma = inf) as the reference calls it (dsm.py:75-77): a point (x, y, z) has the lattice
+ * cell i = floor((x - xoff)/res), j = floor((yoff - y)/res) (fp64, row 0 at the north edge) and adds z, weight 1, to every cell
+ * (i+kx, j+ky), |kx|, |ky| <= radius, inside the lattice extent [0, xsize) x [0, ysize); a cell is the mean of what it received.
+ * Output cell (ii, jj) of an (out_h, out_w) window is lattice cell (ioff + ii, joff + jj): the cloud-bounds grid has
+ * ioff = joff = 0 and out = extent, an ROI on the same lattice a non-zero offset (= the bounds grid cropped, bit for bit). */
+typedef struct SnerfDsmGrid {
+  double xoff, yoff, res;
+  int32_t xsize, ysize;      /* lattice extent: cells outside it receive nothing */
+  int32_t ioff, joff;        /* output window origin on the lattice */
+  int32_t out_w, out_h;      /* output window size */
+} SnerfDsmGrid;
+/* snerf_dsm_accumulate ADDS the points' contributions into count[out_h*out_w] (u32) and sum[out_h*out_w] (int64 of
+ * round((z - z0)/q)): integer sums commute, so the result is bit-reproducible and data-parallel ranks combine by a SUM
+ * all-reduce of both.  stats[4] (u64, zeroed by the caller, accumulated): [0] = max |round((z - z0)/q)| of the points that
+ * reached the window, [1] = points whose quantised altitude is not finite or >= 2^62 in magnitude (they add nothing).
+ * snerf_dsm_finish writes dsm[c] = f32(z0 + q*sum/count), NaN where count = 0, and [2] = the largest count.  The sums cannot
+ * have wrapped iff stats[1] == 0 and stats[0] * stats[2] < 2^63: the caller checks this on the host. */
+int snerf_dsm_accumulate(const double* xyz, int n, const SnerfDsmGrid* grid, int radius, double z0, double q,
+                         unsigned* count, long long* sum, unsigned long long* stats, void* stream);
+int snerf_dsm_finish(const unsigned* count, const long long* sum, long long cells, double z0, double q, float* dsm,
+                     unsigned long long* stats, void* stream);
+/* dsmr.downsample2x of an (h, w) image (fp32 if u_f64 == 0, else fp64) into out[ceil(h/2)][ceil(w/2)] (fp64): out[J][I] is the
+ * NaN-aware mean of u[j:j+2, i:i+2] at j = min(2J+1, h-1), i = min(2I+1, w-1) -- the reference loop's last write wins */
+int snerf_dsm_downsample2x(const void* u, int u_f64, int h, int w, double* out, void* stream);
+/* workspace of snerf_dsm_ncc_search / snerf_dsm_shift_diff for an (h, w) image; 0 on bad arguments (radius in [0, 7]) */
+size_t snerf_dsm_workspace_bytes(int h, int w, int radius);
+/* dsmr.mean_std for every shift (cx + kx, cy + ky), |kx|, |ky| <= radius, of v against u (both (h, w), fp32 if f64 == 0),
+ * over the pixels where u[j][i] and v[j+dy][i+dx] are both finite (out of range = NaN), all in fp64:
+ * stats[s][6] = (count, sum u, sum v, sum (u-muu)^2, sum (v-muv)^2, sum (u-muu)(v-muv)), s = (ky+radius)*(2 radius+1) + kx+radius,
+ * with mu = sum/count (two passes, never E[x^2] - E[x]^2); fixed-order reductions (deterministic). */
+int snerf_dsm_ncc_search(const void* u, const void* v, int f64, int h, int w, int cx, int cy, int radius,
+                         double* stats, void* workspace, size_t workspace_bytes, void* stream);
+/* dsmr.apply_shift_ with a = 1 and compute_mae's difference: rdsm[j][i] = f32(pred[j+dy][i+dx] + b) (NaN out of range),
+ * diff = rdsm - g with g = gt, or 0 where gt < -500; totals[2] = (sum |diff|, count) over the finite diff, fp64, fixed order.
+ * rdsm and diff may be null (not written). */
+int snerf_dsm_shift_diff(const float* pred, const float* gt, int h, int w, int dx, int dy, double b, float* rdsm,
+                         float* diff, double* totals, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- measurement hook ----------------------------------------------------------------------------
  * Between snerf_profile_begin and snerf_profile_end every GEMM launch is bracketed by HIP events on the
  * stream it is launched on; _end synchronises those events and returns, per kernel variant, the summed

@@ -82,6 +82,11 @@ class SnerfLossGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in LOSS_GRAD_FIELDS]
 
 
+class SnerfDsmGrid(C.Structure):
+    _fields_ = [("xoff", C.c_double), ("yoff", C.c_double), ("res", C.c_double)] + [
+        (n, C.c_int32) for n in ("xsize", "ysize", "ioff", "joff", "out_w", "out_h")]
+
+
 class SnerfProfile(C.Structure):
     _fields_ = [("ms", C.c_double * 4), ("flops", C.c_double * 4), ("launches", C.c_int64 * 4)]
 
@@ -155,6 +160,22 @@ def lib():
     L.snerf_adam_step.restype = C.c_int
     L.snerf_adam_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_float, C.c_float,
                                   C.c_float, C.c_float, C.c_int, C.c_float, C.c_void_p]
+    L.snerf_dsm_accumulate.restype = C.c_int
+    L.snerf_dsm_accumulate.argtypes = [C.c_void_p, C.c_int, C.POINTER(SnerfDsmGrid), C.c_int, C.c_double, C.c_double,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.snerf_dsm_finish.restype = C.c_int
+    L.snerf_dsm_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]
+    L.snerf_dsm_downsample2x.restype = C.c_int
+    L.snerf_dsm_downsample2x.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.snerf_dsm_workspace_bytes.restype = C.c_size_t
+    L.snerf_dsm_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    L.snerf_dsm_ncc_search.restype = C.c_int
+    L.snerf_dsm_ncc_search.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.snerf_dsm_shift_diff.restype = C.c_int
+    L.snerf_dsm_shift_diff.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     L.snerf_profile_begin.restype = C.c_int
     L.snerf_profile_end.restype = C.c_int
     L.snerf_profile_end.argtypes = [C.POINTER(SnerfProfile)]
@@ -173,4 +194,6 @@ EXPORTED_SYMBOLS = ("snerf_version", "snerf_last_error", "snerf_packed_floats", 
                     "snerf_pack_params", "snerf_unpack_grads", "snerf_forward", "snerf_backward",
                     "snerf_loss_workspace_bytes", "snerf_loss_partial", "snerf_loss_finish", "snerf_profile_begin",
                     "snerf_profile_end", "snerf_sample_z", "snerf_adam_step", "snerf_test_bsp_roundtrip", "snerf_test_bsp_kc",
-                    "snerf_test_bsp_dw", "snerf_test_set_kc_grid", "snerf_test_set_trunk_fusion", "snerf_embedding_rows", "snerf_embedding_backward")
+                    "snerf_test_bsp_dw", "snerf_test_set_kc_grid", "snerf_test_set_trunk_fusion", "snerf_embedding_rows", "snerf_embedding_backward",
+                    "snerf_dsm_accumulate", "snerf_dsm_finish", "snerf_dsm_downsample2x", "snerf_dsm_workspace_bytes",
+                    "snerf_dsm_ncc_search", "snerf_dsm_shift_diff")

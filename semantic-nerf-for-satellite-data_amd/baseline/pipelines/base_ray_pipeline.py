@@ -1,6 +1,7 @@
 """Ray pipeline -- mirror of baseline/pipelines/base_ray_pipeline.py:14-269: forward = ray-chunk loop over
 render_chunk_size rays with key-wise concatenation, training_step wrapper, validation_step (full-image render under
-no_grad incl. the solar-correction pass -> loss -> PSNR; visualisers / SSIM / DSM-MAE are out of scope), Adam + StepLR."""
+no_grad incl. the solar-correction pass -> loss -> PSNR [-> DSM altitude MAE when the batch carries a "dsm" entry];
+visualisers / SSIM are out of scope), Adam + StepLR."""
 import time
 from collections import defaultdict
 
@@ -63,7 +64,12 @@ class BaseRayPipeline(Pipeline):
         Returns {"loss", "psnr", "sse", "count", <loss_dict>} as 0-d device tensors (no host sync); only the test split
         contributes to the logged test/loss and test/psnr (:160-163).  Under data parallelism `batch` holds this
         rank's slice of the image: the loss kernels all-reduce their sums and counts, and the caller forms the
-        image PSNR from the summed (sse, count)."""
+        image PSNR from the summed (sse, count).
+        With an optional batch["dsm"] = {"gt": (H, W) ground-truth DSM, "roi": roi_txt meta (xoff, yoff, size, resolution)
+        [, "water_mask" | "ignore_mask"] [, "to_world": xyz_n -> (E, N, alt)]} and batch_idx <= 1, the altitude MAE of the
+        DSM rasterised from depth_coarse is logged as f"{split}/mae" and returned under "mae" (:170-185; eval/utils/dsm.py).
+        Under data parallelism every rank rasterises its own rays and the integer accumulators are all-reduced (a
+        collective), so every rank computes the same DSM."""
         from ...eval.utils.util import lean_inference
         from ...eval.utils.metrics import sum_squared_error
         split = batch.get("split", "test")
@@ -80,6 +86,13 @@ class BaseRayPipeline(Pipeline):
         if split == "test":
             self.log("test/loss", loss, batch_size=1)
             self.log("test/psnr", out["psnr"], batch_size=1)
+        d = batch.get("dsm")
+        if d is not None and batch_idx <= 1:
+            from ...eval.utils.dsm import compute_dsm_and_mae
+            mae = compute_dsm_and_mae(rays, results["depth_coarse"], d["gt"], d["roi"], to_world=d.get("to_world"),
+                                      water_mask=d.get("water_mask"), ignore_mask=d.get("ignore_mask"))
+            self.log(f"{split}/mae", float(mae["mean"]), batch_size=1)
+            out["mae"] = mae
         return out
 
     def configure_optimizers(self):

@@ -1,7 +1,8 @@
 """Point clouds from a trained model -- the device side of eval/extract_pointcloud.py:66-114: full-frame inference of
 one image's rays (lean: rgb + depth [+ label] only, written in place per chunk), then the ray end points
-xyz = o + d * depth in double precision (baseline/dataset/satnerf_dataset.py:156-171).  Lat/lon/alt conversion, DSM
-rasterisation and the normals variants stay with the dataset / CPU tooling (out of scope)."""
+xyz = o + d * depth in double precision (baseline/dataset/satnerf_dataset.py:156-171).  DSM rasterisation and the altitude
+MAE of the cloud are eval/utils/dsm.py (device side); lat/lon/alt conversion and the normals variants stay with the dataset /
+CPU tooling (out of scope)."""
 import numpy as np
 import torch
 

@@ -4,7 +4,7 @@ Same definitions as the reference's `mse` / `psnr` (eval/utils/metrics.py:8-18):
 the selected elements, PSNR = -10 log10(MSE) for images in [0, 1].  Written as ONE masked sum-of-squares
 reduction: a `valid_mask` is applied as a 0/1 weight inside the reduction (no boolean-index gather, hence no
 data-dependent shape and no host synchronisation), and the result stays a 0-d device tensor until it is logged.
-SSIM (kornia) is CPU tooling and stays out of scope."""
+The DSM altitude MAE is eval/utils/dsm.py.  SSIM (kornia) is CPU tooling and stays out of scope."""
 import torch
 
 
