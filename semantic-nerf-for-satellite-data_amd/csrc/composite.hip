@@ -54,11 +54,14 @@ __device__ __forceinline__ void sky_forward(const float* __restrict__ sky, int H
 
 // pre-activation of a 1-wide head (sigma, sun visibility): the 32-wide buffer's column 0, or bias + the partial dot products of the
 // producing launch's epilogue summed in a fixed order (CompArgs::sig_part / sun_part)
+// The bias is added LAST, once, as the 32-wide launch's epilogue and torch's addmm do: added first, every partial sum after it rounds at
+// the bias's magnitude -- 8 roundings at W = 512, measured 1.8e-4 on sigma ~ 1000 (fp32 ulp 6.1e-5), beyond OUT_TOL on the `sigmas` output
+// of an opaque model (tests/test_gpu_heads.py: test_compositing_saturated[opaque-*]).
 __device__ __forceinline__ float narrow_pre(const float* full, const float* part, const float* bias, int n, size_t stride, size_t p) {
   if (part == nullptr) return full[p * NARROW];
-  float s = *bias;
+  float s = 0.f;
   for (int q = 0; q < n; ++q) s += part[(size_t)q * stride + p];
-  return s;
+  return s + *bias;
 }
 
 // pre-activation `o` of head `h` (0 rgb, 1 semantic, 2 beta, 3 beta_s; `col` = its column in the 32-wide buffer)

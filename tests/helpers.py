@@ -22,6 +22,8 @@ def load_fixture(name):
 def fixture_params(z, meta, cfg):
     """Parameters regenerate from (cfg, seed); small fixtures also store them, which pins the generator."""
     params = O.init_params_numpy(cfg, meta["seed"])
+    for k, v in meta.get("param_edit", {}).items():   # shifted biases (tools/gen_golden.py: edited_params)
+        params[k] = (params[k] + np.asarray(v, dtype=np.float32)).astype(np.float32)
     stored = [k for k in z.files if k.startswith("param_")]
     for k in stored:
         assert np.array_equal(z[k], params[k[len("param_"):]]), k

@@ -122,6 +122,30 @@ def test_one_plane_mode_refuses_raw_xyz():
         assert L.snerf_packed_floats(C.byref(d)) > 0 and L.snerf_workspace_bytes(C.byref(d)) > 0, (flags, L.snerf_last_error())
 
 
+@pytest.mark.parametrize("kw,flags,msg", [
+    ({"n_classes": 17}, 0, b"n_classes out of range"),                                     # MAX_CLASSES = 16
+    ({"t_dim": 14}, 0, b"3 + t_dim"),                                                      # 3 + 14 > 16 columns of the extras block
+    ({"t_dim": 7, "use_separate_tj_for_semantic": True, "use_tj_for_s": True}, 0, b"3 + t_dim"),   # 3 + 2 x 7 > 16
+    ({"feat_last": 520}, 0, b"feat_last must be"),                                         # > 64 x MAX_SKY_UNITS
+    ({"feat_last": 24}, 0, b"feat_last % 16"),
+    ({"fc_units": 48, "feat_last": 32}, 0, b"fc_units % 32"),
+    ({"fc_units": 96, "feat_last": 48}, "f16x1", b"fc_units % 64"),                        # one plane: LDS stages of 64 columns
+], ids=["C17", "tau14", "tau7-ts", "H520", "H24", "W48", "W96-one-plane"])
+def test_plan_refuses_heads_beyond_its_limits(kw, flags, msg):
+    """make_plan refuses each head shape it cannot compute, with the named reason, and accepts the edge just inside"""
+    from snerf_amd import _lib
+    from snerf_amd.ops import ModelSpec
+    L = _lib.lib()
+    f = _lib.FLAG_TRAIN | (_lib.FLAG_F16X1 if flags == "f16x1" else 0)
+    d = ModelSpec(**kw).desc(64, 8, f)
+    assert L.snerf_packed_floats(C.byref(d)) == 0 and L.snerf_workspace_bytes(C.byref(d)) == 0
+    assert msg in L.snerf_last_error(), L.snerf_last_error()
+    for ok in ({"n_classes": 16}, {"t_dim": 13}, {"t_dim": 6, "use_separate_tj_for_semantic": True, "use_tj_for_s": True},
+               {"feat_last": 512}, {"feat_last": 48}, {"fc_units": 96, "feat_last": 48}, {"fc_units": 1024, "feat_last": 512}):
+        d = ModelSpec(**ok).desc(64, 8, _lib.FLAG_TRAIN)
+        assert L.snerf_workspace_bytes(C.byref(d)) > 0, (ok, L.snerf_last_error())
+
+
 def test_product_path_refuses_cpu_tensors():
     """No CPU fallback: the HIP path raises instead of computing on the host."""
     import torch

@@ -56,13 +56,17 @@ def _subset_parity(cfg, N, n_sub, seed, epoch, monkeypatch=None, mode=None, out_
     idx = torch.arange(0, N, N // n_sub)[:n_sub]
     gp = _gpu_params(pn, dev, requires_grad=True)
     emb_g = torch.from_numpy(emb_np).to(dev).requires_grad_(True)
-    hip = _hip_render(cfg, gp, emb_g, b, dev)
+    sep_ts = cfg.model == "semantic" and cfg.use_separate_tj_for_semantic   # the second embedding as in the fixtures: seed + 1
+    emb_s_np = O.init_embedding_numpy(cfg, seed + 1) if sep_ts else None
+    emb_s_g = torch.from_numpy(emb_s_np).to(dev).requires_grad_(True) if sep_ts else None
+    hip = _hip_render(cfg, gp, emb_g, b, dev, emb_s_g)
     zv = hip.pop("_z_vals")
     # ---- oracle on the subset
     bs = _sub(b, idx)
     po = O.to_torch(pn, requires_grad=True)
     emb_o = torch.from_numpy(emb_np).requires_grad_(True)
-    ora = O.render_rays(po, emb_o, cfg, bs["rays"], bs["extras"], bs["u"])
+    emb_s_o = torch.from_numpy(emb_s_np).requires_grad_(True) if sep_ts else None
+    ora = O.render_rays(po, emb_o, cfg, bs["rays"], bs["extras"], bs["u"], emb_s_o)
     zo = ora.pop("_z_vals")
     if exact_z:
         assert torch.equal(zv[idx.to(dev)].cpu(), zo), "sampled depths are not bit-identical"
@@ -101,6 +105,8 @@ def _subset_parity(cfg, N, n_sub, seed, epoch, monkeypatch=None, mode=None, out_
         assert err <= grad_tol or max_abs(g, r) <= 1e-7 + GRAD_ABS_ESCAPE * (grad_tol / GRAD_REL_TOL) * float(r.abs().max()), (k, err)
     if emb_o.grad is not None:
         assert rel_err(emb_g.grad.cpu(), emb_o.grad) <= grad_tol
+    if sep_ts and emb_s_o.grad is not None:
+        assert rel_err(emb_s_g.grad.cpu(), emb_s_o.grad) <= grad_tol
     if mode is not None and REDUCED_MEASURED:
         REDUCED_MEASURED[-1]["worst_grad_rel_l2"] = worst
         print("reduced-precision config:", REDUCED_MEASURED[-1])
@@ -185,6 +191,7 @@ def test_c5_raised_embedding_vocab_96():
     {"activation_function": "relu"},                                                  # no folded projections: the 32-wide launches at full width
     {"n_classes": 4},                                                                 # labels 0..3 valid, 4 = car = the ignore index (outside [0, C): allowed)
     {"fc_use_full_features": True},                                                   # feat_last = 512: head blocks of two column tiles (no final-layer fold)
+    {"use_separate_tj_for_semantic": True, "use_tj_for_s": True},                     # t_s: extras block [sun | t | t_s], 11 of 16 columns
 ], ids=lambda kw: "+".join(sorted(kw)))
 def test_model_variants_at_full_width(kw):
     """Every model switch of the reference at fc_units = 512 (where the folded projections -- sigma, sun, and for feat_last = 256 the

@@ -14,6 +14,7 @@ fp32 rounding of the sample positions into 1e-3 at 16 frequencies, 1.3e-4 at 12)
 test_gpu_configs.py and the golden tests, and the test asserts that departure.  Bars are the suite's, imported, whatever the yardstick:
 default arithmetic OUT_TOL 1e-4, loss terms 2e-4, gradients GRAD_REL_TOL 2e-4 (tests/test_gpu_kernels.py); one plane the bars of
 test_model_variants_at_full_width_one_plane (5e-3 outputs, class agreement >= 98 %, 1e-2 loss terms, 3 % gradients)."""
+import numpy as np
 import pytest
 import torch
 
@@ -29,35 +30,53 @@ GEOMETRY_STATS = []   # measured worst errors per case (printed with -s)
 FP64_MAX_FREQ = 10    # the fp64 oracle up to here; beyond, the fp32 oracle (module docstring)
 
 
-def _oracle_parity(cfg, N, n_sub, seed, epoch, mode, out_tol, loss_rtol, grad_tol, monkeypatch, car_prob=0.1):
+def _oracle_parity(cfg, N, n_sub, seed, epoch, mode, out_tol, loss_rtol, grad_tol, monkeypatch, car_prob=0.1, n_classes=None,
+                   param_edit=None, fp64=None, stats=None, tag=None):
+    """returns the oracle's outputs on the subset (detached) and its batch; pass-through options of tests/test_gpu_heads.py: `n_classes`
+    (labels of synthetic_batch; default its own 5), `param_edit` ({name: shift} added to the seeded weights on both sides), `fp64` (the
+    yardstick: True / False, "auto" = measured on the subset, default: by frequency count as above), `stats` / `tag` (the list the measured errors go to, and extra fields)"""
     from snerf_amd import ops, _lib
     monkeypatch.setattr(ops, "BASE_FLAGS", _lib.MFMA_FLAGS[mode])
     dev = _dev()
     S = cfg.n_samples
     assert (N * S) % 128 != 0
-    fp64 = cfg.model != "semantic" or cfg.mapping_pos_n_freq <= FP64_MAX_FREQ
+    if fp64 is None:
+        fp64 = cfg.model != "semantic" or cfg.mapping_pos_n_freq <= FP64_MAX_FREQ
     pn = O.init_params_numpy(cfg, seed)
+    for k, v in (param_edit or {}).items():
+        pn[k] = (pn[k] + np.asarray(v, dtype=np.float32)).astype(np.float32)
     emb_np = O.init_embedding_numpy(cfg, seed)
-    bn = O.synthetic_batch(N, S, seed=seed + 100, car_prob=car_prob)
-    b = O.batch_to_torch(bn)
+    sep_ts = cfg.model == "semantic" and cfg.use_separate_tj_for_semantic   # the second embedding as in the fixtures: seed + 1
+    emb_s_np = O.init_embedding_numpy(cfg, seed + 1) if sep_ts else None
+    bn = O.synthetic_batch(N, S, seed=seed + 100, car_prob=car_prob, **({"n_classes": n_classes} if n_classes else {}))
     idx = torch.arange(0, N, N // n_sub)[:n_sub]
+    if fp64 == "auto":   # measured: fp64 where the reference's own fp32 agrees with it to a quarter of OUT_TOL on this subset
+        with torch.no_grad():
+            o = [O.render_rays(O.to_torch(pn, dtype=d), torch.from_numpy(emb_np).to(d), cfg, *(lambda t: (t["rays"], t["extras"], t["u"]))(
+                     O.batch_to_torch({k: v[idx.numpy()] for k, v in bn.items()}, dtype=d)), torch.from_numpy(emb_s_np).to(d) if sep_ts else None)
+                 for d in (torch.float32, torch.float64)]
+        fp64 = max(max_abs(o[0][k], o[1][k]) for k in o[1] if k not in ("semantic_label_coarse", "_z_vals")) <= OUT_TOL / 4
+    b = O.batch_to_torch(bn)
     gp = _gpu_params(pn, dev, requires_grad=True)
     emb_g = torch.from_numpy(emb_np).to(dev).requires_grad_(True)
-    hip = _hip_render(cfg, gp, emb_g, b, dev)
+    emb_s_g = torch.from_numpy(emb_s_np).to(dev).requires_grad_(True) if sep_ts else None
+    hip = _hip_render(cfg, gp, emb_g, b, dev, emb_s_g)
     zv = hip.pop("_z_vals")
     # ---- the oracle on the subset
     dt = torch.float64 if fp64 else torch.float32
     bs = O.batch_to_torch({k: v[idx.numpy()] for k, v in bn.items()}, dtype=dt)
     po = O.to_torch(pn, requires_grad=True, dtype=dt)
     emb_o = torch.from_numpy(emb_np).to(dt).requires_grad_(True)
-    ora = O.render_rays(po, emb_o, cfg, bs["rays"], bs["extras"], bs["u"])
+    emb_s_o = torch.from_numpy(emb_s_np).to(dt).requires_grad_(True) if sep_ts else None
+    ora = O.render_rays(po, emb_o, cfg, bs["rays"], bs["extras"], bs["u"], emb_s_o)
     zo = ora.pop("_z_vals")
     if not fp64:
         assert torch.equal(zv[idx.to(dev)].cpu(), zo), "sampled depths are not bit-identical"
         # why not fp64 here: the reference's own fp32 arithmetic departs from it by more than a quarter of OUT_TOL
         b64 = O.batch_to_torch({k: v[idx.numpy()] for k, v in bn.items()}, dtype=torch.float64)
         with torch.no_grad():
-            o64 = O.render_rays(O.to_torch(pn, dtype=torch.float64), torch.from_numpy(emb_np).double(), cfg, b64["rays"], b64["extras"], b64["u"])
+            o64 = O.render_rays(O.to_torch(pn, dtype=torch.float64), torch.from_numpy(emb_np).double(), cfg, b64["rays"], b64["extras"], b64["u"],
+                                torch.from_numpy(emb_s_np).double() if sep_ts else None)
         dep = max(max_abs(ora[k].detach(), o64[k]) for k in ora if k != "semantic_label_coarse")
         assert dep > OUT_TOL / 4, dep
     hip_sub = {k: v[idx.to(dev)] for k, v in hip.items()}
@@ -100,10 +119,14 @@ def _oracle_parity(cfg, N, n_sub, seed, epoch, mode, out_tol, loss_rtol, grad_to
     assert n >= 2 * cfg.fc_layers
     if emb_o.grad is not None:
         assert rel_err(emb_g.grad.cpu(), emb_o.grad) <= grad_tol
-    GEOMETRY_STATS.append({"mode": mode, "W": cfg.fc_units, "model": cfg.model, "L": cfg.fc_layers, "skips": tuple(cfg.fc_skips),
-                           "n_freq": cfg.mapping_pos_n_freq, "oracle": "fp64" if fp64 else "fp32", "out_abs": worst_out,
-                           "loss_rel": worst_loss, "grad_rel_l2": worst_grad})
-    print("geometry:", GEOMETRY_STATS[-1])
+    if sep_ts and emb_s_o.grad is not None:
+        assert rel_err(emb_s_g.grad.cpu(), emb_s_o.grad) <= grad_tol
+    out = GEOMETRY_STATS if stats is None else stats
+    out.append({"mode": mode, "W": cfg.fc_units, "model": cfg.model, "L": cfg.fc_layers, "skips": tuple(cfg.fc_skips),
+                "n_freq": cfg.mapping_pos_n_freq, "oracle": "fp64" if fp64 else "fp32", "out_abs": worst_out,
+                "loss_rel": worst_loss, "grad_rel_l2": worst_grad, **(tag or {})})
+    print("geometry:" if stats is None else "heads:", out[-1])
+    return {k: v.detach() for k, v in ora.items()}, bs
 
 
 def _cfg(geom, W, S):

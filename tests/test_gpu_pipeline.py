@@ -111,19 +111,34 @@ def _rand_results(N, S, C, seed, sbeta=False):
     return r
 
 
-@pytest.mark.parametrize("N,S", [(77, 16), (77, 64), (77, 100), (4096, 64), (8192, 96)])
+LOSS_SIZES = [(77, 16), (77, 64), (77, 100), (4096, 64), (8192, 96)]
+
+
+@pytest.mark.parametrize("N,S", LOSS_SIZES)
 def test_loss_modules_vs_oracle(N, S):
+    _loss_modules_vs_oracle(N, S, 5)
+
+
+@pytest.mark.parametrize("C", [16, 64])
+@pytest.mark.parametrize("N,S", LOSS_SIZES)
+def test_loss_modules_vs_oracle_many_classes(N, S, C):
+    _loss_modules_vs_oracle(N, S, C)
+
+
+def _loss_modules_vs_oracle(N, S, C):
     """every loss class of the mirror (values + gradients w.r.t. every rendered tensor) vs the oracle -- at a ragged small
     size and at the per-GPU batch sizes of BASELINE configs[1] / [2] (4096 x 64, 8192 x 96: the data-dependent counts of CE with
-    ignore index, L_t over car rays, masks and depth weights then span many workgroups of the partial-sum kernel)"""
+    ignore index, L_t over car rays, masks and depth weights then span many workgroups of the partial-sum kernel); at 5 classes, at the
+    plan's 16 (MAX_CLASSES) and at the 64 check_loss accepts, where the logit gradient uses every lane of the wavefront"""
     from snerf_amd.baseline.components.loss import SNerfLoss, SatNerfLoss, DepthLoss
     from snerf_amd.semantic.components.loss import SemanticLoss, SemanticUncertaintyLoss, SemanticCarRegLoss
-    C = 5
     g = torch.Generator().manual_seed(S + N)
     gt = torch.rand(N, 3, generator=g)
     labels = torch.randint(0, C, (N, 1), generator=g)
     mask = torch.rand(N, generator=g) > 0.3
     dgt, dw = torch.rand(N, generator=g), torch.rand(N, generator=g)
+    if C != 5:   # car rays (label 4) on every draw: among 77 rays of 64 classes there may be none, and L_t over no ray is NaN by definition
+        labels[::6] = 4
     cases = [
         ("snerf", {}, lambda r: SNerfLoss(lambda_sc=0.05)(r, gt.to(DEV)), lambda r, c: O.snerf_loss(r, gt, c)),
         ("snerf_nosc", {"sc_lambda": 0.0}, lambda r: SNerfLoss(lambda_sc=0.0)(r, gt.to(DEV)), lambda r, c: O.snerf_loss(r, gt, c)),
@@ -168,18 +183,32 @@ def test_loss_modules_vs_oracle(N, S):
             assert rel_err(gh.cpu(), go) <= 2e-5 or max_abs(gh.cpu(), go) <= 1e-9, (name, k, rel_err(gh.cpu(), go))
 
 
-@pytest.mark.parametrize("N,S,sem", [(77, 16, "plain"), (4096, 64, "plain"), (4096, 96, "uncertainty"), (513, 64, "uncertainty_sbeta")])
+MERGED_SIZES = [(77, 16, "plain"), (4096, 64, "plain"), (4096, 96, "uncertainty"), (513, 64, "uncertainty_sbeta")]
+
+
+@pytest.mark.parametrize("N,S,sem", MERGED_SIZES)
 def test_merged_loss_call_equals_module_by_module(N, S, sem):
+    _merged_loss_call_equals_module_by_module(N, S, sem, 5)
+
+
+@pytest.mark.parametrize("C", [16, 64])
+@pytest.mark.parametrize("N,S,sem", MERGED_SIZES)
+def test_merged_loss_call_many_classes(N, S, sem, C):
+    _merged_loss_call_equals_module_by_module(N, S, sem, C)
+
+
+def _merged_loss_call_equals_module_by_module(N, S, sem, C):
     """The training steps evaluate colour + semantic (+ L_t) losses as ONE fused call (loss_ops.run_plans).  Against the same modules
     called one by one, as the reference does: the same loss_dict, the same total and the same gradient on every rendered tensor --
-    also on weights / beta, where the colour loss, the beta-weighted CE and L_t all contribute."""
+    also on weights / beta, where the colour loss, the beta-weighted CE and L_t all contribute.  At 5, 16 and 64 classes."""
     from snerf_amd import loss_ops
     from snerf_amd.baseline.components.loss import SatNerfLoss
     from snerf_amd.semantic.components.loss import SemanticLoss, SemanticUncertaintyLoss, SemanticCarRegLoss
-    C = 5
     g = torch.Generator().manual_seed(N + S)
     gt = torch.rand(N, 3, generator=g).to(DEV)
     labels = torch.randint(0, C, (N, 1), generator=g).to(DEV)
+    if C != 5:   # car rays (label 4) on every draw (see _loss_modules_vs_oracle)
+        labels[::6] = 4
     mask = (torch.rand(N, generator=g) > 0.3).to(DEV)
     color = SatNerfLoss(lambda_sc=0.05)
     semantic = SemanticLoss(0.04, 4, ignore_car_index=True) if sem == "plain" else SemanticUncertaintyLoss(0.04, 4, ignore_car_index=True)

@@ -10,6 +10,8 @@ from tests.helpers import load_fixture, fixture_params, fixture_batch, max_abs, 
 TRAIN_CASES = ["sem_siren_small", "sem_relu_small", "sem_variants_small", "sem_tj_small", "sem_cartreg_small",
                "satnerf_small", "satnerf_relu_small", "sem_siren_full", "satnerf_full_c1",
                "sem_geom3_small", "sem_geom5_small", "sem_geom1_small"]   # trunk depths 3 / 5 / 1, two skips, 6 / 16 frequencies
+TRAIN_CASES += ["sem_c9_small", "sem_c16_small", "sem_tau13_small", "sem_ts6_small", "sem_dense_small"]   # 9 / 16 classes, tau 13 / 6 (+ t_s),
+                                                                                                       # saturated head biases at S = 80
 # fp32 oracle vs fp32 reference on the same CPU: same ATen ops, so tight bounds
 OUT_TOL = 2e-6
 GRAD_REL = 2e-5

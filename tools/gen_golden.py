@@ -55,7 +55,16 @@ def ref_cfgs(cfg: O.OracleCfg):
     return types.SimpleNamespace(pipeline=pipe)
 
 
-def build_reference(cfg: O.OracleCfg, seed: int):
+def edited_params(cfg: O.OracleCfg, seed: int, param_edit=None):
+    """init_params_numpy(cfg, seed) with `param_edit` ({name: shift}, a scalar or one value per element) added -- e.g. saturated head
+    biases, the regime of a trained model"""
+    params = O.init_params_numpy(cfg, seed)
+    for k, v in (param_edit or {}).items():
+        params[k] = (params[k] + np.asarray(v, dtype=np.float32)).astype(np.float32)
+    return params
+
+
+def build_reference(cfg: O.OracleCfg, seed: int, param_edit=None):
     cfgs = ref_cfgs(cfg)
     if cfg.model == "semantic":
         model = RSSemanticNeRF(cfgs, types.SimpleNamespace(semantic_n_classes=cfg.n_classes))
@@ -64,7 +73,7 @@ def build_reference(cfg: O.OracleCfg, seed: int):
         model = SatNeRF(cfgs, layers=cfg.fc_layers, feat=cfg.fc_units, skips=list(cfg.fc_skips),
                         t_embedding_dims=cfg.t_embedding_tau, siren=cfg.siren)
         renderer = SatNeRFRendering(cfgs)
-    params = O.init_params_numpy(cfg, seed)
+    params = edited_params(cfg, seed, param_edit)
     sd = model.state_dict()
     assert list(sd.keys()) == list(params.keys()), (list(sd.keys()), list(params.keys()))
     for k in sd:
@@ -128,9 +137,10 @@ def losses_for_epoch(cfg, res, batch, epoch, depth_res=None):
 
 
 def make_case(name, cfg: O.OracleCfg, n_rays, seed, epoch, with_depth=False, store_params=True,
-              per_sample=True, grad_mode="full", adam_steps=0, mask_frac=None, car_prob=0.2, full_grads=(), yard_noise=()):
+              per_sample=True, grad_mode="full", adam_steps=0, mask_frac=None, car_prob=0.2, full_grads=(), yard_noise=(),
+              param_edit=None):
     torch.manual_seed(0)
-    cfgs, models, renderer, params = build_reference(cfg, seed)
+    cfgs, models, renderer, params = build_reference(cfg, seed, param_edit)
     b = O.synthetic_batch(n_rays, cfg.n_samples, seed=seed + 100, n_classes=max(cfg.n_classes, 2), car_prob=car_prob)
     if mask_frac is not None:
         rng = np.random.default_rng(seed + 5)
@@ -183,7 +193,7 @@ def make_case(name, cfg: O.OracleCfg, n_rays, seed, epoch, with_depth=False, sto
         # noise -- the worst absolute deviation of any stored output, the worst relative deviation of a loss term and the worst relative
         # L2 deviation of a parameter gradient from the clean run above.
         torch.manual_seed(0)
-        _, models_n, renderer_n, _ = build_reference(cfg, seed)
+        _, models_n, renderer_n, _ = build_reference(cfg, seed, param_edit)
         rng = np.random.default_rng(seed + 99)
         with torch.no_grad():
             for p_ in models_n["coarse"].parameters():
@@ -220,6 +230,8 @@ def make_case(name, cfg: O.OracleCfg, n_rays, seed, epoch, with_depth=False, sto
     meta = dict(name=name, seed=seed, epoch=epoch, n_rays=n_rays, with_depth=with_depth,
                 cfg={k: (list(v) if isinstance(v, tuple) else v) for k, v in vars(cfg).items()},
                 torch=torch.__version__, reference="wagnva/semantic-nerf-for-satellite-data@2025-03-21")
+    if param_edit:   # (only then: every older fixture keeps its bytes)
+        meta["param_edit"] = {k: (list(v) if isinstance(v, (list, tuple)) else v) for k, v in param_edit.items()}
     fix["meta_json"] = np.array(json.dumps(meta))
     path = os.path.join(OUT, f"{name}.npz")
     np.savez_compressed(path, **fix)
@@ -391,6 +403,24 @@ NAMED_CASES = {
     "sem_geom5_small": lambda: make_case("sem_geom5_small", O.OracleCfg(fc_layers=5, fc_skips=(2, 3), mapping_pos_n_freq=16,
                                                                         use_car_reg_loss=True, **SMALL), 48, seed=16, epoch=3),
     "sem_geom1_small": lambda: make_case("sem_geom1_small", O.OracleCfg(fc_layers=1, fc_skips=(), **SMALL), 48, seed=17, epoch=0),
+    # L: head shapes other than 5 classes / tau = 4, and the saturated regime of a trained model.  The labels come from
+    # synthetic_batch(n_classes=C), whose car class is C - 1: car_index follows it.
+    "sem_c9_small": lambda: make_case("sem_c9_small", O.OracleCfg(n_classes=9, car_index=8, **SMALL), 48, seed=18, epoch=2),
+    # 16 classes + beta_s: all 21 live columns of the 32-wide head buffer
+    "sem_c16_small": lambda: make_case("sem_c16_small", O.OracleCfg(n_classes=16, car_index=15, use_separate_beta_for_s=True,
+                                                                    use_beta_for_s=True, semantic_activation_function="none", **SMALL),
+                                       48, seed=19, epoch=3),
+    # 3 + tau = 16: the extras block [sun | t] fills its 16 columns exactly
+    "sem_tau13_small": lambda: make_case("sem_tau13_small", O.OracleCfg(t_embedding_tau=13, use_tj_instead_of_beta=True, **SMALL),
+                                         48, seed=20, epoch=2),
+    # 3 + 2 * 6 = 15 columns: a separate t_s into the semantic head
+    "sem_ts6_small": lambda: make_case("sem_ts6_small", O.OracleCfg(t_embedding_tau=6, use_separate_tj_for_semantic=True, use_tj_for_s=True,
+                                                                    **SMALL), 48, seed=21, epoch=2),
+    # saturated heads at S = 80 (two 64-sample chunks): sigma + 2 puts a share of the weight behind sample 64; albedo channel 0 at
+    # sigmoid(+12) and sun visibility at sigmoid(+12) push raw rgb above 1, channel 1 at sigmoid(-12) below 0 (both clamp gates closed)
+    "sem_dense_small": lambda: make_case("sem_dense_small", O.OracleCfg(fc_units=32, n_samples=80, render_chunk_size=200), 48, seed=22,
+                                         epoch=2, param_edit={"sigma_from_xyz.0.bias": 2.0, "rgb_from_xyzdir.2.bias": [12.0, -12.0, 0.0],
+                                                              "sun_v_net.6.bias": 12.0}),
 }
 
 
