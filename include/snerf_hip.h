@@ -301,6 +301,22 @@ int snerf_dsm_ncc_search(const void* u, const void* v, int f64, int h, int w, in
 int snerf_dsm_shift_diff(const float* pred, const float* gt, int h, int w, int dx, int dy, double b, float* rdsm,
                          float* diff, double* totals, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- SSIM (eval/utils/metrics.py: kornia's ssim map with window 3, and ssim_inria) ------------------------------------------
+ * x, y: (b, c, h, w) fp32, contiguous; every (image, plane) is filtered on its own (depthwise cross-correlation) with the
+ * ws x ws fp32 table weights2d (row-major, device memory), ws odd in [1, 31].  Border: SNERF_SSIM_REFLECT pads by ws / 2
+ * without repeating the edge (index -1 reads 1; needs ws / 2 < h and < w, as torch's reflect pad), SNERF_SSIM_ZERO pads with
+ * zeros.  In fp64 (inputs and weights exact, products exact): mu1 = K*x, mu2 = K*y, s1 = K*(x^2) - mu1^2, s2 = K*(y^2) - mu2^2,
+ * s12 = K*(xy) - mu1 mu2, value = (2 mu1 mu2 + c1)(2 s12 + c2) / ((mu1^2 + mu2^2 + c1)(s1 + s2 + c2) + eps).
+ * map_or_null (may be null): the values as fp32, (b, c, h, w).  per_image_sum[b] (fp64): the sum of each image's c*h*w values,
+ * in a fixed order that does not depend on b (bit-reproducible; an image gives the same bits alone or in a batch). */
+#define SNERF_SSIM_REFLECT 0
+#define SNERF_SSIM_ZERO 1
+/* fp64 partials of one launch; 0 on bad arguments (zero or too large sizes, even / out-of-range window) */
+size_t snerf_ssim_workspace_bytes(int b, int c, int h, int w, int ws);
+int snerf_ssim(const float* x, const float* y, int b, int c, int h, int w, int ws, int border, const float* weights2d,
+               double c1, double c2, double eps, float* map_or_null, double* per_image_sum, void* workspace,
+               size_t workspace_bytes, void* stream);
+
 /* ---- measurement hook ----------------------------------------------------------------------------
  * Between snerf_profile_begin and snerf_profile_end every GEMM launch is bracketed by HIP events on the
  * stream it is launched on; _end synchronises those events and returns, per kernel variant, the summed

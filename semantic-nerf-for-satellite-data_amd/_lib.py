@@ -87,6 +87,10 @@ class SnerfDsmGrid(C.Structure):
         (n, C.c_int32) for n in ("xsize", "ysize", "ioff", "joff", "out_w", "out_h")]
 
 
+SSIM_REFLECT = 0    # include/snerf_hip.h SNERF_SSIM_REFLECT
+SSIM_ZERO = 1       # include/snerf_hip.h SNERF_SSIM_ZERO
+
+
 class SnerfProfile(C.Structure):
     _fields_ = [("ms", C.c_double * 4), ("flops", C.c_double * 4), ("launches", C.c_int64 * 4)]
 
@@ -176,6 +180,12 @@ def lib():
     L.snerf_dsm_shift_diff.restype = C.c_int
     L.snerf_dsm_shift_diff.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.snerf_ssim_workspace_bytes.restype = C.c_size_t
+    L.snerf_ssim_workspace_bytes.argtypes = [C.c_int] * 5
+    L.snerf_ssim.restype = C.c_int
+    L.snerf_ssim.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_double, C.c_double, C.c_double,
+                                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                                       C.c_void_p]
     L.snerf_profile_begin.restype = C.c_int
     L.snerf_profile_end.restype = C.c_int
     L.snerf_profile_end.argtypes = [C.POINTER(SnerfProfile)]
@@ -196,4 +206,4 @@ EXPORTED_SYMBOLS = ("snerf_version", "snerf_last_error", "snerf_packed_floats", 
                     "snerf_profile_end", "snerf_sample_z", "snerf_adam_step", "snerf_test_bsp_roundtrip", "snerf_test_bsp_kc",
                     "snerf_test_bsp_dw", "snerf_test_set_kc_grid", "snerf_test_set_trunk_fusion", "snerf_embedding_rows", "snerf_embedding_backward",
                     "snerf_dsm_accumulate", "snerf_dsm_finish", "snerf_dsm_downsample2x", "snerf_dsm_workspace_bytes",
-                    "snerf_dsm_ncc_search", "snerf_dsm_shift_diff")
+                    "snerf_dsm_ncc_search", "snerf_dsm_shift_diff", "snerf_ssim_workspace_bytes", "snerf_ssim")

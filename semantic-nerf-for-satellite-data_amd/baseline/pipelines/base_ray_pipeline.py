@@ -1,7 +1,8 @@
 """Ray pipeline -- mirror of baseline/pipelines/base_ray_pipeline.py:14-269: forward = ray-chunk loop over
 render_chunk_size rays with key-wise concatenation, training_step wrapper, validation_step (full-image render under
-no_grad incl. the solar-correction pass -> loss -> PSNR [-> DSM altitude MAE when the batch carries a "dsm" entry];
-visualisers / SSIM are out of scope), Adam + StepLR."""
+no_grad incl. the solar-correction pass -> loss -> PSNR -> SSIM [-> DSM altitude MAE when the batch carries a "dsm" entry];
+visualisers are out of scope), Adam + StepLR."""
+import math
 import time
 from collections import defaultdict
 
@@ -69,7 +70,13 @@ class BaseRayPipeline(Pipeline):
         [, "water_mask" | "ignore_mask"] [, "to_world": xyz_n -> (E, N, alt)]} and batch_idx <= 1, the altitude MAE of the
         DSM rasterised from depth_coarse is logged as f"{split}/mae" and returned under "mae" (:170-185; eval/utils/dsm.py).
         Under data parallelism every rank rasterises its own rays and the integer accumulators are all-reduced (a
-        collective), so every rank computes the same DSM."""
+        collective), so every rank computes the same DSM.
+        SSIM (:141-145,166-168) is logged as f"{split}/ssim" for every split and returned under "ssim": metrics.ssim of
+        rgb_coarse and rgbs through the reference's `.view(1, 3, H, W)` of the (H*W, 3) frames, (W, H) as w_h_from_sample
+        takes them (the batch's "w" / "h", else int(sqrt(n_rays)) for both; w*h must equal the ray count).  Under data
+        parallelism the global ray count is a sum all-reduce of the local counts and the rows of both frames are
+        all-gathered, so every rank computes the same value (collectives).  Without "w" / "h" and with a ray count that is
+        not a perfect square the shape is unknown and the key is left out."""
         from ...eval.utils.util import lean_inference
         from ...eval.utils.metrics import sum_squared_error
         split = batch.get("split", "test")
@@ -86,6 +93,10 @@ class BaseRayPipeline(Pipeline):
         if split == "test":
             self.log("test/loss", loss, batch_size=1)
             self.log("test/psnr", out["psnr"], batch_size=1)
+        ssim_ = self._val_ssim(batch, results["rgb_coarse"], rgbs)
+        if ssim_ is not None:
+            self.log(f"{split}/ssim", ssim_, batch_size=1)
+            out["ssim"] = ssim_
         d = batch.get("dsm")
         if d is not None and batch_idx <= 1:
             from ...eval.utils.dsm import compute_dsm_and_mae
@@ -94,6 +105,27 @@ class BaseRayPipeline(Pipeline):
             self.log(f"{split}/mae", float(mae["mean"]), batch_size=1)
             out["mae"] = mae
         return out
+
+    def _val_ssim(self, batch, rgb, rgbs):
+        """SSIM of one validation image from this rank's rows of it; None when its (H, W) cannot be known"""
+        from ...eval.utils.metrics import ssim
+        from ... import parallel
+        n = rgbs.shape[0]
+        if parallel.world()[1] > 1:
+            # every rank learns the same global count (also with w / h: a mismatch then raises on all ranks alike)
+            cnt = torch.tensor([n], dtype=torch.int64, device=rgbs.device)
+            n = int(parallel.allreduce_sum_(cnt)[0])
+        wh = frame_w_h(batch)
+        if wh is None:
+            side = math.isqrt(n)
+            if side * side != n:
+                return None
+            wh = (side, side)
+        W, H = wh
+        if W * H != n:
+            raise ValueError(f"validation image of {n} rays is not {W} x {H}")
+        rgb, rgbs = parallel.allgather_rows(rgb, n), parallel.allgather_rows(rgbs, n)
+        return ssim(rgb.view(1, 3, H, W), rgbs.view(1, 3, H, W))
 
     def configure_optimizers(self):
         # same optimiser and schedule as the reference (:246-269), as ONE fused HIP launch over a flat parameter
@@ -107,3 +139,14 @@ class BaseRayPipeline(Pipeline):
         self.optimizer = FlatAdam(params, lr=self.cfgs.pipeline.learnrate, weight_decay=0)
         scheduler = StepLR(self.optimizer, step_size=1, gamma=0.9)
         return {"optimizer": self.optimizer, "lr_scheduler": {"scheduler": scheduler, "interval": "epoch"}}
+
+
+def frame_w_h(sample):
+    """(W, H) from a sample's "w" / "h" (ints, 0-d tensors or one-element lists, as framework/util/other.py:55-65 reads
+    them), or None when it carries neither"""
+    if "w" not in sample or "h" not in sample:
+        return None
+    w, h = sample["w"], sample["h"]
+    if isinstance(w, (list, tuple)):
+        w, h = w[0], h[0]
+    return int(w), int(h)

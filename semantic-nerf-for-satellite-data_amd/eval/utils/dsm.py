@@ -39,7 +39,8 @@ the two middle values for an even count).  The reference formats both with "{:.3
 
 Out of scope: lat/lon/UTM conversion (get_latlonalt_from_nerf_prediction, get_utm_cloud: the dataset's) --
 the cloud comes in a metric east/north/up frame, optionally through a caller's `to_world(xyz_n) -> (E, N, alt)`; GeoTIFF
-reading and writing (arrays in, arrays out); SSIM."""
+reading and writing (arrays in, arrays out).  SSIM is eval/utils/metrics.py; eval/eval_nerf.py reports PSNR, SSIM and this
+MAE per image."""
 import ctypes as C
 import math
 from collections import namedtuple

@@ -217,7 +217,9 @@ class TrainLoop:
     def validate(self, rays_per_image: int = None, max_images: int = None):
         """Every image of the `rgb_test` bank through pipeline.validation_step; returns the split's means (loss, PSNR,
         semantic accuracy, per-image mIoU), the split-wide row-normalised confusion matrix and its mIoU
-        (eval/eval_semantic.py:63-77,122-140) -- one host read at the very end.  Ranks share each image's rays."""
+        (eval/eval_semantic.py:63-77,122-140) -- one host read at the very end.  Ranks share each image's rays.
+        test/ssim is the mean of the images' SSIM (every rank holds the whole image's value) over the images whose shape
+        validation_step could know; absent when there is none."""
         pl = self.pipeline
         bank = pl.datasets["rgb_test"]
         # NOTE: the package's only bank factory is the synthetic one (GpuRayBank.synthetic, no image sizes), so from the product's
@@ -230,6 +232,7 @@ class TrainLoop:
         if max_images is not None:
             n = min(n, max_images)
         acc, cm = {}, None
+        ssim_sum, ssim_n = None, 0
         for i in range(n):
             b = dict(bank.image(i, hw, self.rank, self.world), split="test")
             out = pl.validation_step(b, i)
@@ -244,7 +247,12 @@ class TrainLoop:
                 vals["semantic_accuracy"] = torch.diagonal(c).sum() / c.sum()
             for k, v in vals.items():
                 acc[k] = v if k not in acc else acc[k] + v
+            if "ssim" in out:
+                ssim_sum = out["ssim"] if ssim_n == 0 else ssim_sum + out["ssim"]
+                ssim_n += 1
         res = {f"test/{k}": float(v) / max(n, 1) for k, v in acc.items()}
+        if ssim_n:
+            res["test/ssim"] = float(ssim_sum) / ssim_n
         if cm is not None:
             from ..semantic.components import metrics as M
             rows = cm.sum(dim=1, keepdim=True)
