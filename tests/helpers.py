@@ -103,3 +103,106 @@ def check_validation_metrics(device):
     img_mask = (torch.rand(5, 8, generator=g) > 0.3).to(dev)           # an (H, W) mask over an (H, W, 3) image
     ia, ic = torch.rand(5, 8, 3, generator=g).to(dev), torch.rand(5, 8, 3, generator=g).to(dev)
     assert abs(float(mse(ia, ic, img_mask)) - float(((ia - ic) ** 2)[img_mask].mean())) < 1e-6
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# CPU-oracle subsets that do not alias onto the 128-point row tiles
+# ----------------------------------------------------------------------------------------------------------------------
+TILE_ROWS = 128     # rows (points) of a row tile of every point-major launch
+XCD_GROUPS = 8      # workgroups b and b + 8 share an XCD: the tile maps (csrc/tiles.h) group row tiles by index mod 8
+
+
+def dealiased_subset(N, n_sub, S):
+    """n_sub of N rays for the oracle: ray k * stride + ((k + k // 8) mod stride), stride = N // n_sub.  A plain power-of-two stride puts
+    every live ray at the same position of its row tile (4096 x 64, stride 16: rays 0, 16, 32, ... = rows 0-63 of the tiles
+    0, 8, 16, ... only): then only one tile residue mod 8 and one half of a tile carry gradient, and every other 128 x 128 block
+    of dZ / dX is zero.  The per-ray offset walks every position inside the stride; the k // 8 term keeps it from locking to k
+    mod 8 (the plain k mod stride reached four residues at 301 x 96, stride 4).  Returns the indices and the live points'
+    coverage: the row-tile residues mod 8 and the tile halves (rows 0-63 / 64-127) they touch."""
+    stride = N // n_sub
+    k = torch.arange(n_sub)
+    idx = k * stride + (k + k // XCD_GROUPS) % stride
+    assert int(idx[-1]) < N and len(set(idx.tolist())) == n_sub
+    pts = (idx[:, None] * S + torch.arange(S)[None, :]).reshape(-1)
+    residues = set((pts // TILE_ROWS % XCD_GROUPS).tolist())
+    halves = set((pts % TILE_ROWS // (TILE_ROWS // 2)).tolist())
+    return idx, residues, halves
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the oracle over a whole batch, in fp64, on any device
+# ----------------------------------------------------------------------------------------------------------------------
+class PerRayRows:
+    """stands in for an embedding table where the oracle's render_rays looks rows up by image index: hands out the given
+    per-ray rows (a slice of one leaf) whatever the index"""
+
+    def __init__(self, rows):
+        self.rows = rows
+
+    def __getitem__(self, _):
+        return self.rows
+
+
+ORACLE_CHUNK_POINTS = 16384   # points per ray chunk: about 4 GB of fp64 autograd state at W = 512 (main + sc pass)
+
+
+def chunked_oracle(cfg, params_np, emb_np, batch, epoch, device, emb_s_np=None, dtype=torch.float64,
+                   chunk_points=ORACLE_CHUNK_POINTS, g_out=None):
+    """Outputs, loss terms and gradients of O.render_rays + O.training_losses over a WHOLE batch, with the autograd state of
+    one ray chunk at a time.  Phase 1 renders the chunks without grad, concatenates the outputs into leaves and evaluates the
+    loss set on the whole batch (true means, CE ignore-index count and L_t car-ray count) to get d loss / d output of every ray;
+    phase 2 re-renders each chunk with grad and back-propagates its slice of those output gradients, so the parameter
+    gradients accumulate over the chunks.  Rays are independent, so this is the whole-batch backward up to summation order.
+    The transient codes enter as ONE per-ray leaf (the table's rows of the batch): its gradient is d loss / d t per ray, and the
+    table's gradient is its scatter-add by image index.  `batch`: CPU tensors as O.batch_to_torch makes them (floats are cast
+    to `dtype`).  Returns a dict: out (detached), loss ({term: float}), grads ({name: tensor}), emb / emb_s (table gradients or
+    None), t_rows (per-ray d loss / d t or None), g_out ({output: d loss / d output}), peak_bytes (CUDA: peak allocation above
+    the starting level, else None).  `g_out` given ({output: tensor}): phase 2 back-propagates those output gradients (cast to
+    `dtype`) instead of the loss's own, and `loss` is empty -- the backward alone, driven by another oracle's output gradients."""
+    dev = torch.device(device)
+    cuda = dev.type == "cuda"
+    if cuda:
+        torch.cuda.synchronize(dev)
+        base = torch.cuda.memory_allocated(dev)
+        torch.cuda.reset_peak_memory_stats(dev)
+    p = O.to_torch(params_np, dtype=dtype)
+    p = {k: v.to(dev).requires_grad_(True) for k, v in p.items()}
+    b = {k: (v.to(dev, dtype) if v.is_floating_point() else v.to(dev)) for k, v in batch.items()}
+    ts = b["extras"][:, 3].long()
+    tables = [torch.from_numpy(emb_np).to(dev, dtype)] + ([torch.from_numpy(emb_s_np).to(dev, dtype)] if emb_s_np is not None else [])
+    rows = [t[ts].detach().requires_grad_(True) for t in tables]
+    N, S = b["rays"].shape[0], cfg.n_samples
+    R = max(1, chunk_points // S)
+    chunks = [(i, min(N, i + R)) for i in range(0, N, R)]
+
+    def render(i, j):
+        return O.render_rays(p, PerRayRows(rows[0][i:j]), cfg, b["rays"][i:j], b["extras"][i:j], b["u"][i:j],
+                             PerRayRows(rows[1][i:j]) if len(rows) > 1 else None)
+
+    with torch.no_grad():                                                          # phase 1
+        parts = [render(i, j) for i, j in chunks]
+    out = {k: torch.cat([q[k] for q in parts], 0) for k in parts[0]}
+    del parts
+    if g_out is None:
+        leaves = {k: v.requires_grad_(True) for k, v in out.items() if v.is_floating_point() and k != "_z_vals"}
+        ld = O.training_losses({**out, **leaves}, b, cfg, epoch)
+        O.total_loss(ld).backward()
+        g_out = {k: v.grad for k, v in leaves.items() if v.grad is not None}
+    else:
+        ld = {}
+        g_out = {k: v.to(dev, dtype) for k, v in g_out.items()}
+    for i, j in chunks:                                                            # phase 2
+        r = render(i, j)
+        keys = list(g_out)
+        torch.autograd.backward([r[k] for k in keys], [g_out[k][i:j] for k in keys])
+        del r
+    res = {"out": {k: v.detach() for k, v in out.items()}, "loss": {k: float(v.detach()) for k, v in ld.items()},
+           "grads": {k: v.grad for k, v in p.items()}, "emb": None, "emb_s": None, "t_rows": rows[0].grad, "g_out": g_out,
+           "peak_bytes": None}
+    for name, t, r in zip(("emb", "emb_s"), tables, rows):
+        if r.grad is not None:
+            res[name] = torch.zeros_like(t).index_add_(0, ts, r.grad)
+    if cuda:
+        torch.cuda.synchronize(dev)
+        res["peak_bytes"] = torch.cuda.max_memory_allocated(dev) - base
+    return res

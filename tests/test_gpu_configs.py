@@ -4,9 +4,10 @@ The oracle (oracle/snerf_oracle.py, pinned to the reference by tests/test_oracle
 4096-ray batch at fc_units = 512, but rays are independent: the HIP path renders the FULL batch in one launch
 sequence (full-size tile maps, split-K factors, multi-GB workspace offsets, operand scales taken over the whole
 batch) and the oracle re-renders a fixed subset of its rays -- an exact check of those rays in the full-size
-launch.  The backward check uses the real loss set evaluated on the subset's outputs only: every other ray then
+launch.  The subset is de-aliased from the 128-point row tiles (tests/helpers.py: dealiased_subset): its live points fall in
+every row-tile residue mod 8 and in both halves of a tile.  The backward check uses the real loss set evaluated on the subset's outputs only: every other ray then
 has a zero output gradient, so the parameter gradients of the full-size backward launch sequence must equal the
-oracle's gradients of the subset alone.
+oracle's gradients of the subset alone.  Every ray live, against an fp64 oracle of the whole batch: tests/test_gpu_fullbatch.py.
 
 | BASELINE config | per-GPU shape | test |
 |---|---|---|
@@ -28,7 +29,7 @@ import pytest
 import torch
 
 from oracle import snerf_oracle as O
-from tests.helpers import max_abs, rel_err
+from tests.helpers import dealiased_subset, max_abs, rel_err
 from tests.test_gpu_kernels import _dev, _gpu_params, _hip_render, _compare_outputs, OUT_TOL, GRAD_REL_TOL, GRAD_ABS_ESCAPE, LABEL_STATS
 
 pytestmark = pytest.mark.gpu
@@ -43,8 +44,9 @@ REDUCED_MEASURED = []   # what the one-plane mode measured at the configuration 
 
 def _subset_parity(cfg, N, n_sub, seed, epoch, monkeypatch=None, mode=None, out_tol=OUT_TOL, loss_rtol=2e-4,
                    grad_tol=GRAD_REL_TOL, exact_z=True, car_prob=0.03, n_images=19):
-    """Render N rays on the HIP path; oracle on n_sub of them (stride N // n_sub); outputs, loss terms and the
-    parameter gradients of the subset loss must agree."""
+    """Render N rays on the HIP path; oracle on n_sub of them (tests/helpers.py: dealiased_subset -- stride N // n_sub plus an
+    offset per subset ray, so that the live rays reach every row-tile residue mod 8 and both halves of a tile); outputs, loss
+    terms and the parameter gradients of the subset loss must agree."""
     from snerf_amd import ops, _lib
     if mode is not None:
         monkeypatch.setattr(ops, "BASE_FLAGS", _lib.MFMA_FLAGS[mode])
@@ -53,7 +55,8 @@ def _subset_parity(cfg, N, n_sub, seed, epoch, monkeypatch=None, mode=None, out_
     pn = O.init_params_numpy(cfg, seed)
     emb_np = O.init_embedding_numpy(cfg, seed)
     b = O.batch_to_torch(O.synthetic_batch(N, S, seed=seed + 100, car_prob=car_prob, n_images=n_images))
-    idx = torch.arange(0, N, N // n_sub)[:n_sub]
+    idx, residues, halves = dealiased_subset(N, n_sub, S)
+    assert residues == set(range(8)) and halves == {0, 1}, ("live rays miss row tiles", residues, halves)
     gp = _gpu_params(pn, dev, requires_grad=True)
     emb_g = torch.from_numpy(emb_np).to(dev).requires_grad_(True)
     sep_ts = cfg.model == "semantic" and cfg.use_separate_tj_for_semantic   # the second embedding as in the fixtures: seed + 1

@@ -7,8 +7,8 @@ the encoding's padding (Ep = 32 / 64 / 96 / 128) and, in one-plane mode at W = 5
 (csrc/bsp_trunk.hip: 3 <= L <= 8, Ep = 64).
 
 Pattern of tests/test_gpu_configs.py (_subset_parity): the HIP path renders N rays (N x S ragged: not a multiple of the 128-point tile),
-the oracle re-renders a strided subset of them; outputs, the loss set of the subset (epoch 3 with L_t for the semantic model, epoch 2 for
-SatNeRF) and every parameter gradient must agree.  The oracle runs in fp64 wherever the reference's own fp32 arithmetic agrees with fp64
+the oracle re-renders a subset of them (strided, with an offset per ray: tests/helpers.py, dealiased_subset); outputs, the loss set of
+the subset (epoch 3 with L_t for the semantic model, epoch 2 for SatNeRF) and every parameter gradient must agree.  The oracle runs in fp64 wherever the reference's own fp32 arithmetic agrees with fp64
 (up to 10 frequencies: 2.7e-5 on the outputs at most, a quarter of OUT_TOL).  From 12 frequencies on it does not (sin(2^15 x) turns the
 fp32 rounding of the sample positions into 1e-3 at 16 frequencies, 1.3e-4 at 12): there the yardstick is the fp32 oracle, as in
 test_gpu_configs.py and the golden tests, and the test asserts that departure.  Bars are the suite's, imported, whatever the yardstick:
@@ -19,7 +19,7 @@ import pytest
 import torch
 
 from oracle import snerf_oracle as O
-from tests.helpers import max_abs, rel_err
+from tests.helpers import dealiased_subset, max_abs, rel_err
 from tests.test_gpu_kernels import _dev, _gpu_params, _hip_render, _compare_outputs, OUT_TOL, GRAD_REL_TOL, GRAD_ABS_ESCAPE
 
 pytestmark = pytest.mark.gpu
@@ -49,7 +49,8 @@ def _oracle_parity(cfg, N, n_sub, seed, epoch, mode, out_tol, loss_rtol, grad_to
     sep_ts = cfg.model == "semantic" and cfg.use_separate_tj_for_semantic   # the second embedding as in the fixtures: seed + 1
     emb_s_np = O.init_embedding_numpy(cfg, seed + 1) if sep_ts else None
     bn = O.synthetic_batch(N, S, seed=seed + 100, car_prob=car_prob, **({"n_classes": n_classes} if n_classes else {}))
-    idx = torch.arange(0, N, N // n_sub)[:n_sub]
+    idx, residues, halves = dealiased_subset(N, n_sub, S)   # live rays in every row-tile residue mod 8 and both tile halves
+    assert residues == set(range(8)) and halves == {0, 1}, ("live rays miss row tiles", residues, halves)
     if fp64 == "auto":   # measured: fp64 where the reference's own fp32 agrees with it to a quarter of OUT_TOL on this subset
         with torch.no_grad():
             o = [O.render_rays(O.to_torch(pn, dtype=d), torch.from_numpy(emb_np).to(d), cfg, *(lambda t: (t["rays"], t["extras"], t["u"]))(

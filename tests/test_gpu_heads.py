@@ -10,7 +10,8 @@ width feat_last any multiple of 16 up to 512 (fc_units // 2, or fc_units with fc
 - saturated heads -- the regime of a trained model -- run alpha = 1 (tau = 1e-10 and the backward's division by it), transmittance that
   underflows, softplus above its threshold, closed clamp gates of the colour and mass carried from one 64-sample chunk into the next.
 
-Pattern of tests/test_gpu_geometry.py (_oracle_parity): the HIP path renders N rays (N x S ragged), the oracle re-renders a strided subset;
+Pattern of tests/test_gpu_geometry.py (_oracle_parity): the HIP path renders N rays (N x S ragged), the oracle re-renders a subset
+(tests/helpers.py: dealiased_subset -- strided with an offset per ray, live rays in every row-tile residue and both tile halves);
 outputs, the loss set of the subset and every parameter gradient must agree at the suite's bars (imported).  The oracle runs in fp64 where
 the reference's own fp32 agrees with fp64 to a quarter of OUT_TOL on the case's subset, otherwise in fp32 with the departure asserted
 (_oracle_parity, fp64="auto": measured per case, recorded as "oracle").  The departure is on `sigmas` throughout -- the SIREN trunk's w0 = 30

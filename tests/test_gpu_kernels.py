@@ -309,7 +309,8 @@ def test_reduced_precision_mode_full_width(monkeypatch):
     such path here, so the yardsticks are made by the reference itself (tools/gen_golden.py: `yard_*_noise_*` of the fixture): the same
     case from weights carrying 1e-3 relative noise moves its outputs by 5.6e-3 abs, its gradients by 3.5 % relative L2 (3e-4 noise:
     1.7e-3, 1.0 %).  Bars: outputs within the 1e-3 yardstick (measured 7.4e-4: below even the 3e-4 one), loss terms 1 %, gradients
-    within 3x the 1e-3 yardstick of the default arithmetic's (measured 3.8 %) and finite.  The default is held to 1e-4 / 2e-4 right above."""
+    within 1.5x the 1e-3 yardstick of the default arithmetic's (5.2 %; measured 3.8 % = 1.1x the yardstick: the old 3x left a
+    gradient path that lost twice its measured precision passing) and finite.  The default is held to 1e-4 / 2e-4 right above."""
     from snerf_amd import ops, _lib
     dev = _dev()
     z, meta, cfg = load_fixture("sem_siren_full")
@@ -344,7 +345,7 @@ def test_reduced_precision_mode_full_width(monkeypatch):
                           "reference_under_1e-3_weight_noise": {"outputs_abs": yard_out, "grad_rel_l2": yard_grad},
                           "reference_under_3e-4_weight_noise": {"outputs_abs": float(z["yard_out_abs_noise_3e-4"]), "grad_rel_l2": float(z["yard_grad_rel_noise_3e-4"])}})
     print("f16x1 at W=512:", REDUCED_STATS[-1])
-    assert max(rel.values()) <= 3.0 * yard_grad, sorted(rel.items(), key=lambda kv: -kv[1])[:3]
+    assert max(rel.values()) <= 1.5 * yard_grad, sorted(rel.items(), key=lambda kv: -kv[1])[:3]
 
 
 def test_forward_backward_capture_in_a_hip_graph():
