@@ -10,12 +10,17 @@ samples, fp32") per GPU: on-device batch sampling -> main + solar-correction for
 solar correction + SemanticLoss (fused HIP loss kernels) -> backward -> flat gradient all-reduce (RCCL,
 N > 1) -> Adam.  Weak scaling: 4096 rays per GPU.  Prints ONE JSON line (rank 0).
 
-Besides the contract fields the line carries, all measured in the same run (N = 1):
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line: its `roofline` is then the whole step's
+algorithmic FLOPs over wall time.  With --full the same run goes on, after the timed region, to measure (N = 1 unless noted):
   roofline             dominant kernel (the K-contiguous dense-layer GEMM): algorithmic FLOPs / HIP-event duration against the
-                       dense fp16 MFMA peak (`frac`), the matrix-pipe occupancy of the three-product arithmetic next to it
+                       dense fp16 MFMA peak (`frac`), the matrix-pipe occupancy of the three-product arithmetic next to it, and
+                       the clock and package power held over extra steps
+  inference            forward-only rays/s: lean full-frame path and the reference-shaped batched_inference
+  reduced_precision    the step in the one-plane mode at 4096 x 64 / 96 / 128
   cpu_baseline         the CPU oracle on the host cores, bounded sample
   reference_gpu_eager  the same restatement on cuda:0 with stock PyTorch-ROCm eager ops (north_star's denominator)
-  inference            forward-only rays/s: lean full-frame path and the reference-shaped batched_inference
+  inference_sharded    --config c5, any N: the rank-sharded full-frame inference leg
+The --no-* options leave single legs of --full out.
 """
 import argparse
 import ctypes as C
@@ -423,6 +428,8 @@ def main():
                     "loss set and rank count of configs[0] ... configs[4]); without it: --rays / --samples / --mfma (default = c2, the headline)")
     ap.add_argument("--rays", type=int, default=None, help="rays per GPU (default 4096)")
     ap.add_argument("--samples", type=int, default=None)
+    ap.add_argument("--full", action="store_true", help="after the timed region, also measure the per-kernel roofline, clock and power, "
+                    "inference, the reduced-precision legs, the CPU and stock-PyTorch baselines and the c5 frame leg (off: the headline only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true", help="skip the per-GEMM HIP-event timing")
     ap.add_argument("--serial-passes", action="store_true", help="run main and sc pass on one stream (as the roofline phase does)")
@@ -437,6 +444,8 @@ def main():
                     help="after the timed steps, write what the last timed step computed (loss, loss terms, updated parameters, their "
                          "gradients) as DIR/<name>.npy, float32 / float64, at most 64 MB in all (rank 0)")
     args = ap.parse_args()
+    if not args.full:       # a plain run: the headline only; every leg that measures something else belongs to --full
+        args.no_profile = args.no_inference = args.no_reduced = args.no_cpu_baseline = args.no_eager_gpu_baseline = True
     preset = PRESETS.get(args.config or "", None)
     if preset is not None:
         if args.rays is not None or args.samples is not None or args.mfma is not None:
@@ -571,7 +580,7 @@ def main():
     dt = float(tmax.item())
     loss = float(out["loss"].detach())
 
-    if pz.get("frame"):
+    if pz.get("frame") and args.full:
         # configs[4]'s second half: full-frame inference a la eval/extract_pointcloud.py with the frame's rays sharded over the ranks
         # (eval/utils/util.py: sharded_lean_inference -- every rank renders ceil(n / world) rays, one all_gather per per-ray result)
         from snerf_amd.eval.utils.util import sharded_lean_inference
@@ -710,7 +719,7 @@ def main():
     else:
         line["roofline"] = {"bound": "mfma", "achieved": step_tflops, "peak": BF16_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
                             "frac": step_tflops / BF16_MFMA_PEAK_TFLOPS, "traffic": None,
-                            "kernel": "whole step (algorithmic FLOPs / wall time); per-kernel timing disabled"}
+                            "kernel": "whole step (algorithmic FLOPs / wall time); per-kernel timing not run (--full without --no-profile runs it)"}
     if frame_leg is not None:
         line["inference_sharded"] = frame_leg
     if world == 1 and not args.no_inference:

@@ -67,7 +67,8 @@ def test_bench_rank_failure_is_reported():
 def test_bench_presets_run_on_one_gpu():
     """every preset's step runs (one rank on this GPU, two steps): c1 the baseline SatNeRF pipeline, c3 the one-plane mode with L_t, c5
     with the rank-sharded full-frame leg"""
-    common = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-eager-gpu-baseline", "--no-inference", "--no-profile", "--no-reduced"]
+    common = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-eager-gpu-baseline", "--no-inference", "--no-profile",
+              "--no-reduced"]
     d = _run(["--config", "c1"] + common)
     assert d["config"]["preset"] == "c1" and d["config"]["rays_per_gpu"] == 512 and d["config"]["samples"] == 32 and d["value"] > 0
     d = _run(["--config", "c3"] + common)

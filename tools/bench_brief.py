@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Print the headline numbers of a bench.py JSON line (development aid)."""
+"""Print the headline numbers of a `bench.py --full` JSON line (development aid)."""
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 r = d["roofline"]

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Copy the judged summaries of a gpurun_out/<dir> (tools/profile_step.sh + tools/pmc_traffic.sh + a default bench.py run)
-into profiles/rNN/:  make_profile_artifacts.py <gpurun_out dir> <profiles dir> [<default bench json>]"""
+"""Copy the judged summaries of a run's output directory (tools/profile_step.sh + tools/pmc_traffic.sh + a `bench.py --full` run)
+into profiles/rNN/:  make_profile_artifacts.py <output dir> <profiles dir> [<bench --full json>]"""
 import csv
 import json
 import os
