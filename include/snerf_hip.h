@@ -317,6 +317,35 @@ int snerf_ssim(const float* x, const float* y, int b, int c, int h, int w, int w
                double c1, double c2, double eps, float* map_or_null, double* per_image_sum, void* workspace,
                size_t workspace_bytes, void* stream);
 
+/* ---- semantic evaluation (eval/eval_semantic.py:65-152, semantic/components/metrics.py:11-87) -------------------------------
+ * snerf_semeval_accumulate ADDS one chunk of n rays into *acc (device memory, zeroed by the caller before the first chunk):
+ *   pred[n] (int64, the predicted label), gt[n] (the "semantic" target), and the optional targets gt_no_cars[n] and
+ *   gt_non_corrupted[n] (NULL: that term is not accumulated); targets are uint8 (SNERF_SEMEVAL_U8) or int64 (SNERF_SEMEVAL_I64);
+ *   conf[g][p] += rows with gt = g and pred = p, both in [0, n_classes) -- other rows add to out_of_range instead;
+ *   errors[0] += rows with gt != pred, [1] += gt_no_cars != pred, [2] += gt_non_corrupted != pred, [3] += gt_non_corrupted != pred
+ *   and gt_non_corrupted != car_idx (the reference's filter_idx: the car rows count as correct);
+ *   rays += n; car_rays += rows with gt = car_idx (car_idx = -1: no car class);
+ *   weights[n][n_samples], beta[n][n_samples] (fp32, given together or both NULL): beta_car_sum += the sum over the car rays
+ *   of sum_s w_s beta_s, in fp64 (the fp32 products are exact) in a fixed order: one partial per workgroup in the workspace,
+ *   summed by a second launch -- bit-reproducible at a fixed chunking.
+ * The counts are 64-bit integer sums (exact, order-independent); data-parallel ranks combine them by a SUM all-reduce.
+ * Refused: n_classes outside [1, SNERF_SEMEVAL_MAX_CLASSES], car_idx outside [-1, n_classes), n < 0, n_samples < 1 with beta,
+ * a workspace smaller than snerf_semeval_workspace_bytes (needed only with beta). */
+#define SNERF_SEMEVAL_MAX_CLASSES 16
+#define SNERF_SEMEVAL_U8 0
+#define SNERF_SEMEVAL_I64 1
+typedef struct SnerfSemevalAcc {
+  unsigned long long conf[SNERF_SEMEVAL_MAX_CLASSES * SNERF_SEMEVAL_MAX_CLASSES];   /* [gt][pred], row pitch 16 */
+  unsigned long long errors[4];
+  unsigned long long rays, car_rays, out_of_range;
+  double beta_car_sum;
+} SnerfSemevalAcc;
+/* fp64 partials of one call; 0 on bad arguments (n_rays < 0, n_samples < 1) */
+size_t snerf_semeval_workspace_bytes(int n_rays, int n_samples);
+int snerf_semeval_accumulate(const long long* pred, const void* gt, const void* gt_no_cars, const void* gt_non_corrupted,
+                             int label_dtype, int n, int n_classes, int car_idx, const float* weights, const float* beta,
+                             int n_samples, SnerfSemevalAcc* acc, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- measurement hook ----------------------------------------------------------------------------
  * Between snerf_profile_begin and snerf_profile_end every GEMM launch is bracketed by HIP events on the
  * stream it is launched on; _end synchronises those events and returns, per kernel variant, the summed

@@ -90,6 +90,15 @@ class SnerfDsmGrid(C.Structure):
 SSIM_REFLECT = 0    # include/snerf_hip.h SNERF_SSIM_REFLECT
 SSIM_ZERO = 1       # include/snerf_hip.h SNERF_SSIM_ZERO
 
+SEMEVAL_MAX_CLASSES = 16   # include/snerf_hip.h SNERF_SEMEVAL_MAX_CLASSES
+SEMEVAL_U8 = 0             # include/snerf_hip.h SNERF_SEMEVAL_U8
+SEMEVAL_I64 = 1            # include/snerf_hip.h SNERF_SEMEVAL_I64
+
+
+class SnerfSemevalAcc(C.Structure):
+    _fields_ = [("conf", C.c_uint64 * (SEMEVAL_MAX_CLASSES * SEMEVAL_MAX_CLASSES)), ("errors", C.c_uint64 * 4)] + [
+        (n, C.c_uint64) for n in ("rays", "car_rays", "out_of_range")] + [("beta_car_sum", C.c_double)]
+
 
 class SnerfProfile(C.Structure):
     _fields_ = [("ms", C.c_double * 4), ("flops", C.c_double * 4), ("launches", C.c_int64 * 4)]
@@ -186,6 +195,11 @@ def lib():
     L.snerf_ssim.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_double, C.c_double, C.c_double,
                                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                                                        C.c_void_p]
+    L.snerf_semeval_workspace_bytes.restype = C.c_size_t
+    L.snerf_semeval_workspace_bytes.argtypes = [C.c_int, C.c_int]
+    L.snerf_semeval_accumulate.restype = C.c_int
+    L.snerf_semeval_accumulate.argtypes = [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                                              C.c_void_p, C.c_size_t, C.c_void_p]
     L.snerf_profile_begin.restype = C.c_int
     L.snerf_profile_end.restype = C.c_int
     L.snerf_profile_end.argtypes = [C.POINTER(SnerfProfile)]
@@ -206,4 +220,5 @@ EXPORTED_SYMBOLS = ("snerf_version", "snerf_last_error", "snerf_packed_floats", 
                     "snerf_profile_end", "snerf_sample_z", "snerf_adam_step", "snerf_test_bsp_roundtrip", "snerf_test_bsp_kc",
                     "snerf_test_bsp_dw", "snerf_test_set_kc_grid", "snerf_test_set_trunk_fusion", "snerf_embedding_rows", "snerf_embedding_backward",
                     "snerf_dsm_accumulate", "snerf_dsm_finish", "snerf_dsm_downsample2x", "snerf_dsm_workspace_bytes",
-                    "snerf_dsm_ncc_search", "snerf_dsm_shift_diff", "snerf_ssim_workspace_bytes", "snerf_ssim")
+                    "snerf_dsm_ncc_search", "snerf_dsm_shift_diff", "snerf_ssim_workspace_bytes", "snerf_ssim",
+                    "snerf_semeval_workspace_bytes", "snerf_semeval_accumulate")
