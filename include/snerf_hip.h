@@ -346,6 +346,63 @@ int snerf_semeval_accumulate(const long long* pred, const void* gt, const void* 
                              int label_dtype, int n, int n_classes, int car_idx, const float* weights, const float* beta,
                              int n_samples, SnerfSemevalAcc* acc, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- scenes on disk: RPC rays (baseline/components/rays.py satnerf_construct, rpcm RPCModel, framework/util/conversions.py,
+ * baseline/components/normalization.py StandardNormalization) --------------------------------------------------------------
+ * SnerfRpc: rpcm's RPCModel as fp64 (offsets, scales; 20-term numerators / denominators in the RPC00B order
+ * 1, L, P, H, LP, LH, PH, L^2, P^2, H^2, PLH, L^3, LP^2, LH^2, L^2P, P^3, PH^2, L^2H, P^2H, H^3 with L = lon, P = lat, H = alt
+ * (normalised); has_inverse = 1: lat/lon_num/den hold the inverse model, evaluated with (L, P, H) = (ncol, nrow, nalt)).
+ * Localisation: the inverse model when present, else rpcm's iterative inversion (start at lon = lat = -1, neighbours offset by 2
+ * on the first update and 0.1 after; rpcm tests (x0 - col)^2 + (y0 - row)^2 < 1e-18 in normalised image units for ALL points of
+ * a call and updates every point until the last one passes).  Reproduced in two launches: one counts the updates each point
+ * needs and keeps the call's maximum, the next runs every point of the call exactly that many updates.  A point still above
+ * the tolerance where rpcm raises (after 101 updates) is counted as failed; the outputs of such a call are not defined. */
+typedef struct SnerfRpc {
+  double row_offset, col_offset, lat_offset, lon_offset, alt_offset;
+  double row_scale, col_scale, lat_scale, lon_scale, alt_scale;
+  double row_num[20], row_den[20], col_num[20], col_den[20];
+  double lat_num[20], lat_den[20], lon_num[20], lon_den[20];
+  int has_inverse, reserved;
+} SnerfRpc;
+/* one image of a ray-construction launch: rays row0 .. row0 + n_rays - 1 of the output; grid mode needs w * h == n_rays */
+typedef struct SnerfRayImage {
+  SnerfRpc rpc;
+  double min_alt, max_alt;
+  long long row0, n_rays;
+  int w, h;
+} SnerfRayImage;
+/* Rays of every image of a split in one launch.  images_host (host memory) is checked; images_dev is the same table in device
+ * memory.  pixels == NULL: the image's w x h grid, ray i at row = i / w, col = i % w; else (n_rows, 2) fp64 (col, row) per output
+ * row.  Per ray: localise at max_alt and at min_alt, both to custom ECEF (fp64), write the fp32 row
+ * [o = near point (3), d = (far - near) / |far - near| (3), 0, |far - near|] -- un-normalised.  One rpcm call per image and
+ * altitude.  counters[3 * n_images] (int, device, zeroed by the caller): [k] += points of image k whose localisation did not
+ * converge; [n_images + 2k], [n_images + 2k + 1]: the update count of image k at max_alt, min_alt.
+ * Refused without touching the device: null pointers, n_images outside [1, 65535], n_rows < 1, an image with no rays, rows that
+ * are not contiguous in table order, a grid whose w * h overflows or differs from n_rays, min_alt >= max_alt, a zero scale, a
+ * table that does not sum to n_rows. */
+int snerf_rpc_rays(const SnerfRayImage* images_host, const SnerfRayImage* images_dev, int n_images, const double* pixels,
+                   long long n_rows, float* rays, int* counters, void* stream);
+/* rpcm localization of n points as one call (fp64 col, row, alt); normalized = 1 returns normalised lon / lat; counters[2] (int,
+ * device, zeroed by the caller): [0] += failed points, [1]: the call's update count */
+int snerf_rpc_localize(const SnerfRpc* rpc_host, const SnerfRpc* rpc_dev, const double* col, const double* row, const double* alt,
+                       long long n, int normalized, double* lon, double* lat, int* counters, void* stream);
+/* rpcm projection of n points (fp64 lon, lat, alt) to (col, row) */
+int snerf_rpc_project(const SnerfRpc* rpc_host, const SnerfRpc* rpc_dev, const double* lon, const double* lat, const double* alt,
+                      long long n, double* col, double* row, void* stream);
+/* the depth set's keypoint errors (baseline/dataset/satnerf_depth_dataset.py:136-166): ECEF points xyz_ecef (n, 3) fp64 through
+ * ecef_to_latlon_custom and the projection; err[i] = |pts2d[i] - (col, row)| (fp64); col_row (n, 2) may be NULL */
+int snerf_rpc_reprojection_error(const SnerfRpc* rpc_host, const SnerfRpc* rpc_dev, const double* xyz_ecef, const double* pts2d,
+                                 long long n, double* col_row, double* err, void* stream);
+/* Normalisation parameters of a bank set: over the n_arrays (n_rows[a], 8) fp32 ray arrays (rays and n_rows are HOST arrays of
+ * device pointers / counts), per axis the min and max of every origin and every fp32 far point o + far * d (two roundings).
+ * out[13] (fp32, device): min[3], max[3], scale[3] = (max - min) / 2, offset[3] = min + scale, range = max(scale).  Exact and
+ * independent of the grid (min / max commute).  workspace: snerf_ray_bounds_workspace_bytes (0 on bad arguments). */
+size_t snerf_ray_bounds_workspace_bytes(const long long* n_rows, int n_arrays);
+int snerf_ray_bounds(const float* const* rays, const long long* n_rows, int n_arrays, float* out, void* workspace,
+                     size_t workspace_bytes, void* stream);
+/* In place, fp32, correctly rounded: row[0..2] = (row[0..2] - c) / range and, with bounds = 1, row[6] /= range, row[7] /= range.
+ * center_range (device): c[3], range -- out + 9 of snerf_ray_bounds.  stride >= 8 with bounds, >= 3 without. */
+int snerf_normalize_rows(float* rows, long long n, int stride, int bounds, const float* center_range, void* stream);
+
 /* ---- measurement hook ----------------------------------------------------------------------------
  * Between snerf_profile_begin and snerf_profile_end every GEMM launch is bracketed by HIP events on the
  * stream it is launched on; _end synchronises those events and returns, per kernel variant, the summed

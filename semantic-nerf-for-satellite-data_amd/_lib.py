@@ -100,6 +100,18 @@ class SnerfSemevalAcc(C.Structure):
         (n, C.c_uint64) for n in ("rays", "car_rays", "out_of_range")] + [("beta_car_sum", C.c_double)]
 
 
+class SnerfRpc(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("row_offset", "col_offset", "lat_offset", "lon_offset", "alt_offset", "row_scale",
+                                          "col_scale", "lat_scale", "lon_scale", "alt_scale")] + [
+        (n, C.c_double * 20) for n in ("row_num", "row_den", "col_num", "col_den", "lat_num", "lat_den", "lon_num", "lon_den")] + [
+        ("has_inverse", C.c_int), ("reserved", C.c_int)]
+
+
+class SnerfRayImage(C.Structure):
+    _fields_ = [("rpc", SnerfRpc), ("min_alt", C.c_double), ("max_alt", C.c_double), ("row0", C.c_longlong),
+                ("n_rays", C.c_longlong), ("w", C.c_int), ("h", C.c_int)]
+
+
 class SnerfProfile(C.Structure):
     _fields_ = [("ms", C.c_double * 4), ("flops", C.c_double * 4), ("launches", C.c_int64 * 4)]
 
@@ -200,6 +212,20 @@ def lib():
     L.snerf_semeval_accumulate.restype = C.c_int
     L.snerf_semeval_accumulate.argtypes = [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                                                               C.c_void_p, C.c_size_t, C.c_void_p]
+    L.snerf_rpc_rays.restype = C.c_int
+    L.snerf_rpc_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.snerf_rpc_localize.restype = C.c_int
+    L.snerf_rpc_localize.argtypes = [C.c_void_p] * 5 + [C.c_longlong, C.c_int] + [C.c_void_p] * 4
+    L.snerf_rpc_project.restype = C.c_int
+    L.snerf_rpc_project.argtypes = [C.c_void_p] * 5 + [C.c_longlong] + [C.c_void_p] * 3
+    L.snerf_rpc_reprojection_error.restype = C.c_int
+    L.snerf_rpc_reprojection_error.argtypes = [C.c_void_p] * 4 + [C.c_longlong] + [C.c_void_p] * 3
+    L.snerf_ray_bounds_workspace_bytes.restype = C.c_size_t
+    L.snerf_ray_bounds_workspace_bytes.argtypes = [C.c_void_p, C.c_int]
+    L.snerf_ray_bounds.restype = C.c_int
+    L.snerf_ray_bounds.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.snerf_normalize_rows.restype = C.c_int
+    L.snerf_normalize_rows.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.snerf_profile_begin.restype = C.c_int
     L.snerf_profile_end.restype = C.c_int
     L.snerf_profile_end.argtypes = [C.POINTER(SnerfProfile)]
@@ -221,4 +247,6 @@ EXPORTED_SYMBOLS = ("snerf_version", "snerf_last_error", "snerf_packed_floats", 
                     "snerf_test_bsp_dw", "snerf_test_set_kc_grid", "snerf_test_set_trunk_fusion", "snerf_embedding_rows", "snerf_embedding_backward",
                     "snerf_dsm_accumulate", "snerf_dsm_finish", "snerf_dsm_downsample2x", "snerf_dsm_workspace_bytes",
                     "snerf_dsm_ncc_search", "snerf_dsm_shift_diff", "snerf_ssim_workspace_bytes", "snerf_ssim",
-                    "snerf_semeval_workspace_bytes", "snerf_semeval_accumulate")
+                    "snerf_semeval_workspace_bytes", "snerf_semeval_accumulate", "snerf_rpc_rays", "snerf_rpc_localize",
+                    "snerf_rpc_project", "snerf_rpc_reprojection_error", "snerf_ray_bounds_workspace_bytes", "snerf_ray_bounds",
+                    "snerf_normalize_rows")

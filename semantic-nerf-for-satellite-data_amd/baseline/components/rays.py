@@ -1,0 +1,74 @@
+"""Ray construction of the scene loaders -- mirror of baseline/components/rays.py.  satnerf_construct builds the rays of
+every image of a split in ONE launch of csrc/satrays.hip (snerf_rpc_rays): per pixel, rpcm localisation at max_alt and at
+min_alt, custom ECEF in fp64, and the un-normalised fp32 row [o(3), d(3), near = 0, far] that the reference returns after
+`.type(FloatTensor)`."""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from ... import _lib
+from .camera_models import RPCModel, struct_to_device
+
+
+def construct_sun_dir(sun_elevation_deg: float, sun_azimuth_deg: float, n_rays: int) -> torch.Tensor:
+    """(n_rays, 3) fp32 unit sun direction (east, north, up components), evaluated in fp64 and rounded once"""
+    el, az = np.deg2rad(np.array([sun_elevation_deg, sun_azimuth_deg], dtype=np.float64))
+    horizontal = np.cos(el)
+    unit = np.array([np.sin(az) * horizontal, np.cos(az) * horizontal, np.sin(el)], dtype=np.float64).astype(np.float32)
+    return torch.from_numpy(unit).reshape(1, 3).expand(n_rays, 3).contiguous()
+
+
+class LocalizationError(RuntimeError):
+    """rpcm's MaxLocalizationIterationsError: a pixel of the named image did not converge in 100 iterations"""
+
+
+def satnerf_construct(cameras, min_alts, max_alts, sizes=None, pixels=None, names=None, device=None, check=True):
+    """Rays of several images, concatenated in order, as one (R, 8) fp32 tensor on `device`.
+    cameras: RPCModel per image; sizes: (w, h) per image (grid: ray i at row = i // w, col = i % w, the reference's
+    np.meshgrid(arange(w), arange(h)) flattened) -- or pixels: one (n_k, 2) fp64 (col, row) array per image (keypoints).
+    check: read back the per-image count of points that did not converge and raise LocalizationError naming the image
+    (the one host synchronisation; check=False returns (rays, counters) and leaves the read to the caller: raise_on_failures)."""
+    n_img = len(cameras)
+    if n_img == 0:
+        raise ValueError("satnerf_construct: no image")
+    if (sizes is None) == (pixels is None):
+        raise ValueError("satnerf_construct: pass either sizes (pixel grids) or pixels (explicit coordinates)")
+    device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    table = (_lib.SnerfRayImage * n_img)()
+    row0 = 0
+    pix = None
+    if pixels is not None:
+        pix = torch.from_numpy(np.concatenate([np.asarray(p, np.float64).reshape(-1, 2) for p in pixels], 0)).to(device)
+    for k, cam in enumerate(cameras):
+        e = table[k]
+        e.rpc = cam.struct if isinstance(cam, RPCModel) else cam
+        e.min_alt, e.max_alt = float(min_alts[k]), float(max_alts[k])
+        if sizes is not None:
+            w, h = int(sizes[k][0]), int(sizes[k][1])
+            e.w, e.h, n = w, h, w * h
+        else:
+            n = int(np.asarray(pixels[k]).reshape(-1, 2).shape[0])
+        e.row0, e.n_rays = row0, n
+        row0 += n
+    rays = torch.empty((row0, 8), dtype=torch.float32, device=device)
+    fails = torch.zeros(3 * n_img, dtype=torch.int32, device=device)     # failures per image, then update counts
+    dev_table = struct_to_device(table, device)
+    st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    _lib.check(_lib.lib().snerf_rpc_rays(C.byref(table), C.c_void_p(dev_table.data_ptr()), n_img,
+                                         C.c_void_p(pix.data_ptr()) if pix is not None else None, row0,
+                                         C.c_void_p(rays.data_ptr()), C.c_void_p(fails.data_ptr()), st), "snerf_rpc_rays")
+    if not check:
+        return rays, fails
+    raise_on_failures(fails, names)
+    return rays
+
+
+def raise_on_failures(fails: torch.Tensor, names=None):
+    f = fails.cpu().numpy()[: len(fails) // 3]
+    bad = np.nonzero(f)[0]
+    if len(bad):
+        k = int(bad[0])
+        who = names[k] if names is not None else f"#{k}"
+        raise LocalizationError(f"image {who}: {int(f[k])} pixels did not converge in 100 RPC localisation iterations "
+                                "(rpcm: MaxLocalizationIterationsError)")

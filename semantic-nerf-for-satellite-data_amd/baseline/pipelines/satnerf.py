@@ -61,8 +61,14 @@ class SatNeRFPipeline(BaseRayPipeline):
     def _n_classes(self):
         return 5
 
+    _semantic_scene = False     # which loader reads a scene from disk (RSSemanticPipeline: the semantic one)
+
     def _init_datasets(self) -> dict:
         r = self.cfgs.run
+        if r.dataset_dp:
+            from ..dataset.satnerf_dataset import load_scene_banks
+            return load_scene_banks(self.cfgs, semantic=self._semantic_scene, depth=bool(self.cfgs.pipeline.depth_enabled),
+                                    seed=r.synthetic_seed)
         d = {"rgb": GpuRayBank.synthetic(r.synthetic_rays, r.synthetic_images, self._n_classes(), r.synthetic_seed),
              "rgb_test": GpuRayBank.synthetic(4096, r.synthetic_images, self._n_classes(), r.synthetic_seed + 1)}
         if self.cfgs.pipeline.depth_enabled:

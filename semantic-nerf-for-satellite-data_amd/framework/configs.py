@@ -34,6 +34,7 @@ class RunConfig(BaseModel):
     cache_dp: Optional[str] = None
     datasets_dp: Optional[str] = None
     run_dp: Optional[str] = None
+    dataset_dp: Optional[str] = None   # a scene in the reference's on-disk layout (root.json, metas, GeoTIFFs); unset: synthetic banks
     # --- additions of this build (synthetic GPU-resident ray bank; no DFC2019 data in this environment)
     synthetic_rays: int = 1 << 20
     synthetic_images: int = 19

@@ -21,15 +21,21 @@ def shard_bounds(n: int, rank: int, world: int):
 
 
 class GpuRayBank:
-    def __init__(self, tensors: dict, n_classes: int = 5, car_cls_idx: int = 4, seed: int = 0, device=None, image_sizes=None):
+    def __init__(self, tensors: dict, n_classes: int = 5, car_cls_idx: int = 4, seed: int = 0, device=None, image_sizes=None,
+                 image_wh=None):
         """`image_sizes`: H*W of every image of a test bank, in row order (the reference's test DataLoader hands over one image
-        per step, framework/pipelines.py:120-129); without it `image()` cuts equal synthetic slices."""
+        per step, framework/pipelines.py:120-129); without it `image()` cuts equal synthetic slices.  `image_wh`: (W, H) of
+        every image (a scene loaded from disk): `image()` then also hands over the image's "w" / "h", as the reference's
+        test items carry them."""
         self.t = {k: (v.to(device) if device is not None else v) for k, v in tensors.items()}
         self.image_sizes = [int(x) for x in image_sizes] if image_sizes is not None else None
         if self.image_sizes is not None:
             if sum(self.image_sizes) != int(self.t["rays"].shape[0]) or min(self.image_sizes) <= 0:
                 raise ValueError("image_sizes must be positive and sum to the number of rays in the bank")
             self._image_lo = np.concatenate([[0], np.cumsum(self.image_sizes)]).astype(np.int64)
+        self.image_wh = [(int(w), int(h)) for w, h in image_wh] if image_wh is not None else None
+        if self.image_wh is not None and (self.image_sizes is None or [w * h for w, h in self.image_wh] != self.image_sizes):
+            raise ValueError("image_wh needs image_sizes with w * h rays per image")
         self.semantic_n_classes = n_classes
         self.car_cls_idx = car_cls_idx
         self.seed = seed
@@ -94,7 +100,10 @@ class GpuRayBank:
         a, b = min(lo + rank * per, hi), min(lo + (rank + 1) * per, hi)
         if (hi - lo) <= (world - 1) * per:
             raise ValueError(f"validation image {i} has {hi - lo} rays: too few to give each of {world} ranks a slice")
-        return {k: v[a:b] for k, v in self.t.items()}
+        out = {k: v[a:b] for k, v in self.t.items()}
+        if self.image_wh is not None and rays_per_image is None:
+            out["w"], out["h"] = self.image_wh[i]
+        return out
 
     def steps_per_epoch(self, global_batch: int) -> int:
         return max(1, len(self) // global_batch)

@@ -222,8 +222,8 @@ class TrainLoop:
         validation_step could know; absent when there is none."""
         pl = self.pipeline
         bank = pl.datasets["rgb_test"]
-        # NOTE: the package's only bank factory is the synthetic one (GpuRayBank.synthetic, no image sizes), so from the product's
-        # own data path the means below are per-SLICE means; a loader of real data passes `image_sizes` to GpuRayBank.
+        # NOTE: a scene loaded from disk (run.dataset_dp, baseline/dataset/satnerf_dataset.py) gives the test bank `image_sizes`
+        # and `image_wh`; the synthetic banks (GpuRayBank.synthetic) carry neither, and their means are per-SLICE means.
         # images: the bank's own per-image ray counts where it carries them (real data: the reference's per-image means,
         # framework/pipelines.py:120-129, eval_semantic.py:63-77); else equal slices of `rays_per_image` rows -- a SYNTHETIC
         # definition of "image" (the means are then per-slice means)

@@ -28,6 +28,8 @@ class RSSemanticConfig(SatNeRFConfig):
 
 
 class RSSemanticPipeline(SatNeRFPipeline):
+    _semantic_scene = True
+
     def __init__(self, cfgs, ckpt_info=None):
         super().__init__(cfgs, ckpt_info)
         if cfgs.pipeline.use_tj_instead_of_beta:
@@ -36,6 +38,10 @@ class RSSemanticPipeline(SatNeRFPipeline):
     def _init_loss(self):
         super()._init_loss()
         pc, car = self.cfgs.pipeline, self.datasets["rgb"].car_cls_idx
+        if car is None:
+            # the semantic losses (ignore index, car regulariser) and validation's uncertainty at the transient class all
+            # index the car class; a scene without one is refused rather than trained with a made-up index
+            raise ValueError("the scene's semantic_cls_labels have no 'cars' label: the semantic pipeline needs a car class")
         self.semantic_loss = SemanticLoss(pc.lambda_s, car, ignore_car_index=pc.ignore_car_index)
         self.uncertainty_semantic_loss = SemanticUncertaintyLoss(pc.lambda_s, car, detach_beta_for_s=pc.detach_beta_for_s,
                                                                  ignore_car_index=pc.ignore_car_index)
