@@ -1,5 +1,5 @@
-// C-ABI of libsnerf_hip.so (include/snerf_hip.h): layout plan, parameter packing and the
-// forward / backward launch sequences of one rendering pass.
+// C-ABI of libsnerf_hip.so (include/snerf_hip.h): layout plan, parameter packing and the entry points of one rendering
+// pass (its launch sequences: bsp_pass.hip; the single-kernel test hooks: test_hooks.hip).
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -16,7 +16,6 @@ namespace snerf {
 int forward_bsp(const Plan& p, const float* pk, const SnerfInputs* in, const SnerfOutputs* out, void* workspace, hipStream_t st);
 int backward_bsp(const Plan& p, const float* pk, const SnerfInputs* in, const SnerfOutGrads* go, float* gp, float* d_t, float* d_t_s,
                  void* workspace, hipStream_t st);
-void build_wjobs(const Plan& p, bsp::WPackTable& tb);
 
 static thread_local char g_err[512] = "";
 void set_error(const char* fmt, ...) {
@@ -46,53 +45,68 @@ DwSplit dw_choose_bsp(int P, int rows, int cols, bool narrow_rows) {
 }
 
 // ---- block-scaled plane layout: weight operand packs + workspace -------------------------------------------
-static void plan_bsp(Plan& p) {
-  // weight operands: every K-contiguous GEMM's B, as a WF16 pack behind the fp32 region (csrc/bsp.h)
+// Weight operands: every K-contiguous GEMM's B as a WF16 pack behind the fp32 region (csrc/bsp.h).  Each operand is named ONCE here:
+// its fp32 master [m_rows][m_cols] at float offset src (leading dimension ld), read as it lies or transposed.  The pack kernels
+// (snerf_pack_params) and the launches (bsp_pass.hip: weights) both read this table.  A matrix and its transposes share exponent slot e.
+static void plan_weights(Plan& p) {
   size_t off = 0;
-  int n = 0, ne = 0;
-  auto job = [&](int rows, int K, int e) {
-    p.wj_off[n] = off; p.wj_rows[n] = rows; p.wj_K[n] = K; p.wj_e[n] = e;
-    off += bsp::wp16_bytes(rows, K, p.pl);
-    return n++;
+  int ne = 0;
+  p.wj.n = 0;
+  auto op = [&](int e, size_t src, int ld, int m_rows, int m_cols, int transposed = 0) {
+    bsp::WPackJob& w = p.wj.j[p.wj.n];
+    w.src_off = src; w.src_ld = ld; w.transposed = transposed; w.m_rows = m_rows; w.m_cols = m_cols;
+    w.rows = transposed ? m_cols : m_rows; w.K = transposed ? m_rows : m_cols;    // operand(r, k) = master(k, r) when transposed
+    w.dst_off = off; w.e_idx = e;
+    off += bsp::wp16_bytes(w.rows, w.K, p.pl);
+    return p.wj.n++;
   };
-  for (int i = 0; i < p.L; ++i) {
+  const int W = p.W, H = p.H;
+  for (int i = 0; i < p.L; ++i) {   // the transpose of a skip layer [gamma | h]: its h columns only (dX of the layer below)
     const int e = ne++;
-    p.wj_tr[i] = job(p.W, p.k_tr[i], e);
-    p.wj_tt[i] = i > 0 ? job(p.W, p.W, e) : -1;
+    p.wj_tr[i] = op(e, p.w_tr[i], p.k_tr[i], W, p.k_tr[i]);
+    p.wj_tt[i] = i > 0 ? op(e, p.w_tr[i] + (((p.skip_mask >> i) & 1u) ? p.Ep : 0), p.k_tr[i], W, W, 1) : -1;
   }
-  { const int e = ne++; p.wj_fs = job(p.W, p.W, e); p.wj_sig = job(NARROW, p.W, e); p.wj_tfs = job(p.W, p.W + NARROW, e); }
-  { const int e = ne++; p.wj_h1 = job(p.N1, p.FA, e); p.wj_th1 = job(p.FA, p.N1, e); }
-  { const int e = ne++; p.wj_s2 = job(p.H, p.H, e); p.wj_ts2 = job(p.H, p.H, e); }
-  { const int e = ne++; p.wj_s3 = job(p.H, p.H, e); p.wj_ts3 = job(p.H, p.H, e); }
-  { const int e = ne++; p.wj_s4 = job(NARROW, p.H, e); p.wj_ts4 = job(p.H, NARROW, e); }
-  { const int e = ne++; p.wj_fin = job(NARROW, p.KF, e); p.wj_tfin = job(p.KF, NARROW, e); }
-  p.n_wjobs = n;
+  { const int e = ne++; p.wj_fs = op(e, p.w_fs, W, W, W); p.wj_sig = op(e, p.w_fs + (size_t)W * W, W, NARROW, W); p.wj_tfs = op(e, p.w_fs, W, W + NARROW, W, 1); }
+  { const int e = ne++; p.wj_h1 = op(e, p.w_h1, p.FA, p.N1, p.FA); p.wj_th1 = op(e, p.w_h1, p.FA, p.N1, p.FA, 1); }
+  { const int e = ne++; p.wj_s2 = op(e, p.w_s2, H, H, H); p.wj_ts2 = op(e, p.w_s2, H, H, H, 1); }
+  { const int e = ne++; p.wj_s3 = op(e, p.w_s3, H, H, H); p.wj_ts3 = op(e, p.w_s3, H, H, H, 1); }
+  { const int e = ne++; p.wj_s4 = op(e, p.w_s4, H, NARROW, H); p.wj_ts4 = op(e, p.w_s4, H, NARROW, H, 1); }
+  { const int e = ne++; p.wj_fin = op(e, p.w_fin, p.KF, NARROW, p.KF); p.wj_tfin = op(e, p.w_fin, p.KF, NARROW, p.KF, 1); }
   p.wp_bytes = round_up_sz(off, 256);
-  p.packed_floats = p.n_fp32 + (p.wp_bytes + 2 * Plan::WJ_MAX * 4 + 256) / 4;
+  p.packed_floats = p.n_fp32 + (p.wp_bytes + 2 * bsp::WPACK_MAX * 4 + 256) / 4;
+}
 
+static void plan_bsp(Plan& p) {
   // workspace: activations as planes (4 bytes per element, like fp32; 2 with one plane) + exponent tables + sign words
   size_t wo = 0;
   auto wtake = [&](size_t bytes) { size_t o = wo; wo += round_up_sz(bytes, 256); return o; };
   const size_t Pp = p.Pp;
   auto planes = [&](int ld) { return wtake(bsp::plane_bytes(Pp, ld, p.pl)); };
   auto etab = [&](int ld) { return wtake(bsp::etab_ints(Pp, ld) * 4); };
-  auto signs = [&](int ld) { return wtake(bsp::sign_words(Pp, ld) * 4); };
+  // one plane tensor [Pp][ld]: planes, exponent table, sign words (SIREN training passes keep them for the activations)
+  auto tensor = [&](int ld, bool sign = false) {
+    PlaneT t;
+    t.o = planes(ld); t.e = etab(ld); t.s = sign ? wtake(bsp::sign_words(Pp, ld) * 4) : 0; t.ld = ld;
+    return t;
+  };
   const bool keep_c = p.train && p.siren;
   p.h1w = p.sc ? p.H : p.N1;
   p.o_z = wtake(((size_t)p.P + 4) * 4);
   p.o_T = wtake((size_t)p.P * 4);
   p.o_rgbraw = wtake((size_t)p.N * 3 * 4);
-  p.o_pe = planes(p.Ep); p.e_pe = etab(p.Ep);
+  p.pe = tensor(p.Ep);
   if (p.train) {
-    for (int i = 0; i < p.L; ++i) { p.o_h[i] = planes(p.W); p.e_h[i] = etab(p.W); p.o_c[i] = keep_c ? signs(p.W) : 0; }
-  } else {
-    const size_t a = planes(p.W), b = planes(p.W), ea = etab(p.W), eb = etab(p.W);
-    for (int i = 0; i < p.L; ++i) { p.o_h[i] = (i & 1) ? b : a; p.e_h[i] = (i & 1) ? eb : ea; p.o_c[i] = 0; }
+    for (int i = 0; i < p.L; ++i) p.h[i] = tensor(p.W, keep_c);
+  } else {   // inference keeps no layer: two buffers in turn
+    PlaneT a, b;
+    a.ld = b.ld = p.W;
+    a.o = planes(p.W); b.o = planes(p.W); a.e = etab(p.W); b.e = etab(p.W);
+    for (int i = 0; i < p.L; ++i) p.h[i] = (i & 1) ? b : a;
   }
-  p.o_fa = planes(p.FA); p.e_fa = etab(p.FA);
-  p.o_h1 = planes(p.h1w); p.e_h1 = etab(p.h1w); p.o_c1 = keep_c ? signs(p.h1w) : 0;
-  p.o_s2 = planes(p.H); p.e_s2 = etab(p.H); p.o_cs2 = keep_c ? signs(p.H) : 0;
-  p.o_s3 = planes(p.H); p.e_s3 = etab(p.H); p.o_cs3 = keep_c ? signs(p.H) : 0;
+  p.fa = tensor(p.FA);
+  p.h1 = tensor(p.h1w, keep_c);
+  p.s2 = tensor(p.H, keep_c);
+  p.s3 = tensor(p.H, keep_c);
   // the narrow projections: folded into the producing SIREN launch's epilogue where its width is whole 256-column tiles (partial sums
   // per wave, summed by the composite), otherwise a 32-wide fp32 buffer written by a launch of their own
   p.nd_sig = p.siren && p.W % 256 == 0 && p.W <= 1024;
@@ -108,19 +122,19 @@ static void plan_bsp(Plan& p) {
   if (p.nd_sun) p.o_sunpart = wtake((size_t)4 * (p.H / 256) * Pp * 4); else p.o_suno = wtake(Pp * NARROW * 4);
   if (p.nd_fin) p.o_finpart = wtake((size_t)4 * (p.KF / 256) * ND_FIN * Pp * 4); else if (!p.sc) p.o_fino = wtake(Pp * NARROW * 4);
   p.o_kcq = wtake((size_t)KCQ_SLOTS * 64);
-  p.maxw = p.W > p.FA ? p.W : p.FA;
-  if (p.h1w > p.maxw) p.maxw = p.h1w;
-  p.nrb = (p.P + 31) / 32;
   p.comp_blocks = composite_bwd_blocks(p.N);
   if (p.train) {
-    p.o_dza = planes(p.maxw); p.e_dza = etab(p.maxw);
-    p.o_dzb = planes(p.maxw); p.e_dzb = etab(p.maxw);
-    p.o_dsa = planes(p.H); p.e_dsa = etab(p.H);
-    p.o_dsb = planes(p.H); p.e_dsb = etab(p.H);
+    int maxw = p.W > p.FA ? p.W : p.FA;   // widest gradient tensor: dza / dzb hold [h1w], [W] and [FA] ones in turn
+    if (p.h1w > maxw) maxw = p.h1w;
+    auto scratch = [&](int w) { PlaneScratch t; t.o = planes(w); t.e = etab(w); t.maxw = w; return t; };
+    p.dza = scratch(maxw);
+    p.dzb = scratch(maxw);
+    p.dsa = tensor(p.H);
+    p.dsb = tensor(p.H);
     p.o_dsig = wtake(Pp * NARROW * 4); p.o_dfin = wtake(Pp * NARROW * 4); p.o_dsun = wtake(Pp * NARROW * 4);
-    p.o_pdsig = planes(NARROW); p.e_dsig = etab(NARROW);
-    p.o_pdfin = planes(NARROW); p.e_dfin = etab(NARROW);
-    p.o_pdsun = planes(NARROW); p.e_dsun = etab(NARROW);
+    p.pdsig = tensor(NARROW);
+    p.pdfin = tensor(NARROW);
+    p.pdsun = tensor(NARROW);
     p.rq_floats = bsp_rq_floats(p);
     p.o_rq = wtake(p.rq_floats * 4);
     p.o_skyslab = wtake((size_t)p.comp_blocks * 4 * p.sky_floats * 4);
@@ -198,6 +212,7 @@ int make_plan(const SnerfDesc* d, Plan* pl) {
   p.sky_floats = 9 * p.H + 4;
   p.sky = take(p.sky_floats);
   p.n_fp32 = off;
+  plan_weights(p);
   plan_bsp(p);
   return SNERF_OK;
 }
@@ -266,8 +281,6 @@ static void build_tables(const Plan& p, const SnerfParams* w, TableBuilder& tb) 
   tb.add(w->sky_b2, 3, 1, 3, p.sky + 9 * (size_t)H, 3);
 }
 
-#define RC(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
-
 static int check_inputs(const Plan& p, const SnerfInputs* in) {
   if (!in) { set_error("null inputs"); return SNERF_ERR_NULL; }
   if (!in->sun_d || in->sun_stride < 3) { set_error("sun_d (N,3) with stride >= 3 is required"); return SNERF_ERR_NULL; }
@@ -286,16 +299,6 @@ static int check_inputs(const Plan& p, const SnerfInputs* in) {
 
 // =====================================================================================================
 using namespace snerf;
-
-namespace {
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  int alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16) == hipSuccess ? 0 : 1; }
-  template <class T> T* as() const { return reinterpret_cast<T*>(p); }
-};
-#define TALLOC(buf, bytes) do { if ((buf).alloc(bytes)) { set_error("test hook: hipMalloc failed"); return SNERF_ERR_HIP; } } while (0)
-}  // namespace
 
 extern "C" {
 
@@ -332,11 +335,9 @@ int snerf_pack_params(const SnerfDesc* desc, const SnerfParams* params, float* p
   for (int i = 0; i < tb.nt; ++i) RC(launch_copy_table(tb.tabs[i], packed, 0, st));
   // every weight operand (matrix or its transpose) as a fragment-ordered fp16-plane pack with one exponent per matrix -- two
   // launches over a job table (|max| pass, pack pass)
-  bsp::WPackTable wt;
-  build_wjobs(p, wt);
   char* planes = reinterpret_cast<char*>(packed + p.n_fp32);
   int* exps = reinterpret_cast<int*>(planes + p.wp_bytes);
-  return bsp::launch_wpack(wt, packed, planes, exps, reinterpret_cast<unsigned*>(exps + Plan::WJ_MAX), p.pl, st);
+  return bsp::launch_wpack(p.wj, packed, planes, exps, reinterpret_cast<unsigned*>(exps + bsp::WPACK_MAX), p.pl, st);
 }
 
 int snerf_unpack_grads(const SnerfDesc* desc, const float* packed_grads, const SnerfParams* grads, int accumulate,
@@ -392,114 +393,5 @@ int snerf_embedding_backward(const long long* idx, const float* d_rows, int n, i
 
 int snerf_profile_begin(void) { return profile_begin(); }
 int snerf_profile_end(SnerfProfile* out) { return profile_end(out); }
-
-// ---- test hooks of the block-scaled plane kernels (tests/test_gpu_bsp.py): fp32 in / fp32 out around ONE launch of the
-// kernel under test; the conversions run through the library's own to_planes / from_planes / weight pack.  Synchronous,
-// allocating -- never on the product path.
-
-int snerf_test_bsp_roundtrip(const float* src, int rows, int cols, int ld, int col0, float* dst, int* exps_out, int planes, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  DevBuf pl, E;
-  const size_t rp = round_up_sz(rows, 128);
-  TALLOC(pl, bsp::plane_bytes(rp, ld, planes)); TALLOC(E, bsp::etab_ints(rp, ld) * 4);
-  SNERF_HIP_CHECK(hipMemsetAsync(E.p, 0, bsp::etab_ints(rp, ld) * 4, st));
-  RC(bsp::launch_to_planes(src, cols, rows, cols, pl.as<char>(), E.as<int>(), ld, col0, planes, st));
-  RC(bsp::launch_from_planes(pl.as<char>(), E.as<int>(), ld, col0, rows, cols, dst, cols, planes, st));
-  if (exps_out) SNERF_HIP_CHECK(hipMemcpyAsync(exps_out, E.p, bsp::etab_ints(rp, ld) * 4, hipMemcpyDeviceToDevice, st));
-  SNERF_HIP_CHECK(hipStreamSynchronize(st));
-  return SNERF_OK;
-}
-
-// persistent grid of the K-contiguous launches: n workgroups instead of two per CU (0: default) -- small test problems then walk
-// several tiles per workgroup and draw them from the tile counters
-int snerf_test_set_kc_grid(int n) { bsp::kc_set_grid_override(n); bsp::trunk_set_grid_override(n); return SNERF_OK; }
-// 0: every pass takes the launch-per-layer path (the fused trunk of bsp_trunk.hip is compared with it bit for bit); 1: default
-int snerf_test_set_trunk_fusion(int on) { bsp::trunk_set_fusion(on); return SNERF_OK; }
-
-// C[I][J] = epilogue(A[I][Ka] | A2[I][K-Ka]) . W[J][K]^T).  The A tensors are placed at column a_col0 of wider plane
-// tensors and the output at column c_col0 (exercises the column-offset / exponent-block arithmetic).
-int snerf_test_bsp_kc(const float* A, const float* A2, int Ka, const float* W, const float* bias, int I, int J, int K, int a_col0,
-                      int c_col0, int act, float w0, int aux_mode, const float* Hact, const unsigned* Hsign, float* C,
-                      unsigned* Csign, float* colsum, const float* nd_w, float* nd_out, const int* nd_rows, int narrow, int planes, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (K % 16 || Ka % 16 || Ka <= 0 || Ka > K) { set_error("test_bsp_kc: K, Ka % 16"); return SNERF_ERR_BAD_DESC; }
-  if (planes != 1 && planes != 2) { set_error("test_bsp_kc: planes"); return SNERF_ERR_BAD_DESC; }
-  const int pl = planes;
-  const size_t rp = round_up_sz(I, 128);
-  const int lda = a_col0 + Ka, lda2 = K > Ka ? K - Ka : 16, ldc = c_col0 + round_up(J, 16);
-  DevBuf pa, ea, pa2, ea2, wp, we, wm, pc, ec, ph, eh;
-  // (+ 64 pad columns: a one-plane launch whose K is an odd multiple of 16 reads -- against zero weights -- up to 16 columns
-  //  beyond K; in the passes those are the next row's columns, here they must not be uninitialised memory)
-  TALLOC(pa, bsp::plane_bytes(rp + 1, lda, pl)); TALLOC(ea, bsp::etab_ints(rp, lda) * 4);
-  TALLOC(pa2, bsp::plane_bytes(rp + 1, lda2, pl)); TALLOC(ea2, bsp::etab_ints(rp, lda2) * 4);
-  SNERF_HIP_CHECK(hipMemsetAsync(pa.p, 0, bsp::plane_bytes(rp + 1, lda, pl), st));
-  SNERF_HIP_CHECK(hipMemsetAsync(pa2.p, 0, bsp::plane_bytes(rp + 1, lda2, pl), st));
-  RC(bsp::launch_to_planes(A, Ka, I, Ka, pa.as<char>(), ea.as<int>(), lda, a_col0 & ~127, pl, st));
-  if (a_col0 & 127) { set_error("test_bsp_kc: a_col0 % 128"); return SNERF_ERR_BAD_DESC; }
-  if (K > Ka) RC(bsp::launch_to_planes(A2, K - Ka, I, K - Ka, pa2.as<char>(), ea2.as<int>(), lda2, 0, pl, st));
-  bsp::WPackTable tb; tb.n = 1;
-  tb.j[0] = bsp::WPackJob{0ull, K, J, K, 0, 0ull, 0, J, K};
-  TALLOC(wp, bsp::wp16_bytes(J, K, pl)); TALLOC(we, bsp::WPACK_MAX * 4); TALLOC(wm, bsp::WPACK_MAX * 4);
-  RC(bsp::launch_wpack(tb, W, wp.as<char>(), we.as<int>(), wm.as<unsigned>(), pl, st));
-  bsp::KcArgs g;
-  g.pl = pl;
-  g.A = pa.as<char>(); g.EA = ea.as<int>(); g.lda = lda; g.a_col0 = a_col0; g.Ka = Ka;
-  if (K > Ka) { g.A2 = pa2.as<char>(); g.EA2 = ea2.as<int>(); g.lda2 = lda2; g.a2_col0 = 0; }
-  g.W = wp.as<char>(); g.EW = we.as<int>(); g.w_rb32 = (J + 31) / 32; g.w_bytes = (unsigned)bsp::wp16_bytes(J, K, pl);
-  g.I = I; g.J = J; g.K = K; g.bias = bias; g.act = act; g.w0 = w0;
-  if (narrow) {
-    g.Cf = C;
-    RC(bsp::launch_kc_narrow(g, st));
-    SNERF_HIP_CHECK(hipStreamSynchronize(st));
-    return SNERF_OK;
-  }
-  TALLOC(pc, bsp::plane_bytes(rp, ldc, pl)); TALLOC(ec, bsp::etab_ints(rp, ldc) * 4);
-  g.C = pc.as<char>(); g.EC = ec.as<int>(); g.ldc = ldc; g.c_col0 = c_col0; g.Csign = Csign;
-  if (aux_mode != AUX_NONE) {
-    TALLOC(ph, bsp::plane_bytes(rp, ldc, pl)); TALLOC(eh, bsp::etab_ints(rp, ldc) * 4);
-    RC(bsp::launch_to_planes(Hact, J, I, J, ph.as<char>(), eh.as<int>(), ldc, c_col0, pl, st));
-    g.aux_mode = aux_mode; g.H = ph.as<char>(); g.EH = eh.as<int>(); g.ldh = ldc; g.h_col0 = c_col0; g.Hsign = Hsign;
-  }
-  g.colsum = colsum; g.ldcs = J;
-  g.nd_w = nd_w; g.nd_out = nd_out; g.nd_stride = (unsigned long long)I;
-  if (nd_w && nd_rows) {   // several projections per column tile: nd_w [sum rows][J], tile tj's rows follow tile tj - 1's
-    g.nd_omax = ND_FIN; g.nd_ldw = J;
-    for (int tj = 0, r = 0; tj < (J + 255) / 256 && tj < 8; ++tj) { g.nd_rows[tj] = nd_rows[tj]; g.nd_row0[tj] = r; r += nd_rows[tj]; }
-  }
-  DevBuf ctr; TALLOC(ctr, 64);
-  SNERF_HIP_CHECK(hipMemsetAsync(ctr.p, 0, 64, st));
-  g.tile_ctr = ctr.as<int>();
-  RC(bsp::launch_kc(g, st));
-  RC(bsp::launch_from_planes(pc.as<char>(), ec.as<int>(), ldc, c_col0, I, J, C, J, pl, st));
-  SNERF_HIP_CHECK(hipStreamSynchronize(st));
-  return SNERF_OK;
-}
-
-// C[I][J] = sum_p A[p][a_col0 + i] B[p][b_col0 + j] through split-K slabs + the library's deterministic slab reduction
-int snerf_test_bsp_dw(const float* A, int lda_src, const float* B, int ldb_src, int P, int I, int J, int a_col0, int b_col0,
-                      int k_split, int narrow_i, float* C, int planes, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (planes != 1 && planes != 2) { set_error("test_bsp_dw: planes"); return SNERF_ERR_BAD_DESC; }
-  const int pl = planes;
-  const size_t rp = round_up_sz(P, 128);
-  const int lda = round_up(lda_src, 16), ldb = round_up(ldb_src, 16);
-  DevBuf pa, ea, pb, eb, slab, tmp;
-  TALLOC(pa, bsp::plane_bytes(rp, lda, pl)); TALLOC(ea, bsp::etab_ints(rp, lda) * 4);
-  TALLOC(pb, bsp::plane_bytes(rp, ldb, pl)); TALLOC(eb, bsp::etab_ints(rp, ldb) * 4);
-  RC(bsp::launch_to_planes(A, lda_src, P, lda_src, pa.as<char>(), ea.as<int>(), lda, 0, pl, st));
-  RC(bsp::launch_to_planes(B, ldb_src, P, ldb_src, pb.as<char>(), eb.as<int>(), ldb, 0, pl, st));
-  const int ns = (P + k_split - 1) / k_split;
-  const size_t stride = round_up_sz((size_t)I * J, 64);
-  TALLOC(slab, stride * ns * 4); TALLOC(tmp, 64 * stride * 4);
-  bsp::DwArgs g;
-  g.A = pa.as<char>(); g.EA = ea.as<int>(); g.lda = lda; g.a_col0 = a_col0;
-  g.B = pb.as<char>(); g.EB = eb.as<int>(); g.ldb = ldb; g.b_col0 = b_col0;
-  g.I = I; g.J = J; g.P = P; g.C = slab.as<float>(); g.ldc = J; g.k_split = k_split; g.n_split = ns; g.slab_stride = stride; g.pl = pl;
-  RC(bsp::launch_dw(g, narrow_i != 0, st));
-  SNERF_HIP_CHECK(hipMemsetAsync(C, 0, (size_t)I * J * 4, st));
-  RC(reduce_partials(slab.as<float>(), ns, stride, I * J, tmp.as<float>(), C, st));
-  SNERF_HIP_CHECK(hipStreamSynchronize(st));
-  return SNERF_OK;
-}
 
 }  // extern "C"

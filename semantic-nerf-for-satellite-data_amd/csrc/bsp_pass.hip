@@ -9,25 +9,37 @@
 
 namespace snerf {
 
-#define RC(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
-
 namespace {
-// Every other K-contiguous launch of a pass walks its tiles backwards (tiles.h): a consumer starts with the rows its producer
-// wrote last.  Measured 372.0 -> 369.8 us per launch, 28.27 -> 28.12 ms per step (two A/B pairs on one box).
+// The workspace: resolves offsets to pointers and binds a plane tensor (plan.h: PlaneT -- planes, exponent table and leading
+// dimension in one piece) to its role in a launch.
 struct Ws {
   char* base;
   char* c(size_t off) const { return base + off; }
   float* f(size_t off) const { return reinterpret_cast<float*>(base + off); }
   int* i(size_t off) const { return reinterpret_cast<int*>(base + off); }
   unsigned* u(size_t off) const { return reinterpret_cast<unsigned*>(base + off); }
+  // K-contiguous launch: input columns [col0, col0 + k) of t; a second input segment (k from Ka on: all of t); output at column col0
+  // (+ the sign words of cos where t keeps them); the stored activation whose derivative a dX epilogue multiplies by
+  void a(bsp::KcArgs& g, const PlaneT& t, int k, int col0 = 0) const { g.A = c(t.o); g.EA = i(t.e); g.lda = t.ld; g.a_col0 = col0; g.Ka = k; }
+  void a2(bsp::KcArgs& g, const PlaneT& t) const { g.A2 = c(t.o); g.EA2 = i(t.e); g.lda2 = t.ld; }
+  void out(bsp::KcArgs& g, const PlaneT& t, int col0 = 0) const { g.C = c(t.o); g.EC = i(t.e); g.ldc = t.ld; g.c_col0 = col0; g.Csign = t.s ? u(t.s) : nullptr; }
+  void h(bsp::KcArgs& g, const PlaneT& t, int col0 = 0) const { g.H = c(t.o); g.EH = i(t.e); g.ldh = t.ld; g.h_col0 = col0; g.Hsign = t.s ? u(t.s) : nullptr; }
+  // dW launch: dZ (all of it from column 0) and X from column col0
+  void dz(bsp::DwArgs& g, const PlaneT& t) const { g.A = c(t.o); g.EA = i(t.e); g.lda = t.ld; g.a_col0 = 0; }
+  void x(bsp::DwArgs& g, const PlaneT& t, int col0) const { g.B = c(t.o); g.EB = i(t.e); g.ldb = t.ld; g.b_col0 = col0; }
 };
-// weight operand `job` of the packed buffer (rows [row0, ..), k >= k0 of it)
-void weights(bsp::KcArgs& g, const Plan& p, const float* pk, int job, int row0 = 0, int k0 = 0) {
+// weight operand `job` of the plan's table (Plan::wj), resolved in the packed buffer
+struct WOp { const char* W; const int* EW; int rb32; unsigned bytes; int K; };
+WOp wop(const Plan& p, const float* pk, int job) {
   const char* planes = reinterpret_cast<const char*>(pk + p.n_fp32);
-  g.W = planes + p.wj_off[job];
-  g.EW = reinterpret_cast<const int*>(planes + p.wp_bytes) + p.wj_e[job];
-  g.w_rb32 = (p.wj_rows[job] + 31) / 32;
-  g.w_bytes = (unsigned)bsp::wp16_bytes(p.wj_rows[job], p.wj_K[job], p.pl);
+  const bsp::WPackJob& w = p.wj.j[job];
+  return {planes + w.dst_off, reinterpret_cast<const int*>(planes + p.wp_bytes) + w.e_idx, (w.rows + 31) / 32,
+          (unsigned)bsp::wp16_bytes(w.rows, w.K, p.pl), w.K};
+}
+// ... as the B of a K-contiguous launch (rows [row0, ..), k >= k0 of it)
+void weights(bsp::KcArgs& g, const Plan& p, const float* pk, int job, int row0 = 0, int k0 = 0) {
+  const WOp w = wop(p, pk, job);
+  g.W = w.W; g.EW = w.EW; g.w_rb32 = w.rb32; g.w_bytes = w.bytes;
   g.w_row0 = row0; g.w_k0 = k0;
   g.pl = p.pl;
 }
@@ -49,6 +61,8 @@ int forward_bsp(const Plan& p, const float* pk, const SnerfInputs* in, const Sne
   // with hipMemsetAsync the forward's and the backward's memset of this region became two identical memset nodes of a
   // captured HIP graph, and replays on ROCm 7.2 then ran the backward's launches on counters that had not been zeroed.)  The first
   // kernel of the pass does it on the side: the encode kernel here, the composite backward in backward_bsp.
+  // Every other K-contiguous launch of a pass walks its tiles backwards (tiles.h): a consumer starts with the rows its producer
+  // wrote last.  Measured 372.0 -> 369.8 us per launch, 28.27 -> 28.12 ms per step (two A/B pairs on one box).
   int kcq = 0;
   auto launch_kc = [&](bsp::KcArgs& g) { g.rev = kcq & 1; g.tile_ctr = kcq < KCQ_SLOTS ? ws.i(p.o_kcq) + 16 * kcq++ : nullptr; return bsp::launch_kc(g, st); };
   const int P = p.P, W = p.W, H = p.H;
@@ -65,37 +79,28 @@ int forward_bsp(const Plan& p, const float* pk, const SnerfInputs* in, const Sne
   ea.N = p.N; ea.S = p.S; ea.F = p.F; ea.Ep = p.Ep;
   ea.FA = p.FA; ea.W = p.Wf; ea.Xp = p.Xp; ea.x_sun = p.x_sun; ea.x_t = p.x_t; ea.x_ts = p.x_ts; ea.tau = p.tau;
   ea.zero = ws.u(p.o_kcq); ea.zero_n = KCQ_SLOTS * 16;
-  RC(bsp::launch_encode_bsp(ea, ws.c(p.o_pe), ws.i(p.e_pe), ws.c(p.o_fa), ws.i(p.e_fa), p.Wf, p.pl, st));
+  RC(bsp::launch_encode_bsp(ea, ws.c(p.pe.o), ws.i(p.pe.e), ws.c(p.fa.o), ws.i(p.fa.e), p.Wf, p.pl, st));
   const size_t EB = 2 * (size_t)p.pl;   // bytes per element of a plane tensor
   if (p.Wf > W)   // pad columns between feats and extras (narrow test networks only): zero planes, read against zero weights
-    RC(bsp::launch_zero_cols(ws.c(p.o_fa) + (size_t)W * EB, (size_t)p.FA * EB, (size_t)(p.Wf - W) * EB, P, st));
+    RC(bsp::launch_zero_cols(ws.c(p.fa.o) + (size_t)W * EB, (size_t)p.FA * EB, (size_t)(p.Wf - W) * EB, P, st));
   // 3. trunk (rs_semantic.py:325-334)
   const int act = p.siren ? ACT_SIN : ACT_RELU;
   const bool fused = p.fuse_trunk && bsp::trunk_fusion_enabled();
   if (fused) {   // one persistent launch, the activation tile resident in LDS (bsp_trunk.hip); inference: only the last layer's planes + sigma's partials leave
     bsp::TrunkArgs g;
-    g.pe = ws.c(p.o_pe); g.Epe = ws.i(p.e_pe); g.P = P; g.W = W; g.L = p.L; g.skip_mask = p.skip_mask;
-    const char* planes = reinterpret_cast<const char*>(pk + p.n_fp32);
-    for (int i = 0; i < p.L; ++i) {
-      const int job = p.wj_tr[i];
-      g.Wp[i] = planes + p.wj_off[job];
-      g.EW[i] = reinterpret_cast<const int*>(planes + p.wp_bytes) + p.wj_e[job];
-      g.w_bytes[i] = (unsigned)bsp::wp16_bytes(p.wj_rows[job], p.wj_K[job], 1);
-      g.K[i] = p.k_tr[i];
-      g.bias[i] = pk + p.b_tr[i];
+    g.pe = ws.c(p.pe.o); g.Epe = ws.i(p.pe.e); g.P = P; g.W = W; g.L = p.L; g.skip_mask = p.skip_mask;
+    // feats (rs_semantic.py:338) rides as one more layer of an inference pass, entry L: written into the first W columns of the
+    // [feats | sun | t | t_s] tensor.  (One plane: fuse_trunk holds only with p.pl == 1.)
+    const bool fused_feats = !p.train;
+    for (int i = 0; i < p.L + (fused_feats ? 1 : 0); ++i) {
+      const WOp w = wop(p, pk, i < p.L ? p.wj_tr[i] : p.wj_fs);
+      g.Wp[i] = w.W; g.EW[i] = w.EW; g.w_bytes[i] = w.bytes; g.K[i] = w.K;
+      g.bias[i] = pk + (i < p.L ? p.b_tr[i] : p.b_fs);
       g.w0[i] = i == 0 ? 30.f : 1.f;
     }
-    const bool fused_feats = !p.train;
-    if (fused_feats) {  // feats (rs_semantic.py:338) rides as one more layer: written into the first W columns of the [feats | sun | t | t_s] tensor
-      const int job = p.wj_fs, i = p.L;
-      g.Wp[i] = planes + p.wj_off[job];
-      g.EW[i] = reinterpret_cast<const int*>(planes + p.wp_bytes) + p.wj_e[job];
-      g.w_bytes[i] = (unsigned)bsp::wp16_bytes(p.wj_rows[job], p.wj_K[job], 1);
-      g.K[i] = W; g.bias[i] = pk + p.b_fs; g.w0[i] = 1.f;
-      g.F = ws.c(p.o_fa); g.EF = ws.i(p.e_fa); g.ldf = p.FA;
-    }
+    if (fused_feats) { g.F = ws.c(p.fa.o); g.EF = ws.i(p.fa.e); g.ldf = p.fa.ld; }
     for (int i = 0; i < p.L && p.train; ++i) {   // training (feats stays a launch of its own): every layer's planes and sign words leave for the backward pass
-      g.H[i] = ws.c(p.o_h[i]); g.EH[i] = ws.i(p.e_h[i]); g.Hsign[i] = ws.u(p.o_c[i]);
+      g.H[i] = ws.c(p.h[i].o); g.EH[i] = ws.i(p.h[i].e); g.Hsign[i] = ws.u(p.h[i].s);
     }
     g.nd_w = pk + p.w_fs + (size_t)W * W; g.nd_out = ws.f(p.o_sigpart); g.nd_stride = p.Pp;
     g.tile_ctr = ws.i(p.o_kcq) + 16 * kcq++;
@@ -104,40 +109,37 @@ int forward_bsp(const Plan& p, const float* pk, const SnerfInputs* in, const Sne
   for (int i = 0; i < p.L && !fused; ++i) {
     bsp::KcArgs g;
     const bool skip = (p.skip_mask >> i) & 1u;
-    if (i == 0) { g.A = ws.c(p.o_pe); g.EA = ws.i(p.e_pe); g.lda = p.Ep; g.Ka = p.Ep; }
-    else if (skip) { g.A = ws.c(p.o_pe); g.EA = ws.i(p.e_pe); g.lda = p.Ep; g.Ka = p.Ep;
-                     g.A2 = ws.c(p.o_h[i - 1]); g.EA2 = ws.i(p.e_h[i - 1]); g.lda2 = W; }
-    else { g.A = ws.c(p.o_h[i - 1]); g.EA = ws.i(p.e_h[i - 1]); g.lda = W; g.Ka = W; }
+    if (i == 0) ws.a(g, p.pe, p.Ep);
+    else if (skip) { ws.a(g, p.pe, p.Ep); ws.a2(g, p.h[i - 1]); }   // [gamma | h]
+    else ws.a(g, p.h[i - 1], W);
     weights(g, p, pk, p.wj_tr[i]);
     g.I = P; g.J = W; g.K = p.k_tr[i];
-    g.C = ws.c(p.o_h[i]); g.EC = ws.i(p.e_h[i]); g.ldc = W;
+    ws.out(g, p.h[i]);   // (inference: h[i] alternates between two buffers, api.hip: plan_bsp)
     g.bias = pk + p.b_tr[i]; g.act = act; g.w0 = (p.siren && i == 0) ? 30.f : 1.f;
-    if (p.train && p.siren) g.Csign = ws.u(p.o_c[i]);
     if (i == p.L - 1 && p.nd_sig) {   // sigma's 1-wide projection rides in this launch's epilogue (bsp_kc.hip: NDOT)
       g.nd_w = pk + p.w_fs + (size_t)W * W; g.nd_out = ws.f(p.o_sigpart); g.nd_stride = p.Pp;
     }
     RC(launch_kc(g));
   }
-  const char* hl = ws.c(p.o_h[p.L - 1]); const int* ehl = ws.i(p.e_h[p.L - 1]);
+  const PlaneT& hl = p.h[p.L - 1];
   if (!p.nd_sig) {  // sigma pre-activation (rs_semantic.py:337) -> 32-wide fp32 buffer, column 0
     bsp::KcArgs g;
-    g.A = hl; g.EA = ehl; g.lda = W; g.Ka = W; weights(g, p, pk, p.wj_sig);
+    ws.a(g, hl, W); weights(g, p, pk, p.wj_sig);
     g.I = P; g.J = NARROW; g.K = W; g.Cf = ws.f(p.o_sigo); g.bias = pk + p.b_fs + W;
     RC(bsp::launch_kc_narrow(g, st));
   }
   if (!fused || p.train) {  // feats (rs_semantic.py:338), written into the first W columns of the [feats | sun | t | t_s] tensor
     bsp::KcArgs g;
-    g.A = hl; g.EA = ehl; g.lda = W; g.Ka = W; weights(g, p, pk, p.wj_fs);
-    g.I = P; g.J = W; g.K = W; g.C = ws.c(p.o_fa); g.EC = ws.i(p.e_fa); g.ldc = p.FA; g.bias = pk + p.b_fs;
+    ws.a(g, hl, W); weights(g, p, pk, p.wj_fs);
+    g.I = P; g.J = W; g.K = W; ws.out(g, p.fa); g.bias = pk + p.b_fs;
     RC(launch_kc(g));
   }
   const int r0 = p.sc ? p.sun_col : 0;
   {  // first layer of every head in one GEMM (sc pass: sun-visibility block only)
     bsp::KcArgs g;
-    g.A = ws.c(p.o_fa); g.EA = ws.i(p.e_fa); g.lda = p.FA; g.Ka = p.FA; weights(g, p, pk, p.wj_h1, r0);
-    g.I = P; g.J = p.h1w; g.K = p.FA; g.C = ws.c(p.o_h1); g.EC = ws.i(p.e_h1); g.ldc = p.h1w;
+    ws.a(g, p.fa, p.FA); weights(g, p, pk, p.wj_h1, r0);
+    g.I = P; g.J = p.h1w; g.K = p.FA; ws.out(g, p.h1);
     g.bias = pk + p.b_h1 + r0; g.act = act; g.w0 = 1.f;
-    if (p.train && p.siren) g.Csign = ws.u(p.o_c1);
     if (p.nd_fin) {   // the heads' final layers (block-diagonal [32][KF]: block b's rows read only block b's 256 columns) in this launch's epilogue
       g.nd_w = pk + p.w_fin; g.nd_ldw = p.KF; g.nd_omax = ND_FIN; g.nd_out = ws.f(p.o_finpart); g.nd_stride = p.Pp;
       auto blk = [&](int b, int col, int n) { if (b >= 0) { g.nd_rows[b] = n; g.nd_row0[b] = col; } };
@@ -152,25 +154,23 @@ int forward_bsp(const Plan& p, const float* pk, const SnerfInputs* in, const Sne
   const int sun_col = p.sc ? 0 : p.sun_col;
   {  // sun visibility layers 2, 3 (rs_semantic.py:217-227)
     bsp::KcArgs g;
-    g.A = ws.c(p.o_h1); g.EA = ws.i(p.e_h1); g.lda = p.h1w; g.a_col0 = sun_col; g.Ka = H; weights(g, p, pk, p.wj_s2);
-    g.I = P; g.J = H; g.K = H; g.C = ws.c(p.o_s2); g.EC = ws.i(p.e_s2); g.ldc = H; g.bias = pk + p.b_s2; g.act = act;
-    if (p.train && p.siren) g.Csign = ws.u(p.o_cs2);
+    ws.a(g, p.h1, H, sun_col); weights(g, p, pk, p.wj_s2);
+    g.I = P; g.J = H; g.K = H; ws.out(g, p.s2); g.bias = pk + p.b_s2; g.act = act;
     RC(launch_kc(g));
-    g.A = ws.c(p.o_s2); g.EA = ws.i(p.e_s2); g.lda = H; g.a_col0 = 0; weights(g, p, pk, p.wj_s3);
-    g.C = ws.c(p.o_s3); g.EC = ws.i(p.e_s3); g.bias = pk + p.b_s3;
-    if (p.train && p.siren) g.Csign = ws.u(p.o_cs3);
+    ws.a(g, p.s2, H); weights(g, p, pk, p.wj_s3);
+    ws.out(g, p.s3); g.bias = pk + p.b_s3;
     if (p.nd_sun) { g.nd_w = pk + p.w_s4; g.nd_out = ws.f(p.o_sunpart); g.nd_stride = p.Pp; }   // the sun-visibility output likewise
     RC(launch_kc(g));
   }
   if (!p.nd_sun) {  // sun visibility output pre-activation
     bsp::KcArgs g;
-    g.A = ws.c(p.o_s3); g.EA = ws.i(p.e_s3); g.lda = H; g.Ka = H; weights(g, p, pk, p.wj_s4);
+    ws.a(g, p.s3, H); weights(g, p, pk, p.wj_s4);
     g.I = P; g.J = NARROW; g.K = H; g.Cf = ws.f(p.o_suno); g.bias = pk + p.b_s4;
     RC(bsp::launch_kc_narrow(g, st));
   }
   if (!p.sc && !p.nd_fin) {  // last layer of rgb / beta / beta_s / semantic heads: block-diagonal [32][KF]
     bsp::KcArgs g;
-    g.A = ws.c(p.o_h1); g.EA = ws.i(p.e_h1); g.lda = p.h1w; g.Ka = p.KF; weights(g, p, pk, p.wj_fin);
+    ws.a(g, p.h1, p.KF); weights(g, p, pk, p.wj_fin);
     g.I = P; g.J = NARROW; g.K = p.KF; g.Cf = ws.f(p.o_fino); g.bias = pk + p.b_fin;
     RC(bsp::launch_kc_narrow(g, st));
   }
@@ -194,71 +194,62 @@ namespace {
 // its OWN inside the reduction arena (p.o_rq); the reductions into the packed gradient buffer are queued and run as two
 // launches at the end of the pass (aux_kernels.hip: launch_reductions) instead of ~60 small ones in between the GEMMs.
 struct RQ {
-  float* base; size_t cap, used = 0; bool over = false;
+  float* base; size_t cap, used = 0; bool over = false;   // base == null: a counting arena (bsp_rq_floats)
   RedTable elem, col;
   float* take(size_t floats) {
     const size_t n = round_up_sz(floats, 64);
     if (used + n > cap) { over = true; return base; }
-    float* r = base + used; used += n; return r;
+    float* r = base ? base + used : nullptr; used += n; return r;
   }
 };
 struct DwMat { DwSplit sp; size_t stride; int ldw; float* slab; };
-// `split_rows`: the rows the split count is chosen for when they differ from the slab's (the [W + 32][W] matrix of feats + sigma:
-// its wide launch covers W rows -- counting the 32 sigma rows as a third row tile gave it 43 splits, 172 workgroups for 256 CUs)
-DwMat dw_begin(const Plan& p, RQ& rq, int rows, int ldw, int cols, bool narrow_rows, int split_rows = 0) {
-  DwMat m;
-  m.sp = dw_choose_bsp(p.P, split_rows > 0 ? split_rows : rows, cols, narrow_rows);
-  m.stride = round_up_sz((size_t)rows * ldw, 64);
-  m.ldw = ldw;
-  m.slab = rq.take(m.stride * m.sp.ns);
-  return m;
-}
-// slab[split][i][slab_off + j] = sum_p dZ[p][dz_col0 + i] X[p][x_col0 + j]
-int dw_gemm(const Plan& p, const DwMat& m, const char* dz, const int* edz, int lddz, int dz_col0, int I, bool narrow_i,
-            const char* X, const int* ex, int ldx, int x_col0, int J, size_t slab_off, hipStream_t st) {
-  bsp::DwArgs g;
-  g.A = dz; g.EA = edz; g.lda = lddz; g.a_col0 = dz_col0;
-  g.B = X; g.EB = ex; g.ldb = ldx; g.b_col0 = x_col0;
-  g.I = I; g.J = J; g.P = p.P;
-  g.C = m.slab + slab_off; g.ldc = m.ldw;
-  g.k_split = m.sp.k_split; g.n_split = m.sp.ns; g.slab_stride = m.stride; g.pl = p.pl;
-  return bsp::launch_dw(g, narrow_i, st);
-}
-int dw_reduce(RQ& rq, const DwMat& m, size_t count, float* gout) { return red_add_elem(rq.elem, m.slab, m.sp.ns, m.stride, count, gout); }
-// column-sum partials of a dX launch: one row per 128-row tile, `width` columns
 inline int cs_ld(int width) { return (width + 3) & ~3; }
-float* cs_take(const Plan& p, RQ& rq, int width) { return rq.take((size_t)((p.P + 127) / 128) * cs_ld(width)); }
-int bias_from_colsum(const Plan& p, RQ& rq, const float* cs, int width, float* gout) {
-  return red_add_col(rq.col, cs, (p.P + 127) / 128, (size_t)cs_ld(width), width, gout);
-}
-// bias gradient of a 32-wide pre-activation gradient; the same pass writes its planes + exponents (the dX / dW operands)
-int narrow_grad(const Plan& p, RQ& rq, const float* dnar, char* planes, int* E, float* gout, hipStream_t st) {
-  const int nb = (p.P + 255) / 256;
-  float* part = rq.take((size_t)nb * NARROW);
-  RC(bsp::launch_colsum32_bsp(dnar, p.P, part, planes, E, p.pl, st));
-  return red_add_col(rq.col, part, nb, NARROW, NARROW, gout);
+
+// Every region a backward pass takes from the arena, by the launch that fills it: the split-K slabs of each weight matrix (w_*),
+// the column-sum partials of each dX launch (cs_*: one row per 128-row tile) and the 256-row partial sums of the three 32-wide
+// gradients (nar_*).  take_regions is the ONE walk over them: Plan::rq_floats is what it takes from a counting arena, and
+// backward_bsp runs it on the real one before its first launch.
+struct BwdRegions {
+  float *nar_fin = nullptr, *nar_sun = nullptr, *nar_sig = nullptr;
+  DwMat w_fin, w_s4, w_s3, w_s2, w_h1, w_fs;
+  float *cs_fin = nullptr, *cs_s3 = nullptr, *cs_s2 = nullptr, *cs_sun = nullptr, *cs_fa = nullptr, *cs_hl = nullptr;
+  struct Layer { DwMat w, w_gamma; float* cs; } tr[SNERF_MAX_LAYERS];   // w_gamma: skip layers; cs: the dX launch into layer i - 1
+};
+void take_regions(const Plan& p, RQ& rq, BwdRegions& r) {
+  // `split_rows`: the rows the split count is chosen for when they differ from the slab's (the [W + 32][W] matrix of feats + sigma:
+  // its wide launch covers W rows -- counting the 32 sigma rows as a third row tile gave it 43 splits, 172 workgroups for 256 CUs)
+  auto dw = [&](int rows, int ldw, int cols, bool narrow_rows, int split_rows = 0) {
+    DwMat m;
+    m.sp = dw_choose_bsp(p.P, split_rows > 0 ? split_rows : rows, cols, narrow_rows);
+    m.stride = round_up_sz((size_t)rows * ldw, 64);
+    m.ldw = ldw;
+    m.slab = rq.take(m.stride * m.sp.ns);
+    return m;
+  };
+  auto cs = [&](int width) { return rq.take((size_t)((p.P + 127) / 128) * cs_ld(width)); };
+  auto nar = [&]() { return rq.take((size_t)((p.P + 255) / 256) * NARROW); };
+  const int W = p.W, H = p.H;
+  if (!p.sc) { r.nar_fin = nar(); r.w_fin = dw(NARROW, p.KF, p.KF, true); r.cs_fin = cs(p.KF); }
+  r.nar_sun = nar(); r.w_s4 = dw(NARROW, H, H, true); r.w_s3 = dw(H, H, H, false); r.w_s2 = dw(H, H, H, false);   // one slab region per matrix
+  r.cs_s3 = cs(H); r.cs_s2 = cs(H); r.cs_sun = cs(H);
+  r.w_h1 = dw(p.h1w, p.FA, p.FA, false); r.cs_fa = cs(p.FA);
+  r.nar_sig = nar(); r.w_fs = dw(W + NARROW, W, W, false, W); r.cs_hl = cs(W);
+  for (int i = p.L - 1; i >= 0; --i) {
+    // skip layer W_i = [W_gamma (Ep columns) | W_h (W columns)]: the two column blocks are two contractions of very different
+    // width over the same dz, so each gets a slab region and a split count of its own (the 64-column block: two tiles x 128 splits;
+    // sharing the wide block's 64 splits left half the chip idle for it: 275 us against 180) and a 2-D reduction into its columns
+    if (i > 0 && ((p.skip_mask >> i) & 1u)) { r.tr[i].w_gamma = dw(W, p.Ep, p.Ep, false); r.tr[i].w = dw(W, W, W, false); }
+    else r.tr[i].w = dw(W, p.k_tr[i], i == 0 ? p.Ep : W, false);
+    r.tr[i].cs = i > 0 ? cs(W) : nullptr;
+  }
 }
 }  // namespace
 
-// floats of the reduction arena: the same sequence of takes as backward_bsp below
 size_t bsp_rq_floats(const Plan& p) {
-  size_t n = 0;
-  auto take = [&](size_t f) { n += round_up_sz(f, 64); };
-  auto slab = [&](int rows, int ldw, int cols, bool narrow, int split_rows = 0) { take(round_up_sz((size_t)rows * ldw, 64) * dw_choose_bsp(p.P, split_rows > 0 ? split_rows : rows, cols, narrow).ns); };
-  auto cs = [&](int width) { take((size_t)((p.P + 127) / 128) * ((width + 3) & ~3)); };
-  auto nar = [&]() { take((size_t)((p.P + 255) / 256) * NARROW); };
-  const int W = p.W, H = p.H;
-  if (!p.sc) { nar(); slab(NARROW, p.KF, p.KF, true); cs(p.KF); }
-  nar(); slab(NARROW, H, H, true); slab(H, H, H, false); slab(H, H, H, false); cs(H); cs(H); cs(H);
-  slab(p.h1w, p.FA, p.FA, false); cs(p.FA);
-  nar(); slab(W + NARROW, W, W, false, W); cs(W);
-  for (int i = p.L - 1; i >= 0; --i) {
-    const bool skip = i > 0 && ((p.skip_mask >> i) & 1u);
-    if (skip) { slab(W, p.Ep, p.Ep, false); slab(W, W, W, false); }      // [gamma | h] columns: two slab regions (backward_bsp)
-    else slab(W, p.k_tr[i], i == 0 ? p.Ep : W, false);
-    if (i > 0) cs(W);
-  }
-  return n;
+  RQ rq{nullptr, ~(size_t)0};
+  BwdRegions r;
+  take_regions(p, rq, r);
+  return rq.used;
 }
 
 int backward_bsp(const Plan& p, const float* pk, const SnerfInputs* in, const SnerfOutGrads* go, float* gp, float* d_t, float* d_t_s,
@@ -267,16 +258,35 @@ int backward_bsp(const Plan& p, const float* pk, const SnerfInputs* in, const Sn
   const int P = p.P, W = p.W, H = p.H;
   int kcq = 0;     // (the counters are cleared by the composite backward kernel, the first launch of this pass)
   auto launch_kc = [&](bsp::KcArgs& g) { g.rev = kcq & 1; g.tile_ctr = kcq < KCQ_SLOTS ? ws.i(p.o_kcq) + 16 * kcq++ : nullptr; return bsp::launch_kc(g, st); };
-  // activation derivative in a dX epilogue, rebuilt from the stored activation h (planes o_h / exponents e_h, leading
-  // dimension ld, column col0): siren w0 * sign(cos) * sqrt(1 - h^2) with the sign words o_c; relu: h > 0
-  auto dact = [&](bsp::KcArgs& g, size_t o_c, size_t o_h, size_t e_h, int ld, int col0 = 0, float w0 = 1.f) {
-    g.H = ws.c(o_h); g.EH = ws.i(e_h); g.ldh = ld; g.h_col0 = col0;
-    if (p.siren) { g.aux_mode = AUX_SINREC; g.Hsign = ws.u(o_c); g.w0 = w0; }
+  RQ rq{ws.f(p.o_rq), p.rq_floats};
+  BwdRegions r;
+  take_regions(p, rq, r);
+  if (rq.over) { set_error("reduction arena too small (plan / pass mismatch)"); return SNERF_ERR_WORKSPACE; }
+  // activation derivative in a dX epilogue, rebuilt from the stored activation h (column col0 of it): siren
+  // w0 * sign(cos) * sqrt(1 - h^2) with h's sign words; relu: h > 0
+  auto dact = [&](bsp::KcArgs& g, const PlaneT& h, int col0 = 0, float w0 = 1.f) {
+    ws.h(g, h, col0);
+    if (p.siren) { g.aux_mode = AUX_SINREC; g.w0 = w0; }
     else g.aux_mode = AUX_RELU_MASK;
   };
-  RQ rq{ws.f(p.o_rq), p.rq_floats};
-  auto colsum = [&](bsp::KcArgs& g, int width) { g.colsum = cs_take(p, rq, width); g.ldcs = cs_ld(width); return g.colsum; };
-  const float* cs_ = nullptr;
+  // a dX launch leaves the column sums of what it stores, one row per 128-row tile: the bias gradient of the layer below
+  auto colsum = [&](bsp::KcArgs& g, float* cs, int width) { g.colsum = cs; g.ldcs = cs_ld(width); };
+  auto bias_from_colsum = [&](const float* cs, int width, float* gout) { return red_add_col(rq.col, cs, (P + 127) / 128, (size_t)cs_ld(width), width, gout); };
+  // slab[split][i][slab_off + j] = sum_p dZ[p][i] X[p][x_col0 + j]
+  auto dw_gemm = [&](const DwMat& m, const PlaneT& dz, int I, bool narrow_i, const PlaneT& X, int x_col0, int J, size_t slab_off = 0) {
+    bsp::DwArgs g;
+    ws.dz(g, dz); ws.x(g, X, x_col0);
+    g.I = I; g.J = J; g.P = P;
+    g.C = m.slab + slab_off; g.ldc = m.ldw;
+    g.k_split = m.sp.k_split; g.n_split = m.sp.ns; g.slab_stride = m.stride; g.pl = p.pl;
+    return bsp::launch_dw(g, narrow_i, st);
+  };
+  auto dw_reduce = [&](const DwMat& m, size_t count, float* gout) { return red_add_elem(rq.elem, m.slab, m.sp.ns, m.stride, count, gout); };
+  // bias gradient of a 32-wide pre-activation gradient; the same pass writes its planes + exponents (the dX / dW operands)
+  auto narrow_grad = [&](const float* dnar, float* part, const PlaneT& t, float* gout) {
+    RC(bsp::launch_colsum32_bsp(dnar, P, part, ws.c(t.o), ws.i(t.e), p.pl, st));
+    return red_add_col(rq.col, part, (P + 255) / 256, NARROW, NARROW, gout);
+  };
   float* dsig = ws.f(p.o_dsig); float* dfin = ws.f(p.o_dfin); float* dsun = ws.f(p.o_dsun);
   // 0. composite backward -> gradients of the 32-wide pre-activations (+ sky MLP grads)
   CompBwdArgs b;
@@ -295,67 +305,64 @@ int backward_bsp(const Plan& p, const float* pk, const SnerfInputs* in, const Sn
   if (!p.sc)
     RC(red_add_col(rq.col, ws.f(p.o_skyslab), p.comp_blocks * 4, (size_t)p.sky_floats, p.sky_floats, gp + p.sky));
 
-  char* dz1 = ws.c(p.o_dza); int* edz1 = ws.i(p.e_dza);   // d(pre-activation) of the fused first head layer, [P][h1w]
+
+  const PlaneT dz1 = p.dza.view(p.h1w);   // d(pre-activation) of the fused first head layer, [P][h1w]
   const int sun_col = p.sc ? 0 : p.sun_col;
   if (!p.sc) {
     // 1. final head layers: bias gradient + planes of dfin, dW, then dz1[:, :KF] = (dfin . W_fin) * act'
-    RC(narrow_grad(p, rq, dfin, ws.c(p.o_pdfin), ws.i(p.e_dfin), gp + p.b_fin, st));
-    const DwMat mf = dw_begin(p, rq, NARROW, p.KF, p.KF, true);
-    RC(dw_gemm(p, mf, ws.c(p.o_pdfin), ws.i(p.e_dfin), NARROW, 0, NARROW, true, ws.c(p.o_h1), ws.i(p.e_h1), p.h1w, 0, p.KF, 0, st));
-    RC(dw_reduce(rq, mf, (size_t)NARROW * p.KF, gp + p.w_fin));
+    RC(narrow_grad(dfin, r.nar_fin, p.pdfin, gp + p.b_fin));
+    RC(dw_gemm(r.w_fin, p.pdfin, NARROW, true, p.h1, 0, p.KF));
+    RC(dw_reduce(r.w_fin, (size_t)NARROW * p.KF, gp + p.w_fin));
     bsp::KcArgs g;
-    g.A = ws.c(p.o_pdfin); g.EA = ws.i(p.e_dfin); g.lda = NARROW; g.Ka = NARROW; weights(g, p, pk, p.wj_tfin);
-    g.I = P; g.J = p.KF; g.K = NARROW; g.C = dz1; g.EC = edz1; g.ldc = p.h1w;
-    dact(g, p.o_c1, p.o_h1, p.e_h1, p.h1w);
-    cs_ = colsum(g, p.KF);
+    ws.a(g, p.pdfin, NARROW); weights(g, p, pk, p.wj_tfin);
+    g.I = P; g.J = p.KF; g.K = NARROW; ws.out(g, dz1);
+    dact(g, p.h1);
+    colsum(g, r.cs_fin, p.KF);
     RC(launch_kc(g));
-    RC(bias_from_colsum(p, rq, cs_, p.KF, gp + p.b_h1));
+    RC(bias_from_colsum(r.cs_fin, p.KF, gp + p.b_h1));
   }
   {  // 2. sun visibility chain: output layer, layer 3, layer 2
-    RC(narrow_grad(p, rq, dsun, ws.c(p.o_pdsun), ws.i(p.e_dsun), gp + p.b_s4, st));
-    const DwMat m4 = dw_begin(p, rq, NARROW, H, H, true);
-    const DwMat mh = dw_begin(p, rq, H, H, H, false), mh2 = dw_begin(p, rq, H, H, H, false);   // one slab region per matrix
-    RC(dw_gemm(p, m4, ws.c(p.o_pdsun), ws.i(p.e_dsun), NARROW, 0, NARROW, true, ws.c(p.o_s3), ws.i(p.e_s3), H, 0, H, 0, st));
-    RC(dw_reduce(rq, m4, (size_t)NARROW * H, gp + p.w_s4));
+    RC(narrow_grad(dsun, r.nar_sun, p.pdsun, gp + p.b_s4));
+    RC(dw_gemm(r.w_s4, p.pdsun, NARROW, true, p.s3, 0, H));
+    RC(dw_reduce(r.w_s4, (size_t)NARROW * H, gp + p.w_s4));
     bsp::KcArgs g;
-    g.A = ws.c(p.o_pdsun); g.EA = ws.i(p.e_dsun); g.lda = NARROW; g.Ka = NARROW; weights(g, p, pk, p.wj_ts4);
-    g.I = P; g.J = H; g.K = NARROW; g.C = ws.c(p.o_dsa); g.EC = ws.i(p.e_dsa); g.ldc = H;
-    dact(g, p.o_cs3, p.o_s3, p.e_s3, H);
-    cs_ = colsum(g, H);
+    ws.a(g, p.pdsun, NARROW); weights(g, p, pk, p.wj_ts4);
+    g.I = P; g.J = H; g.K = NARROW; ws.out(g, p.dsa);
+    dact(g, p.s3);
+    colsum(g, r.cs_s3, H);
     RC(launch_kc(g));  // dz_s3
-    RC(bias_from_colsum(p, rq, cs_, H, gp + p.b_s3));
-    RC(dw_gemm(p, mh, ws.c(p.o_dsa), ws.i(p.e_dsa), H, 0, H, false, ws.c(p.o_s2), ws.i(p.e_s2), H, 0, H, 0, st));
-    RC(dw_reduce(rq, mh, (size_t)H * H, gp + p.w_s3));
-    g.A = ws.c(p.o_dsa); g.EA = ws.i(p.e_dsa); g.lda = H; g.Ka = H; g.K = H; weights(g, p, pk, p.wj_ts3);
-    g.C = ws.c(p.o_dsb); g.EC = ws.i(p.e_dsb);
-    dact(g, p.o_cs2, p.o_s2, p.e_s2, H);
-    cs_ = colsum(g, H);
+    RC(bias_from_colsum(r.cs_s3, H, gp + p.b_s3));
+    RC(dw_gemm(r.w_s3, p.dsa, H, false, p.s2, 0, H));
+    RC(dw_reduce(r.w_s3, (size_t)H * H, gp + p.w_s3));
+    ws.a(g, p.dsa, H); g.K = H; weights(g, p, pk, p.wj_ts3);
+    ws.out(g, p.dsb);
+    dact(g, p.s2);
+    colsum(g, r.cs_s2, H);
     RC(launch_kc(g));  // dz_s2
-    RC(bias_from_colsum(p, rq, cs_, H, gp + p.b_s2));
-    RC(dw_gemm(p, mh2, ws.c(p.o_dsb), ws.i(p.e_dsb), H, 0, H, false, ws.c(p.o_h1), ws.i(p.e_h1), p.h1w, sun_col, H, 0, st));
-    RC(dw_reduce(rq, mh2, (size_t)H * H, gp + p.w_s2));
-    g.A = ws.c(p.o_dsb); g.EA = ws.i(p.e_dsb); weights(g, p, pk, p.wj_ts2);
-    g.C = dz1; g.EC = edz1; g.ldc = p.h1w; g.c_col0 = sun_col;
-    dact(g, p.o_c1, p.o_h1, p.e_h1, p.h1w, sun_col);
-    cs_ = colsum(g, H);
+    RC(bias_from_colsum(r.cs_s2, H, gp + p.b_s2));
+    RC(dw_gemm(r.w_s2, p.dsb, H, false, p.h1, sun_col, H));
+    RC(dw_reduce(r.w_s2, (size_t)H * H, gp + p.w_s2));
+    ws.a(g, p.dsb, H); weights(g, p, pk, p.wj_ts2);
+    ws.out(g, dz1, sun_col);
+    dact(g, p.h1, sun_col);
+    colsum(g, r.cs_sun, H);
     RC(launch_kc(g));  // dz1[:, sun block]
-    RC(bias_from_colsum(p, rq, cs_, H, gp + p.b_h1 + (size_t)p.sun_col));
+    RC(bias_from_colsum(r.cs_sun, H, gp + p.b_h1 + (size_t)p.sun_col));
   }
-  char* dfa = ws.c(p.o_dzb); int* edfa = ws.i(p.e_dzb);   // [P][FA]
+  const PlaneT dfa = p.dzb.view(p.FA);   // [P][FA]
   {  // 3. fused first head layer: dW, then d[feats | extras]
     const int r0 = p.sc ? p.sun_col : 0;
-    const DwMat m1 = dw_begin(p, rq, p.h1w, p.FA, p.FA, false);
-    RC(dw_gemm(p, m1, dz1, edz1, p.h1w, 0, p.h1w, false, ws.c(p.o_fa), ws.i(p.e_fa), p.FA, 0, p.FA, 0, st));
-    RC(dw_reduce(rq, m1, (size_t)p.h1w * p.FA, gp + p.w_h1 + (size_t)r0 * p.FA));
+    RC(dw_gemm(r.w_h1, dz1, p.h1w, false, p.fa, 0, p.FA));
+    RC(dw_reduce(r.w_h1, (size_t)p.h1w * p.FA, gp + p.w_h1 + (size_t)r0 * p.FA));
     bsp::KcArgs g;
-    g.A = dz1; g.EA = edz1; g.lda = p.h1w; g.Ka = p.h1w; weights(g, p, pk, p.wj_th1, 0, r0);
+    ws.a(g, dz1, p.h1w); weights(g, p, pk, p.wj_th1, 0, r0);
     // d feats only (J = W): the 16 extras columns would be a third column tile of 256 for 16 useful columns (a third of this
     // launch: 954 -> ~640 us at 4096 x 64), and nothing needs d sun_d.  The gradient of the transient codes comes from a 32-wide
     // launch over the head blocks that read them instead (default: the beta block alone, K = H).
-    g.I = P; g.J = W; g.K = p.h1w; g.C = dfa; g.EC = edfa; g.ldc = p.FA;
-    cs_ = colsum(g, p.FA);   // columns [0, W) = bias gradient of feats_from_xyz
+    g.I = P; g.J = W; g.K = p.h1w; ws.out(g, dfa);
+    colsum(g, r.cs_fa, p.FA);   // columns [0, W) = bias gradient of feats_from_xyz
     RC(launch_kc(g));
-    RC(red_add_col(rq.col, cs_, (P + 127) / 128, (size_t)cs_ld(p.FA), W, gp + p.b_fs));
+    RC(red_add_col(rq.col, r.cs_fa, (P + 127) / 128, (size_t)cs_ld(p.FA), W, gp + p.b_fs));
     const bool want_t = d_t != nullptr, want_ts = d_t_s != nullptr && p.x_ts >= 0;
     if (p.sc) {   // the sun-visibility block reads [feats | sun_d] only: no gradient reaches t / t_s through this pass
       if (want_t) RC(launch_zero_bytes(d_t, (size_t)p.N * p.tau * sizeof(float), st));
@@ -368,93 +375,60 @@ int backward_bsp(const Plan& p, const float* pk, const SnerfInputs* in, const Sn
       const int k_lo = b_lo * H, k_n = (b_hi + 1 - b_lo) * H;
       float* dext = ws.f(p.o_dfin);      // [P][32] fp32: the final-layer gradients that lived here were consumed in step 1
       bsp::KcArgs x;
-      x.A = dz1; x.EA = edz1; x.lda = p.h1w; x.a_col0 = k_lo; x.Ka = k_n; weights(x, p, pk, p.wj_th1, p.Wf, k_lo);
+      ws.a(x, dz1, k_n, k_lo); weights(x, p, pk, p.wj_th1, p.Wf, k_lo);
       x.I = P; x.J = p.Xp; x.K = k_n; x.Cf = dext;
       RC(bsp::launch_kc_narrow(x, st));
       if (want_t) RC(launch_ray_sum32(dext, p.x_t, p.N, p.S, p.tau, d_t, st));
       if (want_ts) RC(launch_ray_sum32(dext, p.x_ts, p.N, p.S, p.tau, d_t_s, st));
     }
   }
-  char* dz = ws.c(p.o_dza); int* edz = ws.i(p.e_dza);   // dz1 is dead from here on
+  PlaneT dz_cur = p.dza.view(W);   // dz1 is dead from here on: dz of the trunk layers, [P][W], in dza and dzb in turn
+  PlaneT dz_nxt = p.dzb.view(W);   // (dfa is dead once step 4's launches have read it)
   {  // 4. feats + sigma: dW for the [W + 32][W] matrix, then dz of the last trunk layer
-    const char* hl = ws.c(p.o_h[p.L - 1]); const int* ehl = ws.i(p.e_h[p.L - 1]);
+    const PlaneT& hl = p.h[p.L - 1];
     // The density branch carries a gradient only if one reaches weights / transparency (/ sigmas, depth, rgb, logits in the main
     // pass).  In the solar-correction pass of a training step none does: the loss detaches T' and w' (baseline/components/loss.py:8-10)
     // and the composite backward then writes d sigma = 0 exactly -- its bias sums, its dW launch and the 32 extra contraction columns
     // of the dX launch are skipped (SURVEY 8(d) counts the sc backward "through sun_v / feats / trunk only").
     const bool sig_live = !p.sc || go->weights != nullptr || go->transparency != nullptr || go->sigmas != nullptr;
-    if (sig_live) RC(narrow_grad(p, rq, dsig, ws.c(p.o_pdsig), ws.i(p.e_dsig), gp + p.b_fs + W, st));
-    const DwMat ms = dw_begin(p, rq, W + NARROW, W, W, false, W);
-    RC(dw_gemm(p, ms, dfa, edfa, p.FA, 0, W, false, hl, ehl, W, 0, W, 0, st));
-    if (sig_live) RC(dw_gemm(p, ms, ws.c(p.o_pdsig), ws.i(p.e_dsig), NARROW, 0, NARROW, true, hl, ehl, W, 0, W, (size_t)W * W, st));
-    RC(dw_reduce(rq, ms, (size_t)(sig_live ? W + NARROW : W) * W, gp + p.w_fs));
+    if (sig_live) RC(narrow_grad(dsig, r.nar_sig, p.pdsig, gp + p.b_fs + W));
+    RC(dw_gemm(r.w_fs, dfa, W, false, hl, 0, W));
+    if (sig_live) RC(dw_gemm(r.w_fs, p.pdsig, NARROW, true, hl, 0, W, (size_t)W * W));
+    RC(dw_reduce(r.w_fs, (size_t)(sig_live ? W + NARROW : W) * W, gp + p.w_fs));
     bsp::KcArgs g;
-    g.A = dfa; g.EA = edfa; g.lda = p.FA; g.Ka = W;
-    if (sig_live) { g.A2 = ws.c(p.o_pdsig); g.EA2 = ws.i(p.e_dsig); g.lda2 = NARROW; }
+    ws.a(g, dfa, W);
+    if (sig_live) ws.a2(g, p.pdsig);
     weights(g, p, pk, p.wj_tfs); g.I = P; g.J = W; g.K = sig_live ? W + NARROW : W;
-    g.C = dz; g.EC = edz; g.ldc = W;
-    dact(g, p.o_c[p.L - 1], p.o_h[p.L - 1], p.e_h[p.L - 1], W, 0, (p.L == 1) ? 30.f : 1.f);
-    cs_ = colsum(g, W);
+    ws.out(g, dz_cur);
+    dact(g, hl, 0, (p.L == 1) ? 30.f : 1.f);
+    colsum(g, r.cs_hl, W);
     RC(launch_kc(g));
-    RC(bias_from_colsum(p, rq, cs_, W, gp + p.b_tr[p.L - 1]));
+    RC(bias_from_colsum(r.cs_hl, W, gp + p.b_tr[p.L - 1]));
   }
   // 5. trunk, last layer to first
-  char* dz_cur = dz; int* edz_cur = edz;
-  char* dz_nxt = ws.c(p.o_dzb); int* edz_nxt = ws.i(p.e_dzb);
   for (int i = p.L - 1; i >= 0; --i) {
-    const bool skip = (p.skip_mask >> i) & 1u;
-    if (i > 0 && skip) {
-      // skip layer W_i = [W_gamma (Ep columns) | W_h (W columns)]: the two column blocks are two contractions of very different
-      // width over the same dz, so each gets a slab region and a split count of its own (the 64-column block: two tiles x 128 splits;
-      // sharing the wide block's 64 splits left half the chip idle for it: 275 us against 180) and a 2-D reduction into its columns
-      const DwMat mg = dw_begin(p, rq, W, p.Ep, p.Ep, false), mh = dw_begin(p, rq, W, W, W, false);
-      RC(dw_gemm(p, mg, dz_cur, edz_cur, W, 0, W, false, ws.c(p.o_pe), ws.i(p.e_pe), p.Ep, 0, p.Ep, 0, st));
-      RC(dw_gemm(p, mh, dz_cur, edz_cur, W, 0, W, false, ws.c(p.o_h[i - 1]), ws.i(p.e_h[i - 1]), W, 0, W, 0, st));
-      RC(red_add_elem2d(rq.elem, mg.slab, mg.sp.ns, mg.stride, W, p.Ep, p.Ep, gp + p.w_tr[i], p.k_tr[i]));
-      RC(red_add_elem2d(rq.elem, mh.slab, mh.sp.ns, mh.stride, W, W, W, gp + p.w_tr[i] + p.Ep, p.k_tr[i]));
+    const BwdRegions::Layer& t = r.tr[i];
+    if (i > 0 && ((p.skip_mask >> i) & 1u)) {   // [W_gamma | W_h]: two slab regions (take_regions), each reduced into its columns
+      RC(dw_gemm(t.w_gamma, dz_cur, W, false, p.pe, 0, p.Ep));
+      RC(dw_gemm(t.w, dz_cur, W, false, p.h[i - 1], 0, W));
+      RC(red_add_elem2d(rq.elem, t.w_gamma.slab, t.w_gamma.sp.ns, t.w_gamma.stride, W, p.Ep, p.Ep, gp + p.w_tr[i], p.k_tr[i]));
+      RC(red_add_elem2d(rq.elem, t.w.slab, t.w.sp.ns, t.w.stride, W, W, W, gp + p.w_tr[i] + p.Ep, p.k_tr[i]));
     } else {
-      const DwMat mt = dw_begin(p, rq, W, p.k_tr[i], i == 0 ? p.Ep : W, false);
-      if (i == 0) RC(dw_gemm(p, mt, dz_cur, edz_cur, W, 0, W, false, ws.c(p.o_pe), ws.i(p.e_pe), p.Ep, 0, p.Ep, 0, st));
-      else RC(dw_gemm(p, mt, dz_cur, edz_cur, W, 0, W, false, ws.c(p.o_h[i - 1]), ws.i(p.e_h[i - 1]), W, 0, W, 0, st));
-      RC(dw_reduce(rq, mt, (size_t)W * p.k_tr[i], gp + p.w_tr[i]));
+      if (i == 0) RC(dw_gemm(t.w, dz_cur, W, false, p.pe, 0, p.Ep));
+      else RC(dw_gemm(t.w, dz_cur, W, false, p.h[i - 1], 0, W));
+      RC(dw_reduce(t.w, (size_t)W * p.k_tr[i], gp + p.w_tr[i]));
     }
     if (i == 0) break;
     bsp::KcArgs g;
-    g.A = dz_cur; g.EA = edz_cur; g.lda = W; g.Ka = W; weights(g, p, pk, p.wj_tt[i]);
-    g.I = P; g.J = W; g.K = W; g.C = dz_nxt; g.EC = edz_nxt; g.ldc = W;
-    dact(g, p.o_c[i - 1], p.o_h[i - 1], p.e_h[i - 1], W, 0, (i - 1 == 0) ? 30.f : 1.f);
-    cs_ = colsum(g, W);
+    ws.a(g, dz_cur, W); weights(g, p, pk, p.wj_tt[i]);
+    g.I = P; g.J = W; g.K = W; ws.out(g, dz_nxt);
+    dact(g, p.h[i - 1], 0, (i - 1 == 0) ? 30.f : 1.f);
+    colsum(g, t.cs, W);
     RC(launch_kc(g));
-    RC(bias_from_colsum(p, rq, cs_, W, gp + p.b_tr[i - 1]));
-    char* t = dz_cur; dz_cur = dz_nxt; dz_nxt = t;
-    int* te = edz_cur; edz_cur = edz_nxt; edz_nxt = te;
+    RC(bias_from_colsum(t.cs, W, gp + p.b_tr[i - 1]));
+    const PlaneT sw = dz_cur; dz_cur = dz_nxt; dz_nxt = sw;
   }
-  if (rq.over) { set_error("reduction arena too small (plan / pass mismatch)"); return SNERF_ERR_WORKSPACE; }
   return launch_reductions(rq.elem, rq.col, st);
-}
-
-// weight operand packs of the default arithmetic: table of jobs for bsp::launch_wpack (offsets into the fp32 region)
-void build_wjobs(const Plan& p, bsp::WPackTable& tb) {
-  tb.n = p.n_wjobs;
-  auto set = [&](int j, size_t src_off, int src_ld, int transposed, int m_rows, int m_cols) {
-    bsp::WPackJob& w = tb.j[j];
-    w.src_off = src_off; w.src_ld = src_ld; w.rows = p.wj_rows[j]; w.K = p.wj_K[j]; w.transposed = transposed;
-    w.dst_off = p.wj_off[j]; w.e_idx = p.wj_e[j]; w.m_rows = m_rows; w.m_cols = m_cols;
-  };
-  const int W = p.W, H = p.H;
-  for (int i = 0; i < p.L; ++i) {
-    set(p.wj_tr[i], p.w_tr[i], p.k_tr[i], 0, W, p.k_tr[i]);
-    if (i > 0) set(p.wj_tt[i], p.w_tr[i] + (((p.skip_mask >> i) & 1u) ? p.Ep : 0), p.k_tr[i], 1, W, W);
-  }
-  set(p.wj_fs, p.w_fs, W, 0, W, W);
-  set(p.wj_sig, p.w_fs + (size_t)W * W, W, 0, NARROW, W);
-  set(p.wj_tfs, p.w_fs, W, 1, W + NARROW, W);
-  set(p.wj_h1, p.w_h1, p.FA, 0, p.N1, p.FA);
-  set(p.wj_th1, p.w_h1, p.FA, 1, p.N1, p.FA);
-  set(p.wj_s2, p.w_s2, H, 0, H, H); set(p.wj_ts2, p.w_s2, H, 1, H, H);
-  set(p.wj_s3, p.w_s3, H, 0, H, H); set(p.wj_ts3, p.w_s3, H, 1, H, H);
-  set(p.wj_s4, p.w_s4, H, 0, NARROW, H); set(p.wj_ts4, p.w_s4, H, 1, NARROW, H);
-  set(p.wj_fin, p.w_fin, p.KF, 0, NARROW, p.KF); set(p.wj_tfin, p.w_fin, p.KF, 1, NARROW, p.KF);
 }
 
 }  // namespace snerf

@@ -2,6 +2,7 @@
 // Everything the kernels index is computed here once per call, so host code can check every
 // operand shape before a launch (a faulting kernel can reset the node).
 #pragma once
+#include "bsp.h"
 #include "common.h"
 #include "../../include/snerf_hip.h"
 
@@ -11,6 +12,17 @@ constexpr int NARROW = 32;   // padded width of the 1..(5+C)-wide head outputs
 constexpr int MAX_CLASSES = 16;
 constexpr int ND_FIN = 5;       // projections per column tile of a folded final-layer launch (bsp_kc.hip: NDOT = 5)
 constexpr int MAX_SKY_UNITS = 8;  // feat_last <= 512 (units per lane in the composite kernels)
+
+// One block-scaled plane tensor of the workspace (csrc/bsp.h), byte offsets: its planes [Pp][ld], its exponent table and, for the
+// activations a SIREN training pass keeps, the sign words of cos (0: none).  ld is the leading dimension it was allocated with and
+// the only one it is ever used with.
+struct PlaneT { size_t o = 0, e = 0, s = 0; int ld = 0; };
+// Backward scratch sized for the widest gradient tensor (maxw columns).  It is VIEWED at the leading dimension of the tensor that
+// lives in it at the time (h1w, W, FA) -- the exponent table is indexed by that ld -- so it has none of its own: view(ld) at the use site.
+struct PlaneScratch {
+  size_t o = 0, e = 0; int maxw = 0;
+  PlaneT view(int ld) const { PlaneT t; t.o = o; t.e = e; t.ld = ld; return t; }
+};
 
 struct Plan {
   // dims
@@ -47,9 +59,10 @@ struct Plan {
                      // 1 = SNERF_FLAG_F16X1 (reduced precision)
 
   // workspace layout (byte offsets)
-  size_t o_z = 0, o_T = 0, o_rgbraw = 0, o_pe = 0, o_fa = 0, o_h1 = 0, o_c1 = 0;
-  size_t o_h[SNERF_MAX_LAYERS] = {0}, o_c[SNERF_MAX_LAYERS] = {0};
-  size_t o_s2 = 0, o_s3 = 0, o_cs2 = 0, o_cs3 = 0;
+  size_t o_z = 0, o_T = 0, o_rgbraw = 0;
+  // block-scaled plane tensors: gamma(x) [Ep], [feats | sun | t | t_s] [FA], the fused first head layer [h1w], the sun-visibility
+  // layers 2, 3 [H], the trunk layers [W] (inference: two buffers in turn)
+  PlaneT pe, fa, h1, s2, s3, h[SNERF_MAX_LAYERS];
   size_t o_sigo = 0, o_fino = 0, o_suno = 0;
   // sigma / sun-visibility pre-activations as partial dot products of the producing SIREN launches' epilogues (bsp_kc.hip: NDOT):
   // [4 * (W / 256)][Pp] and [4 * (H / 256)][Pp] floats; folded when the producing layer is a SIREN layer of whole 256-column tiles
@@ -59,28 +72,22 @@ struct Plan {
   // of 64 columns; training passes leave every layer's planes / sign words for the backward pass (round 5)
   bool fuse_trunk = false;
   bool nd_fin = false;   // the final layers of the rgb / semantic / beta heads ride in the fused first head layer's epilogue (H = 256: one column tile per head)
-  // backward scratch
-  size_t o_dza = 0, o_dzb = 0, o_dsa = 0, o_dsb = 0, o_dsig = 0, o_dfin = 0, o_dsun = 0;
+  // backward scratch: two regions of the widest gradient tensor, two of the sun-visibility chain [H], the 32-wide pre-activation
+  // gradients as fp32 (o_d*) and as planes (pd*: the dX / dW operands)
+  PlaneScratch dza, dzb;
+  PlaneT dsa, dsb, pdsig, pdfin, pdsun;
+  size_t o_dsig = 0, o_dfin = 0, o_dsun = 0;
   size_t o_skyslab = 0;
   size_t o_kcq = 0;                 // tile counters of the K-contiguous launches: KCQ_SLOTS slots of 64 bytes, zeroed at the start of a pass
   size_t o_rq = 0, rq_floats = 0;   // reduction arena of the block-scaled plane backward (bsp_pass.hip: per-launch slabs / column-sum partials)
-  // ---- block-scaled plane layout (csrc/bsp.h): every activation buffer above holds G16 planes and has an exponent table; the
-  //      32-wide head gradients also exist as planes
-  size_t e_pe = 0, e_fa = 0, e_h1 = 0, e_s2 = 0, e_s3 = 0, e_h[SNERF_MAX_LAYERS] = {0};
-  size_t e_dza = 0, e_dzb = 0, e_dsa = 0, e_dsb = 0, e_dsig = 0, e_dfin = 0, e_dsun = 0;
-  size_t o_pdsig = 0, o_pdfin = 0, o_pdsun = 0;          // planes [Pp][32] of the narrow gradients
-  // weight operand packs (WF16) behind the fp32 region of the packed buffer
-  enum { WJ_MAX = 48 };
-  int n_wjobs = 0;
+  // weight operands: every K-contiguous GEMM's B (a matrix or its transpose) as a WF16 pack behind the fp32 region of the packed buffer.
+  // ONE table: what the pack kernels need (where the fp32 master lies) and what a launch needs (pack offset, rows, K, exponent slot)
+  bsp::WPackTable wj = {};
   int wj_tr[SNERF_MAX_LAYERS] = {0}, wj_tt[SNERF_MAX_LAYERS] = {0};
   int wj_fs = 0, wj_sig = 0, wj_tfs = 0, wj_h1 = 0, wj_th1 = 0, wj_s2 = 0, wj_ts2 = 0, wj_s3 = 0, wj_ts3 = 0, wj_s4 = 0, wj_ts4 = 0,
       wj_fin = 0, wj_tfin = 0;
-  unsigned long long wj_off[WJ_MAX] = {0};   // byte offset of each pack inside the plane region
-  int wj_rows[WJ_MAX] = {0}, wj_K[WJ_MAX] = {0}, wj_e[WJ_MAX] = {0};
-  size_t wp_bytes = 0;                       // plane region size; then WJ_MAX exponents (int) and WJ_MAX |max| words
+  size_t wp_bytes = 0;                       // plane region size; then WPACK_MAX exponents (int) and WPACK_MAX |max| words
   int h1w = 0;       // width of the h1 buffer in this pass (N1, or H for the sc pass)
-  int maxw = 0;      // widest dz buffer
-  int nrb = 0;       // 32-row blocks (colsum partials)
   int comp_blocks = 0;
   size_t ws_bytes = 0;
 };
@@ -88,6 +95,8 @@ struct Plan {
 constexpr int KCQ_SLOTS = 64;
 struct DwSplit { int ns = 1; int k_split = 32; };
 DwSplit dw_choose_bsp(int P, int rows, int cols, bool narrow_rows);
+
+#define RC(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)   // hand a callee's error code on
 
 // returns SNERF_OK or an error (message via set_error)
 int make_plan(const SnerfDesc* d, Plan* pl);

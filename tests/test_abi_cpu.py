@@ -105,6 +105,33 @@ def test_plan_builder_over_model_variants_and_null_arguments():
     assert L.snerf_grad_floats(C.byref(bad)) == 0 and L.snerf_workspace_bytes(C.byref(bad)) == 0
 
 
+def test_plan_sizes_are_frozen():
+    """The layout the plan gives is part of what a refactor of the plan / pass host code must keep: the packed parameter buffer, the
+    gradient buffer and the workspace of every recorded descriptor have the sizes of tests/golden/plan_sizes.json (recorded by
+    tools/gen_golden_plan.py from a build of the commit named in the file), and every descriptor refused there is refused with
+    the same message.  The sweep: the variants x flag sets x (N, S) of the test above, the five BASELINE.json shapes, 1 / 3 / 16 layers, a
+    skip at the last layer, 0 / 9 / 16 classes, a width with no folded narrow projections, a separate t_s, both arithmetic modes."""
+    import json
+    from snerf_amd import _lib
+    from snerf_amd.ops import ModelSpec
+    L = _lib.lib()
+    doc = json.load(open(os.path.join(ROOT, "tests", "golden", "plan_sizes.json")))
+    assert doc["fields"] == [f for f, _ in _lib.SnerfDesc._fields_]
+    cases = doc["cases"]
+    assert len(cases) == 310 and sum(c["error"] is not None for c in cases) == 12
+    assert {c["group"] for c in cases} == {"variants", "baseline", "shapes"}
+    assert {(c["desc"][0], c["desc"][1]) for c in cases if c["group"] == "baseline"} == {(512, 32), (4096, 64), (8192, 96), (16384, 128), (32768, 128)}
+    for c in cases:
+        d = _lib.SnerfDesc(*c["desc"])
+        spec = {k: tuple(v) if isinstance(v, list) else v for k, v in c["spec"].items()}
+        again = ModelSpec(**spec).desc(d.n_rays, d.n_samples, d.flags)
+        assert bytes(again) == bytes(d), c                               # the recorded descriptor is the one the spec gives today
+        got = [L.snerf_packed_floats(C.byref(d)), L.snerf_grad_floats(C.byref(d)), L.snerf_workspace_bytes(C.byref(d))]
+        assert got == c["sizes"], (c["spec"], c["desc"], got, c["sizes"])
+        if c["error"] is not None:
+            assert got == [0, 0, 0] and L.snerf_last_error().decode() == c["error"], (c["desc"], L.snerf_last_error())
+
+
 def test_one_plane_mode_refuses_raw_xyz():
     """SNERF_FLAG_F16X1 with n_freq = 0 (SatNeRF's raw xyz) is refused by name: one fp16 plane rounds the coordinates entering the
     w0 = 30 first layer to 11 bits (sigma off by 5e-3 against the fp64 oracle).  The default arithmetic, and the one-plane mode with any
