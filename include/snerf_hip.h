@@ -433,6 +433,9 @@ int snerf_test_bsp_kc(const float* A, const float* A2, int Ka, const float* W, c
  * 256-column tile): nd_w [sum nd_rows][J], nd_out [ceil(J/256)*4*5][I] -- the folded final head layers */
 int snerf_test_bsp_dw(const float* A, int lda_src, const float* B, int ldb_src, int P, int I, int J, int a_col0, int b_col0,
                       int k_split, int narrow_i, float* C, int planes, void* stream);
+/* planes = 0: no plane tensors -- one launch of the small fp32 GEMM on the WEIGHTS of the composed first head layer, with the job table
+ * the pack (narrow_i = 0: compose) / a backward pass (narrow_i = 1: un-compose) builds; I = rows of the layer or of a row block of it,
+ * J = FA, P = W; A, B, C: concatenated fp32 operands (csrc/test_hooks.hip lists them) */
 
 #ifdef __cplusplus
 }

@@ -2,7 +2,10 @@
 // pass (its launch sequences: bsp_pass.hip; the single-kernel test hooks: test_hooks.hip).
 #include <stdarg.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
+
+#include <mutex>
 
 #include "aux_kernels.h"
 #include "bsp.h"
@@ -61,19 +64,39 @@ static void plan_weights(Plan& p) {
     return p.wj.n++;
   };
   const int W = p.W, H = p.H;
+  if (p.compose_feats) {
+    // The first head layer's two operands come from the composed matrix, a pack-time fp32 scratch: W_c [N1][FA] and, behind it, the 32
+    // sigma rows (columns [0, W)), so that the transposed pack serves the merged dX launch  dz_last = [dz1 | d sigma] [W_c[:, :W]; w_sigma]
+    // at k = N1 (the sun block is the last of W_c: the sc pass reads k from sun_col on).  The scratch lies under the packs of the other
+    // operands, which are written after these two have been packed from it.
+    const int e1 = ne++, e2 = ne++;   // an exponent each: the transposed operand's matrix has the sigma rows, the plain one's has not
+    p.wj_h1 = op(e1, 0, p.FA, p.N1, p.FA);
+    p.wj_th1 = op(e2, 0, p.FA, p.N1 + NARROW, p.FA, 3);
+    p.wj_first = p.wj.n;
+    p.o_wc = p.n_fp32 + round_up_sz(off, 256) / 4;
+    p.wj.j[p.wj_h1].src_off = p.wj.j[p.wj_th1].src_off = p.o_wc;
+  }
   for (int i = 0; i < p.L; ++i) {   // the transpose of a skip layer [gamma | h]: its h columns only (dX of the layer below)
     const int e = ne++;
     p.wj_tr[i] = op(e, p.w_tr[i], p.k_tr[i], W, p.k_tr[i]);
     p.wj_tt[i] = i > 0 ? op(e, p.w_tr[i] + (((p.skip_mask >> i) & 1u) ? p.Ep : 0), p.k_tr[i], W, W, 1) : -1;
   }
-  { const int e = ne++; p.wj_fs = op(e, p.w_fs, W, W, W); p.wj_sig = op(e, p.w_fs + (size_t)W * W, W, NARROW, W); p.wj_tfs = op(e, p.w_fs, W, W + NARROW, W, 1); }
-  { const int e = ne++; p.wj_h1 = op(e, p.w_h1, p.FA, p.N1, p.FA); p.wj_th1 = op(e, p.w_h1, p.FA, p.N1, p.FA, 1); }
+  if (p.compose_feats) { p.wj_fs = p.wj_tfs = -1; p.wj_sig = op(ne++, p.w_fs + (size_t)W * W, W, NARROW, W); }
+  else {
+    { const int e = ne++; p.wj_fs = op(e, p.w_fs, W, W, W); p.wj_sig = op(e, p.w_fs + (size_t)W * W, W, NARROW, W); p.wj_tfs = op(e, p.w_fs, W, W + NARROW, W, 1); }
+    { const int e = ne++; p.wj_h1 = op(e, p.w_h1, p.FA, p.N1, p.FA); p.wj_th1 = op(e, p.w_h1, p.FA, p.N1, p.FA, 1); }
+  }
   { const int e = ne++; p.wj_s2 = op(e, p.w_s2, H, H, H); p.wj_ts2 = op(e, p.w_s2, H, H, H, 1); }
   { const int e = ne++; p.wj_s3 = op(e, p.w_s3, H, H, H); p.wj_ts3 = op(e, p.w_s3, H, H, H, 1); }
   { const int e = ne++; p.wj_s4 = op(e, p.w_s4, H, NARROW, H); p.wj_ts4 = op(e, p.w_s4, H, NARROW, H, 1); }
   { const int e = ne++; p.wj_fin = op(e, p.w_fin, p.KF, NARROW, p.KF); p.wj_tfin = op(e, p.w_fin, p.KF, NARROW, p.KF, 1); }
+  if (p.compose_feats) {   // the scratch may reach beyond the last pack (narrow trunks under wide heads)
+    const size_t end = (p.o_wc - p.n_fp32) * 4 + (size_t)(p.N1 + NARROW) * p.FA * 4;
+    if (end > off) off = end;
+  }
   p.wp_bytes = round_up_sz(off, 256);
   p.packed_floats = p.n_fp32 + (p.wp_bytes + 2 * bsp::WPACK_MAX * 4 + 256) / 4;
+  if (p.compose_feats) { p.o_bc = p.packed_floats; p.packed_floats += round_up_sz(p.N1, 64); }
 }
 
 static void plan_bsp(Plan& p) {
@@ -96,7 +119,7 @@ static void plan_bsp(Plan& p) {
   p.o_rgbraw = wtake((size_t)p.N * 3 * 4);
   p.pe = tensor(p.Ep);
   if (p.train) {
-    for (int i = 0; i < p.L; ++i) p.h[i] = tensor(p.W, keep_c);
+    for (int i = 0; i < p.L - (p.compose_feats ? 1 : 0); ++i) p.h[i] = tensor(p.W, keep_c);
   } else {   // inference keeps no layer: two buffers in turn
     PlaneT a, b;
     a.ld = b.ld = p.W;
@@ -104,6 +127,13 @@ static void plan_bsp(Plan& p) {
     for (int i = 0; i < p.L; ++i) p.h[i] = (i & 1) ? b : a;
   }
   p.fa = tensor(p.FA);
+  if (p.compose_feats) {
+    // The last trunk layer stores its planes where feats went: columns [0, W) of the [P][FA] tensor, so that the first head layer reads
+    // [h_last | extras] as it read [feats | extras] -- no pass over memory added.  h[L - 1] is that tensor at leading dimension FA
+    // (its sign words, for a SIREN training pass, are laid out for FA columns).
+    p.h[p.L - 1] = p.fa;
+    p.h[p.L - 1].s = keep_c ? wtake(bsp::sign_words(Pp, p.FA) * 4) : 0;
+  }
   p.h1 = tensor(p.h1w, keep_c);
   p.s2 = tensor(p.H, keep_c);
   p.s3 = tensor(p.H, keep_c);
@@ -212,8 +242,25 @@ int make_plan(const SnerfDesc* d, Plan* pl) {
   p.sky_floats = 9 * p.H + 4;
   p.sky = take(p.sky_floats);
   p.n_fp32 = off;
+  {  // SNERF_COMPOSE_FEATS=0: the separate feats layer.  The merged dX launch reads [dz1 | d sigma] as two A segments, the first a whole
+     // number of 32-column LDS stages: h1w % 32 == 0, that is feat_last % 32 == 0 (KF is a multiple of 128), and contracts N1 + 32 columns
+     // in the main pass, within the K-contiguous kernel's 2048 (its exponent table along k: feat_last = 512 with four blocks has
+     // N1 = 2048).  Other shapes stay separate.  The condition reads the model's dimensions only: pack, main and sc pass decide alike.
+    const char* ev = getenv("SNERF_COMPOSE_FEATS");
+    p.compose_feats = p.pl == 2 && (p.H & 31) == 0 && p.N1 + NARROW <= 2048 && !(ev && ev[0] == '0' && ev[1] == 0);
+  }
+  if (!p.compose_feats) { plan_weights(p); plan_bsp(p); return SNERF_OK; }
+  // A composed plan reports no smaller buffers than the separate plan of the same descriptor: buffers sized under either setting of the
+  // switch serve both.  Both layouts are planned for that (two walks of host arithmetic over ~20 tensors and ~30 pack jobs per API
+  // call, no device work): simple, and small beside the ~40 launches a call queues.
+  Plan q = p;
+  q.compose_feats = false;
+  plan_weights(q);
+  plan_bsp(q);
   plan_weights(p);
   plan_bsp(p);
+  if (q.packed_floats > p.packed_floats) p.packed_floats = q.packed_floats;
+  if (q.ws_bytes > p.ws_bytes) p.ws_bytes = q.ws_bytes;
   return SNERF_OK;
 }
 
@@ -281,6 +328,38 @@ static void build_tables(const Plan& p, const SnerfParams* w, TableBuilder& tb) 
   tb.add(w->sky_b2, 3, 1, 3, p.sky + 9 * (size_t)H, 3);
 }
 
+// Pack, forward and backward of one step must be planned under the same setting of SNERF_COMPOSE_FEATS: the packed buffer holds either
+// the separate or the composed operands, the workspace either layout.  The library remembers, per buffer address, which plan wrote it
+// last (host side, at call time -- also under stream capture) and refuses a reader planned the other way.  A buffer it has not seen
+// (a copy made by the caller) is taken on trust.
+// Limits, by construction: the table is process-wide, holds the 256 addresses noted last and never learns that a buffer was freed.  So the
+// check is best effort in both directions -- a mismatch on an address evicted since goes unnoticed, and a buffer the CALLER filled (a
+// clone of packed parameters) at an address last noted under the other setting is refused wrongly.  Both need the switch to change inside
+// one process, which only tests do; a process that keeps one setting never sees either.
+namespace {
+struct BufNote { const void* p; bool composed; };
+constexpr int NOTE_MAX = 256;
+BufNote g_notes[NOTE_MAX];
+int g_n_notes = 0, g_note_next = 0;
+std::mutex g_note_mu;
+void note_plan(const void* buf, bool composed) {
+  std::lock_guard<std::mutex> lk(g_note_mu);
+  for (int i = 0; i < g_n_notes; ++i) if (g_notes[i].p == buf) { g_notes[i].composed = composed; return; }
+  if (g_n_notes < NOTE_MAX) g_notes[g_n_notes++] = {buf, composed};
+  else { g_notes[g_note_next] = {buf, composed}; g_note_next = (g_note_next + 1) % NOTE_MAX; }   // oldest first
+}
+int check_plan_note(const void* buf, bool composed, const char* who, const char* what) {
+  std::lock_guard<std::mutex> lk(g_note_mu);
+  for (int i = 0; i < g_n_notes; ++i)
+    if (g_notes[i].p == buf && g_notes[i].composed != composed) {
+      set_error("%s: the %s was written under SNERF_COMPOSE_FEATS=%d, this call is planned with %d (pack, forward and backward must agree)",
+                who, what, g_notes[i].composed ? 1 : 0, composed ? 1 : 0);
+      return SNERF_ERR_BAD_DESC;
+    }
+  return SNERF_OK;
+}
+}  // namespace
+
 static int check_inputs(const Plan& p, const SnerfInputs* in) {
   if (!in) { set_error("null inputs"); return SNERF_ERR_NULL; }
   if (!in->sun_d || in->sun_stride < 3) { set_error("sun_d (N,3) with stride >= 3 is required"); return SNERF_ERR_NULL; }
@@ -337,7 +416,22 @@ int snerf_pack_params(const SnerfDesc* desc, const SnerfParams* params, float* p
   // launches over a job table (|max| pass, pack pass)
   char* planes = reinterpret_cast<char*>(packed + p.n_fp32);
   int* exps = reinterpret_cast<int*>(planes + p.wp_bytes);
-  return bsp::launch_wpack(p.wj, packed, planes, exps, reinterpret_cast<unsigned*>(exps + bsp::WPACK_MAX), p.pl, st);
+  unsigned* maxbits = reinterpret_cast<unsigned*>(exps + bsp::WPACK_MAX);
+  note_plan(packed, p.compose_feats);
+  if (!p.compose_feats) return bsp::launch_wpack(p.wj, packed, planes, exps, maxbits, p.pl, st);
+  // Compose: W_c = [A W_f | W_h1[:, W:]] with A = W_h1[:, :W], the sigma rows behind it, b_c = b_h1 + A b_f -- once per pack, for the main
+  // and the sc pass alike (the sc pass reads the sun block's rows).  One launch of the small fp32 GEMM; then the two operands packed
+  // from the scratch, then every other operand (their packs overwrite the scratch).
+  {
+    bsp::SgTable tb;
+    bsp::compose_jobs(tb, packed + p.w_h1, packed + p.w_fs, packed + p.b_fs, packed + p.b_h1, packed + p.o_wc, packed + p.o_bc, p.W, p.FA, p.N1);
+    RC(bsp::launch_sgemm(tb, 64, st));
+  }
+  bsp::WPackTable first, rest;
+  first.n = rest.n = 0;
+  for (int i = 0; i < p.wj.n; ++i) (i < p.wj_first ? first.j[first.n++] : rest.j[rest.n++]) = p.wj.j[i];
+  RC(bsp::launch_wpack(first, packed, planes, exps, maxbits, p.pl, st));
+  return bsp::launch_wpack(rest, packed, planes, exps, maxbits, p.pl, st);
 }
 
 int snerf_unpack_grads(const SnerfDesc* desc, const float* packed_grads, const SnerfParams* grads, int accumulate,
@@ -361,6 +455,8 @@ int snerf_forward(const SnerfDesc* desc, const float* packed_params, const Snerf
   if (workspace_bytes < p.ws_bytes) { set_error("snerf_forward: workspace too small (%zu < %zu)", workspace_bytes, p.ws_bytes); return SNERF_ERR_WORKSPACE; }
   if (((uintptr_t)workspace & 255) || ((uintptr_t)packed_params & 255)) { set_error("workspace and packed params must be 256-byte aligned"); return SNERF_ERR_WORKSPACE; }
   RC(check_inputs(p, in));
+  RC(check_plan_note(packed_params, p.compose_feats, "snerf_forward", "packed parameter buffer"));
+  note_plan(workspace, p.compose_feats);
   return forward_bsp(p, packed_params, in, out, workspace, (hipStream_t)stream);
 }
 
@@ -373,6 +469,8 @@ int snerf_backward(const SnerfDesc* desc, const float* packed_params, const Sner
   if (workspace_bytes < p.ws_bytes) { set_error("snerf_backward: workspace too small (%zu < %zu)", workspace_bytes, p.ws_bytes); return SNERF_ERR_WORKSPACE; }
   if (((uintptr_t)workspace & 255) || ((uintptr_t)packed_params & 255) || ((uintptr_t)packed_grads & 255)) { set_error("workspace and packed buffers must be 256-byte aligned"); return SNERF_ERR_WORKSPACE; }
   RC(check_inputs(p, in));
+  RC(check_plan_note(packed_params, p.compose_feats, "snerf_backward", "packed parameter buffer"));
+  RC(check_plan_note(workspace, p.compose_feats, "snerf_backward", "workspace"));
   return backward_bsp(p, packed_params, in, gout, packed_grads, d_t, d_t_s, workspace, (hipStream_t)stream);
 }
 

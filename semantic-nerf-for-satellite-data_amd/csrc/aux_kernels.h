@@ -31,7 +31,7 @@ int reduce_partials(const float* in, int n_in, size_t in_stride, int width, floa
 // batched reductions (aux_kernels.hip): out[e] += sum_q in[q * stride + e], all jobs of a pass in two launches
 // (cols / in_ld / out_ld: a 2-D job -- element e = r * cols + c lies at in[q * stride + r * in_ld + c] and goes to out[r * out_ld + c];
 //  1-D jobs have cols = width)
-struct RedJob { const float* in; float* out; unsigned long long stride; long long width; int n_in; int blk0; int vec; int cols; int in_ld; int out_ld; int pad[2]; };
+struct RedJob { const float* in; float* out; unsigned long long stride; long long width; int n_in; int blk0; int vec; int cols; int in_ld; int out_ld; int store; int pad; };   // store: out = sum (not +=); out may be the first slab / row of in
 constexpr int RED_MAX = 56;
 struct RedTable { RedJob j[RED_MAX]; int n = 0; int blocks = 0; };      // host-side queue
 constexpr int RED_CHUNK = 24;
@@ -39,6 +39,7 @@ struct RedChunk { RedJob j[RED_CHUNK]; int n = 0; };                      // wha
 int red_add_elem(RedTable& tb, const float* in, int n_in, size_t stride, size_t width, float* out);   // few slabs, many elements
 int red_add_elem2d(RedTable& tb, const float* in, int n_in, size_t stride, int rows, int cols, int in_ld, float* out, int out_ld);   // a column block of a wider matrix
 int red_add_col(RedTable& tb, const float* in, int n_in, size_t stride, int width, float* out);       // many partial rows, <= ~1024 columns
+int red_store_last(RedTable& tb);   // the job queued last stores its sum instead of adding it
 int launch_reductions(const RedTable& elem, const RedTable& col, hipStream_t st);
 int launch_ray_sum32(const float* d32, int col0, int N, int S, int tau, float* out, hipStream_t st);   // out[n][c] = sum_s d32[(n S + s)][col0 + c], rows of 32 floats
 int launch_embedding_rows(const float* table, int n_embed, int tau, const long long* idx, int n, float* rows, hipStream_t st);

@@ -260,7 +260,7 @@ __global__ __launch_bounds__(256) void reduce_elem_jobs_kernel(const RedChunk tb
     }
     if (q < jb.n_in) { const float4 a = *reinterpret_cast<const float4*>(jb.in + (size_t)q * jb.stride + e); s0.x += a.x; s0.y += a.y; s0.z += a.z; s0.w += a.w; }
     float4* o = reinterpret_cast<float4*>(jb.out + eo);
-    float4 v = *o;
+    float4 v = jb.store ? make_float4(0.f, 0.f, 0.f, 0.f) : *o;
     v.x += s0.x + s1.x; v.y += s0.y + s1.y; v.z += s0.z + s1.z; v.w += s0.w + s1.w;
     *o = v;
   } else {
@@ -268,7 +268,7 @@ __global__ __launch_bounds__(256) void reduce_elem_jobs_kernel(const RedChunk tb
     int q = 0;
     for (; q + 1 < jb.n_in; q += 2) { s0 += jb.in[(size_t)q * jb.stride + e]; s1 += jb.in[(size_t)(q + 1) * jb.stride + e]; }
     if (q < jb.n_in) s0 += jb.in[(size_t)q * jb.stride + e];
-    jb.out[eo] += s0 + s1;
+    jb.out[eo] = (jb.store ? 0.f : jb.out[eo]) + (s0 + s1);
   }
 }
 
@@ -296,7 +296,7 @@ __global__ __launch_bounds__(256) void reduce_col_jobs_kernel(const RedChunk tb)
     float s = 0.f;
 #pragma unroll
     for (int g = 0; g < 16; ++g) s += part[g][c];
-    jb.out[j] += s;
+    jb.out[j] = (jb.store ? 0.f : jb.out[j]) + s;
   }
 }
 
@@ -307,6 +307,7 @@ int red_add_elem(RedTable& tb, const float* in, int n_in, size_t stride, size_t 
   j.in = in; j.out = out; j.stride = stride; j.n_in = n_in; j.width = (long long)width; j.blk0 = tb.blocks;
   j.cols = (int)(width < 0x7fffffff ? width : 0x7fffffff); j.in_ld = j.out_ld = 0;
   if ((long long)j.cols != j.width) { set_error("reduction job too wide"); return SNERF_ERR_WORKSPACE; }
+  j.store = 0; j.pad = 0;
   j.vec = ((width & 3) == 0 && (stride & 3) == 0 && ((uintptr_t)in & 15) == 0 && ((uintptr_t)out & 15) == 0) ? 1 : 0;
   tb.blocks += (int)((width / (j.vec ? 4 : 1) + 255) / 256);
   return 0;
@@ -317,7 +318,7 @@ int red_add_elem2d(RedTable& tb, const float* in, int n_in, size_t stride, int r
   if (tb.n >= RED_MAX) { set_error("reduction queue full"); return SNERF_ERR_WORKSPACE; }
   RedJob& j = tb.j[tb.n++];
   j.in = in; j.out = out; j.stride = stride; j.n_in = n_in; j.width = (long long)rows * cols; j.blk0 = tb.blocks;
-  j.cols = cols; j.in_ld = in_ld; j.out_ld = out_ld;
+  j.cols = cols; j.in_ld = in_ld; j.out_ld = out_ld; j.store = 0; j.pad = 0;
   j.vec = ((cols & 3) == 0 && (in_ld & 3) == 0 && (out_ld & 3) == 0 && (stride & 3) == 0 && ((uintptr_t)in & 15) == 0 && ((uintptr_t)out & 15) == 0) ? 1 : 0;
   tb.blocks += (int)(((size_t)j.width / (j.vec ? 4 : 1) + 255) / 256);
   return 0;
@@ -327,7 +328,15 @@ int red_add_col(RedTable& tb, const float* in, int n_in, size_t stride, int widt
   if (tb.n >= RED_MAX) { set_error("reduction queue full"); return SNERF_ERR_WORKSPACE; }
   RedJob& j = tb.j[tb.n++];
   j.in = in; j.out = out; j.stride = stride; j.n_in = n_in; j.width = width; j.blk0 = tb.blocks; j.vec = 0;
+  j.cols = width; j.in_ld = j.out_ld = 0; j.store = 0; j.pad = 0;
   tb.blocks += (width + 15) / 16;
+  return 0;
+}
+// The sum of a job may go where its first slab (elem) / first partial row (col) lies: a thread reads all it sums before it writes,
+// and the col kernel's barrier orders its 16 row groups' reads before the one write per column.
+int red_store_last(RedTable& tb) {
+  if (tb.n <= 0) { set_error("reduction queue empty"); return SNERF_ERR_WORKSPACE; }
+  tb.j[tb.n - 1].store = 1;
   return 0;
 }
 // The job tables travel as kernel arguments in chunks of RED_CHUNK jobs (~1.2 KB): by-value arguments beyond ~2 KB did not

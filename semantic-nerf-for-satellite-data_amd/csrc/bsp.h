@@ -229,7 +229,7 @@ struct WPackJob {        // one weight operand: fp32 master matrix (possibly rea
   unsigned long long src_off;   // float offset of the matrix in the packed fp32 region
   int src_ld;                   // its leading dimension
   int rows, K;                  // rows x K of the OPERAND (K % 16 == 0); transposed: operand(r, k) = master(k, r)
-  int transposed;
+  int transposed;               // bit 0: read transposed; bit 1: the job takes the |max| of its own master (it shares its exponent slot with no plain job)
   unsigned long long dst_off;   // byte offset of the pack inside the plane region
   int e_idx;                    // exponent slot (shared by a matrix and its transpose)
   int m_rows, m_cols;           // extent of the master matrix (for the |max| pass)
@@ -240,6 +240,30 @@ constexpr int WPACK_CHUNK = 24;
 struct WPackChunk { WPackJob j[WPACK_CHUNK]; int n; };   // what one launch carries as its argument
 __host__ __device__ inline size_t wp16_bytes(int rows, int K, int pl = 2) { return (size_t)((rows + 31) / 32) * (size_t)(K / 16) * 1024 * pl; }
 int launch_wpack(const WPackTable& tb, const float* master, char* planes, int* exps, unsigned* maxbits, int pl, hipStream_t st);
+
+// ---- small fp32 GEMMs on the WEIGHTS (compose / un-compose of feats_from_xyz and the fused first head layer) ----------------------
+// C[i][j] = (acc ? C[i][j] : 0) + (D ? D[i ldd + j] : 0) + (u ? u[i] v[j] : 0) + sum_{k < K} A[i sa_i + k sa_k] B[k sb_k + j sb_j]
+// fp32 FMAs, k ascending in one accumulator per element: no atomics, no split, bitwise reproducible.  K = 0: a copy / zero fill / add.
+struct SgJob {
+  const float* A = nullptr; long long sa_i = 0, sa_k = 0;
+  const float* B = nullptr; long long sb_k = 0, sb_j = 0;
+  const float* D = nullptr; int ldd = 0;
+  const float* u = nullptr; const float* v = nullptr;
+  float* C = nullptr; int ldc = 0;
+  int M = 0, N = 0, K = 0, acc = 0;
+  int blk0 = 0;                 // first workgroup of the job (filled by launch_sgemm)
+};
+constexpr int SG_MAX = 6;
+struct SgTable { SgJob j[SG_MAX]; int n = 0; };          // ~0.7 KB as a kernel argument
+int launch_sgemm(const SgTable& tb, int tile_m, hipStream_t st);   // tile_m: 64 or 32 rows per workgroup (x 64 columns)
+// The two job tables of the composed first head layer, named once (api.hip: the pack; bsp_pass.hip: the end of a backward pass;
+// test_hooks.hip).  A = W_h1[:, :W] ([N1][FA] with its extras columns), w_f = [W_f; 32 sigma rows] ([W + 32][W]).
+//   compose:     wc [N1 + 32][FA] = [A W_f | W_h1[:, W:]; sigma rows | 0],  bc [N1] = b_h1 + A b_f
+//   un-compose:  dw_h1[:, :W] += G[:, :W] W_f^T + gc (x) b_f,  db_h1 += gc,  dw_f += A^T G[:, :W],  db_f += A^T gc   over the M rows given
+//                (G, w_h1 and dw_h1 at leading dimension FA: a row block of the layer is passed by its first row)
+void compose_jobs(SgTable& tb, const float* w_h1, const float* w_f, const float* b_f, const float* b_h1, float* wc, float* bc, int W, int FA, int N1);
+void uncompose_jobs(SgTable& tb, const float* G, const float* gc, const float* w_h1, const float* w_f, const float* b_f,
+                    float* dw_h1, float* db_h1, float* dw_f, float* db_f, int W, int FA, int M);
 
 }  // namespace bsp
 struct EncodeArgs;

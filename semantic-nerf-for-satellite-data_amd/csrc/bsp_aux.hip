@@ -85,7 +85,7 @@ int launch_from_planes(const char* src, const int* E, int ld, int col0, int rows
 // fragment of v_mfma_f32_32x32x16_f16 for 32 output columns, one contiguous KiB per plane.
 __global__ __launch_bounds__(256) void wmax_kernel(WPackChunk tb, const float* __restrict__ master, unsigned* __restrict__ maxbits) {
   const WPackJob j = tb.j[blockIdx.y];
-  if (j.transposed) return;            // its matrix is covered by the non-transposed job with the same exponent slot
+  if (j.transposed == 1) return;       // its matrix is covered by the non-transposed job with the same exponent slot
   float m = 0.f;
   // a wave per row (rows strided over the grid's waves), lanes along the row: coalesced, no index division per element (the
   // element-strided loop this replaces spent 43 us on 2.8 M parameters, most of it in 64-bit divisions)
@@ -140,6 +140,113 @@ int launch_wpack(const WPackTable& tb, const float* master, char* planes, int* e
       else hipLaunchKernelGGL(wpack_kernel, dim3(128, c.n), dim3(256), 0, st, c, master, planes, exps, maxbits, pl);
       SNERF_LAUNCH_CHECK();
     }
+  return SNERF_OK;
+}
+
+// ---- small fp32 GEMMs on the weights (bsp.h: SgJob) --------------------------------------------------------------------------------
+// LDS-tiled FMA: a workgroup owns a (16 TM) x 64 tile of one job, a thread TM x 4 of it; 16-deep k-steps through LDS, either operand
+// read along whichever of its two strides is 1 (compose: A W_f; un-compose: G W_f^T and A^T G).  Every load and store is bounds-checked
+// against M / N / K, so any shape is safe.  ~0.5 GFLOP per launch: 95 - 120 us measured at the headline shape (profiles/r06), beside GEMMs of 137 GFLOP.
+template <int TM>
+__global__ __launch_bounds__(256) void sgemm_jobs_kernel(const SgTable tb) {
+  constexpr int BM = 16 * TM, BN = 64, BK = 16;
+  __shared__ float As[BK][BM + 1];
+  __shared__ float Bs[BK][BN + 4];
+  int q = 0;
+  while (q + 1 < tb.n && (int)blockIdx.x >= tb.j[q + 1].blk0) ++q;
+  const SgJob jb = tb.j[q];
+  const int tiles_n = (jb.N + BN - 1) / BN;
+  const int tile = (int)blockIdx.x - jb.blk0;
+  const int i0 = (tile / tiles_n) * BM, j0 = (tile % tiles_n) * BN;
+  const int t = threadIdx.x, ty = t >> 4, tx = t & 15;
+  float acc[TM][4];
+#pragma unroll
+  for (int r = 0; r < TM; ++r)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) acc[r][c] = 0.f;
+  const bool a_k_fast = jb.sa_k == 1, b_j_fast = jb.sb_j == 1;
+  for (int k0 = 0; k0 < jb.K; k0 += BK) {
+#pragma unroll
+    for (int s = 0; s < (BM * BK) / 256; ++s) {
+      const int idx = t + 256 * s;
+      const int i = a_k_fast ? idx / BK : idx % BM, k = a_k_fast ? idx % BK : idx / BM;
+      As[k][i] = (i0 + i < jb.M && k0 + k < jb.K) ? jb.A[(long long)(i0 + i) * jb.sa_i + (long long)(k0 + k) * jb.sa_k] : 0.f;
+    }
+#pragma unroll
+    for (int s = 0; s < (BN * BK) / 256; ++s) {
+      const int idx = t + 256 * s;
+      const int j = b_j_fast ? idx % BN : idx / BK, k = b_j_fast ? idx / BN : idx % BK;
+      Bs[k][j] = (j0 + j < jb.N && k0 + k < jb.K) ? jb.B[(long long)(k0 + k) * jb.sb_k + (long long)(j0 + j) * jb.sb_j] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < BK; ++k) {
+      float a[TM], b[4];
+#pragma unroll
+      for (int r = 0; r < TM; ++r) a[r] = As[k][ty * TM + r];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) b[c] = Bs[k][tx * 4 + c];
+#pragma unroll
+      for (int r = 0; r < TM; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[r][c] = fmaf(a[r], b[c], acc[r][c]);
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int r = 0; r < TM; ++r) {
+    const int i = i0 + ty * TM + r;
+    if (i >= jb.M) continue;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int j = j0 + tx * 4 + c;
+      if (j >= jb.N) continue;
+      float x = acc[r][c];
+      if (jb.u) x = fmaf(jb.u[i], jb.v[j], x);
+      if (jb.D) x += jb.D[(size_t)i * jb.ldd + j];
+      float* o = jb.C + (size_t)i * jb.ldc + j;
+      *o = jb.acc ? *o + x : x;
+    }
+  }
+}
+
+void compose_jobs(SgTable& tb, const float* w_h1, const float* w_f, const float* b_f, const float* b_h1, float* wc, float* bc, int W, int FA, int N1) {
+  const int X = FA - W;
+  tb.n = 0;
+  auto job = [&]() -> SgJob& { tb.j[tb.n] = SgJob(); return tb.j[tb.n++]; };
+  { SgJob& j = job(); j.A = w_h1; j.sa_i = FA; j.sa_k = 1; j.B = w_f; j.sb_k = W; j.sb_j = 1; j.C = wc; j.ldc = FA; j.M = N1; j.N = W; j.K = W; }
+  { SgJob& j = job(); j.D = w_h1 + W; j.ldd = FA; j.C = wc + W; j.ldc = FA; j.M = N1; j.N = X; }                              // extras (and pad) columns as they are
+  { SgJob& j = job(); j.D = w_f + (size_t)W * W; j.ldd = W; j.C = wc + (size_t)N1 * FA; j.ldc = FA; j.M = 32; j.N = W; }       // sigma rows
+  { SgJob& j = job(); j.C = wc + (size_t)N1 * FA + W; j.ldc = FA; j.M = 32; j.N = X; }                                       // ... zero beside them
+  { SgJob& j = job(); j.A = w_h1; j.sa_i = FA; j.sa_k = 1; j.B = b_f; j.sb_k = 1; j.sb_j = 0; j.D = b_h1; j.ldd = 1; j.C = bc; j.ldc = 1; j.M = N1; j.N = 1; j.K = W; }
+}
+void uncompose_jobs(SgTable& tb, const float* G, const float* gc, const float* w_h1, const float* w_f, const float* b_f,
+                    float* dw_h1, float* db_h1, float* dw_f, float* db_f, int W, int FA, int M) {
+  tb.n = 0;
+  auto job = [&]() -> SgJob& { tb.j[tb.n] = SgJob(); return tb.j[tb.n++]; };
+  { SgJob& j = job(); j.A = G; j.sa_i = FA; j.sa_k = 1; j.B = w_f; j.sb_k = 1; j.sb_j = W; j.u = gc; j.v = b_f; j.C = dw_h1; j.ldc = FA; j.M = M; j.N = W; j.K = W; j.acc = 1; }
+  { SgJob& j = job(); j.A = w_h1; j.sa_i = 1; j.sa_k = FA; j.B = G; j.sb_k = FA; j.sb_j = 1; j.C = dw_f; j.ldc = W; j.M = W; j.N = W; j.K = M; j.acc = 1; }
+  { SgJob& j = job(); j.A = w_h1; j.sa_i = 1; j.sa_k = FA; j.B = gc; j.sb_k = 1; j.sb_j = 0; j.C = db_f; j.ldc = 1; j.M = W; j.N = 1; j.K = M; j.acc = 1; }
+  { SgJob& j = job(); j.D = gc; j.ldd = 1; j.C = db_h1; j.ldc = 1; j.M = M; j.N = 1; j.acc = 1; }
+}
+
+int launch_sgemm(const SgTable& tb0, int tile_m, hipStream_t st) {
+  if (tb0.n <= 0) return SNERF_OK;
+  if (tb0.n > SG_MAX || (tile_m != 64 && tile_m != 32)) { set_error("sgemm: bad job table"); return SNERF_ERR_BAD_DESC; }
+  SgTable tb = tb0;
+  int blocks = 0;
+  for (int q = 0; q < tb.n; ++q) {
+    SgJob& j = tb.j[q];
+    if (!j.C || j.M <= 0 || j.N <= 0 || j.K < 0 || j.ldc < 1 || (j.K > 0 && (!j.A || !j.B)) || (j.u && !j.v) || (j.D && j.ldd < 1)) {
+      set_error("sgemm: bad job %d", q);
+      return SNERF_ERR_BAD_DESC;
+    }
+    j.blk0 = blocks;
+    blocks += ((j.M + tile_m - 1) / tile_m) * ((j.N + 63) / 64);
+  }
+  if (tile_m == 64) hipLaunchKernelGGL(sgemm_jobs_kernel<4>, dim3(blocks), dim3(256), 0, st, tb);
+  else hipLaunchKernelGGL(sgemm_jobs_kernel<2>, dim3(blocks), dim3(256), 0, st, tb);
+  SNERF_LAUNCH_CHECK();
   return SNERF_OK;
 }
 

@@ -128,7 +128,9 @@ int forward_bsp(const Plan& p, const float* pk, const SnerfInputs* in, const Sne
     g.I = P; g.J = NARROW; g.K = W; g.Cf = ws.f(p.o_sigo); g.bias = pk + p.b_fs + W;
     RC(bsp::launch_kc_narrow(g, st));
   }
-  if (!fused || p.train) {  // feats (rs_semantic.py:338), written into the first W columns of the [feats | sun | t | t_s] tensor
+  // Composed plans (Plan::compose_feats) run no feats layer: h[L - 1] IS columns [0, W) of the [. | sun | t | t_s] tensor, and the first
+  // head layer below multiplies it by W_c = W_h1[:, :W] W_f with the bias b_c that the pack built.
+  if (!p.compose_feats && (!fused || p.train)) {  // feats (rs_semantic.py:338), written into the first W columns of the [feats | sun | t | t_s] tensor
     bsp::KcArgs g;
     ws.a(g, hl, W); weights(g, p, pk, p.wj_fs);
     g.I = P; g.J = W; g.K = W; ws.out(g, p.fa); g.bias = pk + p.b_fs;
@@ -139,7 +141,7 @@ int forward_bsp(const Plan& p, const float* pk, const SnerfInputs* in, const Sne
     bsp::KcArgs g;
     ws.a(g, p.fa, p.FA); weights(g, p, pk, p.wj_h1, r0);
     g.I = P; g.J = p.h1w; g.K = p.FA; ws.out(g, p.h1);
-    g.bias = pk + p.b_h1 + r0; g.act = act; g.w0 = 1.f;
+    g.bias = pk + (p.compose_feats ? p.o_bc : p.b_h1) + r0; g.act = act; g.w0 = 1.f;
     if (p.nd_fin) {   // the heads' final layers (block-diagonal [32][KF]: block b's rows read only block b's 256 columns) in this launch's epilogue
       g.nd_w = pk + p.w_fin; g.nd_ldw = p.KF; g.nd_omax = ND_FIN; g.nd_out = ws.f(p.o_finpart); g.nd_stride = p.Pp;
       auto blk = [&](int b, int col, int n) { if (b >= 0) { g.nd_rows[b] = n; g.nd_row0[b] = col; } };
@@ -213,6 +215,7 @@ struct BwdRegions {
   float *nar_fin = nullptr, *nar_sun = nullptr, *nar_sig = nullptr;
   DwMat w_fin, w_s4, w_s3, w_s2, w_h1, w_fs;
   float *cs_fin = nullptr, *cs_s3 = nullptr, *cs_s2 = nullptr, *cs_sun = nullptr, *cs_fa = nullptr, *cs_hl = nullptr;
+  int ld_cs1 = 0;   // composed: cs_fin and cs_sun are column ranges of ONE [tiles][h1w] region (row 0 of it becomes g_c, the bias gradient of the composed layer)
   struct Layer { DwMat w, w_gamma; float* cs; } tr[SNERF_MAX_LAYERS];   // w_gamma: skip layers; cs: the dX launch into layer i - 1
 };
 void take_regions(const Plan& p, RQ& rq, BwdRegions& r) {
@@ -229,11 +232,19 @@ void take_regions(const Plan& p, RQ& rq, BwdRegions& r) {
   auto cs = [&](int width) { return rq.take((size_t)((p.P + 127) / 128) * cs_ld(width)); };
   auto nar = [&]() { return rq.take((size_t)((p.P + 255) / 256) * NARROW); };
   const int W = p.W, H = p.H;
-  if (!p.sc) { r.nar_fin = nar(); r.w_fin = dw(NARROW, p.KF, p.KF, true); r.cs_fin = cs(p.KF); }
+  if (!p.sc) { r.nar_fin = nar(); r.w_fin = dw(NARROW, p.KF, p.KF, true); if (!p.compose_feats) r.cs_fin = cs(p.KF); }
   r.nar_sun = nar(); r.w_s4 = dw(NARROW, H, H, true); r.w_s3 = dw(H, H, H, false); r.w_s2 = dw(H, H, H, false);   // one slab region per matrix
-  r.cs_s3 = cs(H); r.cs_s2 = cs(H); r.cs_sun = cs(H);
-  r.w_h1 = dw(p.h1w, p.FA, p.FA, false); r.cs_fa = cs(p.FA);
-  r.nar_sig = nar(); r.w_fs = dw(W + NARROW, W, W, false, W); r.cs_hl = cs(W);
+  r.cs_s3 = cs(H); r.cs_s2 = cs(H);
+  if (p.compose_feats) {
+    // no d feats tensor, so no cs_fa; of the [W + 32][W] matrix only the 32 sigma rows are a dW launch (same splits as before)
+    r.ld_cs1 = cs_ld(p.h1w); r.cs_fin = cs(p.h1w); r.cs_sun = r.cs_fin + (p.sc ? 0 : p.sun_col);
+    r.w_h1 = dw(p.h1w, p.FA, p.FA, false);
+    r.nar_sig = nar(); r.w_fs = dw(NARROW, W, W, false, W); r.cs_hl = cs(W);
+  } else {
+    r.cs_sun = cs(H);
+    r.w_h1 = dw(p.h1w, p.FA, p.FA, false); r.cs_fa = cs(p.FA);
+    r.nar_sig = nar(); r.w_fs = dw(W + NARROW, W, W, false, W); r.cs_hl = cs(W);
+  }
   for (int i = p.L - 1; i >= 0; --i) {
     // skip layer W_i = [W_gamma (Ep columns) | W_h (W columns)]: the two column blocks are two contractions of very different
     // width over the same dz, so each gets a slab region and a split count of its own (the 64-column block: two tiles x 128 splits;
@@ -318,8 +329,9 @@ int backward_bsp(const Plan& p, const float* pk, const SnerfInputs* in, const Sn
     g.I = P; g.J = p.KF; g.K = NARROW; ws.out(g, dz1);
     dact(g, p.h1);
     colsum(g, r.cs_fin, p.KF);
+    if (p.compose_feats) g.ldcs = r.ld_cs1;
     RC(launch_kc(g));
-    RC(bias_from_colsum(r.cs_fin, p.KF, gp + p.b_h1));
+    if (!p.compose_feats) RC(bias_from_colsum(r.cs_fin, p.KF, gp + p.b_h1));
   }
   {  // 2. sun visibility chain: output layer, layer 3, layer 2
     RC(narrow_grad(dsun, r.nar_sun, p.pdsun, gp + p.b_s4));
@@ -346,29 +358,17 @@ int backward_bsp(const Plan& p, const float* pk, const SnerfInputs* in, const Sn
     ws.out(g, dz1, sun_col);
     dact(g, p.h1, sun_col);
     colsum(g, r.cs_sun, H);
+    if (p.compose_feats) g.ldcs = r.ld_cs1;
     RC(launch_kc(g));  // dz1[:, sun block]
-    RC(bias_from_colsum(r.cs_sun, H, gp + p.b_h1 + (size_t)p.sun_col));
+    if (!p.compose_feats) RC(bias_from_colsum(r.cs_sun, H, gp + p.b_h1 + (size_t)p.sun_col));
   }
-  const PlaneT dfa = p.dzb.view(p.FA);   // [P][FA]
-  {  // 3. fused first head layer: dW, then d[feats | extras]
-    const int r0 = p.sc ? p.sun_col : 0;
-    RC(dw_gemm(r.w_h1, dz1, p.h1w, false, p.fa, 0, p.FA));
-    RC(dw_reduce(r.w_h1, (size_t)p.h1w * p.FA, gp + p.w_h1 + (size_t)r0 * p.FA));
-    bsp::KcArgs g;
-    ws.a(g, dz1, p.h1w); weights(g, p, pk, p.wj_th1, 0, r0);
-    // d feats only (J = W): the 16 extras columns would be a third column tile of 256 for 16 useful columns (a third of this
-    // launch: 954 -> ~640 us at 4096 x 64), and nothing needs d sun_d.  The gradient of the transient codes comes from a 32-wide
-    // launch over the head blocks that read them instead (default: the beta block alone, K = H).
-    g.I = P; g.J = W; g.K = p.h1w; ws.out(g, dfa);
-    colsum(g, r.cs_fa, p.FA);   // columns [0, W) = bias gradient of feats_from_xyz
-    RC(launch_kc(g));
-    RC(red_add_col(rq.col, r.cs_fa, (P + 127) / 128, (size_t)cs_ld(p.FA), W, gp + p.b_fs));
+  // d extras[p][c] = sum_j dz1[p][j] W_h1[j][Wf + c] over the blocks whose first layer reads t or t_s (api.hip: head1), summed per ray
+  auto transient_grads = [&]() {
     const bool want_t = d_t != nullptr, want_ts = d_t_s != nullptr && p.x_ts >= 0;
     if (p.sc) {   // the sun-visibility block reads [feats | sun_d] only: no gradient reaches t / t_s through this pass
       if (want_t) RC(launch_zero_bytes(d_t, (size_t)p.N * p.tau * sizeof(float), st));
       if (want_ts) RC(launch_zero_bytes(d_t_s, (size_t)p.N * p.tau * sizeof(float), st));
     } else if (want_t || want_ts) {
-      // d extras[p][c] = sum_j dz1[p][j] W_h1[j][Wf + c] over the blocks whose first layer reads t or t_s (api.hip: head1)
       int b_lo = p.blk_beta, b_hi = p.blk_beta;
       auto use = [&](int blk, bool on) { if (on && blk >= 0) { if (blk < b_lo) b_lo = blk; if (blk > b_hi) b_hi = blk; } };
       use(p.blk_rgb, p.rgb_t); use(p.blk_sem, p.sem_t || p.sem_ts); use(p.blk_sbeta, true);
@@ -381,16 +381,68 @@ int backward_bsp(const Plan& p, const float* pk, const SnerfInputs* in, const Sn
       if (want_t) RC(launch_ray_sum32(dext, p.x_t, p.N, p.S, p.tau, d_t, st));
       if (want_ts) RC(launch_ray_sum32(dext, p.x_ts, p.N, p.S, p.tau, d_t_s, st));
     }
+    return (int)SNERF_OK;
+  };
+  PlaneT dz_cur = p.dza.view(W);   // dz of the trunk layers, [P][W], in dza and dzb in turn (dz1 is dead by then)
+  PlaneT dz_nxt = p.dzb.view(W);
+  // The density branch carries a gradient only if one reaches weights / transparency (/ sigmas, depth, rgb, logits in the main
+  // pass).  In the solar-correction pass of a training step none does: the loss detaches T' and w' (baseline/components/loss.py:8-10)
+  // and the composite backward then writes d sigma = 0 exactly -- its bias sums, its dW launch and the 32 extra contraction columns
+  // of the dX launch are skipped (SURVEY 8(d) counts the sc backward "through sun_v / feats / trunk only").
+  const bool sig_live = !p.sc || go->weights != nullptr || go->transparency != nullptr || go->sigmas != nullptr;
+  const PlaneT& hl = p.h[p.L - 1];
+  bool uncompose = false;
+  if (p.compose_feats) {
+    // 3 + 4, composed: the layer is pre1 = W_c [h_last | extras] + b_c with W_c = [A W_f | W_h1[:, W:]], A = W_h1[:, :W].
+    const int r0 = p.sc ? p.sun_col : 0;
+    const int nt = (P + 127) / 128, X = p.FA - W;
+    // G_c = dz1^T [h_last | extras]: the dW launch as before.  Its extras columns are W_h1's own gradient; its first W columns are
+    // summed over the splits INTO the first slab, where the un-compose launch at the end of the pass reads them.
+    RC(dw_gemm(r.w_h1, dz1, p.h1w, false, p.fa, 0, p.FA));
+    RC(red_add_elem2d(rq.elem, r.w_h1.slab + W, r.w_h1.sp.ns, r.w_h1.stride, p.h1w, X, p.FA, gp + p.w_h1 + (size_t)r0 * p.FA + W, p.FA));
+    RC(red_add_elem2d(rq.elem, r.w_h1.slab, r.w_h1.sp.ns, r.w_h1.stride, p.h1w, W, p.FA, r.w_h1.slab, p.FA));
+    RC(red_store_last(rq.elem));
+    // g_c, the column sums of dz1 (steps 1 and 2 left their partials side by side), into row 0 of the partials
+    RC(red_add_col(rq.col, r.cs_fin, nt, (size_t)r.ld_cs1, p.h1w, r.cs_fin));
+    RC(red_store_last(rq.col));
+    uncompose = true;
+    RC(transient_grads());
+    // sigma: bias gradient, planes of d sigma, its 32 rows of the [W + 32][W] gradient
+    if (sig_live) {
+      RC(narrow_grad(dsig, r.nar_sig, p.pdsig, gp + p.b_fs + W));
+      RC(dw_gemm(r.w_fs, p.pdsig, NARROW, true, hl, 0, W));
+      RC(dw_reduce(r.w_fs, (size_t)NARROW * W, gp + p.w_fs + (size_t)W * W));
+    }
+    // ONE dX launch for d feats and dz of the last trunk layer:  dz_last = [dz1 | d sigma] [W_c[:, :W]; w_sigma] * act'(h_last).
+    // It reads dz1 in dza, so it writes dzb, and the trunk walk below starts there.
+    { const PlaneT sw = dz_cur; dz_cur = dz_nxt; dz_nxt = sw; }
+    bsp::KcArgs g;
+    ws.a(g, dz1, p.h1w);
+    if (sig_live) ws.a2(g, p.pdsig);
+    weights(g, p, pk, p.wj_th1, 0, r0); g.I = P; g.J = W; g.K = sig_live ? p.h1w + NARROW : p.h1w;
+    ws.out(g, dz_cur);
+    dact(g, hl, 0, (p.L == 1) ? 30.f : 1.f);
+    colsum(g, r.cs_hl, W);
+    RC(launch_kc(g));
+    RC(bias_from_colsum(r.cs_hl, W, gp + p.b_tr[p.L - 1]));
   }
-  PlaneT dz_cur = p.dza.view(W);   // dz1 is dead from here on: dz of the trunk layers, [P][W], in dza and dzb in turn
-  PlaneT dz_nxt = p.dzb.view(W);   // (dfa is dead once step 4's launches have read it)
-  {  // 4. feats + sigma: dW for the [W + 32][W] matrix, then dz of the last trunk layer
-    const PlaneT& hl = p.h[p.L - 1];
-    // The density branch carries a gradient only if one reaches weights / transparency (/ sigmas, depth, rgb, logits in the main
-    // pass).  In the solar-correction pass of a training step none does: the loss detaches T' and w' (baseline/components/loss.py:8-10)
-    // and the composite backward then writes d sigma = 0 exactly -- its bias sums, its dW launch and the 32 extra contraction columns
-    // of the dX launch are skipped (SURVEY 8(d) counts the sc backward "through sun_v / feats / trunk only").
-    const bool sig_live = !p.sc || go->weights != nullptr || go->transparency != nullptr || go->sigmas != nullptr;
+  const PlaneT dfa = p.dzb.view(p.FA);   // [P][FA]
+  if (!p.compose_feats) {  // 3. fused first head layer: dW, then d[feats | extras]
+    const int r0 = p.sc ? p.sun_col : 0;
+    RC(dw_gemm(r.w_h1, dz1, p.h1w, false, p.fa, 0, p.FA));
+    RC(dw_reduce(r.w_h1, (size_t)p.h1w * p.FA, gp + p.w_h1 + (size_t)r0 * p.FA));
+    bsp::KcArgs g;
+    ws.a(g, dz1, p.h1w); weights(g, p, pk, p.wj_th1, 0, r0);
+    // d feats only (J = W): the 16 extras columns would be a third column tile of 256 for 16 useful columns (a third of this
+    // launch: 954 -> ~640 us at 4096 x 64), and nothing needs d sun_d.  The gradient of the transient codes comes from a 32-wide
+    // launch over the head blocks that read them instead (default: the beta block alone, K = H).
+    g.I = P; g.J = W; g.K = p.h1w; ws.out(g, dfa);
+    colsum(g, r.cs_fa, p.FA);   // columns [0, W) = bias gradient of feats_from_xyz
+    RC(launch_kc(g));
+    RC(red_add_col(rq.col, r.cs_fa, (P + 127) / 128, (size_t)cs_ld(p.FA), W, gp + p.b_fs));
+    RC(transient_grads());
+  }
+  if (!p.compose_feats) {  // 4. feats + sigma: dW for the [W + 32][W] matrix, then dz of the last trunk layer (dfa is dead once these launches have read it)
     if (sig_live) RC(narrow_grad(dsig, r.nar_sig, p.pdsig, gp + p.b_fs + W));
     RC(dw_gemm(r.w_fs, dfa, W, false, hl, 0, W));
     if (sig_live) RC(dw_gemm(r.w_fs, p.pdsig, NARROW, true, hl, 0, W, (size_t)W * W));
@@ -428,7 +480,18 @@ int backward_bsp(const Plan& p, const float* pk, const SnerfInputs* in, const Sn
     RC(bias_from_colsum(t.cs, W, gp + p.b_tr[i - 1]));
     const PlaneT sw = dz_cur; dz_cur = dz_nxt; dz_nxt = sw;
   }
-  return launch_reductions(rq.elem, rq.col, st);
+  RC(launch_reductions(rq.elem, rq.col, st));
+  if (!uncompose) return SNERF_OK;
+  // Un-compose (after the reductions: G_c and g_c are final), ADDING into the packed gradients as every reduction does:
+  //   dW_h1[:, :W] += G_c[:, :W] W_f^T + g_c (x) b_f     db_h1 += g_c     dW_f += A^T G_c[:, :W]     db_f += A^T g_c
+  // with this pass's G_c and g_c alone (the sc pass: the sun block's rows of W_h1 / b_h1).
+  {
+    const size_t r0 = p.sc ? (size_t)p.sun_col : 0;
+    bsp::SgTable tb;
+    bsp::uncompose_jobs(tb, r.w_h1.slab, r.cs_fin, pk + p.w_h1 + r0 * p.FA, pk + p.w_fs, pk + p.b_fs,
+                        gp + p.w_h1 + r0 * p.FA, gp + p.b_h1 + r0, gp + p.w_fs, gp + p.b_fs, W, p.FA, p.h1w);
+    return bsp::launch_sgemm(tb, 32, st);
+  }
 }
 
 }  // namespace snerf

@@ -88,6 +88,14 @@ struct Plan {
       wj_fin = 0, wj_tfin = 0;
   size_t wp_bytes = 0;                       // plane region size; then WPACK_MAX exponents (int) and WPACK_MAX |max| words
   int h1w = 0;       // width of the h1 buffer in this pass (N1, or H for the sc pass)
+  // feats_from_xyz (a Linear with no activation) composed into the fused first head layer: W_c = [W_h1[:, :W] W_f | W_h1[:, W:]],
+  // b_c = b_h1 + W_h1[:, :W] b_f, built by the pack (api.hip: snerf_pack_params); the pass then runs no feats launch forward, no feats
+  // dW launch and one dX launch less backward, and un-composes the gradient of W_c into those of W_h1 and W_f (bsp_pass.hip).
+  // Two planes, feat_last % 32 == 0, N1 + 32 <= 2048, unless SNERF_COMPOSE_FEATS=0 (read when the plan is made).
+  bool compose_feats = false;
+  int wj_first = 0;          // composed: the leading jobs of wj (h1, th1) are packed from the scratch W_c BEFORE the others, whose packs lie over it
+  size_t o_wc = 0;           // float offset (from the packed buffer's start) of the pack-time scratch [N1 + NARROW][FA]: W_c, then the sigma rows
+  size_t o_bc = 0;           // float offset of b_c [N1] behind the exponents
   int comp_blocks = 0;
   size_t ws_bytes = 0;
 };

@@ -103,6 +103,22 @@ int snerf_test_bsp_kc(const float* A, const float* A2, int Ka, const float* W, c
 int snerf_test_bsp_dw(const float* A, int lda_src, const float* B, int ldb_src, int P, int I, int J, int a_col0, int b_col0,
                       int k_split, int narrow_i, float* C, int planes, void* stream) {
   hipStream_t st = (hipStream_t)stream;
+  if (planes == 0) {
+    // No planes: the fp32 GEMMs on the WEIGHTS of the composed first head layer, ONE launch with the job table the product builds
+    // (bsp.h: compose_jobs / uncompose_jobs), on caller buffers.  I = rows of the layer (block), J = FA, P = W; narrow_i picks the table:
+    //   0 compose:     A = [W_h1 [I][FA] | b_h1 [I]],  B = [W_f [P + 32][P] (sigma rows last) | b_f [P]],  C = [W_c [I + 32][FA] | b_c [I]] (written)
+    //   1 un-compose:  A = [G_c [I][FA] | g_c [I]],  B = [W_h1 rows [I][FA] | W_f [P][P] | b_f [P]],
+    //                  C = [dW_h1 rows [I][FA] | db_h1 [I] | dW_f [P][P] | db_f [P]] (added to)
+    const int M = I, FA = J, W = P;
+    if (M <= 0 || W <= 0 || FA <= W || !A || !B || !C) { set_error("test_bsp_dw: fp32 weight GEMMs: bad argument"); return SNERF_ERR_BAD_DESC; }
+    bsp::SgTable tb;
+    if (!narrow_i) bsp::compose_jobs(tb, A, B, B + (size_t)(W + 32) * W, A + (size_t)M * FA, C, C + (size_t)(M + 32) * FA, W, FA, M);
+    else bsp::uncompose_jobs(tb, A, A + (size_t)M * FA, B, B + (size_t)M * FA, B + (size_t)M * FA + (size_t)W * W,
+                             C, C + (size_t)M * FA, C + (size_t)M * FA + M, C + (size_t)M * FA + M + (size_t)W * W, W, FA, M);
+    RC(bsp::launch_sgemm(tb, narrow_i ? 32 : 64, st));
+    SNERF_HIP_CHECK(hipStreamSynchronize(st));
+    return SNERF_OK;
+  }
   if (planes != 1 && planes != 2) { set_error("test_bsp_dw: planes"); return SNERF_ERR_BAD_DESC; }
   const int pl = planes;
   const size_t rp = round_up_sz(P, 128);
