@@ -403,6 +403,34 @@ int snerf_ray_bounds(const float* const* rays, const long long* n_rows, int n_ar
  * center_range (device): c[3], range -- out + 9 of snerf_ray_bounds.  stride >= 8 with bounds, >= 3 without. */
 int snerf_normalize_rows(float* rows, long long n, int stride, int bounds, const float* center_range, void* stream);
 
+/* ---- world clouds: rays + depth -> UTM (east, north, alt) (eval/utils/dsm.py get_utm_cloud, baseline/dataset/satnerf_dataset.py
+ * get_latlonalt_from_nerf_prediction, StandardNormalization.denormalize, framework/util/conversions.py) ----------------------
+ * One launch, one thread per point, every step fp64 with one rounding per operation (no contraction):
+ *   1. xyz_n = o + d * depth, the fp32 ray columns 0..2 / 3..5 and the fp32 depth widened first (rays.double());
+ *   2. ECEF = xyz_n * range + centre (denormalize on an fp64 tensor; centre and range carry fp32 values);
+ *   3. ecef_to_latlon_custom -> lat, lon (degrees), alt;
+ *   4. the utm package's from_latlon series (K0 = 0.9996, E = 0.00669438, R = 6378137) about the central meridian lon0 (radians),
+ *      + 1e7 on the northing when south = 1.  The package is not part of this build: parity with it is UNPINNED.
+ * enu_out (n, 3) fp64: (east, north, alt); lla_out (n, 3) fp64 or NULL: (lat deg, lon deg, alt).
+ * stats: 8 64-bit words the CALLER initialises to {~0, 0, ~0, 0, 0, 0, 0, 0}: [0] / [1] the minimum / maximum east and [2] / [3]
+ * the minimum / maximum north over the finite points as an order-preserving key of the double (bits with the sign bit set for
+ * v >= 0, all bits inverted for v < 0), folded with integer atomics -- exact and independent of the launch order; a word left
+ * at its initial value means no finite point; [4] += points whose east, north or alt is not finite (written as they come,
+ * left out of the bounds); [5..7] reserved.  n = 0 is legal and launches nothing.
+ * Refused without touching the device: null pointers (lla_out excepted), n outside [0, 2^31], ray_stride < 6, a range that is not
+ * positive and finite, a centre that is not finite, lon0 outside [-pi, pi], south other than 0 / 1. */
+typedef struct SnerfGeoParams {
+  double centre[3];
+  double range;
+  double lon0;
+  int south, reserved;
+} SnerfGeoParams;
+int snerf_geo_cloud(const float* rays, int ray_stride, const float* depth, long long n, const SnerfGeoParams* params,
+                    double* enu_out, double* lla_out, unsigned long long* stats, void* stream);
+/* the same kernel entered at step 2: xyz_n (n, 3) fp64 normalised points */
+int snerf_geo_points(const double* xyz_n, long long n, const SnerfGeoParams* params, double* enu_out, double* lla_out,
+                     unsigned long long* stats, void* stream);
+
 /* ---- measurement hook ----------------------------------------------------------------------------
  * Between snerf_profile_begin and snerf_profile_end every GEMM launch is bracketed by HIP events on the
  * stream it is launched on; _end synchronises those events and returns, per kernel variant, the summed

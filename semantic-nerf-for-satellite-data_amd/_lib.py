@@ -112,6 +112,13 @@ class SnerfRayImage(C.Structure):
                 ("n_rays", C.c_longlong), ("w", C.c_int), ("h", C.c_int)]
 
 
+class SnerfGeoParams(C.Structure):
+    _fields_ = [("centre", C.c_double * 3), ("range", C.c_double), ("lon0", C.c_double), ("south", C.c_int), ("reserved", C.c_int)]
+
+
+GEO_STATS_INIT = (2 ** 64 - 1, 0, 2 ** 64 - 1, 0, 0, 0, 0, 0)   # include/snerf_hip.h: the caller's initial stats words
+
+
 class SnerfProfile(C.Structure):
     _fields_ = [("ms", C.c_double * 4), ("flops", C.c_double * 4), ("launches", C.c_int64 * 4)]
 
@@ -226,6 +233,12 @@ def lib():
     L.snerf_ray_bounds.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     L.snerf_normalize_rows.restype = C.c_int
     L.snerf_normalize_rows.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.snerf_geo_cloud.restype = C.c_int
+    L.snerf_geo_cloud.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.POINTER(SnerfGeoParams), C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p]
+    L.snerf_geo_points.restype = C.c_int
+    L.snerf_geo_points.argtypes = [C.c_void_p, C.c_longlong, C.POINTER(SnerfGeoParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]
     L.snerf_profile_begin.restype = C.c_int
     L.snerf_profile_end.restype = C.c_int
     L.snerf_profile_end.argtypes = [C.POINTER(SnerfProfile)]
@@ -249,4 +262,4 @@ EXPORTED_SYMBOLS = ("snerf_version", "snerf_last_error", "snerf_packed_floats", 
                     "snerf_dsm_ncc_search", "snerf_dsm_shift_diff", "snerf_ssim_workspace_bytes", "snerf_ssim",
                     "snerf_semeval_workspace_bytes", "snerf_semeval_accumulate", "snerf_rpc_rays", "snerf_rpc_localize",
                     "snerf_rpc_project", "snerf_rpc_reprojection_error", "snerf_ray_bounds_workspace_bytes", "snerf_ray_bounds",
-                    "snerf_normalize_rows")
+                    "snerf_normalize_rows", "snerf_geo_cloud", "snerf_geo_points")

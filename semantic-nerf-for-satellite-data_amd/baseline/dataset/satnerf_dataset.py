@@ -3,7 +3,14 @@ for a scene in the reference's on-disk layout (the output of its data_prep/): ro
 8-bit RGB GeoTIFFs.  The rays of a split are built on the device in one launch (baseline/components/rays.py); the loader
 returns GpuRayBanks with the reference's columns and row order: train = the images of the split concatenated in split order;
 test = train_split[:1] + test_split, with `image_sizes` and the per-image dicts of `images()`.  Rays are rebuilt on every load
-(the reference's on-disk ray cache is not read or written)."""
+(the reference's on-disk ray cache is not read or written).
+
+World coordinates: once load_scene_banks has attached the normalisation, `geo` is a GeoFrame (framework/components/
+coordinate_systems.py) of the scene's zone (root.json "zone_string"), and get_latlonalt_from_nerf_prediction /
+get_latlonalt_from_points answer on the device (satnerf_dataset.py:156-206).  When root.json's dsm_tif_fp and dsm_txt_fp exist
+on disk, the ground-truth DSM is loaded (framework/util/img_utils.py) and every dict of `scene_images()` carries
+"dsm": {"gt", "roi", "water_mask" | "ignore_mask", "geo"}; a scene without those files loads exactly as one that does not
+name them."""
 import json
 import os
 
@@ -82,6 +89,49 @@ class SatNeRFDataset:
         self.metas = [read_json(os.path.join(self.meta_dp, n)) for n in self.data_names]
         self.t = None
         self.items = None
+        self.zone_string = self.root.get("zone_string")
+        self.dsm_tif_fp, self.dsm_txt_fp, self.dsm_cls_fp, self.ignore_mask_fp = (
+            os.path.join(self.dataset_dp, self.root[k]) if self.root.get(k) else None
+            for k in ("dsm_tif_fp", "dsm_txt_fp", "dsm_cls_fp", "ignore_mask_fp"))
+        self.normalization_component = None
+        self.geo = None       # GeoFrame, set by attach_normalization
+        self.dsm = None       # the images' "dsm" entry, when the ground truth is on disk
+
+    def attach_normalization(self, norm):
+        """the scene's normalisation -> `geo`, and the ground-truth DSM entry when its files are on disk"""
+        from ...framework.components.coordinate_systems import GeoFrame
+        self.normalization_component = norm
+        if self.zone_string:
+            self.geo = GeoFrame(norm, self.zone_string)
+        if self.geo is not None and all(fp and os.path.isfile(fp) for fp in (self.dsm_tif_fp, self.dsm_txt_fp)):
+            gt = img_utils.load_dsm_ground_truth(self.dsm_tif_fp, self.dsm_txt_fp, self.dsm_cls_fp, self.ignore_mask_fp)
+            self.dsm = {k: v.to(self.device) for k, v in gt.items()}
+            self.dsm["geo"] = self.geo
+        return self
+
+    def _need_geo(self):
+        if self.geo is None:
+            raise ValueError("world coordinates need the scene's normalisation and a root.json zone_string "
+                             "(load the scene through load_scene_banks)")
+        return self.geo
+
+    def get_xyz_from_nerf_prediction(self, rays, depth):
+        """normalised end points o + d * depth in fp64 (satnerf_dataset.py:156-171)"""
+        from ...eval.extract_pointcloud import get_xyz_from_nerf_prediction
+        return get_xyz_from_nerf_prediction(rays, depth)
+
+    def get_latlonalt_from_nerf_prediction(self, rays, depth):
+        """(lats, lons, alts) fp64 device tensors of the rays' end points (satnerf_dataset.py:173-187); fp32 rays and depth
+        take the fused launch, anything else goes through get_xyz_from_nerf_prediction"""
+        if rays.dtype == torch.float32 and depth.dtype == torch.float32:
+            lla = self._need_geo().cloud(rays, depth, want_lla=True)[1]
+            return lla[:, 0], lla[:, 1], lla[:, 2]
+        return self.get_latlonalt_from_points(self.get_xyz_from_nerf_prediction(rays, depth))
+
+    def get_latlonalt_from_points(self, points):
+        """(lats, lons, alts) fp64 device tensors of normalised points (satnerf_dataset.py:189-206)"""
+        lla = self._need_geo().points(points, want_lla=True)[1]
+        return lla[:, 0], lla[:, 1], lla[:, 2]
 
     def _rays(self):
         cams = [construct_rpc_camera_model(d, self.device) for d in self.metas]
@@ -129,6 +179,7 @@ class SatNeRFDataset:
         """callable: the per-image dicts (name, rays, extras, rgbs, w, h and the label columns) of the bank's current tensors
         -- what eval_nerf_images / eval_semantic_images take"""
         items = self.items
+        ds = self
 
         def images():
             out, lo = [], 0
@@ -138,6 +189,8 @@ class SatNeRFDataset:
                 for key, v in bank.t.items():
                     if key != "semantic_sparsity_mask":
                         d[key] = v[lo:hi]
+                if ds.dsm is not None:
+                    d["dsm"] = ds.dsm
                 out.append(d)
                 lo = hi
             return out
@@ -159,6 +212,7 @@ def load_scene_banks(cfgs, semantic: bool, depth: bool, device=None, seed=0) -> 
     norm = StandardNormalization(cfgs, rank=world()[0]).initialize([train.t["rays"], test.t["rays"]])
     for ds in (train, test):
         norm.normalize_rays_(ds.t["rays"])
+        ds.attach_normalization(norm)
     out = {"rgb": train.bank(seed=seed), "rgb_test": test.bank(seed=seed + 1)}
     if depth:
         from .satnerf_depth_dataset import SatNeRFDepthDataset
@@ -166,4 +220,5 @@ def load_scene_banks(cfgs, semantic: bool, depth: bool, device=None, seed=0) -> 
                                                                         seed=seed + 2)
     for b in out.values():
         b.normalization = norm
+    out["rgb"].dataset, out["rgb_test"].dataset = train, test
     return out

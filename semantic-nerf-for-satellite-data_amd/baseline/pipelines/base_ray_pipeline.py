@@ -67,8 +67,9 @@ class BaseRayPipeline(Pipeline):
         rank's slice of the image: the loss kernels all-reduce their sums and counts, and the caller forms the
         image PSNR from the summed (sse, count).
         With an optional batch["dsm"] = {"gt": (H, W) ground-truth DSM, "roi": roi_txt meta (xoff, yoff, size, resolution)
-        [, "water_mask" | "ignore_mask"] [, "to_world": xyz_n -> (E, N, alt)]} and batch_idx <= 1, the altitude MAE of the
-        DSM rasterised from depth_coarse is logged as f"{split}/mae" and returned under "mae" (:170-185; eval/utils/dsm.py).
+        [, "water_mask" | "ignore_mask"] [, "to_world": xyz_n -> (E, N, alt) | "geo": a GeoFrame]} and batch_idx <= 1, the altitude
+        MAE of the DSM rasterised from depth_coarse is logged as f"{split}/mae" and returned under "mae" (:170-185;
+        eval/utils/dsm.py).  A DSM with no overlap with the ground truth logs NaN instead of raising.
         Under data parallelism every rank rasterises its own rays and the integer accumulators are all-reduced (a
         collective), so every rank computes the same DSM.
         SSIM (:141-145,166-168) is logged as f"{split}/ssim" for every split and returned under "ssim": metrics.ssim of
@@ -100,8 +101,14 @@ class BaseRayPipeline(Pipeline):
         d = batch.get("dsm")
         if d is not None and batch_idx <= 1:
             from ...eval.utils.dsm import compute_dsm_and_mae
-            mae = compute_dsm_and_mae(rays, results["depth_coarse"], d["gt"], d["roi"], to_world=d.get("to_world"),
-                                      water_mask=d.get("water_mask"), ignore_mask=d.get("ignore_mask"))
+            try:
+                mae = compute_dsm_and_mae(rays, results["depth_coarse"], d["gt"], d["roi"], to_world=d.get("to_world"),
+                                          water_mask=d.get("water_mask"), ignore_mask=d.get("ignore_mask"), geo=d.get("geo"))
+            except RuntimeError as e:
+                # an untrained model's cloud can miss the ROI altogether: that must not end a training run (evaluation raises)
+                if "The predicted DSM is all NaN" not in str(e):
+                    raise
+                mae = {"mean": math.nan, "median": math.nan}
             self.log(f"{split}/mae", float(mae["mean"]), batch_size=1)
             out["mae"] = mae
         return out

@@ -2,7 +2,8 @@
 without checkpoint and dataset loading: the caller hands in the configs, the renderer, the models and the split's images.
 
 For every image: render rgb and depth (lean_inference; with sharded=True, sharded_lean_inference over the process group,
-which gives every rank the whole frame), the DSM altitude MAE when the image carries a "dsm" entry (eval/utils/dsm.py), PSNR,
+which gives every rank the whole frame), the DSM altitude MAE when the image carries a "dsm" entry (eval/utils/dsm.py; with
+the entry's "geo", as the scene loader writes it, the cloud is the UTM one of the fused world-cloud launch), PSNR,
 and SSIM through the reference's `.view(1, 3, H, W)` of the (H*W, 3) frames (eval/utils/metrics.py).  After each image the
 per-image entries and the means are written to `output_dp`/results.json with the reference's keys and formats.
 
@@ -69,7 +70,8 @@ def eval_nerf_images(cfgs, renderer, models, images, output_dp=None, split="test
             g = img["dsm"]
             # the depth is the whole frame on every rank (also when sharded): no all-reduce of the DSM accumulators
             mae = compute_dsm_and_mae(rays, results["depth_coarse"], g["gt"], g["roi"], to_world=g.get("to_world"),
-                                      water_mask=g.get("water_mask"), ignore_mask=g.get("ignore_mask"), distributed=False)
+                                      water_mask=g.get("water_mask"), ignore_mask=g.get("ignore_mask"), distributed=False,
+                                      geo=g.get("geo"))
             entry["mae"] = _mae_floats(mae)
         psnr_ = metrics.psnr(rgb, rgbs)
         ssim_ = metrics.ssim(rgb.view(1, 3, H, W), rgbs.reshape(1, 3, H, W))

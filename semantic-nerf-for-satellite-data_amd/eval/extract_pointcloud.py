@@ -1,8 +1,9 @@
 """Point clouds from a trained model -- the device side of eval/extract_pointcloud.py:66-114: full-frame inference of
 one image's rays (lean: rgb + depth [+ label] only, written in place per chunk), then the ray end points
 xyz = o + d * depth in double precision (baseline/dataset/satnerf_dataset.py:156-171).  DSM rasterisation and the altitude
-MAE of the cloud are eval/utils/dsm.py (device side); lat/lon/alt conversion and the normals variants stay with the dataset /
-CPU tooling (out of scope)."""
+MAE of the cloud are eval/utils/dsm.py (device side); with `geo` (a GeoFrame, framework/components/coordinate_systems.py) the
+reference's un-normalised UTM cloud comes from one more launch (csrc/geo.hip); the normals variants stay with CPU tooling
+(out of scope)."""
 import numpy as np
 import torch
 
@@ -17,8 +18,9 @@ def get_xyz_from_nerf_prediction(rays: torch.Tensor, depth: torch.Tensor) -> tor
 
 
 @torch.no_grad()
-def extract_pointcloud(cfgs, renderer, models, rays, extras, render_options=None, with_labels=None, sharded=False):
+def extract_pointcloud(cfgs, renderer, models, rays, extras, render_options=None, with_labels=None, sharded=False, geo=None):
     """One image -> {"xyz_n" (R,3) f64, "colors" (R,3) f32, "depth" (R) f32 [, "labels" (R) i64]}, all on the device.
+    With `geo` also "xyz_utm" (R,3) f64: the un-normalised UTM (east, north, alt) cloud (GeoFrame.cloud of rays and depth).
     `sharded=False` (default) is the reference's single-device call: safe from one rank of a process group (the usual export
     inside a data-parallel run).  `sharded=True` is a COLLECTIVE: every rank of the group must call it with the same rays;
     the image is rendered in rank shards and the per-ray results gathered, so every rank returns the whole cloud
@@ -33,6 +35,8 @@ def extract_pointcloud(cfgs, renderer, models, rays, extras, render_options=None
            "depth": res["depth_coarse"]}
     if "semantic_label_coarse" in res:
         out["labels"] = res["semantic_label_coarse"]
+    if geo is not None:
+        out["xyz_utm"] = geo.cloud(rays, res["depth_coarse"])[0]
     return out
 
 

@@ -37,10 +37,18 @@ apply_shift: b = muu - muv at the chosen shift (a = 1), rdsm[j, i] = f32(v[j+dy,
 MAE: diff = rdsm - gt; mean = nanmean|diff| (fp64 sum, fixed order), median = nanmedian|diff| as numpy takes it (the mean of
 the two middle values for an even count).  The reference formats both with "{:.3f}"; the raw floats are returned.
 
-Out of scope: lat/lon/UTM conversion (get_latlonalt_from_nerf_prediction, get_utm_cloud: the dataset's) --
-the cloud comes in a metric east/north/up frame, optionally through a caller's `to_world(xyz_n) -> (E, N, alt)`; GeoTIFF
-reading and writing (arrays in, arrays out).  SSIM is eval/utils/metrics.py; eval/eval_nerf.py reports PSNR, SSIM and this
-MAE per image."""
+World clouds (dsm.py:18-36,105-110) -- with `geo` (a GeoFrame, framework/components/coordinate_systems.py: the loader puts
+one into every image's "dsm" entry) compute_dsm_and_mae turns rays and depth into the UTM (east, north, alt) cloud in ONE launch
+of csrc/geo.hip, which also folds the cloud's east / north bounds; create_dsm and dsm_grid_from_cloud take those `bounds` and
+run no reduction of their own.  The bounds are exact (integer atomic min / max), so the DSM is bit for bit the one of the same
+cloud without them.  get_utm_cloud and create_dsm_cloud_from_nerf mirror the reference's helpers on device tensors.  The UTM
+series is the `utm` package's, restated; parity with the package is UNPINNED.  DIVERGENCE: the fused path
+uses the scene's zone (root.json), the reference the zone of the cloud's first point.  Without `geo` the cloud comes in a metric
+east/north/up frame as before, optionally through a caller's `to_world(xyz_n) -> (E, N, alt)`.
+
+Out of scope: writing DSM or error GeoTIFFs (arrays out; the ground truth is READ by framework/util/img_utils.py); training in
+the UTM coordinate system; resampling an off-lattice ground truth or ROI (ValueError); the Norway / Svalbard UTM zone
+exceptions.  SSIM is eval/utils/metrics.py; eval/eval_nerf.py reports PSNR, SSIM and this MAE per image."""
 import ctypes as C
 import math
 from collections import namedtuple
@@ -87,18 +95,25 @@ def _allreduce(t, op):
 
 
 # ---- grids -----------------------------------------------------------------------------------------------------------------
-def dsm_grid_from_cloud(cloud, resolution=RESOLUTION, distributed=False):
-    """create_dsm's cloud-bounds grid (dsm.py:66-72).  `distributed`: the bounds of the union of every rank's cloud."""
+def dsm_grid_from_cloud(cloud, resolution=RESOLUTION, distributed=False, bounds=None):
+    """create_dsm's cloud-bounds grid (dsm.py:66-72).  `distributed`: the bounds of the union of every rank's cloud.
+    `bounds`: the cloud's (xmin, xmax, ymin, ymax) when the caller already holds them (GeoFrame's fused launch): no reduction
+    over the cloud runs here."""
     import torch.distributed as dist
     _require_cuda(cloud)
-    c = cloud.double()
-    if c.shape[0]:
-        ext = torch.stack([-c[:, 0].min(), c[:, 0].max(), -c[:, 1].min(), c[:, 1].max()])
+    if bounds is not None and not (distributed and world()[1] > 1):
+        xmin, xmax, ymin, ymax = (float(v) for v in bounds)
     else:
-        ext = torch.full((4,), -math.inf, dtype=torch.float64, device=c.device)
-    if distributed:
-        _allreduce(ext, dist.ReduceOp.MAX)
-    xmin, xmax, ymin, ymax = (-float(ext[0]), float(ext[1]), -float(ext[2]), float(ext[3]))
+        if bounds is not None:
+            ext = torch.tensor([-bounds[0], bounds[1], -bounds[2], bounds[3]], dtype=torch.float64, device=cloud.device)
+        elif cloud.shape[0]:
+            c = cloud.double()
+            ext = torch.stack([-c[:, 0].min(), c[:, 0].max(), -c[:, 1].min(), c[:, 1].max()])
+        else:
+            ext = torch.full((4,), -math.inf, dtype=torch.float64, device=cloud.device)
+        if distributed:
+            _allreduce(ext, dist.ReduceOp.MAX)
+        xmin, xmax, ymin, ymax = (-float(ext[0]), float(ext[1]), -float(ext[2]), float(ext[3]))
     if not all(math.isfinite(v) for v in (xmin, xmax, ymin, ymax)):
         raise ValueError("dsm_grid_from_cloud: the cloud is empty or not finite")
     xoff = math.floor(xmin / resolution) * resolution
@@ -170,11 +185,12 @@ def rasterize(cloud, grid, radius=1, distributed=False):
     return _rasterize_window(cloud, grid, (0, 0, grid.xsize, grid.ysize), radius, distributed)
 
 
-def create_dsm(cloud, roi=None, resolution=RESOLUTION, radius=1, distributed=False):
+def create_dsm(cloud, roi=None, resolution=RESOLUTION, radius=1, distributed=False, bounds=None):
     """create_dsm (dsm.py:40-109) on an (E, N, alt) cloud: the cloud-bounds grid, or, with `roi` (a DsmGrid from roi_grid,
-    or the roi_txt meta), that grid cropped to the ROI as compute_mae's gdal crop does (see the module docstring)."""
+    or the roi_txt meta), that grid cropped to the ROI as compute_mae's gdal crop does (see the module docstring).
+    `bounds`: the cloud's precomputed (xmin, xmax, ymin, ymax), see dsm_grid_from_cloud."""
     _require_cuda(cloud)
-    bounds = dsm_grid_from_cloud(cloud, resolution, distributed)
+    bounds = dsm_grid_from_cloud(cloud, resolution, distributed, bounds=bounds)
     if roi is None:
         return rasterize(cloud, bounds, radius, distributed)
     if not isinstance(roi, DsmGrid):
@@ -336,20 +352,43 @@ def compute_mae(pred_dsm, gt_dsm, water_mask=None, ignore_mask=None, init=(0, 0)
             "rdsm": rdsm, "diff": diff}
 
 
+def get_utm_cloud(lats, lons, alts):
+    """get_utm_cloud (dsm.py:18-30) on device tensors: ((N, 3) f64 (east, north, alt), zone_string), the zone taken from the
+    first point as the reference's utm_from_latlon without a zone does"""
+    from ...framework.util.conversions import utm_from_latlon
+    _require_cuda(lats, lons, alts)
+    easts, norths, zone_string = utm_from_latlon(lats, lons)
+    return torch.stack([easts, norths, alts.double()], 1), zone_string
+
+
+def create_dsm_cloud_from_nerf(dataset, rays, depths):
+    """create_dsm_cloud_from_nerf (dsm.py:33-36): the UTM cloud of a frame, one launch through the dataset's GeoFrame (the
+    scene's zone; see the module docstring)"""
+    _require_cuda(rays, depths)
+    return dataset._need_geo().cloud(rays, depths)[0]
+
+
 def compute_dsm_and_mae(rays, depth, gt_dsm, roi_meta, to_world=None, water_mask=None, ignore_mask=None,
-                        resolution=RESOLUTION, radius=1, distributed=None):
+                        resolution=RESOLUTION, radius=1, distributed=None, geo=None):
     """compute_dsm_and_mae (dsm.py:112-157) without files: rays + depth -> xyz (get_xyz_from_nerf_prediction, fp64) ->
     to_world (identity by default) -> the DSM on the ROI -> compute_mae.  Returns the MAE dict plus "dsm".
+    `geo` (a GeoFrame; excludes to_world): fp32 rays and depth -> the UTM cloud and its bounds in one launch instead.
     `distributed` (default: whenever a process group of more than one rank is up): each rank passes its own rays and the
     integer accumulators are all-reduced, so every rank gets the same DSM and MAE (a collective)."""
     from ..extract_pointcloud import get_xyz_from_nerf_prediction
     _require_cuda(rays, depth)
-    xyz = get_xyz_from_nerf_prediction(rays.reshape(-1, rays.shape[-1]), depth.reshape(-1))
-    cloud = to_world(xyz) if to_world is not None else xyz
+    bounds = None
+    if geo is not None:
+        if to_world is not None:
+            raise ValueError("compute_dsm_and_mae: pass either geo or to_world, not both")
+        cloud, bounds = geo.cloud(rays, depth)
+    else:
+        xyz = get_xyz_from_nerf_prediction(rays.reshape(-1, rays.shape[-1]), depth.reshape(-1))
+        cloud = to_world(xyz) if to_world is not None else xyz
     if distributed is None:
         distributed = world()[1] > 1
     dsm = create_dsm(cloud.to(torch.float64), roi=roi_grid(roi_meta), resolution=resolution, radius=radius,
-                     distributed=distributed)
+                     distributed=distributed, bounds=bounds)
     out = compute_mae(dsm, gt_dsm, water_mask=water_mask, ignore_mask=ignore_mask)
     out["dsm"] = dsm
     return out

@@ -1,5 +1,12 @@
 """GeoTIFF readers of the scene loaders -- mirror of framework/util/img_utils.py:9-43.  The scenes' RGB and CLS rasters are
-plain 8-bit TIFFs, read with PIL (the reference reads them with rasterio, which this build does not carry)."""
+plain 8-bit TIFFs, read with PIL (the reference reads them with rasterio, which this build does not carry).
+
+The DSM ground truth (framework/datasets.py:35-44, eval/utils/dsm.py:180-231): a float32 single-band raster whose georeference
+is read from the GeoTIFF tags ModelPixelScale (33550) and ModelTiepoint (33922) (north-up, no rotation), the ROI text file
+(xoff, yoff, size, resolution) and the water (class 9) or ignore mask.  Cropping to the ROI replaces the reference's
+gdal.Translate(projWin=...): an integer-offset crop when the raster lies on the ROI's lattice; a raster without the tags must
+already have the ROI's shape.  DIVERGENCE: anything else (another resolution, a corner off the lattice by more than 1e-6 cells,
+an ROI reaching beyond the raster) raises ValueError where gdal would resample or pad."""
 import numpy as np
 import torch
 from PIL import Image
@@ -28,3 +35,68 @@ def load_tensor_from_cls_geotiff(img_path):
     if lab.ndim != 2 or lab.dtype != np.uint8:
         raise ValueError(f"CLS GeoTIFF {img_path!r}: expected an 8-bit single-band raster, got {lab.dtype} {lab.shape}")
     return torch.from_numpy(np.ascontiguousarray(lab.reshape(-1, 1)))
+
+
+TAG_MODEL_PIXEL_SCALE = 33550
+TAG_MODEL_TIEPOINT = 33922
+
+
+def load_dsm_geotiff(fp):
+    """(raster (h, w) ndarray in the file's dtype, geotransform (x0, y0, sx, sy) or None): x0 / y0 = the outer corner of the
+    north-west pixel, sx / sy = the pixel size east / south; None when the file carries no ModelPixelScale / ModelTiepoint"""
+    try:
+        with Image.open(fp) as im:
+            im.load()
+            a = np.array(im)
+            tags = getattr(im, "tag_v2", {})
+            scale, tie = tags.get(TAG_MODEL_PIXEL_SCALE), tags.get(TAG_MODEL_TIEPOINT)
+    except Exception as e:
+        raise ValueError(f"cannot decode the DSM GeoTIFF {fp!r}: {e}") from e
+    if a.ndim != 2:
+        raise ValueError(f"DSM GeoTIFF {fp!r}: expected a single-band raster, got {a.dtype} {a.shape}")
+    if scale is None or tie is None:
+        return a, None
+    scale, tie = [float(v) for v in scale], [float(v) for v in tie]
+    if len(scale) < 2 or len(tie) < 6 or not (scale[0] > 0 and scale[1] > 0):
+        raise ValueError(f"DSM GeoTIFF {fp!r}: malformed ModelPixelScale / ModelTiepoint tags")
+    return a, (tie[3] - tie[0] * scale[0], tie[4] + tie[1] * scale[1], scale[0], scale[1])
+
+
+def crop_to_roi(raster, geotransform, roi_meta, what="DSM"):
+    """the (size, size) window of `raster` that the ROI (xoff, yoff, size, resolution; yoff = the SOUTH edge) covers"""
+    xoff, yoff, size, res = [float(v) for v in np.asarray(roi_meta, np.float64).reshape(-1)[:4]]
+    n = int(size)
+    if geotransform is None:
+        if raster.shape != (n, n):
+            raise ValueError(f"{what} raster of shape {raster.shape} carries no georeference and is not the ROI's {n} x {n}")
+        return raster
+    x0, y0, sx, sy = geotransform
+    if abs(sx - res) > 1e-9 * res or abs(sy - res) > 1e-9 * res:
+        raise ValueError(f"{what} raster resolution ({sx}, {sy}) != ROI resolution {res}: resampling is not supported")
+    fi, fj = (xoff - x0) / res, (y0 - (yoff + n * res)) / res
+    i, j = round(fi), round(fj)
+    if abs(fi - i) > 1e-6 or abs(fj - j) > 1e-6:
+        raise ValueError(f"{what} raster origin ({x0}, {y0}) is off the ROI lattice ({xoff} + k {res}, {yoff} + k {res}): "
+                         "resampling is not supported")
+    if i < 0 or j < 0 or i + n > raster.shape[1] or j + n > raster.shape[0]:
+        raise ValueError(f"the ROI ({n} x {n} cells from column {i}, row {j}) reaches beyond the {what} raster {raster.shape}")
+    return raster[j:j + n, i:i + n]
+
+
+def load_dsm_ground_truth(dsm_tif_fp, dsm_txt_fp, dsm_cls_fp=None, ignore_mask_fp=None):
+    """{"gt": (n, n) f32, "roi": (4,) f64, "water_mask" | "ignore_mask": (n, n) u8} as CPU tensors.  Exactly one mask is used, as
+    eval/utils/dsm.py:124-129,199-219 of the reference: the ignore mask when the scene names one, else the water mask (the CLS
+    raster; class 9 is water) when its file exists."""
+    import os
+    roi = np.loadtxt(dsm_txt_fp, dtype=np.float64).reshape(-1)
+    if roi.size < 4:
+        raise ValueError(f"ROI file {dsm_txt_fp!r}: expected xoff, yoff, size, resolution")
+    gt, gtf = load_dsm_geotiff(dsm_tif_fp)
+    if gt.dtype != np.float32:
+        raise ValueError(f"DSM GeoTIFF {dsm_tif_fp!r}: expected a float32 raster, got {gt.dtype}")
+    out = {"gt": torch.from_numpy(np.ascontiguousarray(crop_to_roi(gt, gtf, roi))), "roi": torch.from_numpy(roi[:4].copy())}
+    key, fp = ("ignore_mask", ignore_mask_fp) if ignore_mask_fp else ("water_mask", dsm_cls_fp)
+    if fp and os.path.isfile(fp):
+        m, mtf = load_dsm_geotiff(fp)
+        out[key] = torch.from_numpy(np.ascontiguousarray(crop_to_roi(m, mtf, roi, what=key)).astype(np.uint8))
+    return out
