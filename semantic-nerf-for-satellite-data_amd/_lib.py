@@ -2,6 +2,8 @@
 import ctypes as C
 import os
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SNERF_LIB_PATH: an alternative build of the library (ablation harness of tools/ablate; diagnostics only)
 LIB_PATH = os.environ.get("SNERF_LIB_PATH") or os.path.join(_HERE, "libsnerf_hip.so")
@@ -126,6 +128,78 @@ class SnerfProfile(C.Structure):
 PROFILE_VARIANTS = ("K-contiguous dense layers (forward X.W^T and dX = dZ.W): gemm_kc_kernel, 128 x 256 tile", "SIREN trunk as one persistent launch (one-plane mode): trunk_kernel, activation tile resident in LDS",
                     "weight gradients (dW = dZ^T.X, split-K slabs): gemm_dw_kernel, 256 x 256 tile", "32-wide head variants (forward + dW)")
 
+
+class c_stream(C.c_void_p):
+    """The `void* stream` parameter of an entry point.  The marker tells call() which slot it fills itself (the current stream of
+    the call's device); a direct caller of lib() passes what a void* takes."""
+
+    @classmethod
+    def from_param(cls, value):
+        return C.c_void_p.from_param(value)
+
+
+def _signatures():
+    i, ll, ull, sz, f, d, p, st, P = C.c_int, C.c_longlong, C.c_ulonglong, C.c_size_t, C.c_float, C.c_double, C.c_void_p, c_stream, C.POINTER
+    desc = P(SnerfDesc)
+    return {
+        "snerf_version": (i, ()),
+        "snerf_last_error": (C.c_char_p, ()),
+        "snerf_packed_floats": (sz, (desc,)),
+        "snerf_grad_floats": (sz, (desc,)),
+        "snerf_workspace_bytes": (sz, (desc,)),
+        "snerf_pack_params": (i, (desc, P(SnerfParams), p, st)),
+        "snerf_unpack_grads": (i, (desc, p, P(SnerfParams), i, st)),
+        "snerf_forward": (i, (desc, p, P(SnerfInputs), P(SnerfOutputs), p, sz, st)),
+        "snerf_sample_z": (i, (p, p, p, p, i, i, st)),
+        "snerf_embedding_rows": (i, (p, i, i, p, i, p, st)),
+        "snerf_embedding_backward": (i, (p, p, i, i, i, p, st)),
+        "snerf_backward": (i, (desc, p, P(SnerfInputs), P(SnerfOutGrads), p, p, p, p, sz, st)),
+        "snerf_loss_workspace_bytes": (sz, (P(SnerfLossCfg),)),
+        "snerf_loss_partial": (i, (P(SnerfLossCfg), P(SnerfLossIn), p, p, sz, st)),
+        "snerf_loss_finish": (i, (P(SnerfLossCfg), P(SnerfLossIn), p, f, f, p, P(SnerfLossGrads), st)),
+        "snerf_adam_step": (i, (p, p, p, p, ull, f, f, f, f, i, f, st)),
+        "snerf_dsm_accumulate": (i, (p, i, P(SnerfDsmGrid), i, d, d, p, p, p, st)),
+        "snerf_dsm_finish": (i, (p, p, ll, d, d, p, p, st)),
+        "snerf_dsm_downsample2x": (i, (p, i, i, i, p, st)),
+        "snerf_dsm_workspace_bytes": (sz, (i, i, i)),
+        "snerf_dsm_ncc_search": (i, (p, p, i, i, i, i, i, i, p, p, sz, st)),
+        "snerf_dsm_shift_diff": (i, (p, p, i, i, i, i, d, p, p, p, p, sz, st)),
+        "snerf_ssim_workspace_bytes": (sz, (i,) * 5),
+        "snerf_ssim": (i, (p, p) + (i,) * 6 + (p, d, d, d, p, p, p, sz, st)),
+        "snerf_semeval_workspace_bytes": (sz, (i, i)),
+        "snerf_semeval_accumulate": (i, (p,) * 4 + (i,) * 4 + (p, p, i, p, p, sz, st)),
+        # SnerfRayImage / SnerfRpc tables go as void*: the same slot type serves the host copy (a ctypes array or byref) and the
+        # device copy (a tensor)
+        "snerf_rpc_rays": (i, (p, p, i, p, ll, p, p, st)),
+        "snerf_rpc_localize": (i, (p,) * 5 + (ll, i) + (p,) * 3 + (st,)),
+        "snerf_rpc_project": (i, (p,) * 5 + (ll, p, p, st)),
+        "snerf_rpc_reprojection_error": (i, (p,) * 4 + (ll, p, p, st)),
+        "snerf_ray_bounds_workspace_bytes": (sz, (p, i)),
+        "snerf_ray_bounds": (i, (p, p, i, p, p, sz, st)),
+        "snerf_normalize_rows": (i, (p, ll, i, i, p, st)),
+        "snerf_geo_cloud": (i, (p, i, p, ll, P(SnerfGeoParams), p, p, p, st)),
+        "snerf_geo_points": (i, (p, ll, P(SnerfGeoParams), p, p, p, st)),
+        "snerf_profile_begin": (i, ()),
+        "snerf_profile_end": (i, (P(SnerfProfile),)),
+        "snerf_test_set_kc_grid": (i, (i,)),
+        "snerf_test_set_trunk_fusion": (i, (i,)),
+        "snerf_test_bsp_roundtrip": (i, (p, i, i, i, i, p, p, i, st)),
+        "snerf_test_bsp_kc": (i, (p, p, i, p, p, i, i, i, i, i, i, f, i) + (p,) * 7 + (P(i), i, i, st)),
+        "snerf_test_bsp_dw": (i, (p, i, p, i, i, i, i, i, i, i, i, p, i, st)),
+    }
+
+
+# THE binding table: symbol -> (restype, argtypes), one row per prototype of include/snerf_hip.h in the header's order
+# (tests/test_abi_cpu.py compares the two, parameter by parameter).  A new entry point is declared there and here.
+SIGNATURES = _signatures()
+EXPORTED_SYMBOLS = tuple(SIGNATURES)
+
+# symbol -> (per argument a caller of call() passes: int / float for a scalar slot, None for a pointer slot; whether a trailing
+# stream follows them)
+_PLANS = {name: (tuple(float if t in (C.c_float, C.c_double) else None if issubclass(t, (C.c_void_p, C._Pointer)) else int
+                       for t in args if t is not c_stream), c_stream in args) for name, (_, args) in SIGNATURES.items()}
+assert all(c_stream not in args[:-1] for _, args in SIGNATURES.values())
+
 _lib = None
 
 
@@ -139,127 +213,64 @@ def lib():
             f"libsnerf_hip.so not found at {LIB_PATH}: the HIP extension is the product path and has no "
             "fallback. Build it with `make -C semantic-nerf-for-satellite-data_amd/csrc` "
             "(or `python -c 'import __graft_entry__ as g; g.build()'`).")
-    # torch bundles its own HIP runtime: import it FIRST so that libsnerf_hip.so binds to the runtime that
+    # torch bundles its own HIP runtime and is imported above, FIRST, so that libsnerf_hip.so binds to the runtime that
     # owns torch's device context and streams (loading ours first brings up a second runtime that then
     # reports "no ROCm-capable device").
-    import torch  # noqa: F401
     L = C.CDLL(LIB_PATH)
-    L.snerf_version.restype = C.c_int
-    L.snerf_last_error.restype = C.c_char_p
-    L.snerf_packed_floats.restype = C.c_size_t
-    L.snerf_packed_floats.argtypes = [C.POINTER(SnerfDesc)]
-    L.snerf_grad_floats.restype = C.c_size_t
-    L.snerf_grad_floats.argtypes = [C.POINTER(SnerfDesc)]
-    L.snerf_workspace_bytes.restype = C.c_size_t
-    L.snerf_workspace_bytes.argtypes = [C.POINTER(SnerfDesc)]
-    L.snerf_pack_params.restype = C.c_int
-    L.snerf_pack_params.argtypes = [C.POINTER(SnerfDesc), C.POINTER(SnerfParams), C.c_void_p, C.c_void_p]
-    L.snerf_unpack_grads.restype = C.c_int
-    L.snerf_unpack_grads.argtypes = [C.POINTER(SnerfDesc), C.c_void_p, C.POINTER(SnerfParams), C.c_int, C.c_void_p]
-    L.snerf_forward.restype = C.c_int
-    L.snerf_forward.argtypes = [C.POINTER(SnerfDesc), C.c_void_p, C.POINTER(SnerfInputs), C.POINTER(SnerfOutputs),
-                                C.c_void_p, C.c_size_t, C.c_void_p]
-    L.snerf_backward.restype = C.c_int
-    L.snerf_backward.argtypes = [C.POINTER(SnerfDesc), C.c_void_p, C.POINTER(SnerfInputs), C.POINTER(SnerfOutGrads),
-                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    L.snerf_test_set_kc_grid.restype = C.c_int
-    L.snerf_test_set_kc_grid.argtypes = [C.c_int]
-    L.snerf_test_set_trunk_fusion.restype = C.c_int
-    L.snerf_test_set_trunk_fusion.argtypes = [C.c_int]
-    L.snerf_test_bsp_roundtrip.restype = C.c_int
-    L.snerf_test_bsp_roundtrip.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    L.snerf_test_bsp_kc.restype = C.c_int
-    L.snerf_test_bsp_kc.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                    C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_void_p]
-    L.snerf_test_bsp_dw.restype = C.c_int
-    L.snerf_test_bsp_dw.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                    C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
-    L.snerf_loss_workspace_bytes.restype = C.c_size_t
-    L.snerf_loss_workspace_bytes.argtypes = [C.POINTER(SnerfLossCfg)]
-    L.snerf_loss_partial.restype = C.c_int
-    L.snerf_loss_partial.argtypes = [C.POINTER(SnerfLossCfg), C.POINTER(SnerfLossIn), C.c_void_p, C.c_void_p,
-                                     C.c_size_t, C.c_void_p]
-    L.snerf_loss_finish.restype = C.c_int
-    L.snerf_loss_finish.argtypes = [C.POINTER(SnerfLossCfg), C.POINTER(SnerfLossIn), C.c_void_p, C.c_float, C.c_float,
-                                    C.c_void_p, C.POINTER(SnerfLossGrads), C.c_void_p]
-    L.snerf_sample_z.restype = C.c_int
-    L.snerf_sample_z.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-    L.snerf_embedding_rows.restype = C.c_int
-    L.snerf_embedding_rows.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    L.snerf_embedding_backward.restype = C.c_int
-    L.snerf_embedding_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    L.snerf_adam_step.restype = C.c_int
-    L.snerf_adam_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_float, C.c_float,
-                                  C.c_float, C.c_float, C.c_int, C.c_float, C.c_void_p]
-    L.snerf_dsm_accumulate.restype = C.c_int
-    L.snerf_dsm_accumulate.argtypes = [C.c_void_p, C.c_int, C.POINTER(SnerfDsmGrid), C.c_int, C.c_double, C.c_double,
-                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.snerf_dsm_finish.restype = C.c_int
-    L.snerf_dsm_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
-                                   C.c_void_p]
-    L.snerf_dsm_downsample2x.restype = C.c_int
-    L.snerf_dsm_downsample2x.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    L.snerf_dsm_workspace_bytes.restype = C.c_size_t
-    L.snerf_dsm_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
-    L.snerf_dsm_ncc_search.restype = C.c_int
-    L.snerf_dsm_ncc_search.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                       C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    L.snerf_dsm_shift_diff.restype = C.c_int
-    L.snerf_dsm_shift_diff.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p,
-                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    L.snerf_ssim_workspace_bytes.restype = C.c_size_t
-    L.snerf_ssim_workspace_bytes.argtypes = [C.c_int] * 5
-    L.snerf_ssim.restype = C.c_int
-    L.snerf_ssim.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_double, C.c_double, C.c_double,
-                                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                                                       C.c_void_p]
-    L.snerf_semeval_workspace_bytes.restype = C.c_size_t
-    L.snerf_semeval_workspace_bytes.argtypes = [C.c_int, C.c_int]
-    L.snerf_semeval_accumulate.restype = C.c_int
-    L.snerf_semeval_accumulate.argtypes = [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                                                              C.c_void_p, C.c_size_t, C.c_void_p]
-    L.snerf_rpc_rays.restype = C.c_int
-    L.snerf_rpc_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.snerf_rpc_localize.restype = C.c_int
-    L.snerf_rpc_localize.argtypes = [C.c_void_p] * 5 + [C.c_longlong, C.c_int] + [C.c_void_p] * 4
-    L.snerf_rpc_project.restype = C.c_int
-    L.snerf_rpc_project.argtypes = [C.c_void_p] * 5 + [C.c_longlong] + [C.c_void_p] * 3
-    L.snerf_rpc_reprojection_error.restype = C.c_int
-    L.snerf_rpc_reprojection_error.argtypes = [C.c_void_p] * 4 + [C.c_longlong] + [C.c_void_p] * 3
-    L.snerf_ray_bounds_workspace_bytes.restype = C.c_size_t
-    L.snerf_ray_bounds_workspace_bytes.argtypes = [C.c_void_p, C.c_int]
-    L.snerf_ray_bounds.restype = C.c_int
-    L.snerf_ray_bounds.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    L.snerf_normalize_rows.restype = C.c_int
-    L.snerf_normalize_rows.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    L.snerf_geo_cloud.restype = C.c_int
-    L.snerf_geo_cloud.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.POINTER(SnerfGeoParams), C.c_void_p, C.c_void_p,
-                                  C.c_void_p, C.c_void_p]
-    L.snerf_geo_points.restype = C.c_int
-    L.snerf_geo_points.argtypes = [C.c_void_p, C.c_longlong, C.POINTER(SnerfGeoParams), C.c_void_p, C.c_void_p, C.c_void_p,
-                                   C.c_void_p]
-    L.snerf_profile_begin.restype = C.c_int
-    L.snerf_profile_end.restype = C.c_int
-    L.snerf_profile_end.argtypes = [C.POINTER(SnerfProfile)]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, list(argtypes)
     if L.snerf_version() != ABI_VERSION:
         raise RuntimeError(f"libsnerf_hip.so ABI version {L.snerf_version()} != {ABI_VERSION}")
     _lib = L
     return L
 
 
-def check(rc, what):
+def check(rc, what, exc=RuntimeError):
     if rc != 0:
-        raise RuntimeError(f"{what} failed (code {rc}): {lib().snerf_last_error().decode()}")
+        raise exc(f"{what} failed (code {rc}): {lib().snerf_last_error().decode()}")
 
 
-EXPORTED_SYMBOLS = ("snerf_version", "snerf_last_error", "snerf_packed_floats", "snerf_grad_floats", "snerf_workspace_bytes",
-                    "snerf_pack_params", "snerf_unpack_grads", "snerf_forward", "snerf_backward",
-                    "snerf_loss_workspace_bytes", "snerf_loss_partial", "snerf_loss_finish", "snerf_profile_begin",
-                    "snerf_profile_end", "snerf_sample_z", "snerf_adam_step", "snerf_test_bsp_roundtrip", "snerf_test_bsp_kc",
-                    "snerf_test_bsp_dw", "snerf_test_set_kc_grid", "snerf_test_set_trunk_fusion", "snerf_embedding_rows", "snerf_embedding_backward",
-                    "snerf_dsm_accumulate", "snerf_dsm_finish", "snerf_dsm_downsample2x", "snerf_dsm_workspace_bytes",
-                    "snerf_dsm_ncc_search", "snerf_dsm_shift_diff", "snerf_ssim_workspace_bytes", "snerf_ssim",
-                    "snerf_semeval_workspace_bytes", "snerf_semeval_accumulate", "snerf_rpc_rays", "snerf_rpc_localize",
-                    "snerf_rpc_project", "snerf_rpc_reprojection_error", "snerf_ray_bounds_workspace_bytes", "snerf_ray_bounds",
-                    "snerf_normalize_rows", "snerf_geo_cloud", "snerf_geo_points")
+def _invoke(name, args, device):
+    slots, has_stream = _PLANS[name]
+    if len(args) != len(slots):
+        raise TypeError(f"{name} takes {len(slots)} arguments{' (the stream is filled in)' if has_stream else ''}, {len(args)} given")
+    out = []
+    for k, (scalar, a) in enumerate(zip(slots, args)):
+        if scalar is not None:
+            a = scalar(a)
+        elif isinstance(a, torch.Tensor):
+            if not a.is_cuda:
+                raise RuntimeError(f"snerf_amd: argument {k} of {name} must live on the GPU (the HIP path has no CPU fallback)")
+            if not a.is_contiguous():
+                raise RuntimeError(f"snerf_amd: argument {k} of {name} must be contiguous (the library takes no strides)")
+            if device is None:
+                device = a.device
+            a = a.data_ptr()
+        elif isinstance(a, C.Structure):
+            a = C.byref(a)
+        # else None (NULL), a raw address, a ctypes array or pointer: as ctypes takes them
+        out.append(a)
+    fn = getattr(lib(), name)
+    if not has_stream:
+        return fn(*out)
+    if device is None:
+        raise TypeError(f"{name}: no tensor argument to take the device from; pass device=")
+    with torch.cuda.device(device):
+        return fn(*out, torch.cuda.current_stream().cuda_stream)
+
+
+def call(name, *args, device=None, exc=RuntimeError):
+    """Call an int-returning entry point by the table: tensors go as their device address (refused unless on the GPU and
+    contiguous; no copies are made here), None as NULL, structs by reference, scalars converted; the stream is not passed --
+    the launch runs under the device of the first tensor argument (or `device`) on that device's current stream.  A non-zero
+    return raises `exc` with the library's message."""
+    check(_invoke(name, args, device), name, exc)
+
+
+def call_size(name, *args, exc=RuntimeError):
+    """The size_t-returning *_bytes / *_floats entries: a returned 0 is the library's refusal and raises with its message."""
+    n = _invoke(name, args, None)
+    if n == 0:
+        check(1, name, exc)
+    return n

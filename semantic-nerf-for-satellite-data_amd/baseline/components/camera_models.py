@@ -1,8 +1,6 @@
 """RPC camera model -- mirror of baseline/components/camera_models.py with rpcm.RPCModel's arithmetic on the device
 (csrc/satrays.hip; the spec is in include/snerf_hip.h).  An RPC is built from a meta JSON's "rpc" dict in rpcm's __dict__ layout
 (row/col/lat/lon/alt _offset and _scale, row/col_num/den, optional inverse lat/lon_num/den)."""
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -38,10 +36,6 @@ def struct_to_device(s, device) -> torch.Tensor:
     return torch.frombuffer(bytearray(bytes(s)), dtype=torch.uint8).to(device)
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
 class RPCModel:
     """rpcm.RPCModel's interface on the device: localization / projection take and return fp64 tensors on `device`"""
 
@@ -74,10 +68,7 @@ class RPCModel:
         r, a = self._f64(rows, c.numel(), "rows"), self._f64(alts, c.numel(), "alts")
         lon, lat = torch.empty_like(c), torch.empty_like(c)
         fails = torch.zeros(2, dtype=torch.int32, device=self.device)       # failed points, the call's update count
-        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(_lib.lib().snerf_rpc_localize(C.byref(self.struct), _ptr(self.dev), _ptr(c), _ptr(r), _ptr(a), c.numel(),
-                                                 int(bool(return_normalized)), _ptr(lon), _ptr(lat), _ptr(fails), st),
-                   "snerf_rpc_localize")
+        _lib.call("snerf_rpc_localize", self.struct, self.dev, c, r, a, c.numel(), bool(return_normalized), lon, lat, fails)
         if int(fails[0].item()):
             raise RuntimeError(f"RPC localization: {int(fails[0].item())} points did not converge in 100 iterations "
                                "(rpcm: MaxLocalizationIterationsError)")
@@ -87,9 +78,7 @@ class RPCModel:
         lon = self._f64(lons)
         lat, a = self._f64(lats, lon.numel(), "lats"), self._f64(alts, lon.numel(), "alts")
         col, row = torch.empty_like(lon), torch.empty_like(lon)
-        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(_lib.lib().snerf_rpc_project(C.byref(self.struct), _ptr(self.dev), _ptr(lon), _ptr(lat), _ptr(a), lon.numel(),
-                                                _ptr(col), _ptr(row), st), "snerf_rpc_project")
+        _lib.call("snerf_rpc_project", self.struct, self.dev, lon, lat, a, lon.numel(), col, row)
         return col, row
 
     def reprojection_error(self, xyz_ecef, pts2d):
@@ -100,9 +89,7 @@ class RPCModel:
         if x.shape[0] != p.shape[0]:
             raise ValueError(f"{x.shape[0]} points for {p.shape[0]} image coordinates")
         err = torch.empty(x.shape[0], dtype=torch.float64, device=self.device)
-        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(_lib.lib().snerf_rpc_reprojection_error(C.byref(self.struct), _ptr(self.dev), _ptr(x), _ptr(p), x.shape[0],
-                                                           None, _ptr(err), st), "snerf_rpc_reprojection_error")
+        _lib.call("snerf_rpc_reprojection_error", self.struct, self.dev, x, p, x.shape[0], None, err)
         return err
 
 

@@ -36,15 +36,9 @@ def ray_bounds(ray_tensors) -> torch.Tensor:
             raise ValueError("ray_bounds: contiguous (R, 8) fp32 ray tensors on one device")
     n = (C.c_longlong * len(ray_tensors))(*[int(t.shape[0]) for t in ray_tensors])
     ptrs = (C.c_void_p * len(ray_tensors))(*[t.data_ptr() for t in ray_tensors])
-    L = _lib.lib()
-    ws_bytes = L.snerf_ray_bounds_workspace_bytes(n, len(ray_tensors))
-    if ws_bytes == 0:
-        raise RuntimeError(f"snerf_ray_bounds_workspace_bytes: {L.snerf_last_error().decode()}")
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    ws = torch.empty(_lib.call_size("snerf_ray_bounds_workspace_bytes", n, len(ray_tensors)), dtype=torch.uint8, device=dev)
     out = torch.empty(13, dtype=torch.float32, device=dev)
-    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(L.snerf_ray_bounds(ptrs, n, len(ray_tensors), C.c_void_p(out.data_ptr()), C.c_void_p(ws.data_ptr()), ws_bytes, st),
-               "snerf_ray_bounds")
+    _lib.call("snerf_ray_bounds", ptrs, n, len(ray_tensors), out, ws, ws.numel())
     return out
 
 
@@ -52,9 +46,7 @@ def normalize_rows_(rows: torch.Tensor, center_range: torch.Tensor, bounds: bool
     if rows.dtype != torch.float32 or not rows.is_contiguous() or rows.dim() != 2:
         raise ValueError("normalize_rows_: contiguous 2-d fp32 rows")
     cr = center_range.to(device=rows.device, dtype=torch.float32).contiguous()
-    st = C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream)
-    _lib.check(_lib.lib().snerf_normalize_rows(C.c_void_p(rows.data_ptr()), rows.shape[0], rows.shape[1], int(bounds),
-                                               C.c_void_p(cr.data_ptr()), st), "snerf_normalize_rows")
+    _lib.call("snerf_normalize_rows", rows, rows.shape[0], rows.shape[1], bounds, cr)
     return rows
 
 

@@ -2,8 +2,6 @@
 every image of a split in ONE launch of csrc/satrays.hip (snerf_rpc_rays): per pixel, rpcm localisation at max_alt and at
 min_alt, custom ECEF in fp64, and the un-normalised fp32 row [o(3), d(3), near = 0, far] that the reference returns after
 `.type(FloatTensor)`."""
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -53,11 +51,7 @@ def satnerf_construct(cameras, min_alts, max_alts, sizes=None, pixels=None, name
         row0 += n
     rays = torch.empty((row0, 8), dtype=torch.float32, device=device)
     fails = torch.zeros(3 * n_img, dtype=torch.int32, device=device)     # failures per image, then update counts
-    dev_table = struct_to_device(table, device)
-    st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    _lib.check(_lib.lib().snerf_rpc_rays(C.byref(table), C.c_void_p(dev_table.data_ptr()), n_img,
-                                         C.c_void_p(pix.data_ptr()) if pix is not None else None, row0,
-                                         C.c_void_p(rays.data_ptr()), C.c_void_p(fails.data_ptr()), st), "snerf_rpc_rays")
+    _lib.call("snerf_rpc_rays", table, struct_to_device(table, device), n_img, pix, row0, rays, fails)
     if not check:
         return rays, fails
     raise_on_failures(fails, names)

@@ -49,14 +49,13 @@ east/north/up frame as before, optionally through a caller's `to_world(xyz_n) ->
 Out of scope: writing DSM or error GeoTIFFs (arrays out; the ground truth is READ by framework/util/img_utils.py); training in
 the UTM coordinate system; resampling an off-lattice ground truth or ROI (ValueError); the Norway / Svalbard UTM zone
 exceptions.  SSIM is eval/utils/metrics.py; eval/eval_nerf.py reports PSNR, SSIM and this MAE per image."""
-import ctypes as C
 import math
 from collections import namedtuple
 
 import torch
 
 from ... import _lib
-from ...parallel import world
+from ...parallel import allreduce_, world
 
 Z0 = 0.0            # quantisation origin of the rasteriser's integer accumulators (metres)
 Q = 2.0 ** -24      # quantisation step (metres): 6e-8, below the fp32 spacing of any altitude above 0.5
@@ -66,41 +65,12 @@ IRANGE = 5          # recursive_ncc's search radius (dsmr.py:134)
 DsmGrid = namedtuple("DsmGrid", "xoff yoff resolution xsize ysize")
 
 
-def _stream(t):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def _require_cuda(*ts):
-    for t in ts:
-        if not (torch.is_tensor(t) and t.is_cuda):
-            raise ValueError("DSM evaluation runs on the device: pass CUDA tensors")
-
-
-# ---- distributed helpers (SUM / MAX over the ranks of the default group) ---------------------------------------------------
-def _allreduce(t, op):
-    import torch.distributed as dist
-    if world()[1] <= 1:
-        return t
-    if t.is_cuda and dist.get_backend() == "gloo":    # test rigs only: gloo ranks sharing one GPU
-        h = t.cpu()
-        dist.all_reduce(h, op=op)
-        t.copy_(h)
-    else:
-        dist.all_reduce(t, op=op)
-    return t
-
-
 # ---- grids -----------------------------------------------------------------------------------------------------------------
 def dsm_grid_from_cloud(cloud, resolution=RESOLUTION, distributed=False, bounds=None):
     """create_dsm's cloud-bounds grid (dsm.py:66-72).  `distributed`: the bounds of the union of every rank's cloud.
     `bounds`: the cloud's (xmin, xmax, ymin, ymax) when the caller already holds them (GeoFrame's fused launch): no reduction
     over the cloud runs here."""
     import torch.distributed as dist
-    _require_cuda(cloud)
     if bounds is not None and not (distributed and world()[1] > 1):
         xmin, xmax, ymin, ymax = (float(v) for v in bounds)
     else:
@@ -112,7 +82,7 @@ def dsm_grid_from_cloud(cloud, resolution=RESOLUTION, distributed=False, bounds=
         else:
             ext = torch.full((4,), -math.inf, dtype=torch.float64, device=cloud.device)
         if distributed:
-            _allreduce(ext, dist.ReduceOp.MAX)
+            allreduce_(ext, dist.ReduceOp.MAX)
         xmin, xmax, ymin, ymax = (-float(ext[0]), float(ext[1]), -float(ext[2]), float(ext[3]))
     if not all(math.isfinite(v) for v in (xmin, xmax, ymin, ymax)):
         raise ValueError("dsm_grid_from_cloud: the cloud is empty or not finite")
@@ -135,7 +105,6 @@ def roi_grid(meta):
 def _accumulate(cloud, lattice, window, radius):
     """integer accumulators (count i32-as-u32, sum i64) and stats (u64[4]) of `cloud` on `lattice` cropped to
     window = (ioff, joff, out_w, out_h)"""
-    L = _lib.lib()
     ioff, joff, w, h = window
     g = _lib.SnerfDsmGrid(float(lattice.xoff), float(lattice.yoff), float(lattice.resolution), int(lattice.xsize),
                           int(lattice.ysize), int(ioff), int(joff), int(w), int(h))
@@ -148,16 +117,13 @@ def _accumulate(cloud, lattice, window, radius):
     count = torch.zeros(h * w, dtype=torch.int32, device=dev)
     total = torch.zeros(h * w, dtype=torch.int64, device=dev)
     stats = torch.zeros(4, dtype=torch.int64, device=dev)
-    _lib.check(L.snerf_dsm_accumulate(_ptr(xyz), xyz.shape[0], C.byref(g), int(radius), Z0, Q, _ptr(count), _ptr(total),
-                                      _ptr(stats), _stream(xyz)), "snerf_dsm_accumulate")
+    _lib.call("snerf_dsm_accumulate", xyz, xyz.shape[0], g, radius, Z0, Q, count, total, stats)
     return count, total, stats
 
 
 def _finish(count, total, stats, h, w):
-    L = _lib.lib()
     dsm = torch.empty(h * w, dtype=torch.float32, device=count.device)
-    _lib.check(L.snerf_dsm_finish(_ptr(count), _ptr(total), h * w, Z0, Q, _ptr(dsm), _ptr(stats), _stream(dsm)),
-               "snerf_dsm_finish")
+    _lib.call("snerf_dsm_finish", count, total, h * w, Z0, Q, dsm, stats)
     kmax, bad, cmax, _ = (int(x) for x in stats.cpu())
     if bad:
         raise OverflowError(f"rasterize: {bad} point(s) with an altitude that is not finite or beyond 2^62 quantisation steps")
@@ -167,19 +133,17 @@ def _finish(count, total, stats, h, w):
 
 
 def _rasterize_window(cloud, lattice, window, radius, distributed):
-    import torch.distributed as dist
     count, total, stats = _accumulate(cloud, lattice, window, radius)
-    if distributed and world()[1] > 1:
-        _allreduce(count, dist.ReduceOp.SUM)
-        _allreduce(total, dist.ReduceOp.SUM)
-        _allreduce(stats, dist.ReduceOp.SUM)   # summed maxima bound the global maximum: a conservative overflow check
+    if distributed:
+        allreduce_(count)
+        allreduce_(total)
+        allreduce_(stats)   # summed maxima bound the global maximum: a conservative overflow check
     return _finish(count, total, stats, window[3], window[2])
 
 
 def rasterize(cloud, grid, radius=1, distributed=False):
     """plyflatten(cloud, *grid, radius, sigma=inf) -> float32 (ysize, xsize), NaN where no point reached.
     `distributed`: every rank passes its own points and receives the DSM of their union (a collective)."""
-    _require_cuda(cloud)
     if radius < 0:
         raise ValueError("radius must be >= 0")
     return _rasterize_window(cloud, grid, (0, 0, grid.xsize, grid.ysize), radius, distributed)
@@ -189,7 +153,6 @@ def create_dsm(cloud, roi=None, resolution=RESOLUTION, radius=1, distributed=Fal
     """create_dsm (dsm.py:40-109) on an (E, N, alt) cloud: the cloud-bounds grid, or, with `roi` (a DsmGrid from roi_grid,
     or the roi_txt meta), that grid cropped to the ROI as compute_mae's gdal crop does (see the module docstring).
     `bounds`: the cloud's precomputed (xmin, xmax, ymin, ymax), see dsm_grid_from_cloud."""
-    _require_cuda(cloud)
     bounds = dsm_grid_from_cloud(cloud, resolution, distributed, bounds=bounds)
     if roi is None:
         return rasterize(cloud, bounds, radius, distributed)
@@ -208,7 +171,6 @@ def create_dsm(cloud, roi=None, resolution=RESOLUTION, radius=1, distributed=Fal
 
 # ---- registration ------------------------------------------------------------------------------------------------------------
 def _image(t):
-    _require_cuda(t)
     if t.dim() != 2:
         raise ValueError("DSMs are 2-d (H, W) tensors")
     if t.dtype not in (torch.float32, torch.float64):
@@ -221,16 +183,12 @@ def downsample2x(u):
     u = _image(u)
     h, w = u.shape
     out = torch.empty(((h + 1) // 2, (w + 1) // 2), dtype=torch.float64, device=u.device)
-    _lib.check(_lib.lib().snerf_dsm_downsample2x(_ptr(u), int(u.dtype == torch.float64), h, w, _ptr(out), _stream(u)),
-               "snerf_dsm_downsample2x")
+    _lib.call("snerf_dsm_downsample2x", u, u.dtype == torch.float64, h, w, out)
     return out
 
 
 def _workspace(h, w, radius, device):
-    n = _lib.lib().snerf_dsm_workspace_bytes(h, w, radius)
-    if n == 0:
-        raise ValueError(_lib.lib().snerf_last_error().decode())
-    return torch.empty(n, dtype=torch.uint8, device=device)
+    return torch.empty(_lib.call_size("snerf_dsm_workspace_bytes", h, w, radius, exc=ValueError), dtype=torch.uint8, device=device)
 
 
 def _shift_stats(u, v, cx, cy, radius):
@@ -241,9 +199,7 @@ def _shift_stats(u, v, cx, cy, radius):
     S = (2 * radius + 1) ** 2
     stats = torch.empty((S, 6), dtype=torch.float64, device=u.device)
     ws = _workspace(h, w, radius, u.device)
-    _lib.check(_lib.lib().snerf_dsm_ncc_search(_ptr(u), _ptr(v), int(u.dtype == torch.float64), h, w, int(cx), int(cy),
-                                               int(radius), _ptr(stats), _ptr(ws), ws.numel(), _stream(u)),
-               "snerf_dsm_ncc_search")
+    _lib.call("snerf_dsm_ncc_search", u, v, u.dtype == torch.float64, h, w, cx, cy, radius, stats, ws, ws.numel())
     return stats.cpu().tolist()
 
 
@@ -307,9 +263,7 @@ def _shift_diff(pred, gt, dx, dy, b, want_rdsm=True, want_diff=True):
     diff = torch.empty_like(pred) if want_diff else None
     totals = torch.empty(2, dtype=torch.float64, device=pred.device)
     ws = _workspace(h, w, 0, pred.device)
-    _lib.check(_lib.lib().snerf_dsm_shift_diff(_ptr(pred), _ptr(gt), h, w, int(dx), int(dy), float(b),
-                                               _ptr(rdsm) if want_rdsm else None, _ptr(diff) if want_diff else None,
-                                               _ptr(totals), _ptr(ws), ws.numel(), _stream(pred)), "snerf_dsm_shift_diff")
+    _lib.call("snerf_dsm_shift_diff", pred, gt, h, w, dx, dy, b, rdsm, diff, totals, ws, ws.numel())
     return rdsm, diff, totals
 
 
@@ -356,7 +310,6 @@ def get_utm_cloud(lats, lons, alts):
     """get_utm_cloud (dsm.py:18-30) on device tensors: ((N, 3) f64 (east, north, alt), zone_string), the zone taken from the
     first point as the reference's utm_from_latlon without a zone does"""
     from ...framework.util.conversions import utm_from_latlon
-    _require_cuda(lats, lons, alts)
     easts, norths, zone_string = utm_from_latlon(lats, lons)
     return torch.stack([easts, norths, alts.double()], 1), zone_string
 
@@ -364,7 +317,6 @@ def get_utm_cloud(lats, lons, alts):
 def create_dsm_cloud_from_nerf(dataset, rays, depths):
     """create_dsm_cloud_from_nerf (dsm.py:33-36): the UTM cloud of a frame, one launch through the dataset's GeoFrame (the
     scene's zone; see the module docstring)"""
-    _require_cuda(rays, depths)
     return dataset._need_geo().cloud(rays, depths)[0]
 
 
@@ -376,7 +328,6 @@ def compute_dsm_and_mae(rays, depth, gt_dsm, roi_meta, to_world=None, water_mask
     `distributed` (default: whenever a process group of more than one rank is up): each rank passes its own rays and the
     integer accumulators are all-reduced, so every rank gets the same DSM and MAE (a collective)."""
     from ..extract_pointcloud import get_xyz_from_nerf_prediction
-    _require_cuda(rays, depth)
     bounds = None
     if geo is not None:
         if to_world is not None:

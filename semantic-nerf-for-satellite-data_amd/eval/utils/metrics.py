@@ -112,30 +112,21 @@ def ssim_sums(img1, img2, window, border, c1, c2, eps=0.0, return_map=False):
     """The kernel behind both forms: per-image fp64 sums of the SSIM map of two CUDA fp32 (B, C, H, W) images under the
     (ws, ws) fp32 `window` with `border` "reflect" or "zero"; with return_map also the fp32 map.  Returns (sums, map|None)."""
     from ... import _lib
-    import ctypes as C
     _check_images(img1, img2)
     if border not in ("reflect", "zero"):
         raise ValueError(f"border must be 'reflect' or 'zero', not {border!r}")
-    L = _lib.lib()
     x, y = img1.contiguous(), img2.contiguous()
     b, c, h, w = x.shape
     k = window.to(device=x.device, dtype=torch.float32).contiguous()
     ws = k.shape[-1]
     if k.dim() != 2 or k.shape[0] != ws:
         raise ValueError(f"the window must be (ws, ws), not {tuple(k.shape)}")
-    nbytes = L.snerf_ssim_workspace_bytes(b, c, h, w, ws)
-    if nbytes == 0:
-        raise ValueError(L.snerf_last_error().decode())
+    nbytes = _lib.call_size("snerf_ssim_workspace_bytes", b, c, h, w, ws, exc=ValueError)
     work = torch.empty(nbytes // 8, dtype=torch.float64, device=x.device)
     sums = torch.empty(b, dtype=torch.float64, device=x.device)
     smap = torch.empty_like(x) if return_map else None
     mode = _lib.SSIM_REFLECT if border == "reflect" else _lib.SSIM_ZERO
-    rc = L.snerf_ssim(C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), b, c, h, w, ws, mode, C.c_void_p(k.data_ptr()),
-                      float(c1), float(c2), float(eps), C.c_void_p(smap.data_ptr() if smap is not None else None),
-                      C.c_void_p(sums.data_ptr()), C.c_void_p(work.data_ptr()), nbytes,
-                      C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
-    if rc != 0:
-        raise ValueError(f"snerf_ssim failed (code {rc}): {L.snerf_last_error().decode()}")
+    _lib.call("snerf_ssim", x, y, b, c, h, w, ws, mode, k, c1, c2, eps, smap, sums, work, nbytes, exc=ValueError)
     return sums, smap
 
 

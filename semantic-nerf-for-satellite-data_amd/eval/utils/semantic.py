@@ -72,9 +72,7 @@ def entry_from_stats(conf, errors, n, car_rays, beta_car_sum, no_cars=True, non_
 
 
 def _labels(t, n, what):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise ValueError(f"{what} must be a CUDA tensor")
-    if t.dtype not in (torch.uint8, torch.int64):
+    if not torch.is_tensor(t) or t.dtype not in (torch.uint8, torch.int64):
         raise ValueError(f"{what} must be uint8 or int64, not {t.dtype}")
     if t.numel() != n:
         raise ValueError(f"{what} has {t.numel()} entries for {n} rays")
@@ -107,8 +105,8 @@ class SemanticEvalAccumulator:
     def add(self, pred, gt, gt_no_cars=None, gt_non_corrupted=None, weights=None, beta=None):
         """fold one chunk: pred (n,) int64 labels; gt, gt_no_cars, gt_non_corrupted (n,) or (n, 1) uint8 / int64 targets;
         weights (n, S) and beta (n, S, 1) fp32, given together or not at all.  Asynchronous on the current stream."""
-        if not torch.is_tensor(pred) or not pred.is_cuda or pred.dtype != torch.int64:
-            raise ValueError("pred must be a CUDA int64 tensor")
+        if not torch.is_tensor(pred) or pred.dtype != torch.int64:
+            raise ValueError("pred must be an int64 tensor")
         n = pred.numel()
         if n >= 2 ** 31:
             raise ValueError(f"{n} rays in one chunk: at most 2^31 - 1")
@@ -123,49 +121,36 @@ class SemanticEvalAccumulator:
             raise ValueError("weights and beta are given together or not at all")
         S = 1
         if weights is not None:
-            if weights.dim() != 2 or weights.shape[0] != n or weights.dtype != torch.float32 or not weights.is_cuda:
-                raise ValueError(f"weights must be CUDA fp32 (n, S) with n = {n}")
+            if weights.dim() != 2 or weights.shape[0] != n or weights.dtype != torch.float32:
+                raise ValueError(f"weights must be fp32 (n, S) with n = {n}")
             S = weights.shape[1]
-            if beta.shape not in ((n, S, 1), (n, S)) or beta.dtype != torch.float32 or not beta.is_cuda:
-                raise ValueError(f"beta must be CUDA fp32 ({n}, {S}, 1)")
+            if beta.shape not in ((n, S, 1), (n, S)) or beta.dtype != torch.float32:
+                raise ValueError(f"beta must be fp32 ({n}, {S}, 1)")
             weights, beta = weights.contiguous(), beta.contiguous()
         self._seen("semantic_no_cars", gt_no_cars is not None)
         self._seen("semantic_non_corrupted", gt_non_corrupted is not None)
         self._seen("beta", weights is not None)
-        L = _lib.lib()
         nbytes = 0
         if weights is not None:
-            nbytes = L.snerf_semeval_workspace_bytes(n, S)
-            if nbytes == 0:
-                raise ValueError(L.snerf_last_error().decode())
+            nbytes = _lib.call_size("snerf_semeval_workspace_bytes", n, S, exc=ValueError)
             if self._work is None or self._work.numel() * 8 < nbytes:
                 self._work = torch.empty(nbytes // 8, dtype=torch.float64, device=self.device)
             nbytes = self._work.numel() * 8
-        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)      # noqa: E731
-        rc = L.snerf_semeval_accumulate(ptr(p), ptr(tg[0]), ptr(tg[1]), ptr(tg[2]),
-                                        _lib.SEMEVAL_I64 if i64 else _lib.SEMEVAL_U8, n, self.n_classes, self.car_cls_idx,
-                                        ptr(weights), ptr(beta), S, ptr(self.buf),
-                                        ptr(self._work if weights is not None else None), nbytes,
-                                        C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
-        if rc != 0:
-            raise ValueError(f"snerf_semeval_accumulate failed (code {rc}): {L.snerf_last_error().decode()}")
+        _lib.call("snerf_semeval_accumulate", p, tg[0], tg[1], tg[2], _lib.SEMEVAL_I64 if i64 else _lib.SEMEVAL_U8, n,
+                  self.n_classes, self.car_cls_idx, weights, beta, S, self.buf, self._work if weights is not None else None,
+                  nbytes, exc=ValueError)
         self._host = None
         return self
 
     def allreduce_(self):
         """combine the ranks' accumulators: the integer counts by one SUM all-reduce, the fp64 beta sum by an all_gather summed
         in rank order (every rank holds the same bits).  Single process: nothing."""
-        _, w = parallel.world()
-        if w == 1:
+        if parallel.world()[1] == 1:
             return self
-        import torch.distributed as dist
         counts = self.buf[:_NCOUNT].clone()
         parallel.allreduce_sum_(counts)
         bsum = self.buf[_NCOUNT:].view(torch.float64)
-        hop = bsum.is_cuda and dist.get_backend() == "gloo"      # test rigs only: gloo ranks sharing one GPU
-        src = bsum.cpu() if hop else bsum.clone()
-        parts = [torch.empty_like(src) for _ in range(w)]
-        dist.all_gather(parts, src)
+        parts = parallel.allgather(bsum)
         total = parts[0].clone()
         for part in parts[1:]:
             total += part

@@ -57,18 +57,19 @@ class GeoFrame:
         self.params = _lib.SnerfGeoParams((C.c_double * 3)(*[float(v) for v in center]), float(rng), zone_central_meridian(number),
                                           int(zone_is_south(zone_string)), 0)
 
-    def _run(self, n, dev, want_lla, call, check=True):
+    @staticmethod
+    def _outputs(n, dev, want_lla):
         enu = torch.empty((n, 3), dtype=torch.float64, device=dev)
         lla = torch.empty((n, 3), dtype=torch.float64, device=dev) if want_lla else None
         # int64 holds the unsigned words bit for bit (2^64 - 1 = -1)
-        stats = torch.tensor([-1, 0, -1, 0, 0, 0, 0, 0], dtype=torch.int64, device=dev)
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        call(C.byref(self.params), C.c_void_p(enu.data_ptr()), C.c_void_p(lla.data_ptr()) if want_lla else None,
-             C.c_void_p(stats.data_ptr()), st)
+        return enu, lla, torch.tensor([-1, 0, -1, 0, 0, 0, 0, 0], dtype=torch.int64, device=dev)
+
+    @staticmethod
+    def _result(enu, lla, stats):
         bounds, bad = decode_geo_stats(stats.cpu().tolist())
-        if bad and check:
-            raise ValueError(f"GeoFrame: {bad} of {n} point(s) are not finite")
-        return (enu, lla, bounds) if want_lla else (enu, bounds)
+        if bad:
+            raise ValueError(f"GeoFrame: {bad} of {enu.shape[0]} point(s) are not finite")
+        return (enu, bounds) if lla is None else (enu, lla, bounds)
 
     def cloud(self, rays, depth, want_lla=False):
         """rays (R, >= 6) fp32 (normalised), depth (R,) fp32 -> (cloud (R, 3) f64 (east, north, alt)[, lla (R, 3) f64
@@ -82,10 +83,9 @@ class GeoFrame:
         if rays.shape[1] < 6 or depth.shape[0] != rays.shape[0]:
             raise ValueError(f"GeoFrame.cloud: rays {tuple(rays.shape)} and depth {tuple(depth.shape)} do not match")
         rays, depth = rays.contiguous(), depth.contiguous()
-        L = _lib.lib()
-        return self._run(rays.shape[0], rays.device, want_lla, lambda p, enu, lla, stats, st: _lib.check(
-            L.snerf_geo_cloud(C.c_void_p(rays.data_ptr()), rays.shape[1], C.c_void_p(depth.data_ptr()), rays.shape[0], p, enu,
-                              lla, stats, st), "snerf_geo_cloud"))
+        out = self._outputs(rays.shape[0], rays.device, want_lla)
+        _lib.call("snerf_geo_cloud", rays, rays.shape[1], depth, rays.shape[0], self.params, *out)
+        return self._result(*out)
 
     def points(self, xyz_n, want_lla=False):
         """normalised points (N, 3) -> as `cloud`; computed in fp64 (an fp32 input is widened first)"""
@@ -94,6 +94,6 @@ class GeoFrame:
         if xyz_n.dim() != 2 or xyz_n.shape[1] != 3:
             raise ValueError("GeoFrame.points: (N, 3) points")
         xyz_n = xyz_n.double().contiguous()
-        L = _lib.lib()
-        return self._run(xyz_n.shape[0], xyz_n.device, want_lla, lambda p, enu, lla, stats, st: _lib.check(
-            L.snerf_geo_points(C.c_void_p(xyz_n.data_ptr()), xyz_n.shape[0], p, enu, lla, stats, st), "snerf_geo_points"))
+        out = self._outputs(xyz_n.shape[0], xyz_n.device, want_lla)
+        _lib.call("snerf_geo_points", xyz_n, xyz_n.shape[0], self.params, *out)
+        return self._result(*out)

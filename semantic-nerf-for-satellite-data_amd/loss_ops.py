@@ -9,14 +9,13 @@ result.
 """
 from __future__ import annotations
 
-import ctypes as C
 import os
 from dataclasses import dataclass
 
 import torch
 
 from . import _lib
-from .ops import _ptr, _stream, _check_dev
+from .ops import _check_dev
 
 
 @dataclass(frozen=True)
@@ -50,7 +49,6 @@ def _dist_world():
 class _FusedLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, spec: LossSpec, aux: dict, sync: bool, *diff):
-        L = _lib.lib()
         t = dict(zip(_DIFF, diff))
         ref = next(v for v in diff if v is not None)
         dev = ref.device
@@ -90,13 +88,10 @@ class _FusedLoss(torch.autograd.Function):
             v = (v.view(torch.uint8) if v.dtype == torch.bool else v.to(torch.uint8)).contiguous()   # bool -> uint8: a view, no launch
             keep.append(v)
             li.mask = v.data_ptr()
-        nws = L.snerf_loss_workspace_bytes(C.byref(cfg))
-        ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+        ws = torch.empty(_lib.call_size("snerf_loss_workspace_bytes", cfg), dtype=torch.uint8, device=dev)
         totals = torch.empty(_lib.LOSS_NTOT, dtype=torch.float32, device=dev)
         terms = torch.empty(8, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.snerf_loss_partial(C.byref(cfg), C.byref(li), _ptr(totals), _ptr(ws), nws, _stream()),
-                       "snerf_loss_partial")
+        _lib.call("snerf_loss_partial", cfg, li, totals, ws, ws.numel())
         n_global = float(N)
         if sync and _dist_world() > 1:
             from .parallel import allreduce_sum_
@@ -109,9 +104,7 @@ class _FusedLoss(torch.autograd.Function):
         for k in _DIFF:
             if grads[k] is not None:
                 setattr(lg, k, grads[k].data_ptr())
-        with torch.cuda.device(dev):
-            _lib.check(L.snerf_loss_finish(C.byref(cfg), C.byref(li), _ptr(totals), n_global, 1.0, _ptr(terms),
-                                           C.byref(lg), _stream()), "snerf_loss_finish")
+        _lib.call("snerf_loss_finish", cfg, li, totals, n_global, 1.0, terms, lg)
         ctx.grads = [grads[k] for k in _DIFF]
         ctx._keep = keep
         total = terms.sum()

@@ -5,7 +5,6 @@ path runs in libsnerf_hip.so.  There is no fallback: a CPU tensor or a missing l
 """
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass, field
 
 import torch
@@ -127,21 +126,16 @@ class ModelSpec:
         return names
 
 
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+def _poison(t):
+    """with SNERF_WS_POISON=1 (diagnostic) a fresh tensor is filled with 0xFF bytes, so that a kernel which reads bytes nobody
+    wrote shows up as NaN / a wild value instead of depending on what the allocator happens to hand out"""
+    if _WS_POISON and t.numel():
+        t.view(torch.uint8).fill_(0xFF)
+    return t
 
 
 def _empty(*a, **k):
-    """torch.empty; with SNERF_WS_POISON=1 (diagnostic) filled with 0xFF bytes, so that a kernel which reads bytes nobody
-    wrote shows up as NaN / a wild value instead of depending on what the allocator happens to hand out"""
-    t = torch.empty(*a, **k)
-    if _WS_POISON:
-        t.view(torch.uint8).fill_(0xFF) if t.numel() else None
-    return t
+    return _poison(torch.empty(*a, **k))
 
 
 # ---- pass workspaces -------------------------------------------------------------------------------------------------
@@ -210,13 +204,6 @@ def release_workspaces():
     global _WS_FREE_BYTES
     _WS_FREE.clear()
     _WS_FREE_BYTES = 0
-
-
-def _empty_like(x):
-    t = torch.empty_like(x)
-    if _WS_POISON and t.numel():
-        t.view(torch.uint8).fill_(0xFF)
-    return t
 
 
 # ---- gradient sinks -------------------------------------------------------------------------------------------------
@@ -337,31 +324,21 @@ def params_struct(spec: ModelSpec, tensors: dict) -> _lib.SnerfParams:
 
 def pack_params(spec: ModelSpec, tensors: dict) -> torch.Tensor:
     """state_dict tensors -> packed MFMA-friendly buffer (snerf_pack_params)."""
-    L = _lib.lib()
     d = spec.desc(1, 1)
-    n = L.snerf_packed_floats(C.byref(d))
-    if n == 0:
-        _lib.check(1, "snerf_packed_floats")
     dev = tensors[spec.param_names()[0]].device
-    packed = _empty(n, dtype=torch.float32, device=dev)
-    ps = params_struct(spec, tensors)
-    with torch.cuda.device(dev):
-        _lib.check(L.snerf_pack_params(C.byref(d), C.byref(ps), _ptr(packed), _stream()), "snerf_pack_params")
+    packed = _empty(_lib.call_size("snerf_packed_floats", d), dtype=torch.float32, device=dev)
+    _lib.call("snerf_pack_params", d, params_struct(spec, tensors), packed)
     return packed
 
 
 def unpack_grads(spec: ModelSpec, packed_grads: torch.Tensor, like: dict, accumulate_into: dict | None = None) -> dict:
     """packed gradient buffer -> dict name -> gradient tensor shaped like the parameters."""
-    L = _lib.lib()
     d = spec.desc(1, 1)
     if accumulate_into is None:
-        grads = {n: _empty_like(like[n]) for n in spec.param_names()}
+        grads = {n: _poison(torch.empty_like(like[n])) for n in spec.param_names()}
     else:
         grads = accumulate_into
-    ps = params_struct(spec, grads)
-    with torch.cuda.device(packed_grads.device):
-        _lib.check(L.snerf_unpack_grads(C.byref(d), _ptr(packed_grads), C.byref(ps), int(accumulate_into is not None),
-                                        _stream()), "snerf_unpack_grads")
+    _lib.call("snerf_unpack_grads", d, packed_grads, params_struct(spec, grads), accumulate_into is not None)
     return grads
 
 
@@ -416,24 +393,31 @@ def output_keys(spec: ModelSpec, sc_pass: bool) -> list:
     return keys
 
 
+def _forward_setup(spec, pin, t, t_s, flags):
+    """What both forward entries do before they allocate: S from the inputs, the descriptor, the workspace size, contiguous
+    t / t_s and the inputs struct.  Returns (S, desc, workspace bytes, tc, tsc, launch); launch(packed, so, ws) is the
+    snerf_forward call on the workspace tensor `ws`."""
+    S = (pin.z_vals.shape[1] if pin.z_vals is not None else
+         (pin.u.shape[1] if pin.u is not None else pin.z_steps.shape[0]))
+    d = spec.desc(t.shape[0], S, flags)
+    nbytes = _lib.call_size("snerf_workspace_bytes", d)
+    _check_dev(t, "t")
+    tc = t.contiguous()
+    tsc = t_s.contiguous() if t_s is not None else None
+    si = pin.struct(tc, tsc)
+    return S, d, nbytes, tc, tsc, lambda packed, so, ws: _lib.call("snerf_forward", d, packed, si, so, ws, ws.numel())
+
+
 class _RenderPass(torch.autograd.Function):
     """forward = snerf_forward, backward = snerf_backward (+ snerf_unpack_grads)."""
 
     @staticmethod
     def forward(ctx, spec, pin, sc_pass, need_grad, packed, names, t, t_s, *params):
-        L = _lib.lib()
-        N = t.shape[0]
-        S = (pin.z_vals.shape[1] if pin.z_vals is not None else
-             (pin.u.shape[1] if pin.u is not None else pin.z_steps.shape[0]))
-        dev = t.device
+        N, dev = t.shape[0], t.device
         flags = (_lib.FLAG_TRAIN if need_grad else 0) | (_lib.FLAG_SC_PASS if sc_pass else 0)
-        d = spec.desc(N, S, flags)
-        nbytes = L.snerf_workspace_bytes(C.byref(d))
-        if nbytes == 0:
-            _lib.check(1, "snerf_workspace_bytes")
+        S, d, nbytes, tc, tsc, launch = _forward_setup(spec, pin, t, t_s, flags)
         with torch.cuda.device(dev):
             lease = lease_workspace(dev, nbytes)
-        ws = lease.t
         keys = output_keys(spec, sc_pass)
         outs = {k: _empty(_OUT_SHAPES[k](N, S, spec.n_classes), dtype=torch.float32, device=dev) for k in keys}
         label = _empty((N,), dtype=torch.int64, device=dev) if (spec.n_classes > 0 and not sc_pass) else None
@@ -449,13 +433,7 @@ class _RenderPass(torch.autograd.Function):
         else:
             z_out = _empty((N, S), dtype=torch.float32, device=dev)
             so.z_vals = z_out.data_ptr()
-        _check_dev(t, "t")
-        tc = t.contiguous()
-        tsc = t_s.contiguous() if t_s is not None else None
-        si = pin.struct(tc, tsc)
-        with torch.cuda.device(dev):
-            _lib.check(L.snerf_forward(C.byref(d), _ptr(packed), C.byref(si), C.byref(so), _ptr(ws), nbytes,
-                                       _stream()), "snerf_forward")
+        launch(packed, so, lease.t)
         if not need_grad:
             lease.release()    # nothing is kept for a backward: the next pass of this size on this stream may have it
         ctx.spec, ctx.pin, ctx.desc, ctx.lease, ctx.nbytes = spec, pin, d, lease, nbytes
@@ -471,7 +449,6 @@ class _RenderPass(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *gouts):
-        L = _lib.lib()
         if not ctx.train:
             raise RuntimeError("snerf_amd: backward through a pass that was run without SNERF_FLAG_TRAIN")
         spec, d = ctx.spec, ctx.desc
@@ -488,13 +465,10 @@ class _RenderPass(torch.autograd.Function):
         if not live:
             return (None,) * (8 + len(ctx.names))
         dev = ctx.tc.device
-        pg = torch.zeros(int(L.snerf_grad_floats(C.byref(d))), dtype=torch.float32, device=dev)   # the fp32 region only: the backward touches nothing else
-        d_t = _empty_like(ctx.tc)
-        d_ts = _empty_like(ctx.tsc) if ctx.tsc is not None else None
-        si = ctx.pin.struct(ctx.tc, ctx.tsc)
-        with torch.cuda.device(dev):
-            _lib.check(L.snerf_backward(C.byref(d), _ptr(ctx.packed), C.byref(si), C.byref(go), _ptr(pg), _ptr(d_t),
-                                        _ptr(d_ts), _ptr(ctx.lease.t), ctx.nbytes, _stream()), "snerf_backward")
+        pg = torch.zeros(_lib.call_size("snerf_grad_floats", d), dtype=torch.float32, device=dev)   # the fp32 region only: the backward touches nothing else
+        d_t = _poison(torch.empty_like(ctx.tc))
+        d_ts = _poison(torch.empty_like(ctx.tsc)) if ctx.tsc is not None else None
+        _lib.call("snerf_backward", d, ctx.packed, ctx.pin.struct(ctx.tc, ctx.tsc), go, pg, d_t, d_ts, ctx.lease.t, ctx.nbytes)
         like = dict(zip(ctx.names, ctx.param_like))
         ctx.lease.release()
         sinks = _sinks_for(ctx.param_like)
@@ -549,15 +523,8 @@ def render_pass_into(spec: ModelSpec, params: dict, pin: PassInputs, t: torch.Te
     pass's shapes -- typically row slices of full-frame buffers, so a chunked render never concatenates
     (eval/utils/util.py:13-42 re-concatenates every key per chunk).  Every other SnerfOutputs pointer stays NULL and
     the composite kernel skips it.  Returns the workspace (pass it back in for the next chunk of the same size)."""
-    L = _lib.lib()
-    N = t.shape[0]
-    S = (pin.z_vals.shape[1] if pin.z_vals is not None else
-         (pin.u.shape[1] if pin.u is not None else pin.z_steps.shape[0]))
-    dev = t.device
-    d = spec.desc(N, S, _lib.FLAG_SC_PASS if sc_pass else 0)
-    nbytes = L.snerf_workspace_bytes(C.byref(d))
-    if nbytes == 0:
-        _lib.check(1, "snerf_workspace_bytes")
+    N, dev = t.shape[0], t.device
+    S, _, nbytes, _, _, launch = _forward_setup(spec, pin, t, t_s, _lib.FLAG_SC_PASS if sc_pass else 0)
     if workspace is None or workspace.numel() < nbytes or workspace.device != dev:
         workspace = _empty(nbytes, dtype=torch.uint8, device=dev)
     allowed = set(output_keys(spec, sc_pass)) | {"z_vals"} | ({"semantic_label"} if spec.n_classes > 0 and not sc_pass else set())
@@ -575,13 +542,7 @@ def render_pass_into(spec: ModelSpec, params: dict, pin: PassInputs, t: torch.Te
         setattr(so, k, v.data_ptr())
     if packed is None:
         packed = pack_params(spec, params)
-    _check_dev(t, "t")
-    tc = t.contiguous()
-    tsc = t_s.contiguous() if t_s is not None else None
-    si = pin.struct(tc, tsc)
-    with torch.cuda.device(dev):
-        _lib.check(L.snerf_forward(C.byref(d), _ptr(packed), C.byref(si), C.byref(so), _ptr(workspace), workspace.numel(),
-                                   _stream()), "snerf_forward")
+    launch(packed, so, workspace)
     return workspace
 
 
@@ -590,14 +551,11 @@ class _EmbedRows(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, table, idx):
-        L = _lib.lib()
         _check_dev(table, "embedding table")
         tb = table.detach().contiguous()
         ix = idx.contiguous()
         rows = torch.empty((ix.shape[0], tb.shape[1]), dtype=torch.float32, device=tb.device)
-        with torch.cuda.device(tb.device):
-            _lib.check(L.snerf_embedding_rows(_ptr(tb), tb.shape[0], tb.shape[1], _ptr(ix), ix.shape[0], _ptr(rows), _stream()),
-                       "snerf_embedding_rows")
+        _lib.call("snerf_embedding_rows", tb, tb.shape[0], tb.shape[1], ix, ix.shape[0], rows)
         ctx.save_for_backward(ix)
         ctx.shape = tuple(tb.shape)
         return rows
@@ -605,12 +563,8 @@ class _EmbedRows(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (ix,) = ctx.saved_tensors
-        L = _lib.lib()
         grad = torch.zeros(ctx.shape, dtype=torch.float32, device=g.device)
-        gc = g.contiguous()
-        with torch.cuda.device(g.device):
-            _lib.check(L.snerf_embedding_backward(_ptr(ix), _ptr(gc), ix.shape[0], ctx.shape[1], ctx.shape[0], _ptr(grad), _stream()),
-                       "snerf_embedding_backward")
+        _lib.call("snerf_embedding_backward", ix, g.contiguous(), ix.shape[0], ctx.shape[1], ctx.shape[0], grad)
         return grad, None
 
 
@@ -625,12 +579,8 @@ def embed_rows(embedding: torch.nn.Module, idx: torch.Tensor) -> torch.Tensor:
 
 def sample_z(rays: torch.Tensor, z_steps: torch.Tensor, u: torch.Tensor | None) -> torch.Tensor:
     """stratified depths (N,S) -- snerf_sample_z"""
-    L = _lib.lib()
     _check_dev(rays, "rays")
-    rays = rays.contiguous()
     N, S = rays.shape[0], z_steps.shape[0]
     z = torch.empty((N, S), dtype=torch.float32, device=rays.device)
-    uc = u.contiguous() if u is not None else None
-    with torch.cuda.device(rays.device):
-        _lib.check(L.snerf_sample_z(_ptr(rays), _ptr(z_steps.contiguous()), _ptr(uc), _ptr(z), N, S, _stream()), "snerf_sample_z")
+    _lib.call("snerf_sample_z", rays.contiguous(), z_steps.contiguous(), u.contiguous() if u is not None else None, z, N, S)
     return z

@@ -7,7 +7,6 @@
 * state_dict() / load_state_dict() speak torch.optim.Adam's format, so optimizer_states of a Lightning-style
   checkpoint written by the reference resume here and vice versa (framework/util/load_ckpoint.py).
 """
-import ctypes as C
 from typing import Iterable, List
 
 import torch
@@ -146,18 +145,15 @@ class FlatAdam:
     def step(self, grad_scale: float = 1.0):
         self._collect_foreign_grads()
         grp = self.param_groups[0]
-        L = _lib.lib()
-        st = torch.cuda.current_stream(self.flat_p.device).cuda_stream
         esz = 4
         for a, b in self._runs():
             lo = self.offsets[a]
             hi = self.offsets[b] if b < len(self.params) else self.numel
             for i in range(a, b):
                 self.steps[i] += 1
-            _lib.check(L.snerf_adam_step(self.flat_p.data_ptr() + lo * esz, self.flat_g.data_ptr() + lo * esz,
-                                         self.exp_avg.data_ptr() + lo * esz, self.exp_avg_sq.data_ptr() + lo * esz,
-                                         C.c_ulonglong(hi - lo), grp["lr"], grp["betas"][0], grp["betas"][1], grp["eps"],
-                                         self.steps[a], float(grad_scale), C.c_void_p(st)), "snerf_adam_step")
+            _lib.call("snerf_adam_step", self.flat_p.data_ptr() + lo * esz, self.flat_g.data_ptr() + lo * esz,
+                      self.exp_avg.data_ptr() + lo * esz, self.exp_avg_sq.data_ptr() + lo * esz, hi - lo, grp["lr"],
+                      grp["betas"][0], grp["betas"][1], grp["eps"], self.steps[a], grad_scale, device=self.flat_p.device)
         self._active = None
 
     def state_dict(self):

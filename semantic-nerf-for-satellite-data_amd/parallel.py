@@ -38,19 +38,34 @@ def init_distributed(backend: str = None):
     return rank, ws, device
 
 
-def _all_reduce(t: torch.Tensor):
-    if t.is_cuda and dist.get_backend() == "gloo":  # test rigs only: gloo ranks sharing one GPU
-        h = t.cpu()
-        dist.all_reduce(h, op=dist.ReduceOp.SUM)
-        t.copy_(h)
-    else:
-        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+def _host_hop(t: torch.Tensor) -> bool:
+    """test rigs only: gloo ranks sharing one GPU exchange through the host"""
+    return t.is_cuda and dist.get_backend() == "gloo"
+
+
+def allreduce_(t: torch.Tensor, op=None) -> torch.Tensor:
+    """all-reduce `t` in place over the ranks of the default group (a dist.ReduceOp; SUM by default); single process: nothing"""
+    if world()[1] > 1:
+        op = dist.ReduceOp.SUM if op is None else op
+        if _host_hop(t):
+            h = t.cpu()
+            dist.all_reduce(h, op=op)
+            t.copy_(h)
+        else:
+            dist.all_reduce(t, op=op)
+    return t
 
 
 def allreduce_sum_(t: torch.Tensor) -> torch.Tensor:
-    if world()[1] > 1:
-        _all_reduce(t)
-    return t
+    return allreduce_(t)
+
+
+def allgather(t: torch.Tensor) -> list:
+    """every rank's `t` (equal shapes) in rank order; the parts are host tensors when the exchange went through the host"""
+    src = t.cpu() if _host_hop(t) else t
+    parts = [torch.empty_like(src) for _ in range(world()[1])]
+    dist.all_gather(parts, src)
+    return parts
 
 
 def frame_shard(n: int, rank: int = None, world_size: int = None):
@@ -75,13 +90,7 @@ def allgather_rows(local: torch.Tensor, n_total: int) -> torch.Tensor:
     if local.shape[0] != per:
         piece = local.new_zeros((per,) + tuple(local.shape[1:]))
         piece[:local.shape[0]] = local
-    piece = piece.contiguous()
-    hop = piece.is_cuda and dist.get_backend() == "gloo"      # test rigs only: gloo ranks sharing one GPU
-    src = piece.cpu() if hop else piece
-    parts = [torch.empty_like(src) for _ in range(w)]
-    dist.all_gather(parts, src)
-    full = torch.cat(parts, 0)[:n_total]
-    return full.to(local.device) if hop else full
+    return torch.cat(allgather(piece.contiguous()), 0)[:n_total].to(local.device)
 
 
 def allreduce_gradients(params, flat_buffer: torch.Tensor = None) -> torch.Tensor:
@@ -92,6 +101,6 @@ def allreduce_gradients(params, flat_buffer: torch.Tensor = None) -> torch.Tenso
         return flat_buffer
     grads = [p.grad for p in params]
     flat = torch.cat([g.reshape(-1) for g in grads])
-    _all_reduce(flat)
+    allreduce_(flat)
     torch._foreach_copy_(grads, [v.view_as(g) for v, g in zip(flat.split([g.numel() for g in grads]), grads)])
     return flat

@@ -25,6 +25,93 @@ def test_library_exports_every_declared_symbol():
     assert sorted(_lib.EXPORTED_SYMBOLS) == declared
 
 
+_SCALARS = {"int": ("int", 4, True), "unsigned": ("int", 4, False), "long long": ("int", 8, True),
+            "unsigned long long": ("int", 8, False), "size_t": ("int", 8, False), "float": ("float", 4, True),
+            "double": ("float", 8, True)}
+
+
+def _c_type(text):
+    """a C parameter or return type -> ("pointer", pointee) or (class, bytes, signed)"""
+    words = text.replace("*", " * ").split()
+    base = " ".join(w for w in words if w not in ("const", "*"))
+    return ("pointer", base) if "*" in words else _SCALARS[base]
+
+
+def _header_prototypes():
+    """include/snerf_hip.h without comments, preprocessor lines and struct bodies -> {symbol: (return type, [(type, name)])}"""
+    src = open(os.path.join(ROOT, "include", "snerf_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = re.sub(r"^\s*#.*$", "", src, flags=re.M)
+    src = re.sub(r"typedef struct \w+ \{.*?\} \w+;", "", src, flags=re.S)
+    protos = {}
+    for ret, name, params in re.findall(r"([\w \*]+?)\b(snerf_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", src):
+        params = [] if params.strip() == "void" else [re.fullmatch(r"\s*(.*?)(\w+)\s*", p).groups() for p in params.split(",")]
+        protos[name] = (_c_type(ret), [(_c_type(t), n) for t, n in params])
+    return protos
+
+
+def _table_type(t):
+    """a ctypes type of the table, in _c_type's terms"""
+    from snerf_amd import _lib
+    if t is C.c_char_p:
+        return ("pointer", "char")
+    if issubclass(t, C.c_void_p):
+        return ("pointer", None)                       # void*: stands for a pointer to anything (device memory, host tables)
+    if issubclass(t, C._Pointer):
+        inner = t._type_
+        if issubclass(inner, C.Structure):
+            assert getattr(_lib, inner.__name__) is inner
+            return ("pointer", inner.__name__)
+        return ("pointer", {v: k for k, v in _SCALARS.items()}[_table_type(inner)])
+    if t in (C.c_float, C.c_double):
+        return ("float", C.sizeof(t), True)
+    return ("int", C.sizeof(t), t(-1).value < 0)
+
+
+def test_binding_table_matches_header_prototypes():
+    """Every prototype of the header against its row of _lib.SIGNATURES: the return type, the parameter count and, per parameter,
+    class, width and signedness; a pointer to a struct against POINTER() of the mirror with that name (or void*); the stream
+    marker exactly where the header's parameter is called `stream`.  No symbol is left out: the parser must give a prototype
+    for every name _declared_symbols() finds."""
+    from snerf_amd import _lib
+    protos = _header_prototypes()
+    assert sorted(protos) == _declared_symbols() == sorted(_lib.SIGNATURES) and len(protos) >= 42
+    for name, (ret, params) in protos.items():
+        restype, argtypes = _lib.SIGNATURES[name]
+        assert _table_type(restype) == ret, (name, "return type", restype, ret)
+        assert len(argtypes) == len(params), (name, len(argtypes), len(params))
+        for k, (t, (want, pname)) in enumerate(zip(argtypes, params)):
+            got = _table_type(t)
+            assert got == want or (want[0] == "pointer" and got == ("pointer", None)), (name, k, pname, t, want)
+            assert (t is _lib.c_stream) == (pname == "stream"), (name, k, pname, t)
+    L = _lib.lib()
+    for name, (restype, argtypes) in _lib.SIGNATURES.items():       # lib() applied the table
+        assert getattr(L, name).restype is restype and tuple(getattr(L, name).argtypes) == tuple(argtypes), name
+
+
+def test_call_argument_handling_without_a_launch():
+    """_lib.call refuses what must not reach the library before anything is launched, and direct callers of lib() can still
+    hand a stream slot what a void* takes."""
+    import torch
+    from snerf_amd import _lib
+    from snerf_amd.ops import ModelSpec
+    rays, steps, z = torch.zeros(5, 8), torch.zeros(3), torch.zeros(5, 3)
+    with pytest.raises(RuntimeError, match=r"must live on the GPU \(the HIP path has no CPU fallback\)"):
+        _lib.call("snerf_sample_z", rays, steps, None, z, 5, 3)
+    with pytest.raises(TypeError, match="snerf_sample_z takes 6 arguments"):
+        _lib.call("snerf_sample_z", None, None, None, None, 5)
+    with pytest.raises(TypeError, match="snerf_sample_z takes 6 arguments"):
+        _lib.call("snerf_sample_z", None, None, None, None, 5, 3, None)        # the stream is not the caller's to pass
+    with pytest.raises(TypeError, match="device"):
+        _lib.call("snerf_sample_z", None, None, None, None, 5, 3)              # no tensor, no device=: no stream to take
+    with pytest.raises(TypeError):
+        _lib.call_size("snerf_workspace_bytes")
+    d = ModelSpec().desc(64, 8)
+    assert _lib.call_size("snerf_workspace_bytes", d) == _lib.lib().snerf_workspace_bytes(C.byref(d)) > 0
+    for v in (None, 0, C.c_void_p(16), _lib.c_stream(16)):
+        _lib.c_stream.from_param(v)
+
+
 def test_struct_sizes_match_header():
     """ctypes mirrors must match the C layout (64-bit pointers, 4-byte ints)."""
     from snerf_amd import _lib
@@ -57,7 +144,8 @@ def test_host_only_sizes_and_errors():
     assert L.snerf_workspace_bytes(C.byref(bad)) == 0
     assert b"n_rays" in L.snerf_last_error()
     bad = ModelSpec(fc_units=520).desc(16, 8)
-    assert L.snerf_packed_floats(C.byref(bad)) == 0
+    with pytest.raises(RuntimeError, match=r"snerf_packed_floats failed \(code 1\): .*fc_units"):      # a returned 0, through the binding
+        _lib.call_size("snerf_packed_floats", bad)
     assert b"fc_units" in L.snerf_last_error()
     # the two arithmetic flags exclude each other (flags = 0 is the default arithmetic, f16x2)
     both = ModelSpec().desc(16, 8, _lib.FLAG_F16X2 | _lib.FLAG_F16X1)
