@@ -346,6 +346,77 @@ int snerf_semeval_accumulate(const long long* pred, const void* gt, const void* 
                              int label_dtype, int n, int n_classes, int car_idx, const float* weights, const float* beta,
                              int n_samples, SnerfSemevalAcc* acc, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- per-image visualisation maps (framework/visualize.py, baseline/components/visualize.py, semantic/components/visualize.py,
+ * framework/util/other.py visualize_image_numpy) -------------------------------------------------------------------------------
+ * snerf_vis_fold takes one render chunk of m rays and writes columns [row0, row0 + m) of the frame's planes; planes are planar
+ * (bands, n) with frame stride n.  Every pointer of SnerfVisIn / SnerfVisOut may be NULL: its products are skipped (an output
+ * given without its input is refused).
+ *   per sample: weights (m, S), albedo (m, S, 3), sun (m, S, 1), sky (m, S, 3), beta (m, S, 1), beta_semantic (m, S, 1), fp32 ->
+ *     albedo_map (3, n), sun_map (n), sky_map (3, n), beta_map (n), beta_semantic_map (n) = sum_s fl32(w_s f_s): the product
+ *     rounded to fp32 (torch's weights.unsqueeze(-1) * factor), the sum in fp64, rounded once to fp32.  One wave per ray: lane l
+ *     adds the row's floats l, l + 64, ... in ascending order, then a fixed xor butterfly over the 64 lanes.  The order depends on
+ *     S alone: a ray's value does not depend on its place in the chunk, on m or on row0.  Each tensor is read once, flat.
+ *   per ray: depth (m) -> depth_map (n), a copy; rgb, rgbs_gt (m, 3) -> rgb_diff (3, n) = |gt - rgb| and rgb_diff_distance (n) =
+ *     sqrt((d0^2 + d1^2) + d2^2), every step fp32 and rounded once; label (m) int64 and palette (n_palette, 3) uint8 ->
+ *     sem_color (3, n) uint8 = palette[label] and sem_shaded (3, n) uint8 = the fp32 product float(palette[label]) * sun_map
+ *     truncated (through int32, low eight bits: plain truncation in [0, 256)); label and semantic_gt (m) uint8 (SNERF_VIS_U8) or
+ *     int64 (SNERF_VIS_I64) -> sem_error (n) fp32 = clamp(|gt - label|, 0, 1).  A label outside [0, n_palette) is coloured
+ *     (0, 0, 0) and adds 1 to stats->bad_labels; the palette is not read for it.
+ *   stats (device memory, ZEROED by the caller before an image's first chunk): per scalar plane (SNERF_VIS_SLOT_*) the exact
+ *     minimum and maximum of the values as numpy.nan_to_num makes them (NaN -> 0, +-inf -> +-FLT_MAX; -0.0 counts as +0.0), as
+ *     order-preserving 64-bit keys of the value widened to fp64 (bits with the sign bit set for v >= 0, all bits inverted for
+ *     v < 0), folded with integer atomic max: minmax[slot][1] = max key, minmax[slot][0] = max of the INVERTED key (= the minimum);
+ *     0 = no value yet.  Exact and independent of the launch order; ranks combine them by an unsigned max.
+ * snerf_vis_minmax folds the same bounds of any plane (fp32: SNERF_VIS_F32, fp64: SNERF_VIS_F64; +-inf -> +-DBL_MAX there) into
+ * a slot: the fp64 altitude plane uses SNERF_VIS_SLOT_USER.
+ * snerf_vis_colormap is visualize_image_numpy: x = nan_to_num(x); x = (x - mi) / (ma - mi + 1e-8); index = (255 * x) truncated to
+ * uint8 (as above); out (3, n) uint8 = table[index] for a (256, 3) uint8 table.  Every step in the plane's own precision with one
+ * rounding per operation.  slot >= 0: mi, ma are that slot's bounds, read on the device (an empty slot: 0, 0), and the
+ * denominator is fl(fl(ma - mi) + fl(1e-8)) in the plane's type -- numpy >= 2 (NEP 50: the Python float takes the array scalars'
+ * type); slot < 0: the explicit bounds lo, hi (cmap_bounds, Python floats): mi = fl(lo), denominator = fl(hi - lo + 1e-8)
+ * with the sum formed in fp64.
+ * All three launch on `stream`, allocate nothing and do not synchronise.  Refused without touching the device: null in / out /
+ * stats / plane / table, rows outside the frame, per-sample inputs without weights, n_samples outside [1,
+ * SNERF_VIS_MAX_SAMPLES], rgb without rgbs_gt or the reverse, semantic_gt / palette without label, sem_shaded without sun and
+ * palette, unknown dtypes, a slot outside [0, SNERF_VIS_SLOTS), NaN explicit bounds. */
+#define SNERF_VIS_MAX_SAMPLES 1024
+#define SNERF_VIS_SLOTS 8
+#define SNERF_VIS_SLOT_DEPTH 0
+#define SNERF_VIS_SLOT_SUN 1
+#define SNERF_VIS_SLOT_BETA 2
+#define SNERF_VIS_SLOT_BETA_SEMANTIC 3
+#define SNERF_VIS_SLOT_RGB_DIFF_DISTANCE 4
+#define SNERF_VIS_SLOT_SEM_ERROR 5
+#define SNERF_VIS_SLOT_USER 6
+#define SNERF_VIS_U8 0
+#define SNERF_VIS_I64 1
+#define SNERF_VIS_F32 0
+#define SNERF_VIS_F64 1
+typedef struct SnerfVisIn {
+  const float *weights, *albedo, *sun, *sky, *beta, *beta_semantic;
+  const float *depth, *rgb, *rgbs_gt;
+  const long long* label;
+  const void* semantic_gt;
+  const unsigned char* palette;
+  int gt_dtype, n_palette;
+} SnerfVisIn;
+typedef struct SnerfVisOut {
+  float *albedo_map, *sun_map, *sky_map, *beta_map, *beta_semantic_map;
+  float *depth_map, *rgb_diff, *rgb_diff_distance;
+  unsigned char *sem_color, *sem_shaded;
+  float* sem_error;
+} SnerfVisOut;
+typedef struct SnerfVisStats {
+  unsigned long long minmax[SNERF_VIS_SLOTS][2];
+  unsigned long long bad_labels;
+  unsigned long long reserved[7];
+} SnerfVisStats;
+int snerf_vis_fold(const SnerfVisIn* in, const SnerfVisOut* out, int m, int n_samples, long long row0, long long n,
+                   SnerfVisStats* stats, void* stream);
+int snerf_vis_minmax(const void* plane, int plane_dtype, long long n, SnerfVisStats* stats, int slot, void* stream);
+int snerf_vis_colormap(const void* plane, int plane_dtype, long long n, const SnerfVisStats* stats, int slot, double lo, double hi,
+                       const unsigned char* table, unsigned char* out, void* stream);
+
 /* ---- scenes on disk: RPC rays (baseline/components/rays.py satnerf_construct, rpcm RPCModel, framework/util/conversions.py,
  * baseline/components/normalization.py StandardNormalization) --------------------------------------------------------------
  * SnerfRpc: rpcm's RPCModel as fp64 (offsets, scales; 20-term numerators / denominators in the RPC00B order

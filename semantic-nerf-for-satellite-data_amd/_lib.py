@@ -102,6 +102,29 @@ class SnerfSemevalAcc(C.Structure):
         (n, C.c_uint64) for n in ("rays", "car_rays", "out_of_range")] + [("beta_car_sum", C.c_double)]
 
 
+VIS_MAX_SAMPLES = 1024     # include/snerf_hip.h SNERF_VIS_MAX_SAMPLES
+VIS_SLOTS = 8              # include/snerf_hip.h SNERF_VIS_SLOTS
+VIS_SLOT = {"depth": 0, "sun": 1, "beta": 2, "beta_semantic": 3, "rgb_diff_distance": 4, "sem_error": 5, "user": 6}   # SNERF_VIS_SLOT_*
+VIS_U8, VIS_I64 = 0, 1     # include/snerf_hip.h SNERF_VIS_U8 / SNERF_VIS_I64
+VIS_F32, VIS_F64 = 0, 1    # include/snerf_hip.h SNERF_VIS_F32 / SNERF_VIS_F64
+VIS_IN_FIELDS = ("weights", "albedo", "sun", "sky", "beta", "beta_semantic", "depth", "rgb", "rgbs_gt", "label", "semantic_gt",
+                 "palette")
+VIS_OUT_FIELDS = ("albedo_map", "sun_map", "sky_map", "beta_map", "beta_semantic_map", "depth_map", "rgb_diff",
+                  "rgb_diff_distance", "sem_color", "sem_shaded", "sem_error")
+
+
+class SnerfVisIn(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in VIS_IN_FIELDS] + [("gt_dtype", C.c_int32), ("n_palette", C.c_int32)]
+
+
+class SnerfVisOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in VIS_OUT_FIELDS]
+
+
+class SnerfVisStats(C.Structure):
+    _fields_ = [("minmax", C.c_uint64 * 2 * VIS_SLOTS), ("bad_labels", C.c_uint64), ("reserved", C.c_uint64 * 7)]
+
+
 class SnerfRpc(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("row_offset", "col_offset", "lat_offset", "lon_offset", "alt_offset", "row_scale",
                                           "col_scale", "lat_scale", "lon_scale", "alt_scale")] + [
@@ -168,6 +191,10 @@ def _signatures():
         "snerf_ssim": (i, (p, p) + (i,) * 6 + (p, d, d, d, p, p, p, sz, st)),
         "snerf_semeval_workspace_bytes": (sz, (i, i)),
         "snerf_semeval_accumulate": (i, (p,) * 4 + (i,) * 4 + (p, p, i, p, p, sz, st)),
+        # SnerfVisStats lives in device memory: void*
+        "snerf_vis_fold": (i, (P(SnerfVisIn), P(SnerfVisOut), i, i, ll, ll, p, st)),
+        "snerf_vis_minmax": (i, (p, i, ll, p, i, st)),
+        "snerf_vis_colormap": (i, (p, i, ll, p, i, d, d, p, p, st)),
         # SnerfRayImage / SnerfRpc tables go as void*: the same slot type serves the host copy (a ctypes array or byref) and the
         # device copy (a tensor)
         "snerf_rpc_rays": (i, (p, p, i, p, ll, p, p, st)),

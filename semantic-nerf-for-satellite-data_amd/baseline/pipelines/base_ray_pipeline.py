@@ -1,7 +1,7 @@
 """Ray pipeline -- mirror of baseline/pipelines/base_ray_pipeline.py:14-269: forward = ray-chunk loop over
 render_chunk_size rays with key-wise concatenation, training_step wrapper, validation_step (full-image render under
 no_grad incl. the solar-correction pass -> loss -> PSNR -> SSIM [-> DSM altitude MAE when the batch carries a "dsm" entry];
-visualisers are out of scope), Adam + StepLR."""
+validation draws nothing: the visualisers run through framework/visualize.py run_visualizer), Adam + StepLR."""
 import math
 import time
 from collections import defaultdict

@@ -94,6 +94,20 @@ class SatNeRFPipeline(BaseRayPipeline):
     def _init_training_step(self):
         return SatNeRFTrainingStep()
 
+    @staticmethod
+    def create_visualizers(cfgs) -> list:
+        """the reference's _init_visualizers list (satnerf.py:74-108) without its TensorBoard summary: what run_visualizer's
+        create_visualizers_fn returns.  `_init_visualizers` itself keeps returning []: validation draws nothing."""
+        from ..components import visualize
+        from ...framework.util.colormaps import COLORMAP_BONE
+        kw = dict(save_as_tif=True, send_to_tensorboard=True)
+        return [visualize.FactorVisualization(cfgs, factor_name="rgb", **kw),
+                visualize.FactorVisualization(cfgs, factor_name="depth", **kw),
+                visualize.FactorVisualization(cfgs, factor_name="albedo", **kw),
+                visualize.FactorVisualization(cfgs, factor_name="sun", cmap=COLORMAP_BONE, **kw),
+                visualize.FactorVisualization(cfgs, factor_name="beta", cmap=COLORMAP_BONE, **kw),
+                visualize.RGBDiffDistanceVisualization(cfgs, **kw)]
+
     @classmethod
     def init_config(cls, cfg_information):
         return SatNeRFConfig(**cfg_information)

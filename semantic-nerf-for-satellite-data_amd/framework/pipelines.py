@@ -90,7 +90,7 @@ class Pipeline(torch.nn.Module):
         pass
 
     def _init_visualizers(self) -> list:
-        return []  # visualisers are out of scope
+        return []  # validation draws nothing; the visualisers are create_visualizers() + framework/visualize.py run_visualizer
 
     @abc.abstractmethod
     def _init_training_step(self):

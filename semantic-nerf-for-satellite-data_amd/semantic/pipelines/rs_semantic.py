@@ -85,6 +85,15 @@ class RSSemanticPipeline(SatNeRFPipeline):
             self.log("test/mIoU", out["mIoU"], batch_size=1)
         return out
 
+    @staticmethod
+    def create_visualizers(cfgs) -> list:
+        """the baseline list plus the reference's semantic visualisers (rs_semantic.py:87-118) that are in scope"""
+        from ..components import visualize as visualize_semantic
+        return SatNeRFPipeline.create_visualizers(cfgs) + [
+            visualize_semantic.SemanticColorVisualization(cfgs, save_as_tif=True, send_to_tensorboard=False),
+            visualize_semantic.SemanticErrorVisualization(cfgs, save_as_tif=True, send_to_tensorboard=False),
+            visualize_semantic.SemanticColorShadingVisualization(cfgs, save_as_tif=True, send_to_tensorboard=True)]
+
     @classmethod
     def init_config(cls, cfg_information):
         return RSSemanticConfig(**cfg_information)
