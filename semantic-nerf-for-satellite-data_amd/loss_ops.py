@@ -15,7 +15,7 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
-from .ops import _check_dev
+from .ops import _check_dev, _empty, _poison
 
 
 @dataclass(frozen=True)
@@ -88,9 +88,9 @@ class _FusedLoss(torch.autograd.Function):
             v = (v.view(torch.uint8) if v.dtype == torch.bool else v.to(torch.uint8)).contiguous()   # bool -> uint8: a view, no launch
             keep.append(v)
             li.mask = v.data_ptr()
-        ws = torch.empty(_lib.call_size("snerf_loss_workspace_bytes", cfg), dtype=torch.uint8, device=dev)
-        totals = torch.empty(_lib.LOSS_NTOT, dtype=torch.float32, device=dev)
-        terms = torch.empty(8, dtype=torch.float32, device=dev)
+        ws = _empty(_lib.call_size("snerf_loss_workspace_bytes", cfg), dtype=torch.uint8, device=dev)
+        totals = _empty(_lib.LOSS_NTOT, dtype=torch.float32, device=dev)
+        terms = _empty(8, dtype=torch.float32, device=dev)
         _lib.call("snerf_loss_partial", cfg, li, totals, ws, ws.numel())
         n_global = float(N)
         if sync and _dist_world() > 1:
@@ -98,7 +98,7 @@ class _FusedLoss(torch.autograd.Function):
             allreduce_sum_(totals)           # sums and counts over all ranks (tiny: 16 floats)
             n_global = 0.0                   # = take the global ray count from totals (it is one of the summed counts):
             #                                  right for unequal shards too (e.g. the depth-ray bank)
-        grads = {k: (torch.empty_like(t[k], memory_format=torch.contiguous_format) if t[k] is not None else None)
+        grads = {k: (_poison(torch.empty_like(t[k], memory_format=torch.contiguous_format)) if t[k] is not None else None)
                  for k in _DIFF}
         lg = _lib.SnerfLossGrads()
         for k in _DIFF:

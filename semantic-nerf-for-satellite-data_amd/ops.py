@@ -13,6 +13,7 @@ import os
 import weakref
 
 _WS_POISON = os.environ.get("SNERF_WS_POISON", "0") == "1"
+_WS_POISON_BYTE = 0xFF      # the fill of _poison / lease_workspace: 0xFF is NaN in fp16 / fp32 / fp64 and -1 as an integer (tests set others)
 
 from . import _lib
 
@@ -127,10 +128,10 @@ class ModelSpec:
 
 
 def _poison(t):
-    """with SNERF_WS_POISON=1 (diagnostic) a fresh tensor is filled with 0xFF bytes, so that a kernel which reads bytes nobody
-    wrote shows up as NaN / a wild value instead of depending on what the allocator happens to hand out"""
+    """with SNERF_WS_POISON=1 (diagnostic) a fresh tensor is filled with _WS_POISON_BYTE bytes (0xFF), so that a kernel which reads
+    bytes nobody wrote shows up as NaN / a wild value instead of depending on what the allocator happens to hand out"""
     if _WS_POISON and t.numel():
-        t.view(torch.uint8).fill_(0xFF)
+        t.view(torch.uint8).fill_(_WS_POISON_BYTE)
     return t
 
 
@@ -187,7 +188,7 @@ def lease_workspace(dev, nbytes: int) -> _WsLease:
         if not lst:
             del _WS_FREE[key]
         if _WS_POISON:
-            t.fill_(0xFF)
+            t.fill_(_WS_POISON_BYTE)
     else:
         try:
             t = _empty(nbytes, dtype=torch.uint8, device=dev)
@@ -554,7 +555,7 @@ class _EmbedRows(torch.autograd.Function):
         _check_dev(table, "embedding table")
         tb = table.detach().contiguous()
         ix = idx.contiguous()
-        rows = torch.empty((ix.shape[0], tb.shape[1]), dtype=torch.float32, device=tb.device)
+        rows = _empty((ix.shape[0], tb.shape[1]), dtype=torch.float32, device=tb.device)
         _lib.call("snerf_embedding_rows", tb, tb.shape[0], tb.shape[1], ix, ix.shape[0], rows)
         ctx.save_for_backward(ix)
         ctx.shape = tuple(tb.shape)
@@ -581,6 +582,6 @@ def sample_z(rays: torch.Tensor, z_steps: torch.Tensor, u: torch.Tensor | None) 
     """stratified depths (N,S) -- snerf_sample_z"""
     _check_dev(rays, "rays")
     N, S = rays.shape[0], z_steps.shape[0]
-    z = torch.empty((N, S), dtype=torch.float32, device=rays.device)
+    z = _empty((N, S), dtype=torch.float32, device=rays.device)
     _lib.call("snerf_sample_z", rays.contiguous(), z_steps.contiguous(), u.contiguous() if u is not None else None, z, N, S)
     return z

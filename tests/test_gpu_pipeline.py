@@ -125,11 +125,12 @@ def test_loss_modules_vs_oracle_many_classes(N, S, C):
     _loss_modules_vs_oracle(N, S, C)
 
 
-def _loss_modules_vs_oracle(N, S, C):
+def _loss_modules_vs_oracle(N, S, C, collect=None):
     """every loss class of the mirror (values + gradients w.r.t. every rendered tensor) vs the oracle -- at a ragged small
     size and at the per-GPU batch sizes of BASELINE configs[1] / [2] (4096 x 64, 8192 x 96: the data-dependent counts of CE with
     ignore index, L_t over car rays, masks and depth weights then span many workgroups of the partial-sum kernel); at 5 classes, at the
-    plan's 16 (MAX_CLASSES) and at the 64 check_loss accepts, where the logit gradient uses every lane of the wavefront"""
+    plan's 16 (MAX_CLASSES) and at the 64 check_loss accepts, where the logit gradient uses every lane of the wavefront.
+    `collect` (a dict) receives every value and gradient the HIP side produced, by "<case>/<name>" (tests/test_gpu_fill.py)"""
     from snerf_amd.baseline.components.loss import SNerfLoss, SatNerfLoss, DepthLoss
     from snerf_amd.semantic.components.loss import SemanticLoss, SemanticUncertaintyLoss, SemanticCarRegLoss
     g = torch.Generator().manual_seed(S + N)
@@ -181,6 +182,10 @@ def _loss_modules_vs_oracle(N, S, C):
                 continue
             assert gh is not None, (name, k)
             assert rel_err(gh.cpu(), go) <= 2e-5 or max_abs(gh.cpu(), go) <= 1e-9, (name, k, rel_err(gh.cpu(), go))
+        if collect is not None:
+            collect[f"{name}/total"] = loss_h.detach()
+            collect.update({f"{name}/loss_{k}": v.detach() for k, v in ld_h.items()})
+            collect.update({f"{name}/grad_{k}": v.grad for k, v in rh.items() if v.grad is not None})
 
 
 MERGED_SIZES = [(77, 16, "plain"), (4096, 64, "plain"), (4096, 96, "uncertainty"), (513, 64, "uncertainty_sbeta")]
@@ -197,7 +202,7 @@ def test_merged_loss_call_many_classes(N, S, sem, C):
     _merged_loss_call_equals_module_by_module(N, S, sem, C)
 
 
-def _merged_loss_call_equals_module_by_module(N, S, sem, C):
+def _merged_loss_call_equals_module_by_module(N, S, sem, C, collect=None):
     """The training steps evaluate colour + semantic (+ L_t) losses as ONE fused call (loss_ops.run_plans).  Against the same modules
     called one by one, as the reference does: the same loss_dict, the same total and the same gradient on every rendered tensor --
     also on weights / beta, where the colour loss, the beta-weighted CE and L_t all contribute.  At 5, 16 and 64 classes."""
@@ -238,6 +243,10 @@ def _merged_loss_call_equals_module_by_module(N, S, sem, C):
             assert gb is None or float(gb.abs().max()) == 0.0, k
             continue
         assert rel_err(gb.cpu(), ga.cpu()) <= 2e-6, (k, rel_err(gb.cpu(), ga.cpu()))
+    if collect is not None:     # everything the merged call produced, by name (tests/test_gpu_fill.py)
+        collect["total"] = total_b.detach()
+        collect.update({f"loss_{k}": v.detach() for k, v in dict_b.items()})
+        collect.update({f"grad_{k}": v.grad for k, v in rb.items() if v.grad is not None})
     # two modules that own the same terms do not merge: evaluated one by one, summed
     two = [color.plan(rb, gt), SatNerfLoss(lambda_sc=0.0).plan(rb, gt)]
     assert loss_ops.merge_plans(two) is None
