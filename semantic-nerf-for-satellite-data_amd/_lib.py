@@ -1,4 +1,4 @@
-"""ctypes binding of libsnerf_hip.so -- mirrors include/snerf_hip.h field for field."""
+"""ctypes binding of libsnerf_hip.so -- mirrors include/snerf_hip.h (and include/snerf_ortho.h) field for field."""
 import ctypes as C
 import os
 
@@ -221,11 +221,35 @@ def _signatures():
 SIGNATURES = _signatures()
 EXPORTED_SYMBOLS = tuple(SIGNATURES)
 
+ORTHO_VERSION = 1          # include/snerf_ortho.h SNERF_ORTHO_VERSION
+ORTHO_MAX_RADIUS = 7       # include/snerf_ortho.h SNERF_ORTHO_MAX_RADIUS
+ORTHO_MAX_CLASSES = 255    # include/snerf_ortho.h SNERF_ORTHO_MAX_CLASSES
+ORTHO_NO_LABEL = 255       # include/snerf_ortho.h SNERF_ORTHO_NO_LABEL
+
+
+def _ortho_signatures():
+    i, ll, d, p, st, grid = C.c_int, C.c_longlong, C.c_double, C.c_void_p, c_stream, C.POINTER(SnerfDsmGrid)
+    return {
+        "snerf_ortho_version": (i, ()),
+        "snerf_ortho_top": (i, (p, ll, ll, grid, i, d, d, p, p, st)),
+        "snerf_ortho_gather": (i, (p, ll, ll, ll, d, d) + (p,) * 8 + (st,)),
+        "snerf_ortho_votes": (i, (p, p, ll, grid, i, i, p, p, st)),
+        "snerf_ortho_votes_finish": (i, (p, i, ll, p, p, p, st)),
+    }
+
+
+# The second table: one row per prototype of include/snerf_ortho.h, in the header's order (tests/test_ortho_cpu.py compares the
+# two).  Same library, same call path; kept apart from SIGNATURES / EXPORTED_SYMBOLS, which mirror include/snerf_hip.h alone.
+ORTHO_SIGNATURES = _ortho_signatures()
+assert not set(ORTHO_SIGNATURES) & set(SIGNATURES)
+_TABLES = (SIGNATURES, ORTHO_SIGNATURES)
+
 # symbol -> (per argument a caller of call() passes: int / float for a scalar slot, None for a pointer slot; whether a trailing
 # stream follows them)
 _PLANS = {name: (tuple(float if t in (C.c_float, C.c_double) else None if issubclass(t, (C.c_void_p, C._Pointer)) else int
-                       for t in args if t is not c_stream), c_stream in args) for name, (_, args) in SIGNATURES.items()}
-assert all(c_stream not in args[:-1] for _, args in SIGNATURES.values())
+                       for t in args if t is not c_stream), c_stream in args)
+          for table in _TABLES for name, (_, args) in table.items()}
+assert all(c_stream not in args[:-1] for table in _TABLES for _, args in table.values())
 
 _lib = None
 
@@ -244,11 +268,14 @@ def lib():
     # owns torch's device context and streams (loading ours first brings up a second runtime that then
     # reports "no ROCm-capable device").
     L = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in SIGNATURES.items():
-        fn = getattr(L, name)
-        fn.restype, fn.argtypes = restype, list(argtypes)
+    for table in _TABLES:
+        for name, (restype, argtypes) in table.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, list(argtypes)
     if L.snerf_version() != ABI_VERSION:
         raise RuntimeError(f"libsnerf_hip.so ABI version {L.snerf_version()} != {ABI_VERSION}")
+    if L.snerf_ortho_version() != ORTHO_VERSION:
+        raise RuntimeError(f"libsnerf_hip.so ortho version {L.snerf_ortho_version()} != {ORTHO_VERSION}")
     _lib = L
     return L
 

@@ -1,0 +1,74 @@
+"""Write the geo-referenced ortho products of a trained model (eval/utils/ortho.py ortho_products): the fused map of a split's
+images as PNGs for the eye and GeoTIFFs for a GIS.  The reference has no counterpart.
+
+Files under `output_dp`/ortho/{split}/:
+    rgb.png, rgb.tif                     the true ortho-image: the colour of the highest point of every cell (empty cells black);
+                                         uint8 by torchvision's save_image rule x * 255 + 0.5 (framework/visualize.py)
+    label_top.png/.tif, label_vote.png/.tif   the class of the highest point / of the most votes (a semantic model only): the
+                                         .tif holds the class ids (255 = no data), the .png the palette's colours, 255 as black
+    top_alt.png/.tif, dsm.png/.tif       the top-surface altitude and the mean DSM: float32 in the .tif (NaN = no data), JET
+                                         between the plane's own bounds in the .png (NaN as the colormap treats it: as 0)
+    vote_share.png/.tif                  the winning class's share of a cell's votes: float32, BONE in the .png
+GeoTIFFs carry ModelPixelScale, ModelTiepoint and, with the scene's zone, a GeoKeyDirectory (img_utils.save_geotiff)."""
+import os
+
+import numpy as np
+import torch
+from PIL import Image
+
+from ..framework.util import colormaps, img_utils
+from ..framework.visualize import to_uint8_image
+from ..parallel import world
+from .utils import vismaps
+from .utils.ortho import NO_LABEL, ortho_products
+
+
+def _png(fp, chw_u8):
+    Image.fromarray(chw_u8.permute(1, 2, 0).contiguous().cpu().numpy()).save(fp)
+
+
+def label_colors(label, palette):
+    """(H, W) uint8 labels -> (3, H, W) uint8 through `palette` ((K, 3) uint8); 255 and any label beyond the palette are black"""
+    pal = torch.as_tensor(np.asarray(palette, np.uint8))
+    lut = torch.zeros((256, 3), dtype=torch.uint8)
+    lut[:min(len(pal), NO_LABEL)] = pal[:NO_LABEL]
+    return lut.to(label.device)[label.long()].permute(2, 0, 1).contiguous()
+
+
+@torch.no_grad()
+def export_ortho(cfgs, renderer, models, images, output_dp, split="test", palette=None, zone_string=None, **kwargs):
+    """ortho_products(cfgs, renderer, models, images, **kwargs) of the split's images, written to `output_dp`/ortho/{split}/.
+    On the test split item 0 is skipped, as the evaluators do (it is also a training view).  `palette`: (K, 3) uint8, default
+    colormaps.DEFAULT_PALETTE.  `zone_string`: the GeoTIFFs' UTM zone, default the zone of the GeoFrame in use.  Every rank
+    computes the products (with sharded=True each renders its share of a frame); only rank 0 writes.  Returns the products
+    plus "files": {name: path}."""
+    todo = list(images)[1 if split == "test" else 0:]
+    if not todo:
+        raise ValueError(f"no {split} image to export")
+    prod = ortho_products(cfgs, renderer, models, todo, **kwargs)
+    if zone_string is None:
+        g = kwargs.get("geo") or (todo[0].get("dsm") or {}).get("geo")
+        zone_string = getattr(g, "zone_string", None)
+    grid = prod["grid"]
+    out_dp = os.path.join(output_dp, "ortho", split)
+    files = {}
+    if world()[0] == 0:
+        os.makedirs(out_dp, exist_ok=True)
+        fp = lambda name: files.setdefault(name, os.path.join(out_dp, name))      # noqa: E731
+        rgb8 = to_uint8_image(torch.nan_to_num(prod["rgb"], nan=0.0))
+        _png(fp("rgb.png"), rgb8)
+        img_utils.save_geotiff(fp("rgb.tif"), rgb8.permute(1, 2, 0).contiguous(), grid, zone_string)
+        pal = colormaps.DEFAULT_PALETTE if palette is None else palette
+        for key in ("label_top", "label_vote"):
+            if key in prod:
+                _png(fp(key + ".png"), label_colors(prod[key], pal))
+                img_utils.save_geotiff(fp(key + ".tif"), prod[key], grid, zone_string)
+        planes = [("top_alt", colormaps.COLORMAP_JET), ("dsm", colormaps.COLORMAP_JET)]
+        if "vote_share" in prod:
+            planes.append(("vote_share", colormaps.COLORMAP_BONE))
+        for key, cmap in planes:
+            plane = prod[key]
+            stats = vismaps.plane_minmax(plane, vismaps.new_stats(plane.device), "user")
+            _png(fp(key + ".png"), vismaps.colormap(plane, colormaps.table(cmap, plane.device), stats, "user"))
+            img_utils.save_geotiff(fp(key + ".tif"), plane, grid, zone_string)
+    return dict(prod, files=files)

@@ -46,7 +46,8 @@ series is the `utm` package's, restated; parity with the package is UNPINNED (DE
 uses the scene's zone (root.json), the reference the zone of the cloud's first point.  Without `geo` the cloud comes in a metric
 east/north/up frame as before, optionally through a caller's `to_world(xyz_n) -> (E, N, alt)`.
 
-Out of scope: writing DSM or error GeoTIFFs (arrays out; the ground truth is READ by framework/util/img_utils.py); training in
+Out of scope: writing error GeoTIFFs (arrays out; eval/ortho.py writes the DSM of a fused map as a GeoTIFF, the ground truth is
+READ by framework/util/img_utils.py); training in
 the UTM coordinate system; resampling an off-lattice ground truth or ROI (ValueError); the Norway / Svalbard UTM zone
 exceptions.  SSIM is eval/utils/metrics.py; eval/eval_nerf.py reports PSNR, SSIM and this MAE per image."""
 import math

@@ -1,0 +1,235 @@
+"""Geo-referenced ortho products: the colour, the class and the votes of a semantic satellite NeRF ON THE MAP -- a true
+ortho-image, a land-cover map and the fusion of a scene's views into one raster, on the lattice of the DSM rasteriser
+(eval/utils/dsm.py).  The reference has no counterpart; the spec is include/snerf_ortho.h, the stages
+are the kernels of csrc/ortho.hip, torch is plumbing.  All functions take and return device tensors.
+
+Top surface -- every point of a UTM (east, north, alt) cloud offers a 64-bit key to the cells of its (2 radius + 1)^2 window:
+(round((z - Z0)/Q) + 2^31) << 32 | (2^32 - 1 - global point index), folded with an integer atomic max.  The highest quantised
+altitude wins a cell, the lowest index on a tie; 0 means no point.  Keys commute, so a map does not depend on launch order, on
+how a cloud is cut into calls, on the order of the images, or on ranks (a MAX all-reduce of `top` would combine them).  Z0 and Q
+are constants (all ranks agree): Q = 2^-16 m keeps 2^32 steps over +-32,768 m, and 15 um is below the fp32 spacing of any
+altitude above 128 m -- the key holds the altitude in 32 bits where the DSM's int64 sums afford 2^-24.
+
+Gather -- per cell the winner's altitude and global index; colour, label or any per-point scalar are copied only where the
+winner belongs to the image of the call ([index0, index0 + n)), so a fused map gathers once per image into shared buffers.
+
+Votes -- every point adds 1 to votes[label][cell] over the same window (integer atomic add); finish_votes gives the argmax
+(the lowest class on a tie, 255 for a cell without a vote) and the winner's share of the cell's votes.
+
+ortho_products walks a set of images and returns the fused map; eval/ortho.py writes it (PNG and GeoTIFF).
+
+Out of scope: map-space accuracy against a ground-truth class raster (the US3D classes of dsm_cls_fp are not the scene's
+label set), finite-sigma splats, occlusion reasoning beyond the highest point, RPC tags."""
+import torch
+
+from ... import _lib
+from . import dsm as D
+
+Z0 = 0.0             # quantisation origin of the key's altitude (metres)
+Q = 2.0 ** -16       # quantisation step (metres): 2^32 steps span +-32,768 m
+NO_LABEL = _lib.ORTHO_NO_LABEL
+MAX_INDEX = 2 ** 32 - 1
+
+
+def grid_struct(grid):
+    """a DsmGrid (the window is the whole extent) or a ready _lib.SnerfDsmGrid (a window of a lattice) -> _lib.SnerfDsmGrid"""
+    if isinstance(grid, _lib.SnerfDsmGrid):
+        return grid
+    return _lib.SnerfDsmGrid(float(grid.xoff), float(grid.yoff), float(grid.resolution), int(grid.xsize), int(grid.ysize), 0, 0,
+                             int(grid.xsize), int(grid.ysize))
+
+
+def _cloud(cloud):
+    if not (torch.is_tensor(cloud) and cloud.is_cuda):
+        raise ValueError("ortho: the cloud must be a GPU tensor (the HIP path has no CPU fallback)")
+    if cloud.dim() != 2 or cloud.shape[1] != 3:
+        raise ValueError("the cloud must be (N, 3)")
+    return cloud.to(torch.float64).contiguous()
+
+
+def _cells(g):
+    cells = g.out_h * g.out_w
+    if cells > 2 ** 31 - 1:
+        raise ValueError(f"a map of {g.out_h} x {g.out_w} cells is too large")
+    return cells
+
+
+def new_stats(device):
+    """a zeroed stats block (4 u64 words, held as int64)"""
+    return torch.zeros(4, dtype=torch.int64, device=device)
+
+
+def top_surface(cloud, grid, radius=0, index0=0, top=None, stats=None):
+    """fold `cloud` (N, 3) (east, north, alt) into the top-surface keys of `grid` -> (top (out_h, out_w) int64 holding the
+    u64 words, stats).  `index0`: the global index of the cloud's first point (the running ray offset of a fused map);
+    `top` / `stats`: accumulators of earlier calls (zeroed ones are made otherwise)."""
+    g = grid_struct(grid)
+    xyz = _cloud(cloud)
+    if top is None:
+        top = torch.zeros((g.out_h, g.out_w), dtype=torch.int64, device=xyz.device)
+    if top.dtype != torch.int64 or top.numel() != _cells(g):
+        raise ValueError(f"top must hold {g.out_h} x {g.out_w} int64 words")
+    stats = new_stats(xyz.device) if stats is None else stats
+    _lib.call("snerf_ortho_top", xyz, xyz.shape[0], index0, g, radius, Z0, Q, top, stats, exc=ValueError)
+    return top, stats
+
+
+def gather(top, index0, n, rgb=None, labels=None, scalar=None, out=None):
+    """the winners of `top`: {"alt" f32 (NaN where empty), "index" int64 (-1 where empty)[, "rgb" (3, ...) f32, "label" u8,
+    "scalar" f32]}, shaped like `top`.  Payload rows are those of the points [index0, index0 + n): rgb (n, 3) fp32, labels (n)
+    int64 (a label outside [0, 254] is written as 255), scalar (n) fp32; their outputs are written only in the cells those
+    points won.  `out`: buffers of an earlier call to go on writing into (a fused map); fresh payload buffers are pre-filled
+    with NaN / 255."""
+    shape, dev = tuple(top.shape), top.device
+    cells = top.numel()
+    out = dict(out) if out else {}
+    fills = {"alt": (torch.float32, shape, float("nan")), "index": (torch.int64, shape, -1),
+             "rgb": (torch.float32, (3,) + shape, float("nan")), "label": (torch.uint8, shape, NO_LABEL),
+             "scalar": (torch.float32, shape, float("nan"))}
+    given = {"rgb": rgb, "label": labels, "scalar": scalar}
+    for k, (dt, shp, fill) in fills.items():
+        if k in ("alt", "index") or given[k] is not None:
+            if k not in out:
+                out[k] = torch.full(shp, fill, dtype=dt, device=dev)
+            elif out[k].dtype != dt or tuple(out[k].shape) != shp or not out[k].is_contiguous():
+                raise ValueError(f"gather: out['{k}'] must be a contiguous {dt} tensor of shape {shp}")
+    want = {"rgb": (torch.float32, 3 * n), "label": (torch.int64, n), "scalar": (torch.float32, n)}
+    args = []
+    for k in ("rgb", "label", "scalar"):
+        t = given[k]
+        if t is not None:
+            if t.dtype != want[k][0] or t.numel() != want[k][1]:
+                raise ValueError(f"gather: '{k}' must hold {want[k][1]} values of {want[k][0]}, not {t.numel()} of {t.dtype}")
+            t = t.contiguous()
+        args.append(t)
+    _lib.call("snerf_ortho_gather", top.contiguous(), cells, index0, n, Z0, Q, *args, out["alt"], out["index"],
+              *(out[k] if given[k] is not None else None for k in ("rgb", "label", "scalar")), exc=ValueError)
+    return out
+
+
+def label_votes(cloud, labels, grid, n_classes, radius=0, votes=None, stats=None):
+    """add the cloud's label votes: -> (votes (n_classes, out_h, out_w) int32 holding the u32 counts, stats); labels (N) int64"""
+    g = grid_struct(grid)
+    xyz = _cloud(cloud)
+    labels = labels.reshape(-1)
+    if labels.dtype != torch.int64 or labels.shape[0] != xyz.shape[0]:
+        raise ValueError(f"label_votes: {xyz.shape[0]} int64 labels expected, got {labels.shape[0]} of {labels.dtype}")
+    cells = _cells(g)
+    if votes is None:
+        if not 1 <= n_classes <= _lib.ORTHO_MAX_CLASSES:
+            raise ValueError(f"n_classes must lie in [1, {_lib.ORTHO_MAX_CLASSES}]")
+        votes = torch.zeros((n_classes, g.out_h, g.out_w), dtype=torch.int32, device=xyz.device)
+    if votes.dtype != torch.int32 or votes.numel() != n_classes * cells:
+        raise ValueError(f"votes must hold {n_classes} x {g.out_h} x {g.out_w} int32 words")
+    stats = new_stats(xyz.device) if stats is None else stats
+    _lib.call("snerf_ortho_votes", xyz, labels.contiguous(), xyz.shape[0], g, radius, n_classes, votes, stats, exc=ValueError)
+    return votes, stats
+
+
+def finish_votes(votes, h, w, stats=None):
+    """(label (h, w) u8: the class with the most votes, the lowest on a tie, 255 without a vote; share (h, w) f32: the
+    winner's share of the cell's votes, NaN without one; stats, whose word 1 holds the largest total of a cell)"""
+    if votes.dtype != torch.int32 or votes.numel() % (h * w) or not votes.numel():
+        raise ValueError(f"votes must hold n_classes x {h} x {w} int32 words")
+    n_classes = votes.numel() // (h * w)
+    label = torch.empty((h, w), dtype=torch.uint8, device=votes.device)
+    share = torch.empty((h, w), dtype=torch.float32, device=votes.device)
+    stats = new_stats(votes.device) if stats is None else stats
+    _lib.call("snerf_ortho_votes_finish", votes.contiguous(), n_classes, h * w, label, share, stats, exc=ValueError)
+    return label, share, stats
+
+
+def _flat(img, key):
+    t = img.get(key)
+    return t.reshape(-1, t.shape[-1]) if t is not None else None
+
+
+@torch.no_grad()
+def ortho_products(cfgs, renderer, models, images, geo=None, roi=None, resolution=D.RESOLUTION, radius=0, dsm_radius=1,
+                   sharded=False, grid=None, render_options={}):
+    """The fused map of `images` (dicts with the evaluators' keys: "rays", "extras"[, "dsm": {"geo": GeoFrame}]).
+
+    Per image, in the order given: lean_inference (sharded_lean_inference with `sharded`: every rank then holds the whole
+    frame, and nothing is all-reduced here) for rgb, depth and, when the model has classes, the label; geo.cloud(rays, depth)
+    (`geo` defaults to the image's "dsm"["geo"]); the cloud folded into the shared accumulators -- the top-surface keys with
+    index0 = the running ray offset, the label votes, and the DSM's count / sum (snerf_dsm_accumulate, radius `dsm_radius`).
+    The grid: `grid` (a DsmGrid), else the ROI grid of `roi` (a DsmGrid or the roi_txt meta) used as the lattice, else the
+    bounds grid of the union of the clouds' exact bounds -- known only after every image has been rendered, so the frames'
+    rgb, depth and labels are kept and the clouds are made again (one launch each) for the fold; nothing is rendered twice.
+    Then one gather per image and the finishes.  `render_options` go to the renderer: as everywhere in evaluation it jitters the
+    sample depths from torch's generator unless {"perturb": 0} (or a pinned "perturb_rand") says otherwise, so two walks give the
+    same map only from the same generator state.
+
+    Returns {"grid": DsmGrid, "dsm": (H, W) f32 -- the mean DSM, the bits of dsm.rasterize on the concatenated cloud --,
+    "top_alt": (H, W) f32, "top_index": (H, W) int64 (index into the concatenated rays, -1 where empty), "rgb": (3, H, W) f32
+    (NaN where empty)[, "label_top": (H, W) u8, "label_vote": (H, W) u8, "vote_share": (H, W) f32], "n_points", "bad_points"
+    (altitudes that are not finite or beyond +-32,768 m: left out of the top surface), "bad_labels" (labels outside the
+    model's classes: no vote), "max_votes"}."""
+    from .util import lean_inference, sharded_lean_inference
+    images = list(images)
+    if not images:
+        raise ValueError("ortho_products: no image")
+    model = models["coarse"]
+    n_classes = model.spec.n_classes
+    if n_classes > _lib.ORTHO_MAX_CLASSES:
+        raise ValueError(f"ortho_products: {n_classes} classes, at most {_lib.ORTHO_MAX_CLASSES} fit a uint8 label map")
+    infer = sharded_lean_inference if sharded else lean_inference
+    keys = ("rgb_coarse", "depth_coarse") + (("semantic_label_coarse",) if n_classes else ())
+    if grid is None and roi is not None:
+        grid = roi if isinstance(roi, D.DsmGrid) else D.roi_grid(roi)
+
+    acc = {}
+
+    def fold(cloud, labels, index0):
+        if not acc:
+            g = grid_struct(grid)
+            dev = cloud.device
+            acc.update(g=g, top=None, tstats=new_stats(dev), votes=None, vstats=new_stats(dev),
+                       count=torch.zeros(_cells(g), dtype=torch.int32, device=dev),
+                       total=torch.zeros(_cells(g), dtype=torch.int64, device=dev), dstats=new_stats(dev))
+        acc["top"], _ = top_surface(cloud, acc["g"], radius, index0, acc["top"], acc["tstats"])
+        if n_classes:
+            acc["votes"], _ = label_votes(cloud, labels, acc["g"], n_classes, radius, acc["votes"], acc["vstats"])
+        _lib.call("snerf_dsm_accumulate", cloud, cloud.shape[0], acc["g"], dsm_radius, D.Z0, D.Q, acc["count"], acc["total"],
+                  acc["dstats"])
+
+    frames, index0 = [], 0
+    ext = [float("inf"), float("-inf"), float("inf"), float("-inf")]
+    for img in images:
+        rays, extras = _flat(img, "rays"), _flat(img, "extras")
+        g_img = geo if geo is not None else (img.get("dsm") or {}).get("geo")
+        if g_img is None:
+            raise ValueError(f"ortho_products: image {img.get('name')!r} carries no 'dsm'['geo'] and no geo= was given")
+        if index0 + rays.shape[0] > MAX_INDEX:
+            raise ValueError(f"ortho_products: more than {MAX_INDEX} rays do not fit the key's 32-bit index")
+        res = infer(cfgs, renderer, models, rays, extras, keys=keys, render_options=render_options)
+        f = {"rays": rays, "geo": g_img, "index0": index0, "n": rays.shape[0], "rgb": res["rgb_coarse"],
+             "depth": res["depth_coarse"], "labels": res.get("semantic_label_coarse")}
+        cloud, b = g_img.cloud(rays, f["depth"])
+        ext = [min(ext[0], b.xmin), max(ext[1], b.xmax), min(ext[2], b.ymin), max(ext[3], b.ymax)]
+        if grid is not None:
+            fold(cloud, f["labels"], index0)
+        del cloud
+        frames.append(f)
+        index0 += f["n"]
+    if grid is None:
+        grid = D.dsm_grid_from_cloud(None, resolution, bounds=tuple(ext))
+        for f in frames:
+            fold(f["geo"].cloud(f["rays"], f["depth"])[0], f["labels"], f["index0"])
+    h, w = acc["g"].out_h, acc["g"].out_w
+    out = None
+    for f in frames:
+        out = gather(acc["top"], f["index0"], f["n"], rgb=f["rgb"], labels=f["labels"], out=out)
+    res = {"grid": grid if isinstance(grid, D.DsmGrid) else D.DsmGrid(grid.xoff, grid.yoff, grid.res, grid.xsize, grid.ysize),
+           "dsm": D._finish(acc["count"], acc["total"], acc["dstats"], h, w), "top_alt": out["alt"], "top_index": out["index"],
+           "rgb": out["rgb"], "n_points": index0}
+    bad_points = int(acc["tstats"][0])
+    if n_classes:
+        res["label_top"] = out["label"]
+        res["label_vote"], res["vote_share"], vstats = finish_votes(acc["votes"], h, w, acc["vstats"])
+        bad_labels, max_votes = (int(v) for v in vstats[:2].cpu())
+        if max_votes >= 2 ** 32:
+            raise OverflowError(f"ortho_products: a cell received {max_votes} votes, its u32 counts could have wrapped")
+        res.update(bad_labels=bad_labels, max_votes=max_votes)
+    res["bad_points"] = bad_points
+    return res

@@ -1,4 +1,4 @@
-"""GeoTIFF readers of the scene loaders -- mirror of framework/util/img_utils.py:9-43.  The scenes' RGB and CLS rasters are
+"""GeoTIFF readers of the scene loaders -- mirror of framework/util/img_utils.py:9-43 -- and the writer of the ortho products.  The scenes' RGB and CLS rasters are
 plain 8-bit TIFFs, read with PIL (the reference reads them with rasterio, which this build does not carry).
 
 The DSM ground truth (framework/datasets.py:35-44, eval/utils/dsm.py:180-231): a float32 single-band raster whose georeference
@@ -6,7 +6,12 @@ is read from the GeoTIFF tags ModelPixelScale (33550) and ModelTiepoint (33922) 
 (xoff, yoff, size, resolution) and the water (class 9) or ignore mask.  Cropping to the ROI replaces the reference's
 gdal.Translate(projWin=...): an integer-offset crop when the raster lies on the ROI's lattice; a raster without the tags must
 already have the ROI's shape.  DIVERGENCE: anything else (another resolution, a corner off the lattice by more than 1e-6 cells,
-an ROI reaching beyond the raster) raises ValueError where gdal would resample or pad."""
+an ROI reaching beyond the raster) raises ValueError where gdal would resample or pad.
+
+save_geotiff writes a north-up raster on a DsmGrid with the same two tags and, given the scene's UTM zone, a GeoKeyDirectory
+(34735) naming the projected CRS (EPSG 326zz north / 327zz south).  The reference writes its DSMs with rasterio; neither
+rasterio nor GDAL is part of this build, so what their readers make of these files is UNPINNED (as `utm` and cv2 are, DESIGN.md
+5h / 5i): the tests pin the round trip through PIL and load_dsm_geotiff."""
 import numpy as np
 import torch
 from PIL import Image
@@ -39,6 +44,7 @@ def load_tensor_from_cls_geotiff(img_path):
 
 TAG_MODEL_PIXEL_SCALE = 33550
 TAG_MODEL_TIEPOINT = 33922
+TAG_GEO_KEY_DIRECTORY = 34735
 
 
 def load_dsm_geotiff(fp):
@@ -100,3 +106,44 @@ def load_dsm_ground_truth(dsm_tif_fp, dsm_txt_fp, dsm_cls_fp=None, ignore_mask_f
         m, mtf = load_dsm_geotiff(fp)
         out[key] = torch.from_numpy(np.ascontiguousarray(crop_to_roi(m, mtf, roi, what=key)).astype(np.uint8))
     return out
+
+
+def utm_epsg(zone_string):
+    """EPSG code of WGS 84 / UTM zone zz: 326zz on the northern hemisphere, 327zz on the southern"""
+    from .conversions import split_zone_string, zone_is_south
+    number = split_zone_string(zone_string)[0]
+    if not 1 <= number <= 60:
+        raise ValueError(f"UTM zone number {number} outside [1, 60]")
+    return (32700 if zone_is_south(zone_string) else 32600) + number
+
+
+def save_geotiff(fp, array, grid, zone_string=None):
+    """Write `array` -- (h, w) float32 ("F"), (h, w) uint8 ("L") or (h, w, 3) uint8 ("RGB"); a tensor or an ndarray -- as an
+    uncompressed TIFF on `grid` (a DsmGrid: xoff / yoff = the outer corner of the north-west cell): ModelPixelScale =
+    (res, res, 0), ModelTiepoint = (0, 0, 0, xoff, yoff, 0) and, with `zone_string`, a GeoKeyDirectory (projected model,
+    pixel-is-area, ProjectedCSTypeGeoKey = utm_epsg(zone_string)).  No RPC tags."""
+    from PIL import TiffImagePlugin
+    a = array.detach().cpu().numpy() if torch.is_tensor(array) else np.asarray(array)
+    if a.ndim == 2 and a.dtype == np.float32:
+        mode = "F"
+    elif a.ndim == 2 and a.dtype == np.uint8:
+        mode = "L"
+    elif a.ndim == 3 and a.shape[2] == 3 and a.dtype == np.uint8:
+        mode = "RGB"
+    else:
+        raise ValueError(f"save_geotiff: expected (h, w) float32, (h, w) uint8 or (h, w, 3) uint8, got {a.dtype} {a.shape}")
+    if a.shape[:2] != (int(grid.ysize), int(grid.xsize)):
+        raise ValueError(f"save_geotiff: the raster is {a.shape[0]} x {a.shape[1]}, the grid {grid.ysize} x {grid.xsize}")
+    res = float(grid.resolution)
+    ifd = TiffImagePlugin.ImageFileDirectory_v2()
+    ifd[TAG_MODEL_PIXEL_SCALE] = (res, res, 0.0)
+    ifd.tagtype[TAG_MODEL_PIXEL_SCALE] = 12          # DOUBLE
+    ifd[TAG_MODEL_TIEPOINT] = (0.0, 0.0, 0.0, float(grid.xoff), float(grid.yoff), 0.0)
+    ifd.tagtype[TAG_MODEL_TIEPOINT] = 12
+    if zone_string is not None:
+        # header (version 1, revision 1.0, 3 keys); GTModelTypeGeoKey = 1 (projected); GTRasterTypeGeoKey = 1 (pixel is area);
+        # ProjectedCSTypeGeoKey = the EPSG code
+        ifd[TAG_GEO_KEY_DIRECTORY] = (1, 1, 0, 3, 1024, 0, 1, 1, 1025, 0, 1, 1, 3072, 0, 1, utm_epsg(zone_string))
+        ifd.tagtype[TAG_GEO_KEY_DIRECTORY] = 3       # SHORT
+    Image.fromarray(np.ascontiguousarray(a), mode=mode).save(fp, format="TIFF", tiffinfo=ifd)
+    return fp
