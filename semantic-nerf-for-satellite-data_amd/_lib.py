@@ -1,4 +1,4 @@
-"""ctypes binding of libsnerf_hip.so -- mirrors include/snerf_hip.h (and include/snerf_ortho.h) field for field."""
+"""ctypes binding of libsnerf_hip.so -- mirrors include/snerf_hip.h field for field."""
 import ctypes as C
 import os
 
@@ -8,7 +8,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # SNERF_LIB_PATH: an alternative build of the library (ablation harness of tools/ablate; diagnostics only)
 LIB_PATH = os.environ.get("SNERF_LIB_PATH") or os.path.join(_HERE, "libsnerf_hip.so")
 MAX_LAYERS = 16
-ABI_VERSION = 5   # include/snerf_hip.h SNERF_ABI_VERSION
+ABI_VERSION = 6   # include/snerf_hip.h SNERF_ABI_VERSION
 
 FLAG_TRAIN = 1
 FLAG_SC_PASS = 2
@@ -163,7 +163,7 @@ class c_stream(C.c_void_p):
 
 def _signatures():
     i, ll, ull, sz, f, d, p, st, P = C.c_int, C.c_longlong, C.c_ulonglong, C.c_size_t, C.c_float, C.c_double, C.c_void_p, c_stream, C.POINTER
-    desc = P(SnerfDesc)
+    desc, grid = P(SnerfDesc), P(SnerfDsmGrid)
     return {
         "snerf_version": (i, ()),
         "snerf_last_error": (C.c_char_p, ()),
@@ -181,12 +181,16 @@ def _signatures():
         "snerf_loss_partial": (i, (P(SnerfLossCfg), P(SnerfLossIn), p, p, sz, st)),
         "snerf_loss_finish": (i, (P(SnerfLossCfg), P(SnerfLossIn), p, f, f, p, P(SnerfLossGrads), st)),
         "snerf_adam_step": (i, (p, p, p, p, ull, f, f, f, f, i, f, st)),
-        "snerf_dsm_accumulate": (i, (p, i, P(SnerfDsmGrid), i, d, d, p, p, p, st)),
+        "snerf_dsm_accumulate": (i, (p, i, grid, i, d, d, p, p, p, st)),
         "snerf_dsm_finish": (i, (p, p, ll, d, d, p, p, st)),
         "snerf_dsm_downsample2x": (i, (p, i, i, i, p, st)),
         "snerf_dsm_workspace_bytes": (sz, (i, i, i)),
         "snerf_dsm_ncc_search": (i, (p, p, i, i, i, i, i, i, p, p, sz, st)),
         "snerf_dsm_shift_diff": (i, (p, p, i, i, i, i, d, p, p, p, p, sz, st)),
+        "snerf_ortho_top": (i, (p, ll, ll, grid, i, d, d, p, p, st)),
+        "snerf_ortho_gather": (i, (p, ll, ll, ll, d, d) + (p,) * 8 + (st,)),
+        "snerf_ortho_votes": (i, (p, p, ll, grid, i, i, p, p, st)),
+        "snerf_ortho_votes_finish": (i, (p, i, ll, p, p, p, st)),
         "snerf_ssim_workspace_bytes": (sz, (i,) * 5),
         "snerf_ssim": (i, (p, p) + (i,) * 6 + (p, d, d, d, p, p, p, sz, st)),
         "snerf_semeval_workspace_bytes": (sz, (i, i)),
@@ -221,35 +225,15 @@ def _signatures():
 SIGNATURES = _signatures()
 EXPORTED_SYMBOLS = tuple(SIGNATURES)
 
-ORTHO_VERSION = 1          # include/snerf_ortho.h SNERF_ORTHO_VERSION
-ORTHO_MAX_RADIUS = 7       # include/snerf_ortho.h SNERF_ORTHO_MAX_RADIUS
-ORTHO_MAX_CLASSES = 255    # include/snerf_ortho.h SNERF_ORTHO_MAX_CLASSES
-ORTHO_NO_LABEL = 255       # include/snerf_ortho.h SNERF_ORTHO_NO_LABEL
-
-
-def _ortho_signatures():
-    i, ll, d, p, st, grid = C.c_int, C.c_longlong, C.c_double, C.c_void_p, c_stream, C.POINTER(SnerfDsmGrid)
-    return {
-        "snerf_ortho_version": (i, ()),
-        "snerf_ortho_top": (i, (p, ll, ll, grid, i, d, d, p, p, st)),
-        "snerf_ortho_gather": (i, (p, ll, ll, ll, d, d) + (p,) * 8 + (st,)),
-        "snerf_ortho_votes": (i, (p, p, ll, grid, i, i, p, p, st)),
-        "snerf_ortho_votes_finish": (i, (p, i, ll, p, p, p, st)),
-    }
-
-
-# The second table: one row per prototype of include/snerf_ortho.h, in the header's order (tests/test_ortho_cpu.py compares the
-# two).  Same library, same call path; kept apart from SIGNATURES / EXPORTED_SYMBOLS, which mirror include/snerf_hip.h alone.
-ORTHO_SIGNATURES = _ortho_signatures()
-assert not set(ORTHO_SIGNATURES) & set(SIGNATURES)
-_TABLES = (SIGNATURES, ORTHO_SIGNATURES)
+ORTHO_MAX_RADIUS = 7       # include/snerf_hip.h SNERF_ORTHO_MAX_RADIUS
+ORTHO_MAX_CLASSES = 255    # include/snerf_hip.h SNERF_ORTHO_MAX_CLASSES
+ORTHO_NO_LABEL = 255       # include/snerf_hip.h SNERF_ORTHO_NO_LABEL
 
 # symbol -> (per argument a caller of call() passes: int / float for a scalar slot, None for a pointer slot; whether a trailing
 # stream follows them)
 _PLANS = {name: (tuple(float if t in (C.c_float, C.c_double) else None if issubclass(t, (C.c_void_p, C._Pointer)) else int
-                       for t in args if t is not c_stream), c_stream in args)
-          for table in _TABLES for name, (_, args) in table.items()}
-assert all(c_stream not in args[:-1] for table in _TABLES for _, args in table.values())
+                       for t in args if t is not c_stream), c_stream in args) for name, (_, args) in SIGNATURES.items()}
+assert all(c_stream not in args[:-1] for _, args in SIGNATURES.values())
 
 _lib = None
 
@@ -268,14 +252,11 @@ def lib():
     # owns torch's device context and streams (loading ours first brings up a second runtime that then
     # reports "no ROCm-capable device").
     L = C.CDLL(LIB_PATH)
-    for table in _TABLES:
-        for name, (restype, argtypes) in table.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = restype, list(argtypes)
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, list(argtypes)
     if L.snerf_version() != ABI_VERSION:
         raise RuntimeError(f"libsnerf_hip.so ABI version {L.snerf_version()} != {ABI_VERSION}")
-    if L.snerf_ortho_version() != ORTHO_VERSION:
-        raise RuntimeError(f"libsnerf_hip.so ortho version {L.snerf_ortho_version()} != {ORTHO_VERSION}")
     _lib = L
     return L
 

@@ -3,27 +3,16 @@
 // (eval/utils/dsmr.py:17-144), and the shifted difference against the ground truth (dsm.py:235-266).  The spec and the
 // numerics are stated in include/snerf_hip.h and in snerf_amd/eval/utils/dsm.py; every reduction here is in a fixed order,
 // so every result is bit-reproducible run to run.
-#include "common.h"
-#include "../../include/snerf_hip.h"
-
-#include <math.h>
+#include "lattice.h"
 
 namespace snerf {
 
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long w = __shfl_xor(v, o, 64);
-    v = w > v ? w : v;
-  }
-  return v;
-}
-
 // ---- rasterisation ---------------------------------------------------------------------------------------------------
-// One pass over the points; a point adds round((z - z0)/q) to the int64 sum and 1 to the u32 count of every lattice cell of
-// its (2r+1)^2 window that lies inside the lattice extent AND the output window.  Integer atomics commute, so the result
-// does not depend on the order in which points arrive.  stats[0] = max |round((z - z0)/q)| (the host bounds the sums with
-// it), stats[1] = number of points whose quantised altitude is not finite or not below 2^62 (they add nothing).
+// One pass over the points; a point adds round((z - z0)/q) to the int64 sum and 1 to the u32 count of every cell of its
+// cell_window() (lattice.h): its (2r+1)^2 window inside the lattice extent AND the output window.  Integer atomics commute, so
+// the result does not depend on the order in which points arrive.  stats[0] = max |round((z - z0)/q)| of the points that
+// reached a cell (the host bounds the sums with it), stats[1] = number of points whose quantised altitude is not finite or not
+// below 2^62 (they add nothing).
 __global__ __launch_bounds__(256) void dsm_accumulate_kernel(const double* __restrict__ xyz, int n, SnerfDsmGrid g, int r,
                                                              double z0, double inv_q, unsigned* __restrict__ count,
                                                              unsigned long long* __restrict__ sum,
@@ -34,29 +23,20 @@ __global__ __launch_bounds__(256) void dsm_accumulate_kernel(const double* __res
     const double x = xyz[3 * p], y = xyz[3 * p + 1], z = xyz[3 * p + 2];
     const double kq = rint((z - z0) * inv_q);
     if (!(fabs(kq) < lim)) { bad++; continue; }
-    const double fi = floor((x - g.xoff) / g.res), fj = floor((g.yoff - y) / g.res);
-    // lattice cells the window can reach, clipped to both windows before any conversion to int (NaN coordinates fail here)
-    const double lo_i = fmax((double)g.ioff, 0.0), hi_i = fmin((double)g.ioff + g.out_w, (double)g.xsize);
-    const double lo_j = fmax((double)g.joff, 0.0), hi_j = fmin((double)g.joff + g.out_h, (double)g.ysize);
-    if (!(fi + r >= lo_i && fi - r < hi_i && fj + r >= lo_j && fj - r < hi_j)) continue;
+    const CellWindow w = cell_window(x, y, g, r);
+    if (w.i0 >= w.i1 || w.j0 >= w.j1) continue;
     const long long k = (long long)kq;
     const unsigned long long ak = (unsigned long long)(k < 0 ? -k : k);
     kmax = ak > kmax ? ak : kmax;
-    const int ci = (int)fi, cj = (int)fj;
-    for (int dy = -r; dy <= r; ++dy) {
-      const int lj = cj + dy;
-      if (lj < lo_j || lj >= hi_j) continue;
-      for (int dx = -r; dx <= r; ++dx) {
-        const int li = ci + dx;
-        if (li < lo_i || li >= hi_i) continue;
-        const long long cell = (long long)(lj - g.joff) * g.out_w + (li - g.ioff);
+    for (long long lj = w.j0; lj < w.j1; ++lj)
+      for (long long li = w.i0; li < w.i1; ++li) {
+        const long long cell = (lj - g.joff) * g.out_w + (li - g.ioff);
         atomicAdd(&count[cell], 1u);
         atomicAdd(&sum[cell], (unsigned long long)k);   // two's complement: a signed sum
       }
-    }
   }
   kmax = wave_max_u64(kmax);
-  bad = wave_max_u64(bad);
+  bad = wave_sum_u64(bad);
   if ((threadIdx.x & 63) == 0) {
     if (kmax) atomicMax(&stats[0], kmax);
     if (bad) atomicAdd(&stats[1], bad);
@@ -186,11 +166,6 @@ __global__ __launch_bounds__(256) void ncc_reduce_kernel(const double* __restric
 constexpr int DIFF_THREADS = 256;
 constexpr int DIFF_MAX_BLOCKS = 1024;
 
-__host__ __device__ inline int diff_blocks(long long cells) {
-  const long long want = (cells + DIFF_THREADS - 1) / DIFF_THREADS;
-  return (int)(want < DIFF_MAX_BLOCKS ? (want > 0 ? want : 1) : DIFF_MAX_BLOCKS);
-}
-
 __global__ __launch_bounds__(DIFF_THREADS) void shift_diff_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
                                                                   int h, int w, int dx, int dy, double b,
                                                                   float* __restrict__ rdsm, float* __restrict__ diff,
@@ -229,16 +204,6 @@ __global__ __launch_bounds__(64) void diff_total_kernel(const double* __restrict
   }
 }
 
-static unsigned grid_for(long long n, int threads, unsigned cap) {
-  const long long want = (n + threads - 1) / threads;
-  return (unsigned)(want < 1 ? 1 : (want < (long long)cap ? want : cap));
-}
-
-static bool grid_ok(const SnerfDsmGrid* g) {
-  return g->res > 0.0 && isfinite(g->res) && isfinite(g->xoff) && isfinite(g->yoff) && g->xsize > 0 && g->ysize > 0 &&
-         g->out_w > 0 && g->out_h > 0;
-}
-
 }  // namespace snerf
 
 using namespace snerf;
@@ -247,11 +212,11 @@ extern "C" int snerf_dsm_accumulate(const double* xyz, int n, const SnerfDsmGrid
                                     unsigned* count, long long* sum, unsigned long long* stats, void* stream) {
   if (!grid || !count || !sum || !stats || (n > 0 && !xyz)) { set_error("snerf_dsm_accumulate: null pointer"); return SNERF_ERR_NULL; }
   if (n < 0) { set_error("snerf_dsm_accumulate: n must be >= 0"); return SNERF_ERR_BAD_DESC; }
-  if (!grid_ok(grid)) { set_error("snerf_dsm_accumulate: grid needs res > 0 and positive sizes"); return SNERF_ERR_BAD_DESC; }
+  if (!lattice_grid_ok("snerf_dsm_accumulate", grid)) return SNERF_ERR_BAD_DESC;
   if (radius < 0 || radius > 64) { set_error("snerf_dsm_accumulate: radius must lie in [0, 64]"); return SNERF_ERR_BAD_DESC; }
-  if (!(q > 0.0) || !isfinite(q) || !isfinite(z0)) { set_error("snerf_dsm_accumulate: q > 0 and finite z0 required"); return SNERF_ERR_BAD_DESC; }
+  if (!quant_ok("snerf_dsm_accumulate", z0, q, "q > 0 and finite z0 required")) return SNERF_ERR_BAD_DESC;
   if (n == 0) return SNERF_OK;
-  hipLaunchKernelGGL(dsm_accumulate_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, (hipStream_t)stream, xyz, n, *grid,
+  hipLaunchKernelGGL(dsm_accumulate_kernel, dim3(blocks_for(n, 256, 4096)), dim3(256), 0, (hipStream_t)stream, xyz, n, *grid,
                      radius, z0, 1.0 / q, count, (unsigned long long*)sum, stats);
   SNERF_LAUNCH_CHECK();
   return SNERF_OK;
@@ -261,8 +226,8 @@ extern "C" int snerf_dsm_finish(const unsigned* count, const long long* sum, lon
                                 unsigned long long* stats, void* stream) {
   if (!count || !sum || !dsm || !stats) { set_error("snerf_dsm_finish: null pointer"); return SNERF_ERR_NULL; }
   if (cells <= 0) { set_error("snerf_dsm_finish: cells must be > 0"); return SNERF_ERR_BAD_DESC; }
-  if (!(q > 0.0) || !isfinite(q) || !isfinite(z0)) { set_error("snerf_dsm_finish: q > 0 and finite z0 required"); return SNERF_ERR_BAD_DESC; }
-  hipLaunchKernelGGL(dsm_finish_kernel, dim3(grid_for(cells, 256, 4096)), dim3(256), 0, (hipStream_t)stream, count, sum, cells,
+  if (!quant_ok("snerf_dsm_finish", z0, q, "q > 0 and finite z0 required")) return SNERF_ERR_BAD_DESC;
+  hipLaunchKernelGGL(dsm_finish_kernel, dim3(blocks_for(cells, 256, 4096)), dim3(256), 0, (hipStream_t)stream, count, sum, cells,
                      z0, q, dsm, stats);
   SNERF_LAUNCH_CHECK();
   return SNERF_OK;
@@ -272,7 +237,7 @@ extern "C" int snerf_dsm_downsample2x(const void* u, int u_f64, int h, int w, do
   if (!u || !out) { set_error("snerf_dsm_downsample2x: null pointer"); return SNERF_ERR_NULL; }
   if (h <= 0 || w <= 0) { set_error("snerf_dsm_downsample2x: h, w must be > 0"); return SNERF_ERR_BAD_DESC; }
   const long long total = (long long)((h + 1) / 2) * ((w + 1) / 2);
-  const dim3 grid(grid_for(total, 256, 4096));
+  const dim3 grid(blocks_for(total, 256, 4096));
   if (u_f64) hipLaunchKernelGGL(downsample2x_kernel<double>, grid, dim3(256), 0, (hipStream_t)stream, (const double*)u, h, w, out);
   else hipLaunchKernelGGL(downsample2x_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)u, h, w, out);
   SNERF_LAUNCH_CHECK();
@@ -322,7 +287,7 @@ extern "C" int snerf_dsm_shift_diff(const float* pred, const float* gt, int h, i
   if (dx < -(1 << 20) || dx > (1 << 20) || dy < -(1 << 20) || dy > (1 << 20)) { set_error("snerf_dsm_shift_diff: shift out of range"); return SNERF_ERR_BAD_DESC; }
   if (workspace_bytes < (size_t)(2 * DIFF_MAX_BLOCKS) * sizeof(double)) {
     set_error("snerf_dsm_shift_diff: workspace of %zu bytes is too small", workspace_bytes); return SNERF_ERR_WORKSPACE; }
-  const int nblk = diff_blocks((long long)h * w);
+  const int nblk = (int)blocks_for((long long)h * w, DIFF_THREADS, DIFF_MAX_BLOCKS);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(shift_diff_kernel, dim3(nblk), dim3(DIFF_THREADS), 0, st, pred, gt, h, w, dx, dy, b, rdsm, diff,
                      (double*)workspace);

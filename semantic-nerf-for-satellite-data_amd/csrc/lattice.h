@@ -1,0 +1,79 @@
+// The DSM lattice (SnerfDsmGrid, include/snerf_hip.h) as csrc/dsm.hip and csrc/ortho.hip share it: which cells a point offers
+// itself to, the 64-bit wave reductions of the per-launch statistics, the launch grid of a grid-stride kernel, and the host-side
+// checks of a grid and of a quantisation (z0, q).  Every splat on this lattice goes through cell_window(); nothing here depends
+// on what a kernel does with the cells.
+#pragma once
+#include "common.h"
+#include "../../include/snerf_hip.h"
+
+#include <math.h>
+
+namespace snerf {
+
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long w = __shfl_xor(v, o, 64);
+    v = w > v ? w : v;
+  }
+  return v;
+}
+
+// The cells a point offers itself to: the (2r+1)^2 window round its own cell, clipped to the lattice extent and to the output
+// window BEFORE any conversion to an integer (a NaN or infinite coordinate fails the comparisons and offers nothing).
+struct CellWindow {
+  long long i0, i1, j0, j1;      // lattice cells [i0, i1) x [j0, j1); empty when i0 >= i1 or j0 >= j1
+};
+
+__device__ __forceinline__ CellWindow cell_window(double x, double y, const SnerfDsmGrid& g, int r) {
+  CellWindow w = {0, 0, 0, 0};
+  const double fi = floor((x - g.xoff) / g.res), fj = floor((g.yoff - y) / g.res);
+  const double lo_i = fmax((double)g.ioff, 0.0), hi_i = fmin((double)g.ioff + g.out_w, (double)g.xsize);
+  const double lo_j = fmax((double)g.joff, 0.0), hi_j = fmin((double)g.joff + g.out_h, (double)g.ysize);
+  if (!(fi + r >= lo_i && fi - r < hi_i && fj + r >= lo_j && fj - r < hi_j)) return w;
+  // fi, fj now lie within r of [0, 2^31): exact as 64-bit integers
+  const long long ci = (long long)fi, cj = (long long)fj;
+  const long long li = (long long)lo_i, hi = (long long)hi_i, lj = (long long)lo_j, hj = (long long)hi_j;
+  w.i0 = ci - r > li ? ci - r : li;
+  w.i1 = ci + r + 1 < hi ? ci + r + 1 : hi;
+  w.j0 = cj - r > lj ? cj - r : lj;
+  w.j1 = cj + r + 1 < hj ? cj + r + 1 : hj;
+  return w;
+}
+
+// blocks of a grid-stride launch over n items: ceil(n / threads) in [1, cap]
+static inline unsigned blocks_for(long long n, int threads, unsigned cap) {
+  const long long want = (n + threads - 1) / threads;
+  return (unsigned)(want < 1 ? 1 : (want < (long long)cap ? want : cap));
+}
+
+// the grid of an accumulating entry: res > 0, finite offsets, positive sizes
+static inline bool lattice_grid_ok(const char* who, const SnerfDsmGrid* g) {
+  if (g->res > 0.0 && isfinite(g->res) && isfinite(g->xoff) && isfinite(g->yoff) && g->xsize > 0 && g->ysize > 0 && g->out_w > 0 &&
+      g->out_h > 0)
+    return true;
+  set_error("%s: grid needs res > 0 and positive sizes", who);
+  return false;
+}
+
+// a window whose cells are int32 indices (the ortho entries refuse any other; snerf_dsm_accumulate does not)
+static inline bool lattice_window_fits_int32(const char* who, const SnerfDsmGrid* g) {
+  if ((long long)g->ioff + g->out_w <= 2147483647LL && (long long)g->joff + g->out_h <= 2147483647LL) return true;
+  set_error("%s: the output window reaches beyond int32 cell indices", who);
+  return false;
+}
+
+// q > 0 and finite, z0 finite; `what` is the entry's own wording of the rule
+static inline bool quant_ok(const char* who, double z0, double q, const char* what = "q > 0 and finite, z0 finite required") {
+  if (q > 0.0 && isfinite(q) && isfinite(z0)) return true;
+  set_error("%s: %s", who, what);
+  return false;
+}
+
+}  // namespace snerf

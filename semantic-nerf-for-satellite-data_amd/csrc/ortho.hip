@@ -1,12 +1,9 @@
 // Geo-referenced ortho products on the DSM lattice: the top-surface z-buffer of an (E, N, alt) cloud (one 64-bit key per cell,
 // integer atomic max), the gather of the winners' colour / label / scalar, and per-cell label votes (integer atomic add) with
-// their argmax.  The spec is include/snerf_ortho.h and DESIGN.md section 5j; the cell arithmetic is dsm_accumulate_kernel's
-// (csrc/dsm.hip), restated here so that the DSM's code stays as it is.  Integer atomics only: every result is independent of
-// the order in which points arrive.
-#include "common.h"
-#include "../../include/snerf_ortho.h"
-
-#include <math.h>
+// their argmax.  The spec is the ortho section of include/snerf_hip.h and DESIGN.md section 5j; the cell arithmetic is
+// cell_window() of csrc/lattice.h, which dsm_accumulate_kernel (csrc/dsm.hip) shares.  Integer atomics only: every result is
+// independent of the order in which points arrive.
+#include "lattice.h"
 
 #pragma clang fp contract(off)
 
@@ -15,43 +12,7 @@ namespace snerf {
 constexpr long long ORTHO_MAX_N = 2147483648LL;          // 2^31
 constexpr long long ORTHO_MAX_INDEX = 4294967295LL;      // 2^32 - 1: index0 + n may not exceed it
 constexpr int ORTHO_THREADS = 256;
-
-__device__ __forceinline__ unsigned long long ortho_wave_sum(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ unsigned long long ortho_wave_max(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long w = __shfl_xor(v, o, 64);
-    v = w > v ? w : v;
-  }
-  return v;
-}
-
-// The cells a point offers itself to: the (2r+1)^2 window round its own cell, clipped to the lattice extent and to the output
-// window BEFORE any conversion to an integer (a NaN or infinite coordinate fails the comparisons and offers nothing).
-struct CellWindow {
-  long long i0, i1, j0, j1;      // lattice cells [i0, i1) x [j0, j1); empty when i0 >= i1 or j0 >= j1
-};
-
-__device__ __forceinline__ CellWindow cell_window(double x, double y, const SnerfDsmGrid& g, int r) {
-  CellWindow w = {0, 0, 0, 0};
-  const double fi = floor((x - g.xoff) / g.res), fj = floor((g.yoff - y) / g.res);
-  const double lo_i = fmax((double)g.ioff, 0.0), hi_i = fmin((double)g.ioff + g.out_w, (double)g.xsize);
-  const double lo_j = fmax((double)g.joff, 0.0), hi_j = fmin((double)g.joff + g.out_h, (double)g.ysize);
-  if (!(fi + r >= lo_i && fi - r < hi_i && fj + r >= lo_j && fj - r < hi_j)) return w;
-  // fi, fj now lie within r of [0, 2^31): exact as 64-bit integers
-  const long long ci = (long long)fi, cj = (long long)fj;
-  const long long li = (long long)lo_i, hi = (long long)hi_i, lj = (long long)lo_j, hj = (long long)hi_j;
-  w.i0 = ci - r > li ? ci - r : li;
-  w.i1 = ci + r + 1 < hi ? ci + r + 1 : hi;
-  w.j0 = cj - r > lj ? cj - r : lj;
-  w.j1 = cj + r + 1 < hj ? cj + r + 1 : hj;
-  return w;
-}
+constexpr unsigned ORTHO_MAX_BLOCKS = 4096;
 
 // ---- top surface -----------------------------------------------------------------------------------------------------------
 // One thread per point (grid-stride above 4096 x 256 points).  key = (quantised altitude + 2^31) << 32 | (2^32 - 1 - global index).
@@ -72,8 +33,8 @@ __global__ __launch_bounds__(ORTHO_THREADS) void ortho_top_kernel(const double* 
       for (long long li = w.i0; li < w.i1; ++li) atomicMax(&top[(lj - g.joff) * g.out_w + (li - g.ioff)], key);
     reached++;
   }
-  bad = ortho_wave_sum(bad);
-  reached = ortho_wave_sum(reached);
+  bad = wave_sum_u64(bad);
+  reached = wave_sum_u64(reached);
   if ((threadIdx.x & 63) == 0) {
     if (bad) atomicAdd(&stats[0], bad);
     if (reached) atomicAdd(&stats[1], reached);
@@ -131,7 +92,7 @@ __global__ __launch_bounds__(ORTHO_THREADS) void ortho_votes_kernel(const double
     for (long long lj = w.j0; lj < w.j1; ++lj)
       for (long long li = w.i0; li < w.i1; ++li) atomicAdd(&plane[(lj - g.joff) * g.out_w + (li - g.ioff)], 1u);
   }
-  bad = ortho_wave_sum(bad);
+  bad = wave_sum_u64(bad);
   if ((threadIdx.x & 63) == 0 && bad) atomicAdd(&stats[0], bad);
 }
 
@@ -153,34 +114,13 @@ __global__ __launch_bounds__(ORTHO_THREADS) void ortho_votes_finish_kernel(const
     share_out[c] = total ? (float)((double)best / (double)total) : __builtin_nanf("");
     tmax = total > tmax ? total : tmax;
   }
-  tmax = ortho_wave_max(tmax);
+  tmax = wave_max_u64(tmax);
   if ((threadIdx.x & 63) == 0 && tmax) atomicMax(&stats[1], tmax);
-}
-
-static unsigned ortho_blocks(long long n) {
-  const long long want = (n + ORTHO_THREADS - 1) / ORTHO_THREADS;
-  return (unsigned)(want < 1 ? 1 : (want < 4096 ? want : 4096));
-}
-
-// the grid of an accumulating entry: res > 0, positive sizes, a window whose cells are int32 indices
-static bool ortho_grid_ok(const char* who, const SnerfDsmGrid* g) {
-  if (!(g->res > 0.0) || !isfinite(g->res) || !isfinite(g->xoff) || !isfinite(g->yoff) || g->xsize <= 0 || g->ysize <= 0 ||
-      g->out_w <= 0 || g->out_h <= 0) {
-    set_error("%s: grid needs res > 0 and positive sizes", who);
-    return false;
-  }
-  if ((long long)g->ioff + g->out_w > 2147483647LL || (long long)g->joff + g->out_h > 2147483647LL) {
-    set_error("%s: the output window reaches beyond int32 cell indices", who);
-    return false;
-  }
-  return true;
 }
 
 }  // namespace snerf
 
 using namespace snerf;
-
-extern "C" int snerf_ortho_version(void) { return SNERF_ORTHO_VERSION; }
 
 extern "C" int snerf_ortho_top(const double* xyz, long long n, long long index0, const SnerfDsmGrid* grid, int radius, double z0,
                                double q, unsigned long long* top, unsigned long long* stats, void* stream) {
@@ -191,10 +131,10 @@ extern "C" int snerf_ortho_top(const double* xyz, long long n, long long index0,
     return SNERF_ERR_BAD_DESC;
   }
   if (radius < 0 || radius > SNERF_ORTHO_MAX_RADIUS) { set_error("snerf_ortho_top: radius must lie in [0, %d]", SNERF_ORTHO_MAX_RADIUS); return SNERF_ERR_BAD_DESC; }
-  if (!ortho_grid_ok("snerf_ortho_top", grid)) return SNERF_ERR_BAD_DESC;
-  if (!(q > 0.0) || !isfinite(q) || !isfinite(z0)) { set_error("snerf_ortho_top: q > 0 and finite, z0 finite required"); return SNERF_ERR_BAD_DESC; }
+  if (!lattice_grid_ok("snerf_ortho_top", grid) || !lattice_window_fits_int32("snerf_ortho_top", grid)) return SNERF_ERR_BAD_DESC;
+  if (!quant_ok("snerf_ortho_top", z0, q)) return SNERF_ERR_BAD_DESC;
   if (n == 0) return SNERF_OK;
-  hipLaunchKernelGGL(ortho_top_kernel, dim3(ortho_blocks(n)), dim3(ORTHO_THREADS), 0, (hipStream_t)stream, xyz, n,
+  hipLaunchKernelGGL(ortho_top_kernel, dim3(blocks_for(n, ORTHO_THREADS, ORTHO_MAX_BLOCKS)), dim3(ORTHO_THREADS), 0, (hipStream_t)stream, xyz, n,
                      (unsigned long long)index0, *grid, radius, z0, q, top, stats);
   SNERF_LAUNCH_CHECK();
   return SNERF_OK;
@@ -212,9 +152,9 @@ extern "C" int snerf_ortho_gather(const unsigned long long* top, long long cells
     set_error("snerf_ortho_gather: index0 >= 0 and index0 + n <= 2^32 - 1 required (index0 = %lld, n = %lld)", index0, n);
     return SNERF_ERR_BAD_DESC;
   }
-  if (!(q > 0.0) || !isfinite(q) || !isfinite(z0)) { set_error("snerf_ortho_gather: q > 0 and finite, z0 finite required"); return SNERF_ERR_BAD_DESC; }
+  if (!quant_ok("snerf_ortho_gather", z0, q)) return SNERF_ERR_BAD_DESC;
   if (n == 0) return SNERF_OK;
-  hipLaunchKernelGGL(ortho_gather_kernel, dim3(ortho_blocks(cells)), dim3(ORTHO_THREADS), 0, (hipStream_t)stream, top, cells, index0,
+  hipLaunchKernelGGL(ortho_gather_kernel, dim3(blocks_for(cells, ORTHO_THREADS, ORTHO_MAX_BLOCKS)), dim3(ORTHO_THREADS), 0, (hipStream_t)stream, top, cells, index0,
                      n, z0, q, rgb, labels, scalar, alt_out, idx_out, rgb_out, label_out, scalar_out);
   SNERF_LAUNCH_CHECK();
   return SNERF_OK;
@@ -226,9 +166,9 @@ extern "C" int snerf_ortho_votes(const double* xyz, const long long* labels, lon
   if (n < 0 || n > ORTHO_MAX_N) { set_error("snerf_ortho_votes: n must lie in [0, 2^31]"); return SNERF_ERR_BAD_DESC; }
   if (radius < 0 || radius > SNERF_ORTHO_MAX_RADIUS) { set_error("snerf_ortho_votes: radius must lie in [0, %d]", SNERF_ORTHO_MAX_RADIUS); return SNERF_ERR_BAD_DESC; }
   if (n_classes < 1 || n_classes > SNERF_ORTHO_MAX_CLASSES) { set_error("snerf_ortho_votes: n_classes must lie in [1, %d]", SNERF_ORTHO_MAX_CLASSES); return SNERF_ERR_BAD_DESC; }
-  if (!ortho_grid_ok("snerf_ortho_votes", grid)) return SNERF_ERR_BAD_DESC;
+  if (!lattice_grid_ok("snerf_ortho_votes", grid) || !lattice_window_fits_int32("snerf_ortho_votes", grid)) return SNERF_ERR_BAD_DESC;
   if (n == 0) return SNERF_OK;
-  hipLaunchKernelGGL(ortho_votes_kernel, dim3(ortho_blocks(n)), dim3(ORTHO_THREADS), 0, (hipStream_t)stream, xyz, labels, n, *grid,
+  hipLaunchKernelGGL(ortho_votes_kernel, dim3(blocks_for(n, ORTHO_THREADS, ORTHO_MAX_BLOCKS)), dim3(ORTHO_THREADS), 0, (hipStream_t)stream, xyz, labels, n, *grid,
                      radius, n_classes, votes, stats);
   SNERF_LAUNCH_CHECK();
   return SNERF_OK;
@@ -239,7 +179,7 @@ extern "C" int snerf_ortho_votes_finish(const unsigned* votes, int n_classes, lo
   if (!votes || !label_out || !share_out || !stats) { set_error("snerf_ortho_votes_finish: null pointer"); return SNERF_ERR_NULL; }
   if (n_classes < 1 || n_classes > SNERF_ORTHO_MAX_CLASSES) { set_error("snerf_ortho_votes_finish: n_classes must lie in [1, %d]", SNERF_ORTHO_MAX_CLASSES); return SNERF_ERR_BAD_DESC; }
   if (cells < 1 || cells > (1LL << 53)) { set_error("snerf_ortho_votes_finish: cells must be >= 1"); return SNERF_ERR_BAD_DESC; }
-  hipLaunchKernelGGL(ortho_votes_finish_kernel, dim3(ortho_blocks(cells)), dim3(ORTHO_THREADS), 0, (hipStream_t)stream, votes,
+  hipLaunchKernelGGL(ortho_votes_finish_kernel, dim3(blocks_for(cells, ORTHO_THREADS, ORTHO_MAX_BLOCKS)), dim3(ORTHO_THREADS), 0, (hipStream_t)stream, votes,
                      n_classes, cells, label_out, share_out, stats);
   SNERF_LAUNCH_CHECK();
   return SNERF_OK;

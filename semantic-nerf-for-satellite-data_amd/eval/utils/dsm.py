@@ -11,7 +11,8 @@ data-parallel ranks combine exactly by a SUM all-reduce of the accumulators.  Z0
 data, so all ranks agree); |z - Z0| is off its exact value by at most Q/2 = 3e-8 before the fp32 rounding.  Accumulator
 overflow raises OverflowError, it never wraps.  plyflatten (a C extension) is not available here: parity with it is
 UNPINNED; the tests pin the kernels to the spec through a numpy restatement.  Finite `sigma` is out of scope (the reference
-only ever passes inf).
+only ever passes inf).  Which cells a point reaches is cell_window() of csrc/lattice.h, shared with the ortho products
+(eval/utils/ortho.py), which also go through grid_struct, cloud_f64, cell_count and new_stats below.
 
 Grids -- the cloud-bounds grid of create_dsm without roi_txt (dsm.py:66-72, resolution 0.5) and the ROI grid of the
 roi_txt arithmetic (dsm.py:58-63: xsize = ysize = int(meta[2]), the ROI is square; yoff += size * res).
@@ -103,21 +104,46 @@ def roi_grid(meta):
 
 
 # ---- rasterisation -----------------------------------------------------------------------------------------------------------
-def _accumulate(cloud, lattice, window, radius):
-    """integer accumulators (count i32-as-u32, sum i64) and stats (u64[4]) of `cloud` on `lattice` cropped to
-    window = (ioff, joff, out_w, out_h)"""
-    ioff, joff, w, h = window
-    g = _lib.SnerfDsmGrid(float(lattice.xoff), float(lattice.yoff), float(lattice.resolution), int(lattice.xsize),
-                          int(lattice.ysize), int(ioff), int(joff), int(w), int(h))
-    if h * w > 2 ** 31 - 1:
-        raise ValueError(f"DSM of {h} x {w} cells is too large")
+def grid_struct(lattice, window=None):
+    """a DsmGrid cropped to window = (ioff, joff, out_w, out_h) (the whole extent without one), or a ready _lib.SnerfDsmGrid
+    (a window of a lattice), -> _lib.SnerfDsmGrid"""
+    if isinstance(lattice, _lib.SnerfDsmGrid):
+        return lattice
+    ioff, joff, w, h = window if window is not None else (0, 0, lattice.xsize, lattice.ysize)
+    return _lib.SnerfDsmGrid(float(lattice.xoff), float(lattice.yoff), float(lattice.resolution), int(lattice.xsize),
+                             int(lattice.ysize), int(ioff), int(joff), int(w), int(h))
+
+
+def cell_count(g, what="DSM"):
+    """out_h * out_w of a _lib.SnerfDsmGrid; the accumulators of a window are indexed with 31 bits"""
+    if g.out_h * g.out_w > 2 ** 31 - 1:
+        raise ValueError(f"{what} of {g.out_h} x {g.out_w} cells is too large")
+    return g.out_h * g.out_w
+
+
+def cloud_f64(cloud):
+    """the (N, 3) (east, north, alt) cloud as the kernels of the lattice read it: fp64, contiguous"""
     xyz = cloud.to(torch.float64).contiguous()
     if xyz.dim() != 2 or xyz.shape[1] != 3:
         raise ValueError("the cloud must be (N, 3)")
-    dev = xyz.device
-    count = torch.zeros(h * w, dtype=torch.int32, device=dev)
-    total = torch.zeros(h * w, dtype=torch.int64, device=dev)
-    stats = torch.zeros(4, dtype=torch.int64, device=dev)
+    return xyz
+
+
+def new_stats(device):
+    """a zeroed stats block (4 u64 words, held as int64)"""
+    return torch.zeros(4, dtype=torch.int64, device=device)
+
+
+def _accumulate(cloud, lattice, window, radius, acc=None):
+    """integer accumulators (count i32-as-u32, sum i64) and stats (u64[4]) of `cloud` on `lattice` cropped to
+    window = (ioff, joff, out_w, out_h) (see grid_struct); `acc`: the (count, total, stats) of earlier calls to go on adding to"""
+    g = grid_struct(lattice, window)
+    cells = cell_count(g)
+    xyz = cloud_f64(cloud)
+    if acc is None:
+        acc = (torch.zeros(cells, dtype=torch.int32, device=xyz.device), torch.zeros(cells, dtype=torch.int64, device=xyz.device),
+               new_stats(xyz.device))
+    count, total, stats = acc
     _lib.call("snerf_dsm_accumulate", xyz, xyz.shape[0], g, radius, Z0, Q, count, total, stats)
     return count, total, stats
 

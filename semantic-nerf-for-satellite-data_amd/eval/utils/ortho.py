@@ -1,7 +1,7 @@
 """Geo-referenced ortho products: the colour, the class and the votes of a semantic satellite NeRF ON THE MAP -- a true
 ortho-image, a land-cover map and the fusion of a scene's views into one raster, on the lattice of the DSM rasteriser
-(eval/utils/dsm.py).  The reference has no counterpart; the spec is include/snerf_ortho.h, the stages
-are the kernels of csrc/ortho.hip, torch is plumbing.  All functions take and return device tensors.
+(eval/utils/dsm.py).  The reference has no counterpart; the spec is the ortho section of include/snerf_hip.h (DESIGN.md section
+5j), the stages are the kernels of csrc/ortho.hip, torch is plumbing.  All functions take and return device tensors.
 
 Top surface -- every point of a UTM (east, north, alt) cloud offers a 64-bit key to the cells of its (2 radius + 1)^2 window:
 (round((z - Z0)/Q) + 2^31) << 32 | (2^32 - 1 - global point index), folded with an integer atomic max.  The highest quantised
@@ -24,6 +24,7 @@ import torch
 
 from ... import _lib
 from . import dsm as D
+from .dsm import grid_struct, new_stats      # the lattice plumbing is the DSM's
 
 Z0 = 0.0             # quantisation origin of the key's altitude (metres)
 Q = 2.0 ** -16       # quantisation step (metres): 2^32 steps span +-32,768 m
@@ -31,32 +32,14 @@ NO_LABEL = _lib.ORTHO_NO_LABEL
 MAX_INDEX = 2 ** 32 - 1
 
 
-def grid_struct(grid):
-    """a DsmGrid (the window is the whole extent) or a ready _lib.SnerfDsmGrid (a window of a lattice) -> _lib.SnerfDsmGrid"""
-    if isinstance(grid, _lib.SnerfDsmGrid):
-        return grid
-    return _lib.SnerfDsmGrid(float(grid.xoff), float(grid.yoff), float(grid.resolution), int(grid.xsize), int(grid.ysize), 0, 0,
-                             int(grid.xsize), int(grid.ysize))
-
-
 def _cloud(cloud):
     if not (torch.is_tensor(cloud) and cloud.is_cuda):
         raise ValueError("ortho: the cloud must be a GPU tensor (the HIP path has no CPU fallback)")
-    if cloud.dim() != 2 or cloud.shape[1] != 3:
-        raise ValueError("the cloud must be (N, 3)")
-    return cloud.to(torch.float64).contiguous()
+    return D.cloud_f64(cloud)
 
 
 def _cells(g):
-    cells = g.out_h * g.out_w
-    if cells > 2 ** 31 - 1:
-        raise ValueError(f"a map of {g.out_h} x {g.out_w} cells is too large")
-    return cells
-
-
-def new_stats(device):
-    """a zeroed stats block (4 u64 words, held as int64)"""
-    return torch.zeros(4, dtype=torch.int64, device=device)
+    return D.cell_count(g, "a map")
 
 
 def top_surface(cloud, grid, radius=0, index0=0, top=None, stats=None):
@@ -152,7 +135,7 @@ def ortho_products(cfgs, renderer, models, images, geo=None, roi=None, resolutio
     Per image, in the order given: lean_inference (sharded_lean_inference with `sharded`: every rank then holds the whole
     frame, and nothing is all-reduced here) for rgb, depth and, when the model has classes, the label; geo.cloud(rays, depth)
     (`geo` defaults to the image's "dsm"["geo"]); the cloud folded into the shared accumulators -- the top-surface keys with
-    index0 = the running ray offset, the label votes, and the DSM's count / sum (snerf_dsm_accumulate, radius `dsm_radius`).
+    index0 = the running ray offset, the label votes, and the DSM's count / sum (dsm._accumulate, radius `dsm_radius`).
     The grid: `grid` (a DsmGrid), else the ROI grid of `roi` (a DsmGrid or the roi_txt meta) used as the lattice, else the
     bounds grid of the union of the clouds' exact bounds -- known only after every image has been rendered, so the frames'
     rgb, depth and labels are kept and the clouds are made again (one launch each) for the fold; nothing is rendered twice.
@@ -182,16 +165,12 @@ def ortho_products(cfgs, renderer, models, images, geo=None, roi=None, resolutio
 
     def fold(cloud, labels, index0):
         if not acc:
-            g = grid_struct(grid)
-            dev = cloud.device
-            acc.update(g=g, top=None, tstats=new_stats(dev), votes=None, vstats=new_stats(dev),
-                       count=torch.zeros(_cells(g), dtype=torch.int32, device=dev),
-                       total=torch.zeros(_cells(g), dtype=torch.int64, device=dev), dstats=new_stats(dev))
+            acc.update(g=grid_struct(grid), top=None, tstats=new_stats(cloud.device), votes=None, vstats=new_stats(cloud.device),
+                       dsm=None)
         acc["top"], _ = top_surface(cloud, acc["g"], radius, index0, acc["top"], acc["tstats"])
         if n_classes:
             acc["votes"], _ = label_votes(cloud, labels, acc["g"], n_classes, radius, acc["votes"], acc["vstats"])
-        _lib.call("snerf_dsm_accumulate", cloud, cloud.shape[0], acc["g"], dsm_radius, D.Z0, D.Q, acc["count"], acc["total"],
-                  acc["dstats"])
+        acc["dsm"] = D._accumulate(cloud, acc["g"], None, dsm_radius, acc["dsm"])
 
     frames, index0 = [], 0
     ext = [float("inf"), float("-inf"), float("inf"), float("-inf")]
@@ -221,7 +200,7 @@ def ortho_products(cfgs, renderer, models, images, geo=None, roi=None, resolutio
     for f in frames:
         out = gather(acc["top"], f["index0"], f["n"], rgb=f["rgb"], labels=f["labels"], out=out)
     res = {"grid": grid if isinstance(grid, D.DsmGrid) else D.DsmGrid(grid.xoff, grid.yoff, grid.res, grid.xsize, grid.ysize),
-           "dsm": D._finish(acc["count"], acc["total"], acc["dstats"], h, w), "top_alt": out["alt"], "top_index": out["index"],
+           "dsm": D._finish(*acc["dsm"], h, w), "top_alt": out["alt"], "top_index": out["index"],
            "rgb": out["rgb"], "n_points": index0}
     bad_points = int(acc["tstats"][0])
     if n_classes:

@@ -1,4 +1,4 @@
-"""NumPy restatement of the ortho products (tests only), written from the spec in include/snerf_ortho.h: the lattice of the DSM
+"""NumPy restatement of the ortho products (tests only), written from the ortho section of include/snerf_hip.h: the lattice of the DSM
 rasteriser, the 64-bit top-surface key in Python / NumPy integer arithmetic, the gather of the winners' payloads and the label
 votes.  Two forms of each accumulating stage: a plain loop over points and window cells (Python ints, the spec read aloud) and
 a vectorised one on np.maximum.at / np.add.at for the larger cases; tests/test_ortho_cpu.py holds the two to each other, the

@@ -72,10 +72,11 @@ def test_binding_table_matches_header_prototypes():
     """Every prototype of the header against its row of _lib.SIGNATURES: the return type, the parameter count and, per parameter,
     class, width and signedness; a pointer to a struct against POINTER() of the mirror with that name (or void*); the stream
     marker exactly where the header's parameter is called `stream`.  No symbol is left out: the parser must give a prototype
-    for every name _declared_symbols() finds."""
+    for every name _declared_symbols() finds; the rows stand in the header's order."""
     from snerf_amd import _lib
     protos = _header_prototypes()
-    assert sorted(protos) == _declared_symbols() == sorted(_lib.SIGNATURES) and len(protos) >= 42
+    assert sorted(protos) == _declared_symbols() == sorted(_lib.SIGNATURES) and len(protos) >= 49
+    assert list(_lib.SIGNATURES) == list(protos)                    # the header's declaration order, for the whole table
     for name, (ret, params) in protos.items():
         restype, argtypes = _lib.SIGNATURES[name]
         assert _table_type(restype) == ret, (name, "return type", restype, ret)
@@ -87,6 +88,7 @@ def test_binding_table_matches_header_prototypes():
     L = _lib.lib()
     for name, (restype, argtypes) in _lib.SIGNATURES.items():       # lib() applied the table
         assert getattr(L, name).restype is restype and tuple(getattr(L, name).argtypes) == tuple(argtypes), name
+        assert name in _lib._PLANS                                  # _lib.call works by name
 
 
 def test_call_argument_handling_without_a_launch():
@@ -158,7 +160,7 @@ def test_host_only_sizes_and_errors():
     assert L.snerf_workspace_bytes(C.byref(ModelSpec(fc_units=96, feat_last=48).desc(16, 8))) > 0
     # the default arithmetic is the same object for a C caller (flags = 0) and for Python's ModelSpec()
     assert L.snerf_workspace_bytes(C.byref(ModelSpec().desc(64, 8))) == L.snerf_workspace_bytes(C.byref(ModelSpec().desc(64, 8, _lib.FLAG_F16X2)))
-    assert L.snerf_version() == 5
+    assert L.snerf_version() == 6
 
 
 def test_plan_builder_over_model_variants_and_null_arguments():

@@ -97,6 +97,100 @@ def test_rasterize_overflow_is_an_error(monkeypatch):
     assert bool(torch.isfinite(D.rasterize(c, grid)).any())
 
 
+def test_bad_point_count_is_a_count():
+    """stats[1] counts the points with an unusable altitude (include/snerf_hip.h): three in the first wave, one of them at its
+    last lane, and one in each of the next two waves give 6 -- a sum over the waves, not a maximum per wave"""
+    D = _dsm()
+    grid = D.DsmGrid(1000.0, 2000.0 + 7 * 0.5, 0.5, 9, 7)
+    cloud = _cloud(200, 9, 7, 0.5, 300.0, 20.0, seed=23, margin=0.0)
+    bad = [0, 1, 2, 63, 64, 130]
+    cloud[bad, 2] = np.nan
+    c = torch.from_numpy(cloud).to(DEV)
+    count, _, stats = D._accumulate(c, grid, (0, 0, grid.xsize, grid.ysize), 1)
+    print("stats", stats.tolist())
+    assert int(stats[1]) == len(bad) == 6
+    assert np.array_equal(count.cpu().numpy().reshape(7, 9), N.rasterize(np.delete(cloud, bad, 0), *grid, radius=1)[1])
+    with pytest.raises(OverflowError, match="6 point"):
+        D.rasterize(c, grid)
+
+
+# ---- one cell arithmetic for the DSM, the top surface and the votes (csrc/lattice.h) --------------------------------------------
+LW, LH, LRES = 9, 7, 0.5
+LGRID = (1000.0, 2000.0 + LH * LRES, LRES, LW, LH)
+# (ioff, joff, out_w, out_h): the whole extent, inside it, larger than the lattice from a negative origin, over the east edge
+LWINDOWS = {"whole": (0, 0, LW, LH), "inside": (2, 1, 6, 5), "beyond": (-2, -1, 20, 30), "east-edge": (6, 2, 6, 4)}
+_LATTICE = {}
+
+
+def _lattice_cloud():
+    """2,000 points up to 8 cells outside the 9 x 7 lattice on every side, five of them without a finite x or y; labels in range"""
+    if not _LATTICE:
+        xyz = _cloud(2000, LW, LH, LRES, 100.0, 150.0, seed=29, margin=8.0)
+        xyz[:, 2] = np.clip(xyz[:, 2], -1000.0, 1000.0)
+        xyz[[3, 700], 0] = np.nan, -np.inf
+        xyz[[64, 1999], 1] = np.inf, np.nan
+        xyz[1000, :2] = np.inf, -np.inf
+        _LATTICE.update(xyz=xyz, labels=np.random.default_rng(30).integers(0, 5, 2000), dev=torch.from_numpy(xyz).to(DEV), counts={})
+        _LATTICE["dev_labels"] = torch.from_numpy(_LATTICE["labels"]).to(DEV)
+    return _LATTICE
+
+
+def _window_count(radius, window):
+    """tests/dsm_numpy.py's count on the whole extent (once per radius), read through the window; 0 outside the lattice"""
+    L = _lattice_cloud()
+    if radius not in L["counts"]:
+        L["counts"][radius] = N.rasterize(L["xyz"], *LGRID, radius=radius)[1]
+    ioff, joff, w, h = window
+    out = np.zeros((h, w), np.int64)
+    i0, i1, j0, j1 = max(ioff, 0), min(ioff + w, LW), max(joff, 0), min(joff + h, LH)
+    out[j0 - joff:j1 - joff, i0 - ioff:i1 - ioff] = L["counts"][radius][j0:j1, i0:i1]
+    return out
+
+
+@pytest.mark.parametrize("radius", (0, 1, 2, 7))
+@pytest.mark.parametrize("window", LWINDOWS)
+def test_the_three_splats_agree_cell_for_cell(window, radius):
+    """a cell's DSM count = the sum of its votes over the classes, and it has a top-surface key exactly when that count is not 0:
+    all three entries offer a point to the same cells (both header sections state one rule); the count is dsm_numpy's"""
+    from snerf_amd import _lib
+    from snerf_amd.eval.utils import ortho as OR
+    D = _dsm()
+    L = _lattice_cloud()
+    ioff, joff, w, h = LWINDOWS[window]
+    grid = D.DsmGrid(*LGRID)
+    g = _lib.SnerfDsmGrid(*LGRID, ioff, joff, w, h)
+    count, _, dstats = D._accumulate(L["dev"], grid, LWINDOWS[window], radius)
+    top, tstats = OR.top_surface(L["dev"], g, radius)
+    votes, vstats = OR.label_votes(L["dev"], L["dev_labels"], g, 5, radius)
+    count = count.cpu().numpy().astype(np.int64).reshape(h, w)
+    want = _window_count(radius, LWINDOWS[window])
+    print(window, radius, "cells reached", int((count > 0).sum()), "of", h * w, "offers", int(count.sum()), "bad", int(dstats[1]),
+          int(tstats[0]), int(vstats[0]))
+    assert (want > 0).any()
+    assert np.array_equal(count, want)
+    assert np.array_equal(votes.cpu().numpy().astype(np.int64).sum(0), count)
+    assert np.array_equal(top.cpu().numpy() != 0, count > 0)
+    assert int(dstats[1]) == 0 and int(tstats[0]) == 0 and int(vstats[0]) == 5
+
+
+@pytest.mark.parametrize("radius", (8, 64))
+def test_rasterize_radius_beyond_the_ortho_limit(radius):
+    """the DSM's own radius bound is 64, above the ortho entries' 7: windows far wider than the lattice, clipped on every side"""
+    D = _dsm()
+    grid = D.DsmGrid(*LGRID)
+    cloud = _cloud(300, LW, LH, LRES, 300.0, 20.0, seed=31, margin=radius + 6.0)      # some own cells lie too far out to reach a cell
+    want, cnt = N.rasterize(cloud, *grid, radius=radius)
+    c = torch.from_numpy(cloud).to(DEV)
+    got = D.rasterize(c, grid, radius=radius).cpu().numpy()
+    count, _, _ = D._accumulate(c, grid, (0, 0, grid.xsize, grid.ysize), radius)
+    print(radius, "count min / max", int(cnt.min()), int(cnt.max()))
+    assert np.array_equal(count.cpu().numpy().reshape(LH, LW), cnt) and 1 < cnt.max() < 300
+    assert np.array_equal(np.isnan(got), cnt == 0)
+    ulp = float(np.spacing(np.float32(np.abs(cloud[:, 2]).max())))
+    ok = cnt > 0
+    assert np.abs(got[ok].astype(np.float64) - want[ok]).max() <= ulp
+
+
 @pytest.mark.parametrize("path", GOLDEN, ids=lambda p: os.path.basename(p)[:-4])
 def test_registration_and_mae_vs_reference_golden(path):
     D = _dsm()

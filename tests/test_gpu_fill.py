@@ -63,6 +63,11 @@ POINTERS = {
     "snerf_dsm_downsample2x": {"u": "in", "out": "out"},
     "snerf_dsm_ncc_search": {"u": "in", "v": "in", "stats": "out", "workspace": "ws"},
     "snerf_dsm_shift_diff": {"pred": "in", "gt": "in", "rdsm": "out", "diff": "out", "totals": "out", "workspace": "ws"},
+    "snerf_ortho_top": {"xyz": "in", "grid": "in", "top": "acc", "stats": "acc"},
+    "snerf_ortho_gather": {"top": "in", "rgb": "in", "labels": "in", "scalar": "in", "alt_out": "out", "idx_out": "out",
+                           "rgb_out": "inout", "label_out": "inout", "scalar_out": "inout"},      # payloads: written only in won cells
+    "snerf_ortho_votes": {"xyz": "in", "labels": "in", "grid": "in", "votes": "acc", "stats": "acc"},
+    "snerf_ortho_votes_finish": {"votes": "in", "label_out": "out", "share_out": "out", "stats": "acc"},
     "snerf_ssim": {"x": "in", "y": "in", "weights2d": "in", "map_or_null": "out", "per_image_sum": "out", "workspace": "ws"},
     "snerf_semeval_accumulate": {"pred": "in", "gt": "in", "gt_no_cars": "in", "gt_non_corrupted": "in", "weights": "in",
                                  "beta": "in", "acc": "acc", "workspace": "ws"},

@@ -1,6 +1,7 @@
-"""CPU-side checks of the ortho products (include/snerf_ortho.h, csrc/ortho.hip, eval/utils/ortho.py, img_utils.save_geotiff):
-the second binding table against its header -- what tests/test_abi_cpu.py does for include/snerf_hip.h --, every refusal without
-a GPU, the key's layout, the two forms of the numpy restatement against each other, and the GeoTIFF writer's round trip."""
+"""CPU-side checks of the ortho products (the ortho section of include/snerf_hip.h, csrc/ortho.hip, eval/utils/ortho.py,
+img_utils.save_geotiff): the constants of the header against their mirrors (tests/test_abi_cpu.py holds the binding rows to the
+prototypes), every refusal without a GPU, the key's layout, the two forms of the numpy restatement against each other, and the
+GeoTIFF writer's round trip."""
 import ctypes as C
 import os
 import re
@@ -9,62 +10,18 @@ import numpy as np
 import pytest
 
 from tests import ortho_numpy as R
-from tests.test_abi_cpu import _c_type, _table_type
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "snerf_ortho.h")
+HEADER = os.path.join(ROOT, "include", "snerf_hip.h")
 
 
-def _stripped():
-    src = open(HEADER).read()
-    return re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-
-
-def _declared():
-    return sorted(set(re.findall(r"\b(snerf_[a-z_0-9]+)\s*\(", _stripped())))
-
-
-def _prototypes():
-    """the method of test_abi_cpu._header_prototypes on include/snerf_ortho.h"""
-    src = re.sub(r"^\s*#.*$", "", _stripped(), flags=re.M)
-    src = re.sub(r"typedef struct \w+ \{.*?\} \w+;", "", src, flags=re.S)
-    protos = {}
-    for ret, name, params in re.findall(r"([\w \*]+?)\b(snerf_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", src):
-        params = [] if params.strip() == "void" else [re.fullmatch(r"\s*(.*?)(\w+)\s*", p).groups() for p in params.split(",")]
-        protos[name] = (_c_type(ret), [(_c_type(t), n) for t, n in params])
-    return protos
-
-
-def test_ortho_table_matches_its_header_and_the_library():
+def test_ortho_constants_match_the_header_and_the_library():
     from snerf_amd import _lib
-    protos = _prototypes()
-    assert sorted(protos) == _declared() == sorted(_lib.ORTHO_SIGNATURES) and len(protos) == 5
-    assert list(_lib.ORTHO_SIGNATURES) == re.findall(r"\b(snerf_[a-z_0-9]+)\s*\(", _stripped())       # the header's order
-    for name, (ret, params) in protos.items():
-        restype, argtypes = _lib.ORTHO_SIGNATURES[name]
-        assert _table_type(restype) == ret, (name, "return type", restype, ret)
-        assert len(argtypes) == len(params), (name, len(argtypes), len(params))
-        for k, (t, (want, pname)) in enumerate(zip(argtypes, params)):
-            got = _table_type(t)
-            assert got == want or (want[0] == "pointer" and got == ("pointer", None)), (name, k, pname, t, want)
-            assert (t is _lib.c_stream) == (pname == "stream"), (name, k, pname, t)
     L = _lib.lib()
-    for name, (restype, argtypes) in _lib.ORTHO_SIGNATURES.items():        # exported, and lib() applied the table
-        fn = getattr(L, name)
-        assert fn.restype is restype and tuple(fn.argtypes) == tuple(argtypes), name
-        assert name in _lib._PLANS                                          # _lib.call works by name
-    assert "#include \"snerf_hip.h\"" in open(HEADER).read()
-
-
-def test_ortho_table_is_apart_from_the_main_table():
-    from snerf_amd import _lib
-    assert not set(_lib.ORTHO_SIGNATURES) & set(_lib.SIGNATURES)
-    assert not set(_lib.ORTHO_SIGNATURES) & set(_lib.EXPORTED_SYMBOLS)
-    L = _lib.lib()
-    assert L.snerf_version() == _lib.ABI_VERSION == 5
-    assert L.snerf_ortho_version() == _lib.ORTHO_VERSION == 1
+    assert L.snerf_version() == _lib.ABI_VERSION == 6
+    assert not hasattr(L, "snerf_ortho_version")                # the ortho entries have no version of their own any more
     text = open(HEADER).read()
-    assert int(re.search(r"#define SNERF_ORTHO_VERSION (\d+)", text).group(1)) == _lib.ORTHO_VERSION
+    assert int(re.search(r"#define SNERF_ABI_VERSION (\d+)", text).group(1)) == _lib.ABI_VERSION
     assert int(re.search(r"#define SNERF_ORTHO_MAX_RADIUS (\d+)", text).group(1)) == _lib.ORTHO_MAX_RADIUS == 7
     assert int(re.search(r"#define SNERF_ORTHO_MAX_CLASSES (\d+)", text).group(1)) == _lib.ORTHO_MAX_CLASSES == 255
     assert int(re.search(r"#define SNERF_ORTHO_NO_LABEL (\d+)", text).group(1)) == _lib.ORTHO_NO_LABEL == R.NO_LABEL
