@@ -4,6 +4,7 @@
 // numerics are stated in include/snerf_hip.h and in snerf_amd/eval/utils/dsm.py; every reduction here is in a fixed order,
 // so every result is bit-reproducible run to run.
 #include "lattice.h"
+#include "reduce.h"
 
 namespace snerf {
 
@@ -35,8 +36,8 @@ __global__ __launch_bounds__(256) void dsm_accumulate_kernel(const double* __res
         atomicAdd(&sum[cell], (unsigned long long)k);   // two's complement: a signed sum
       }
   }
-  kmax = wave_max_u64(kmax);
-  bad = wave_sum_u64(bad);
+  kmax = wave_reduce(kmax, OpMax());
+  bad = wave_reduce(bad, OpSum());
   if ((threadIdx.x & 63) == 0) {
     if (kmax) atomicMax(&stats[0], kmax);
     if (bad) atomicAdd(&stats[1], bad);
@@ -53,7 +54,7 @@ __global__ __launch_bounds__(256) void dsm_finish_kernel(const unsigned* __restr
     cmax = m > cmax ? m : cmax;
     dsm[c] = m ? (float)(z0 + q * ((double)sum[c] / (double)m)) : __builtin_nanf("");
   }
-  cmax = wave_max_u64(cmax);
+  cmax = wave_reduce(cmax, OpMax());
   if ((threadIdx.x & 63) == 0 && cmax) atomicMax(&stats[2], cmax);
 }
 
@@ -146,19 +147,12 @@ __global__ __launch_bounds__(NCC_THREADS) void ncc_tile_kernel(const T* __restri
   }
 }
 
-// one workgroup per (component, shift): the per-block partials summed in a fixed order (strided per thread, then a fixed tree)
+// one workgroup per (component k, shift s): the per-block partials partial[(b * 3 + k) * S + s], b ascending (reduce.h)
 __global__ __launch_bounds__(256) void ncc_reduce_kernel(const double* __restrict__ partial, long long nblk, int S, int pass,
                                                          double* __restrict__ stats) {
   __shared__ double red[256];
   const int k = blockIdx.x / S, s = blockIdx.x % S;
-  double a = 0.0;
-  for (long long b = threadIdx.x; b < nblk; b += 256) a += partial[(b * 3 + k) * S + s];
-  red[threadIdx.x] = a;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
+  block_strided_sum<256>(red, threadIdx.x, partial + k * S + s, nblk, 3LL * S);
   if (threadIdx.x == 0) stats[s * 6 + 3 * pass + k] = red[0];
 }
 
@@ -170,7 +164,7 @@ __global__ __launch_bounds__(DIFF_THREADS) void shift_diff_kernel(const float* _
                                                                   int h, int w, int dx, int dy, double b,
                                                                   float* __restrict__ rdsm, float* __restrict__ diff,
                                                                   double* __restrict__ partial) {
-  __shared__ double rs[DIFF_THREADS], rc[DIFF_THREADS];
+  __shared__ double red[2 * DIFF_THREADS];             // the sums of |d|, then the counts
   const long long cells = (long long)h * w;
   double s = 0.0, c = 0.0;
   for (long long p = (long long)blockIdx.x * DIFF_THREADS + threadIdx.x; p < cells; p += (long long)gridDim.x * DIFF_THREADS) {
@@ -185,16 +179,12 @@ __global__ __launch_bounds__(DIFF_THREADS) void shift_diff_kernel(const float* _
     if (diff) diff[p] = d;
     if (__builtin_isfinite(d)) { s += fabs((double)d); c += 1.0; }
   }
-  rs[threadIdx.x] = s;
-  rc[threadIdx.x] = c;
-  __syncthreads();
-  for (int o = DIFF_THREADS / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) { rs[threadIdx.x] += rs[threadIdx.x + o]; rc[threadIdx.x] += rc[threadIdx.x + o]; }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) { partial[2 * blockIdx.x] = rs[0]; partial[2 * blockIdx.x + 1] = rc[0]; }
+  const double sc[2] = {s, c};
+  block_tree<DIFF_THREADS, 2>(red, threadIdx.x, sc, [](int, double a, double b) { return a + b; });
+  if (threadIdx.x == 0) { partial[2 * blockIdx.x] = red[0]; partial[2 * blockIdx.x + 1] = red[DIFF_THREADS]; }
 }
 
+// one thread, serially over the blocks in ascending order: this order is part of the totals' bits
 __global__ __launch_bounds__(64) void diff_total_kernel(const double* __restrict__ partial, int nblk, double* __restrict__ totals) {
   if (threadIdx.x == 0) {
     double s = 0.0, c = 0.0;

@@ -9,8 +9,8 @@
 //     Min and max are exact and commute, so the bounds do not depend on the grid or on the order the workgroups arrive in;
 //   - a point that is not finite is written as it comes, left out of the bounds and counted.
 // No allocation and no host synchronisation; both entries run on the caller's stream.
-#include "common.h"
 #include "geo_dev.h"
+#include "reduce.h"
 #include "../../include/snerf_hip.h"
 
 #include <stdint.h>
@@ -69,17 +69,8 @@ __device__ __forceinline__ void latlon_to_utm(double lat, double lon, double lon
   *north = nn;
 }
 
-// order-preserving integer key of a double: a < b (as numbers) <=> key(a) < key(b) (as unsigned integers)
-__device__ __forceinline__ unsigned long long order_key(double v) {
-  const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-
 constexpr unsigned long long KEY_MIN_IDENTITY = ~0ull;   // what the host writes into the two minimum words
 constexpr unsigned long long KEY_MAX_IDENTITY = 0ull;    // ... and into the two maximum words
-
-__device__ __forceinline__ unsigned long long umin64(unsigned long long a, unsigned long long b) { return a < b ? a : b; }
-__device__ __forceinline__ unsigned long long umax64(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
 
 // rays != nullptr: step 1 (end points from the rays) first; else the points come in as xyz_n
 __global__ __launch_bounds__(GEO_THREADS) void geo_cloud_kernel(const float* __restrict__ rays, int ray_stride,
@@ -122,23 +113,20 @@ __global__ __launch_bounds__(GEO_THREADS) void geo_cloud_kernel(const float* __r
     }
     if (__builtin_isfinite(east) && __builtin_isfinite(north) && __builtin_isfinite(alt)) {
       const unsigned long long ke = order_key(east), kn = order_key(north);
-      k_emin = umin64(k_emin, ke);
-      k_emax = umax64(k_emax, ke);
-      k_nmin = umin64(k_nmin, kn);
-      k_nmax = umax64(k_nmax, kn);
+      k_emin = OpMin()(k_emin, ke);
+      k_emax = OpMax()(k_emax, ke);
+      k_nmin = OpMin()(k_nmin, kn);
+      k_nmax = OpMax()(k_nmax, kn);
     } else {
       ++bad;
     }
   }
   // wave64 butterflies (every lane takes part: the loop above has ended for the whole wave)
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    k_emin = umin64(k_emin, __shfl_xor(k_emin, o, 64));
-    k_emax = umax64(k_emax, __shfl_xor(k_emax, o, 64));
-    k_nmin = umin64(k_nmin, __shfl_xor(k_nmin, o, 64));
-    k_nmax = umax64(k_nmax, __shfl_xor(k_nmax, o, 64));
-    bad += __shfl_xor(bad, o, 64);
-  }
+  k_emin = wave_reduce(k_emin, OpMin());
+  k_emax = wave_reduce(k_emax, OpMax());
+  k_nmin = wave_reduce(k_nmin, OpMin());
+  k_nmax = wave_reduce(k_nmax, OpMax());
+  bad = wave_reduce(bad, OpSum());
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) {
     red[0][wave] = k_emin;
@@ -151,10 +139,10 @@ __global__ __launch_bounds__(GEO_THREADS) void geo_cloud_kernel(const float* __r
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int w = 1; w < GEO_WAVES; ++w) {
-      k_emin = umin64(k_emin, red[0][w]);
-      k_emax = umax64(k_emax, red[1][w]);
-      k_nmin = umin64(k_nmin, red[2][w]);
-      k_nmax = umax64(k_nmax, red[3][w]);
+      k_emin = OpMin()(k_emin, red[0][w]);
+      k_emax = OpMax()(k_emax, red[1][w]);
+      k_nmin = OpMin()(k_nmin, red[2][w]);
+      k_nmax = OpMax()(k_nmax, red[3][w]);
       bad += red_bad[w];
     }
     // a workgroup without a finite point holds the identities: nothing to fold
@@ -179,9 +167,7 @@ static int geo_launch(const char* who, const float* rays, int ray_stride, const 
   if (params->south != 0 && params->south != 1) { set_error("%s: south = %d", who, params->south); return SNERF_ERR_BAD_DESC; }
   if (n == 0) return SNERF_OK;
   if (!enu_out) { set_error("%s: null pointer", who); return SNERF_ERR_NULL; }
-  long long g = (n + GEO_THREADS - 1) / GEO_THREADS;
-  g = g < GEO_MAX_GRID ? g : GEO_MAX_GRID;
-  hipLaunchKernelGGL(geo_cloud_kernel, dim3((unsigned)g), dim3(GEO_THREADS), 0, (hipStream_t)stream, rays, ray_stride, depth, xyz_n, n,
+  hipLaunchKernelGGL(geo_cloud_kernel, dim3(blocks_for(n, GEO_THREADS, GEO_MAX_GRID)), dim3(GEO_THREADS), 0, (hipStream_t)stream, rays, ray_stride, depth, xyz_n, n,
                      *params, enu_out, lla_out, stats);
   SNERF_LAUNCH_CHECK();
   return SNERF_OK;

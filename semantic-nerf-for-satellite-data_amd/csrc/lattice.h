@@ -1,7 +1,6 @@
 // The DSM lattice (SnerfDsmGrid, include/snerf_hip.h) as csrc/dsm.hip and csrc/ortho.hip share it: which cells a point offers
-// itself to, the 64-bit wave reductions of the per-launch statistics, the launch grid of a grid-stride kernel, and the host-side
-// checks of a grid and of a quantisation (z0, q).  Every splat on this lattice goes through cell_window(); nothing here depends
-// on what a kernel does with the cells.
+// itself to, and the host-side checks of a grid and of a quantisation (z0, q).  Every splat on this lattice goes through
+// cell_window(); nothing here depends on what a kernel does with the cells.
 #pragma once
 #include "common.h"
 #include "../../include/snerf_hip.h"
@@ -9,21 +8,6 @@
 #include <math.h>
 
 namespace snerf {
-
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long w = __shfl_xor(v, o, 64);
-    v = w > v ? w : v;
-  }
-  return v;
-}
 
 // The cells a point offers itself to: the (2r+1)^2 window round its own cell, clipped to the lattice extent and to the output
 // window BEFORE any conversion to an integer (a NaN or infinite coordinate fails the comparisons and offers nothing).
@@ -45,12 +29,6 @@ __device__ __forceinline__ CellWindow cell_window(double x, double y, const Sner
   w.j0 = cj - r > lj ? cj - r : lj;
   w.j1 = cj + r + 1 < hj ? cj + r + 1 : hj;
   return w;
-}
-
-// blocks of a grid-stride launch over n items: ceil(n / threads) in [1, cap]
-static inline unsigned blocks_for(long long n, int threads, unsigned cap) {
-  const long long want = (n + threads - 1) / threads;
-  return (unsigned)(want < 1 ? 1 : (want < (long long)cap ? want : cap));
 }
 
 // the grid of an accumulating entry: res > 0, finite offsets, positive sizes

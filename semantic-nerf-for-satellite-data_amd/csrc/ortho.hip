@@ -4,6 +4,7 @@
 // cell_window() of csrc/lattice.h, which dsm_accumulate_kernel (csrc/dsm.hip) shares.  Integer atomics only: every result is
 // independent of the order in which points arrive.
 #include "lattice.h"
+#include "reduce.h"
 
 #pragma clang fp contract(off)
 
@@ -33,8 +34,8 @@ __global__ __launch_bounds__(ORTHO_THREADS) void ortho_top_kernel(const double* 
       for (long long li = w.i0; li < w.i1; ++li) atomicMax(&top[(lj - g.joff) * g.out_w + (li - g.ioff)], key);
     reached++;
   }
-  bad = wave_sum_u64(bad);
-  reached = wave_sum_u64(reached);
+  bad = wave_reduce(bad, OpSum());
+  reached = wave_reduce(reached, OpSum());
   if ((threadIdx.x & 63) == 0) {
     if (bad) atomicAdd(&stats[0], bad);
     if (reached) atomicAdd(&stats[1], reached);
@@ -92,7 +93,7 @@ __global__ __launch_bounds__(ORTHO_THREADS) void ortho_votes_kernel(const double
     for (long long lj = w.j0; lj < w.j1; ++lj)
       for (long long li = w.i0; li < w.i1; ++li) atomicAdd(&plane[(lj - g.joff) * g.out_w + (li - g.ioff)], 1u);
   }
-  bad = wave_sum_u64(bad);
+  bad = wave_reduce(bad, OpSum());
   if ((threadIdx.x & 63) == 0 && bad) atomicAdd(&stats[0], bad);
 }
 
@@ -114,7 +115,7 @@ __global__ __launch_bounds__(ORTHO_THREADS) void ortho_votes_finish_kernel(const
     share_out[c] = total ? (float)((double)best / (double)total) : __builtin_nanf("");
     tmax = total > tmax ? total : tmax;
   }
-  tmax = wave_max_u64(tmax);
+  tmax = wave_reduce(tmax, OpMax());
   if ((threadIdx.x & 63) == 0 && tmax) atomicMax(&stats[1], tmax);
 }
 

@@ -9,8 +9,8 @@
 //     max are exact and commute, so the result does not depend on the grid;
 //   - normalise: one thread per row, correctly rounded fp32 subtract and divide.
 // No allocation and no host synchronisation; every entry runs on the caller's stream.
-#include "common.h"
 #include "geo_dev.h"
+#include "reduce.h"
 #include "../../include/snerf_hip.h"
 
 #include <stdint.h>
@@ -249,10 +249,15 @@ __global__ __launch_bounds__(RAY_THREADS) void rpc_reproject_kernel(const SnerfR
   err[i] = sqrt(ec * ec + er * er);   // np.linalg.norm(pts2d - reprojected, axis=1)
 }
 
+// the workgroup's three minima (components 0..2, fminf) and three maxima (3..5, fmaxf): results at red[k * BND_THREADS]
+__device__ __forceinline__ void bounds_tree(float* red, int t, const float* v) {
+  block_tree<BND_THREADS, 6>(red, t, v, [](int k, float a, float b) { return k < 3 ? fminf(a, b) : fmaxf(a, b); });
+}
+
 // per-workgroup min (slots 0..2) and max (3..5) over the origins and the far points o + far * d (fp32, two roundings)
 __global__ __launch_bounds__(BND_THREADS) void ray_bounds_partial_kernel(const float* __restrict__ rays, long long n,
                                                                          float* __restrict__ partial) {
-  __shared__ float red[6][BND_THREADS];
+  __shared__ float red[6 * BND_THREADS];
   float v[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
   for (long long i = (long long)blockIdx.x * BND_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * BND_THREADS) {
     const float* r = rays + i * 8;
@@ -266,26 +271,14 @@ __global__ __launch_bounds__(BND_THREADS) void ray_bounds_partial_kernel(const f
     }
   }
   const int t = threadIdx.x;
-#pragma unroll
-  for (int k = 0; k < 6; ++k) red[k][t] = v[k];
-  __syncthreads();
-  for (int s = BND_THREADS / 2; s > 0; s >>= 1) {
-    if (t < s) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        red[k][t] = fminf(red[k][t], red[k][t + s]);
-        red[3 + k][t] = fmaxf(red[3 + k][t], red[3 + k][t + s]);
-      }
-    }
-    __syncthreads();
-  }
-  if (t < 6) partial[(long long)blockIdx.x * 6 + t] = red[t][0];
+  bounds_tree(red, t, v);
+  if (t < 6) partial[(long long)blockIdx.x * 6 + t] = red[t * BND_THREADS];
 }
 
 // folds n_partials slots; out: min[3], max[3], scale[3] = (max - min) / 2, offset[3] = min + scale, range = max(scale)
 __global__ __launch_bounds__(BND_THREADS) void ray_bounds_finish_kernel(const float* __restrict__ partial, int n_partials,
                                                                         float* __restrict__ out) {
-  __shared__ float red[6][BND_THREADS];
+  __shared__ float red[6 * BND_THREADS];
   const int t = threadIdx.x;
   float v[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
   for (int p = t; p < n_partials; p += BND_THREADS) {
@@ -295,23 +288,11 @@ __global__ __launch_bounds__(BND_THREADS) void ray_bounds_finish_kernel(const fl
       v[3 + k] = fmaxf(v[3 + k], partial[6 * p + 3 + k]);
     }
   }
-#pragma unroll
-  for (int k = 0; k < 6; ++k) red[k][t] = v[k];
-  __syncthreads();
-  for (int s = BND_THREADS / 2; s > 0; s >>= 1) {
-    if (t < s) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        red[k][t] = fminf(red[k][t], red[k][t + s]);
-        red[3 + k][t] = fmaxf(red[3 + k][t], red[3 + k][t + s]);
-      }
-    }
-    __syncthreads();
-  }
+  bounds_tree(red, t, v);
   if (t == 0) {
     float range = -INFINITY;
     for (int k = 0; k < 3; ++k) {
-      const float mn = red[k][0], mx = red[3 + k][0];
+      const float mn = red[k * BND_THREADS], mx = red[(3 + k) * BND_THREADS];
       const float scale = __fmul_rn(__fsub_rn(mx, mn), 0.5f);   // numpy float32 (max - min) / 2: the halving is exact
       out[k] = mn;
       out[3 + k] = mx;
@@ -337,6 +318,7 @@ __global__ __launch_bounds__(NRM_THREADS) void normalize_rows_kernel(float* __re
   }
 }
 
+// one item per thread, no grid stride: n <= 2^31 at every caller
 static inline long long blocks_of(long long n, int threads) { return (n + threads - 1) / threads; }
 
 static int check_rpc(const SnerfRpc& r, const char* who, int idx) {
@@ -375,12 +357,11 @@ extern "C" int snerf_rpc_rays(const SnerfRayImage* images_host, const SnerfRayIm
     max_n = im.n_rays > max_n ? im.n_rays : max_n;
   }
   if (sum != n_rows) { set_error("%s: the images hold %lld rays, the output %lld rows", who, sum, n_rows); return SNERF_ERR_BAD_DESC; }
-  long long gx = blocks_of(max_n, RAY_THREADS);
-  gx = gx < RAY_MAX_GRID_X ? gx : RAY_MAX_GRID_X;
-  hipLaunchKernelGGL(rpc_rays_count_kernel, dim3((unsigned)gx, (unsigned)n_images), dim3(RAY_THREADS), 0, (hipStream_t)stream,
+  const unsigned gx = blocks_for(max_n, RAY_THREADS, RAY_MAX_GRID_X);
+  hipLaunchKernelGGL(rpc_rays_count_kernel, dim3(gx, (unsigned)n_images), dim3(RAY_THREADS), 0, (hipStream_t)stream,
                      images_dev, n_images, pixels, counters);
   SNERF_LAUNCH_CHECK();
-  hipLaunchKernelGGL(rpc_rays_kernel, dim3((unsigned)gx, (unsigned)n_images), dim3(RAY_THREADS), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(rpc_rays_kernel, dim3(gx, (unsigned)n_images), dim3(RAY_THREADS), 0, (hipStream_t)stream,
                      images_dev, n_images, pixels, rays, (const int*)counters);
   SNERF_LAUNCH_CHECK();
   return SNERF_OK;
@@ -429,17 +410,12 @@ extern "C" int snerf_rpc_reprojection_error(const SnerfRpc* rpc_host, const Sner
   return SNERF_OK;
 }
 
-static long long bounds_grid(long long n) {
-  const long long g = blocks_of(n, BND_THREADS);
-  return g < BND_MAX_GRID ? g : BND_MAX_GRID;
-}
-
 extern "C" size_t snerf_ray_bounds_workspace_bytes(const long long* n_rows, int n_arrays) {
   if (!n_rows || n_arrays < 1) { set_error("snerf_ray_bounds_workspace_bytes: need at least one array"); return 0; }
   long long slots = 0;
   for (int a = 0; a < n_arrays; ++a) {
     if (n_rows[a] < 1 || n_rows[a] > (long long)1 << 40) { set_error("snerf_ray_bounds_workspace_bytes: array %d has %lld rows", a, n_rows[a]); return 0; }
-    slots += bounds_grid(n_rows[a]);
+    slots += blocks_for(n_rows[a], BND_THREADS, BND_MAX_GRID);
   }
   return (size_t)slots * 6 * sizeof(float);
 }
@@ -453,7 +429,7 @@ extern "C" int snerf_ray_bounds(const float* const* rays, const long long* n_row
   for (int a = 0; a < n_arrays; ++a) {
     if (!rays[a]) { set_error("%s: array %d is null", who, a); return SNERF_ERR_NULL; }
     if (n_rows[a] < 1 || n_rows[a] > (long long)1 << 40) { set_error("%s: array %d has %lld rows", who, a, n_rows[a]); return SNERF_ERR_BAD_DESC; }
-    slots += bounds_grid(n_rows[a]);
+    slots += blocks_for(n_rows[a], BND_THREADS, BND_MAX_GRID);
   }
   if (workspace_bytes < (size_t)slots * 6 * sizeof(float)) {
     set_error("%s: workspace of %zu bytes < %zu", who, workspace_bytes, (size_t)slots * 6 * sizeof(float)); return SNERF_ERR_WORKSPACE; }
@@ -462,8 +438,8 @@ extern "C" int snerf_ray_bounds(const float* const* rays, const long long* n_row
   float* part = (float*)workspace;
   long long at = 0;
   for (int a = 0; a < n_arrays; ++a) {
-    const long long g = bounds_grid(n_rows[a]);
-    hipLaunchKernelGGL(ray_bounds_partial_kernel, dim3((unsigned)g), dim3(BND_THREADS), 0, st, rays[a], n_rows[a], part + at * 6);
+    const unsigned g = blocks_for(n_rows[a], BND_THREADS, BND_MAX_GRID);
+    hipLaunchKernelGGL(ray_bounds_partial_kernel, dim3(g), dim3(BND_THREADS), 0, st, rays[a], n_rows[a], part + at * 6);
     SNERF_LAUNCH_CHECK();
     at += g;
   }

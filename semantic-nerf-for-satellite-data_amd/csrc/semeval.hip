@@ -6,9 +6,9 @@
 //     so the counts are exact and do not depend on arrival order;
 //   - the composited beta of the car rays is summed in fp64 (the fp32 products w * beta are exact in fp64) and written as
 //     one partial per workgroup at a fixed slot; a second launch sums the slots in a fixed order and adds the result into
-//     the accumulator (the ssim.hip pattern; no float atomics), so the sum is bit-reproducible at a fixed chunking.
+//     the accumulator (reduce.h; no float atomics), so the sum is bit-reproducible at a fixed chunking.
 // No host synchronisation, no allocation.
-#include "common.h"
+#include "reduce.h"
 #include "../../include/snerf_hip.h"
 
 #include <stdint.h>
@@ -21,11 +21,6 @@ constexpr int SEM_REDUCE_THREADS = 256;
 constexpr int SEM_NCOUNT = 6;           // LDS counters: errors[0..3], car rays, out-of-range rows
 
 static_assert(SNERF_SEMEVAL_MAX_CLASSES * SNERF_SEMEVAL_MAX_CLASSES <= SEM_THREADS, "one thread per bin in the flush");
-
-static inline long long sem_grid(int n) {
-  const long long tiles = ((long long)n + SEM_THREADS - 1) / SEM_THREADS;
-  return tiles < 1 ? 1 : (tiles < SEM_MAX_GRID ? tiles : SEM_MAX_GRID);
-}
 
 // Tile loop: the label phase reads one ray per thread (pred 8 B, targets 1 or 8 B: coalesced), bins (gt, pred) into the LDS
 // histogram and marks the car rays in LDS.  If any ray of the tile is a car, the beta phase walks the tile's weights and
@@ -98,28 +93,16 @@ __global__ __launch_bounds__(SEM_THREADS) void semeval_kernel(const long long* _
   }
   if (blockIdx.x == 0 && t == 0) atomicAdd(&acc->rays, (unsigned long long)n);
   if (with_beta) {
-    red[t] = bsum;
-    __syncthreads();
-    for (int o = SEM_THREADS / 2; o > 0; o >>= 1) {
-      if (t < o) red[t] += red[t + o];
-      __syncthreads();
-    }
+    block_tree<SEM_THREADS>(red, t, bsum, OpSum());
     if (t == 0) partial[blockIdx.x] = red[0];
   }
 }
 
-// one workgroup: the grid's partials strided over the threads, a fixed tree, then added into the accumulator
+// one workgroup: the sum of the grid's partials in the order of reduce.h, added into the accumulator
 __global__ __launch_bounds__(SEM_REDUCE_THREADS) void semeval_reduce_kernel(const double* __restrict__ partial, int count,
                                                                             SnerfSemevalAcc* __restrict__ acc) {
   __shared__ double red[SEM_REDUCE_THREADS];
-  double a = 0.0;
-  for (int k = threadIdx.x; k < count; k += SEM_REDUCE_THREADS) a += partial[k];
-  red[threadIdx.x] = a;
-  __syncthreads();
-  for (int o = SEM_REDUCE_THREADS / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
+  block_strided_sum<SEM_REDUCE_THREADS>(red, threadIdx.x, partial, count, 1);
   if (threadIdx.x == 0) acc->beta_car_sum += red[0];
 }
 
@@ -129,7 +112,7 @@ using namespace snerf;
 
 extern "C" size_t snerf_semeval_workspace_bytes(int n_rays, int n_samples) {
   if (n_rays < 0 || n_samples < 1) { set_error("snerf_semeval_workspace_bytes: n_rays must be >= 0 and n_samples >= 1"); return 0; }
-  return (size_t)sem_grid(n_rays) * sizeof(double);
+  return (size_t)blocks_for(n_rays, SEM_THREADS, SEM_MAX_GRID) * sizeof(double);
 }
 
 extern "C" int snerf_semeval_accumulate(const long long* pred, const void* gt, const void* gt_no_cars, const void* gt_non_corrupted,
@@ -148,7 +131,7 @@ extern "C" int snerf_semeval_accumulate(const long long* pred, const void* gt, c
     set_error("snerf_semeval_accumulate: weights and beta are given together or not at all"); return SNERF_ERR_NULL; }
   const bool with_beta = weights != nullptr;
   if (with_beta && n_samples < 1) { set_error("snerf_semeval_accumulate: n_samples = %d < 1", n_samples); return SNERF_ERR_BAD_DESC; }
-  const long long grid = sem_grid(n);
+  const unsigned grid = blocks_for(n, SEM_THREADS, SEM_MAX_GRID);
   if (with_beta) {
     if (!workspace) { set_error("snerf_semeval_accumulate: null workspace"); return SNERF_ERR_NULL; }
     if (workspace_bytes < (size_t)grid * sizeof(double)) {
@@ -160,11 +143,11 @@ extern "C" int snerf_semeval_accumulate(const long long* pred, const void* gt, c
   double* part = (double*)workspace;
   const int S = with_beta ? n_samples : 1;
   if (label_dtype == SNERF_SEMEVAL_U8) {
-    hipLaunchKernelGGL(semeval_kernel<uint8_t>, dim3((unsigned)grid), dim3(SEM_THREADS), 0, st, pred, (const uint8_t*)gt,
+    hipLaunchKernelGGL(semeval_kernel<uint8_t>, dim3(grid), dim3(SEM_THREADS), 0, st, pred, (const uint8_t*)gt,
                        (const uint8_t*)gt_no_cars, (const uint8_t*)gt_non_corrupted, n, n_classes, car_idx, weights, beta, S,
                        acc, part);
   } else {
-    hipLaunchKernelGGL(semeval_kernel<long long>, dim3((unsigned)grid), dim3(SEM_THREADS), 0, st, pred, (const long long*)gt,
+    hipLaunchKernelGGL(semeval_kernel<long long>, dim3(grid), dim3(SEM_THREADS), 0, st, pred, (const long long*)gt,
                        (const long long*)gt_no_cars, (const long long*)gt_non_corrupted, n, n_classes, car_idx, weights,
                        beta, S, acc, part);
   }

@@ -3,7 +3,7 @@
 // snerf_amd/eval/utils/metrics.py.  Two launches, no atomics: the tile kernel writes one fp64 partial sum per workgroup at a
 // fixed slot, and the reduce kernel sums each image's slots in a fixed order, so every result is bit-reproducible run to run
 // and an image's value does not depend on the other images of the batch.
-#include "common.h"
+#include "reduce.h"
 #include "../../include/snerf_hip.h"
 
 #include <math.h>
@@ -83,28 +83,15 @@ __global__ __launch_bounds__(SSIM_THREADS) void ssim_tile_kernel(const float* __
     val = num / (den + eps);
     if (map) map[plane * h * (long long)w + (long long)oy * w + ox] = (float)val;
   }
-  red[threadIdx.x] = val;
-  __syncthreads();
-  for (int o = SSIM_THREADS / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
+  block_tree<SSIM_THREADS>(red, threadIdx.x, val, OpSum());
   if (threadIdx.x == 0) partial[blk] = red[0];
 }
 
-// one workgroup per image: its per_image partials (c planes x tiles, contiguous) strided over the threads, then a fixed tree
+// one workgroup per image: the sum of its per_image partials (c planes x tiles, contiguous) in the order of reduce.h
 __global__ __launch_bounds__(SSIM_REDUCE_THREADS) void ssim_reduce_kernel(const double* __restrict__ partial, long long per_image,
                                                                           double* __restrict__ sums) {
   __shared__ double red[SSIM_REDUCE_THREADS];
-  const double* p = partial + (long long)blockIdx.x * per_image;
-  double a = 0.0;
-  for (long long k = threadIdx.x; k < per_image; k += SSIM_REDUCE_THREADS) a += p[k];
-  red[threadIdx.x] = a;
-  __syncthreads();
-  for (int o = SSIM_REDUCE_THREADS / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
+  block_strided_sum<SSIM_REDUCE_THREADS>(red, threadIdx.x, partial + (long long)blockIdx.x * per_image, per_image, 1);
   if (threadIdx.x == 0) sums[blockIdx.x] = red[0];
 }
 

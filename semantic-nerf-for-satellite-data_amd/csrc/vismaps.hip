@@ -11,7 +11,7 @@
 //   vis_minmax_kernel: the same bounds of a plane that was not made by the fold (the fp64 altitude plane).
 //   vis_colormap_kernel: nan_to_num, normalise by the bounds, * 255, truncate, look up a (256, 3) table held in LDS.
 // No float atomics, no allocation, no synchronisation; everything on the caller's stream.
-#include "common.h"
+#include "reduce.h"
 #include "../../include/snerf_hip.h"
 
 #include <float.h>
@@ -29,15 +29,8 @@ constexpr int VIS_FOLD_SLOTS = 6;                    // depth, sun, beta, beta_s
 
 static_assert(SNERF_VIS_SLOT_SEM_ERROR + 1 == VIS_FOLD_SLOTS && VIS_FOLD_SLOTS <= SNERF_VIS_SLOTS, "slot numbering");
 
-// order-preserving key of a double that is not NaN: a larger value has a larger key, and no value has key 0
-__device__ __forceinline__ unsigned long long vis_key(double v) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(v + 0.0);     // -0.0 -> +0.0
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double vis_unkey(unsigned long long k) {
-  const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-  return __longlong_as_double((long long)b);
-}
+// the order-preserving key (reduce.h) of a double that is not NaN, with -0.0 -> +0.0
+__device__ __forceinline__ unsigned long long vis_key(double v) { return order_key(v + 0.0); }
 // numpy.nan_to_num in the plane's own precision
 __device__ __forceinline__ float vis_n2n(float x) {
   if (x != x) return 0.0f;
@@ -59,17 +52,11 @@ __device__ __forceinline__ unsigned char vis_u8(double v) {
   return (unsigned char)((int)c & 255);
 }
 
-__device__ __forceinline__ double vis_butterfly(double a) {
-#pragma unroll
-  for (int o = VIS_WAVE / 2; o > 0; o >>= 1) a += __shfl_xor(a, o, VIS_WAVE);
-  return a;
-}
-
 // sum_s fl32(w_s f_s) of a one-band row: lane l takes samples l, l + 64, ... in ascending order
 __device__ __forceinline__ double vis_sum1(const float* __restrict__ f, const float* wl, int S, int lane) {
   double a = 0.0;
   for (int s = lane; s < S; s += VIS_WAVE) a += (double)__fmul_rn(wl[s], f[s]);
-  return vis_butterfly(a);
+  return wave_reduce(a, OpSum());
 }
 
 // the three band sums of a (S, 3) row read flat: lane l takes floats l, l + 64, ... ; float e is sample e / 3, band e % 3
@@ -84,9 +71,9 @@ __device__ __forceinline__ void vis_sum3(const float* __restrict__ f, const floa
     s += 21;
     if (++c == 3) { c = 0; ++s; }
   }
-  out[0] = vis_butterfly(a0);
-  out[1] = vis_butterfly(a1);
-  out[2] = vis_butterfly(a2);
+  out[0] = wave_reduce(a0, OpSum());
+  out[1] = wave_reduce(a1, OpSum());
+  out[2] = wave_reduce(a2, OpSum());
 }
 
 struct VisBounds {
@@ -207,27 +194,19 @@ __global__ __launch_bounds__(VIS_THREADS) void vis_fold_kernel(SnerfVisIn in, Sn
 template <typename T>
 __global__ __launch_bounds__(VIS_EW_THREADS) void vis_minmax_kernel(const T* __restrict__ x, long long n, int slot,
                                                                     SnerfVisStats* __restrict__ stats) {
-  __shared__ double red[2][VIS_EW_THREADS];
+  __shared__ double red[2 * VIS_EW_THREADS];           // the minima, then the maxima
   double lo = DBL_MAX, hi = -DBL_MAX;
   for (long long i = (long long)blockIdx.x * VIS_EW_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * VIS_EW_THREADS) {
     const double v = (double)vis_n2n(x[i]);
     lo = v < lo ? v : lo;
     hi = v > hi ? v : hi;
   }
-  const int t = threadIdx.x;
-  red[0][t] = lo;
-  red[1][t] = hi;
-  __syncthreads();
-  for (int o = VIS_EW_THREADS / 2; o > 0; o >>= 1) {
-    if (t < o) {
-      red[0][t] = red[0][t + o] < red[0][t] ? red[0][t + o] : red[0][t];
-      red[1][t] = red[1][t + o] > red[1][t] ? red[1][t + o] : red[1][t];
-    }
-    __syncthreads();
-  }
-  if (t == 0 && red[0][0] <= red[1][0]) {
-    atomicMax(&stats->minmax[slot][0], ~vis_key(red[0][0]));
-    atomicMax(&stats->minmax[slot][1], vis_key(red[1][0]));
+  const double lh[2] = {lo, hi};
+  block_tree<VIS_EW_THREADS, 2>(red, threadIdx.x, lh,
+                                [](int k, double a, double b) { return k == 0 ? OpMin()(a, b) : OpMax()(a, b); });
+  if (threadIdx.x == 0 && red[0] <= red[VIS_EW_THREADS]) {
+    atomicMax(&stats->minmax[slot][0], ~vis_key(red[0]));
+    atomicMax(&stats->minmax[slot][1], vis_key(red[VIS_EW_THREADS]));
   }
 }
 
@@ -249,7 +228,7 @@ __global__ __launch_bounds__(VIS_EW_THREADS) void vis_colormap_kernel(const T* _
   if (slot >= 0) {
     const unsigned long long klo = stats->minmax[slot][0], khi = stats->minmax[slot][1];
     // an untouched slot (no element was folded): bounds 0, 0
-    const T a = klo ? (T)vis_unkey(~klo) : (T)0, b = khi ? (T)vis_unkey(khi) : (T)0;
+    const T a = klo ? (T)order_unkey(~klo) : (T)0, b = khi ? (T)order_unkey(khi) : (T)0;
     mi = a;
     den = (T)(b - a) + (T)1e-8;
   } else {
@@ -264,11 +243,6 @@ __global__ __launch_bounds__(VIS_EW_THREADS) void vis_colormap_kernel(const T* _
     out[n + i] = tab[idx * 3 + 1];
     out[2 * n + i] = tab[idx * 3 + 2];
   }
-}
-
-static inline unsigned ew_grid(long long n) {
-  const long long g = (n + VIS_EW_THREADS - 1) / VIS_EW_THREADS;
-  return (unsigned)(g < 1 ? 1 : (g < VIS_EW_MAX_GRID ? g : VIS_EW_MAX_GRID));
 }
 
 }  // namespace snerf
@@ -298,8 +272,7 @@ extern "C" int snerf_vis_fold(const SnerfVisIn* in, const SnerfVisOut* out, int 
       (out->sem_error && !in->semantic_gt)) {
     set_error("snerf_vis_fold: an output plane is given without the input it is made from"); return SNERF_ERR_NULL; }
   if (m == 0) return SNERF_OK;
-  const long long blocks = ((long long)m + VIS_WAVES - 1) / VIS_WAVES;
-  const unsigned grid = (unsigned)(blocks < VIS_MAX_GRID ? blocks : VIS_MAX_GRID);
+  const unsigned grid = blocks_for(m, VIS_WAVES, VIS_MAX_GRID);      // one wave per ray
   hipStream_t st = (hipStream_t)stream;
   const int S = in->weights ? n_samples : 1;
   if (in->semantic_gt && in->gt_dtype == SNERF_VIS_I64)
@@ -324,9 +297,9 @@ extern "C" int snerf_vis_minmax(const void* plane, int plane_dtype, long long n,
   if (n == 0) return SNERF_OK;
   hipStream_t st = (hipStream_t)stream;
   if (plane_dtype == SNERF_VIS_F32)
-    hipLaunchKernelGGL(vis_minmax_kernel<float>, dim3(ew_grid(n)), dim3(VIS_EW_THREADS), 0, st, (const float*)plane, n, slot, stats);
+    hipLaunchKernelGGL(vis_minmax_kernel<float>, dim3(blocks_for(n, VIS_EW_THREADS, VIS_EW_MAX_GRID)), dim3(VIS_EW_THREADS), 0, st, (const float*)plane, n, slot, stats);
   else
-    hipLaunchKernelGGL(vis_minmax_kernel<double>, dim3(ew_grid(n)), dim3(VIS_EW_THREADS), 0, st, (const double*)plane, n, slot, stats);
+    hipLaunchKernelGGL(vis_minmax_kernel<double>, dim3(blocks_for(n, VIS_EW_THREADS, VIS_EW_MAX_GRID)), dim3(VIS_EW_THREADS), 0, st, (const double*)plane, n, slot, stats);
   SNERF_LAUNCH_CHECK();
   return SNERF_OK;
 }
@@ -341,10 +314,10 @@ extern "C" int snerf_vis_colormap(const void* plane, int plane_dtype, long long 
   if (n == 0) return SNERF_OK;
   hipStream_t st = (hipStream_t)stream;
   if (plane_dtype == SNERF_VIS_F32)
-    hipLaunchKernelGGL(vis_colormap_kernel<float>, dim3(ew_grid(n)), dim3(VIS_EW_THREADS), 0, st, (const float*)plane, n, stats,
+    hipLaunchKernelGGL(vis_colormap_kernel<float>, dim3(blocks_for(n, VIS_EW_THREADS, VIS_EW_MAX_GRID)), dim3(VIS_EW_THREADS), 0, st, (const float*)plane, n, stats,
                        slot, lo, hi, table, out);
   else
-    hipLaunchKernelGGL(vis_colormap_kernel<double>, dim3(ew_grid(n)), dim3(VIS_EW_THREADS), 0, st, (const double*)plane, n, stats,
+    hipLaunchKernelGGL(vis_colormap_kernel<double>, dim3(blocks_for(n, VIS_EW_THREADS, VIS_EW_MAX_GRID)), dim3(VIS_EW_THREADS), 0, st, (const double*)plane, n, stats,
                        slot, lo, hi, table, out);
   SNERF_LAUNCH_CHECK();
   return SNERF_OK;

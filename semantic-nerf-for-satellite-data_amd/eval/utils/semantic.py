@@ -193,14 +193,13 @@ def _slice(t, lo, hi):
 @torch.no_grad()
 def lean_semantic_eval(cfgs, renderer, models, rays, extras, semantic, semantic_no_cars=None, semantic_non_corrupted=None,
                        car_cls_idx=None, n_classes=None, render_options={}, acc=None):
-    """Render the frame `rays` chunk by chunk (render_chunk_size, as lean_inference: the same per-chunk jitter from the same
+    """Render the frame `rays` chunk by chunk (util.render_chunks, as lean_inference: the same per-chunk jitter from the same
     RNG state, hence the same labels) and fold every chunk's labels, weights and beta into `acc` (a new
     SemanticEvalAccumulator over n_classes, default the model's class count, if None).  The chunk-sized result buffers are
     allocated once; no (N, S) tensor of the frame exists.  Returns the accumulator (nothing is read back)."""
     from ... import ops
-    from .util import _chunk_options
-    model = models["coarse"]
-    Cn = model.spec.n_classes
+    from .util import render_chunks, result_buffers
+    Cn = models["coarse"].spec.n_classes
     if Cn == 0:
         raise ValueError("the model has no semantic head (n_classes = 0)")
     n = rays.shape[0]
@@ -211,22 +210,11 @@ def lean_semantic_eval(cfgs, renderer, models, rays, extras, semantic, semantic_
         if t is not None and t.shape[0] != n:
             raise ValueError(f"{what} has {t.shape[0]} rows for {n} rays")
     ops.release_workspaces()
-    chunk = cfgs.pipeline.render_chunk_size
-    S = cfgs.pipeline.n_samples
-    m = min(chunk, n)
-    bufs = {"semantic_label_coarse": torch.empty((m,), dtype=torch.int64, device=rays.device),
-            "weights_coarse": torch.empty((m, S), dtype=torch.float32, device=rays.device),
-            "beta_coarse": torch.empty((m, S, 1), dtype=torch.float32, device=rays.device)}
-    packed = ops.pack_params(model.spec, dict(model.named_parameters()))
-    ws = None
-    for i in range(0, n, chunk):
-        k = min(chunk, n - i)
-        sl = {key: v[:k] for key, v in bufs.items()}
-        opts = _chunk_options(render_options, i, chunk, n)
-        opts["packed_params"], opts["workspace"] = packed, ws
-        ws = renderer.render_rays_into(models, rays[i:i + chunk], extras[i:i + chunk] if extras is not None else None, sl, opts)
-        acc.add(sl["semantic_label_coarse"], semantic[i:i + k], _slice(semantic_no_cars, i, i + k),
-                _slice(semantic_non_corrupted, i, i + k), weights=sl["weights_coarse"], beta=sl["beta_coarse"])
+    bufs = result_buffers(("semantic_label", "weights", "beta"), min(cfgs.pipeline.render_chunk_size, n), cfgs.pipeline.n_samples,
+                          Cn, rays.device)
+    for i, k, v in render_chunks(cfgs, renderer, models, rays, extras, bufs, render_options):
+        acc.add(v["semantic_label_coarse"], semantic[i:i + k], _slice(semantic_no_cars, i, i + k),
+                _slice(semantic_non_corrupted, i, i + k), weights=v["weights_coarse"], beta=v["beta_coarse"])
     return acc
 
 
@@ -237,7 +225,7 @@ def sharded_lean_semantic_eval(cfgs, renderer, models, rays, extras, semantic, s
     into its own accumulator, then allreduce_() gives every rank the frame's statistics (counts bit-equal to one process;
     the beta sum differs from it only by the grouping of its fp64 partials).  Per-ray jitter given for the whole frame is
     sliced with the rays; drawn jitter is each rank's own."""
-    from .util import _chunk_options
+    from .util import shard_options
     n = rays.shape[0]
     Cn = models["coarse"].spec.n_classes
     if Cn == 0:
@@ -245,10 +233,9 @@ def sharded_lean_semantic_eval(cfgs, renderer, models, rays, extras, semantic, s
     acc = SemanticEvalAccumulator(Cn if n_classes is None else n_classes, car_cls_idx, rays.device)
     lo, hi = parallel.frame_shard(n)
     if hi > lo:
-        opts = _chunk_options(render_options, lo, hi - lo, n) if n > hi - lo else render_options
         lean_semantic_eval(cfgs, renderer, models, rays[lo:hi], extras[lo:hi] if extras is not None else None,
                            semantic[lo:hi], _slice(semantic_no_cars, lo, hi), _slice(semantic_non_corrupted, lo, hi),
-                           render_options=opts, acc=acc)
+                           render_options=shard_options(render_options, lo, hi, n), acc=acc)
     else:    # more ranks than rays: nothing to add, but the optional terms must match the other ranks'
         acc.has.update(semantic_no_cars=semantic_no_cars is not None,
                        semantic_non_corrupted=semantic_non_corrupted is not None, beta=True)

@@ -42,6 +42,50 @@ _KEY_SHAPES = {  # per-ray trailing shape of the render_rays results (S = n_samp
 }
 
 
+def _bare(key):
+    return key[:-len("_coarse")] if key.endswith("_coarse") else key
+
+
+def result_buffers(keys, rows, S, n_classes, device) -> dict:
+    """uninitialised render_rays_into result tensors of `rows` rays for the results `keys` (with or without the `_coarse`
+    postfix), under their `_coarse` names"""
+    return {_bare(k) + "_coarse": torch.empty((rows,) + _KEY_SHAPES[_bare(k)](S, n_classes),
+                                              dtype=torch.int64 if _bare(k) == "semantic_label" else torch.float32, device=device)
+            for k in keys}
+
+
+def shard_options(render_options, lo, hi, n):
+    """render options of the rays [lo, hi) of an n-ray frame: per-ray tensors given for the whole frame are sliced"""
+    return _chunk_options(render_options, lo, hi - lo, n) if n > hi - lo else render_options
+
+
+def render_chunks(cfgs, renderer, models, rays, extras, buffers, render_options, frame_sized=False, show_tqdm=False):
+    """The chunk loop of the lean evaluators: renders `rays` render_chunk_size rays at a time into `buffers` (result_buffers)
+    with render_rays_into, the weights packed once and the inference workspace carried from chunk to chunk, and yields
+    (i, k, views) after the chunk of k rays starting at ray i: views = buffers[key][i:i + k] of frame-sized buffers,
+    buffers[key][:k] of chunk-sized ones.  The order of the render calls, and with it the jitter drawn from torch's generator,
+    is the chunks' order.  A caller allocates its buffers after ops.release_workspaces(): full-frame inference has its own
+    memory profile, and the idle TRAINING workspaces (8-20 GB each, held outside torch's allocator by the lease pool) go back
+    to torch first, so that the frame's tensors and the inference workspace can use that memory."""
+    from ... import ops
+    chunk = cfgs.pipeline.render_chunk_size
+    n = rays.shape[0]
+    model = models["coarse"]
+    packed = ops.pack_params(model.spec, dict(model.named_parameters()))
+    ws = None
+    steps = range(0, n, chunk)
+    if show_tqdm:
+        from tqdm import tqdm
+        steps = tqdm(steps)
+    for i in steps:
+        k = min(chunk, n - i)
+        views = {key: v[i:i + k] if frame_sized else v[:k] for key, v in buffers.items()}
+        opts = _chunk_options(render_options, i, chunk, n)
+        opts["packed_params"], opts["workspace"] = packed, ws
+        ws = renderer.render_rays_into(models, rays[i:i + chunk], extras[i:i + chunk] if extras is not None else None, views, opts)
+        yield i, k, views
+
+
 @torch.no_grad()
 def lean_inference(cfgs, renderer, models, rays, extras, keys=("rgb_coarse", "depth_coarse", "semantic_label_coarse"),
                    render_options={}, show_tqdm=False):
@@ -51,33 +95,13 @@ def lean_inference(cfgs, renderer, models, rays, extras, keys=("rgb_coarse", "de
     tensors unless asked for), the solar-correction pass is skipped unless one of its results is requested, and the
     weights are packed once for all chunks."""
     from ... import ops
-    # full-frame inference has its own memory profile: the idle TRAINING workspaces (8-20 GB each, held outside torch's allocator
-    # by the lease pool) go back to torch first, so a frame's result tensors and inference workspace can use that memory
-    ops.release_workspaces()
-    chunk = cfgs.pipeline.render_chunk_size
-    n = rays.shape[0]
-    S = cfgs.pipeline.n_samples
-    model = models["coarse"]
-    Cn = model.spec.n_classes
-    out = {}
     for k in keys:
-        bare = k[:-len("_coarse")] if k.endswith("_coarse") else k
-        if bare not in _KEY_SHAPES:
+        if _bare(k) not in _KEY_SHAPES:
             raise KeyError(f"lean_inference: unknown result '{k}'")
-        dt = torch.int64 if bare == "semantic_label" else torch.float32
-        out[bare + "_coarse"] = torch.empty((n,) + _KEY_SHAPES[bare](S, Cn), dtype=dt, device=rays.device)
-    packed = ops.pack_params(model.spec, dict(model.named_parameters()))
-    ws = None
-    steps = range(0, n, chunk)
-    if show_tqdm:
-        from tqdm import tqdm
-        steps = tqdm(steps)
-    for i in steps:
-        sl = {k: v[i:i + chunk] for k, v in out.items()}
-        opts = _chunk_options(render_options, i, chunk, n)
-        opts["packed_params"], opts["workspace"] = packed, ws
-        ws = renderer.render_rays_into(models, rays[i:i + chunk], extras[i:i + chunk] if extras is not None else None,
-                                       sl, opts)
+    ops.release_workspaces()
+    out = result_buffers(keys, rays.shape[0], cfgs.pipeline.n_samples, models["coarse"].spec.n_classes, rays.device)
+    for _ in render_chunks(cfgs, renderer, models, rays, extras, out, render_options, frame_sized=True, show_tqdm=show_tqdm):
+        pass
     return out
 
 
@@ -94,8 +118,7 @@ def shard_and_gather(render_rows, n: int, rank: int = None, world: int = None) -
     local = render_rows(lo, hi)
     out = {"_rows": (lo, hi)}
     for k, v in local.items():
-        bare = k[:-len("_coarse")] if k.endswith("_coarse") else k
-        out[k] = parallel.allgather_rows(v, n) if bare in PER_RAY_RESULTS else v
+        out[k] = parallel.allgather_rows(v, n) if _bare(k) in PER_RAY_RESULTS else v
     return out
 
 
@@ -111,14 +134,7 @@ def sharded_lean_inference(cfgs, renderer, models, rays, extras, keys=("rgb_coar
 
     def rows(lo, hi):
         if hi == lo:      # more ranks than rays: contribute nothing (a zero-ray launch has no defined result)
-            S, Cn = cfgs.pipeline.n_samples, models["coarse"].spec.n_classes
-            out = {}
-            for k in keys:
-                bare = k[:-len("_coarse")] if k.endswith("_coarse") else k
-                dt = torch.int64 if bare == "semantic_label" else torch.float32
-                out[bare + "_coarse"] = torch.empty((0,) + _KEY_SHAPES[bare](S, Cn), dtype=dt, device=rays.device)
-            return out
-        opts = _chunk_options(render_options, lo, hi - lo, n) if n > hi - lo else render_options
+            return result_buffers(keys, 0, cfgs.pipeline.n_samples, models["coarse"].spec.n_classes, rays.device)
         return lean_inference(cfgs, renderer, models, rays[lo:hi], extras[lo:hi] if extras is not None else None, keys=keys,
-                              render_options=opts, show_tqdm=show_tqdm)
+                              render_options=shard_options(render_options, lo, hi, n), show_tqdm=show_tqdm)
     return shard_and_gather(rows, n)

@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from ... import _lib, parallel
+from ...framework.components.coordinate_systems import key_to_double
 
 # product -> (render results it needs, per-ray inputs it needs)
 PRODUCTS = {
@@ -40,18 +41,13 @@ def new_stats(device) -> torch.Tensor:
     return torch.zeros(_NWORDS, dtype=torch.int64, device=device)
 
 
-def _unkey(k: int) -> float:
-    b = (k & (2 ** 63 - 1)) if k >> 63 else (~k) & (2 ** 64 - 1)
-    return float(np.array([b], np.uint64).view(np.float64)[0])
-
-
 def decode_stats(words) -> dict:
     """host copy of the stats words -> {"bounds": {slot name: (min, max) or None}, "bad_labels": int}"""
     w = np.asarray(words).astype(np.int64).view(np.uint64)
     out = {}
     for name, s in SLOT.items():
         lo, hi = int(w[2 * s]), int(w[2 * s + 1])
-        out[name] = (_unkey((~lo) & (2 ** 64 - 1)), _unkey(hi)) if lo and hi else None
+        out[name] = (key_to_double((~lo) & (2 ** 64 - 1)), key_to_double(hi)) if lo and hi else None
     return {"bounds": out, "bad_labels": int(w[_BAD])}
 
 
@@ -179,13 +175,13 @@ def _needs(products, model, rgbs, semantic, palette):
 @torch.no_grad()
 def lean_frame_maps(cfgs, renderer, models, rays, extras, rgbs=None, semantic=None, palette=None, products=BASELINE_PRODUCTS,
                     render_options={}):
-    """Render the frame `rays` chunk by chunk exactly as lean_semantic_eval does (render_chunk_size, the same per-chunk jitter
-    from the same RNG state, chunk-sized result buffers allocated once, render_rays_into, weights packed once) and fold every
-    chunk into the frame's planes of the requested `products` (PRODUCTS).  Only the per-sample results a requested product
-    needs are rendered; no (N, S) tensor of the frame exists.  rgbs (n, 3) fp32, semantic (n,) / (n, 1) uint8 or int64 and
-    palette (K, 3) uint8 are needed by the products that read them.  Returns a FrameMaps; nothing is read back."""
+    """Render the frame `rays` chunk by chunk (util.render_chunks, as lean_semantic_eval: the same per-chunk jitter from the same
+    RNG state, chunk-sized result buffers allocated once) and fold every chunk into the frame's planes of the requested
+    `products` (PRODUCTS).  Only the per-sample results a requested product needs are rendered; no (N, S) tensor of the frame
+    exists.  rgbs (n, 3) fp32, semantic (n,) / (n, 1) uint8 or int64 and palette (K, 3) uint8 are needed by the products that
+    read them.  Returns a FrameMaps; nothing is read back."""
     from ... import ops
-    from .util import _KEY_SHAPES, _chunk_options
+    from .util import render_chunks, result_buffers
     model = models["coarse"]
     products = tuple(products)
     keys = _needs(products, model, rgbs, semantic, palette)
@@ -197,10 +193,7 @@ def lean_frame_maps(cfgs, renderer, models, rays, extras, rgbs=None, semantic=No
     if semantic is not None and semantic.dtype not in (torch.uint8, torch.int64):
         raise ValueError(f"semantic must be uint8 or int64, not {semantic.dtype}")
     ops.release_workspaces()
-    chunk = cfgs.pipeline.render_chunk_size
-    m = min(chunk, n)
-    bufs = {k + "_coarse": torch.empty((m,) + _KEY_SHAPES[k](S, Cn), dtype=torch.int64 if k == "semantic_label" else torch.float32,
-                                       device=dev) for k in keys}
+    bufs = result_buffers(keys, min(cfgs.pipeline.render_chunk_size, n), S, Cn, dev)
     planes = {}
     for p in products:
         if p == "rgb":
@@ -214,14 +207,7 @@ def lean_frame_maps(cfgs, renderer, models, rays, extras, rgbs=None, semantic=No
     pal = palette.to(dev).contiguous() if palette is not None and want("sem_color", "sem_shaded") else None
     sem = semantic.reshape(-1) if semantic is not None and want("sem_error") else None
     gt_rgb = rgbs if want("rgb_diff", "rgb_diff_distance") else None
-    packed = ops.pack_params(model.spec, dict(model.named_parameters()))
-    ws = None
-    for i in range(0, n, chunk):
-        k = min(chunk, n - i)
-        sl = {key: v[:k] for key, v in bufs.items()}
-        opts = _chunk_options(render_options, i, chunk, n)
-        opts["packed_params"], opts["workspace"] = packed, ws
-        ws = renderer.render_rays_into(models, rays[i:i + chunk], extras[i:i + chunk] if extras is not None else None, sl, opts)
+    for i, k, sl in render_chunks(cfgs, renderer, models, rays, extras, bufs, render_options):
         g = lambda key: sl.get(key + "_coarse")                  # noqa: E731
         if "rgb" in planes:
             planes["rgb"][i:i + k].copy_(g("rgb"))
@@ -256,15 +242,15 @@ def sharded_lean_frame_maps(cfgs, renderer, models, rays, extras, rgbs=None, sem
     """lean_frame_maps with the frame's rays sharded over the process group, as sharded_lean_inference: every rank folds rows
     frame_shard(n), the planes are all-gathered (one all_gather per plane) and the stats combined by allreduce_stats_, so every
     rank holds the frame's planes and bounds -- bit-equal to one process (a ray's values do not depend on its chunk)."""
-    from .util import _chunk_options
+    from .util import shard_options
     n, dev = rays.shape[0], rays.device
     products = tuple(products)
     _needs(products, models["coarse"], rgbs, semantic, palette)
     lo, hi = parallel.frame_shard(n)
     cut = lambda t: t[lo:hi] if t is not None else None         # noqa: E731
     if hi > lo:
-        opts = _chunk_options(render_options, lo, hi - lo, n) if n > hi - lo else render_options
-        local = lean_frame_maps(cfgs, renderer, models, rays[lo:hi], cut(extras), cut(rgbs), cut(semantic), palette, products, opts)
+        local = lean_frame_maps(cfgs, renderer, models, rays[lo:hi], cut(extras), cut(rgbs), cut(semantic), palette, products,
+                                shard_options(render_options, lo, hi, n))
         planes, stats = local.planes, local.stats
     else:        # more ranks than rays
         planes, stats = {}, new_stats(dev)

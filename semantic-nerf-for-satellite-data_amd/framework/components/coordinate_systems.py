@@ -32,8 +32,8 @@ def init_coordinate_system(cfgs) -> str:
     return CUSTOM_ECEF
 
 
-def _key_to_double(key: int) -> float:
-    """inverse of the kernel's order-preserving key (include/snerf_hip.h)"""
+def key_to_double(key: int) -> float:
+    """inverse of the kernels' order-preserving key of a double (csrc/reduce.h order_key)"""
     bits = key ^ (1 << 63) if key >> 63 else ~key & (2 ** 64 - 1)
     return struct.unpack("<d", struct.pack("<Q", bits))[0]
 
@@ -44,7 +44,7 @@ def decode_geo_stats(words):
     inf = float("inf")
     if u[0] == _lib.GEO_STATS_INIT[0]:
         return GeoBounds(inf, -inf, inf, -inf), u[4]
-    return GeoBounds(*(_key_to_double(k) for k in u[:4])), u[4]
+    return GeoBounds(*(key_to_double(k) for k in u[:4])), u[4]
 
 
 class GeoFrame:

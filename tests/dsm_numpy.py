@@ -6,6 +6,8 @@ import math
 
 import numpy as np
 
+from tests import reduce_numpy as RN
+
 
 def bounds_grid(cloud, resolution=0.5):
     x, y = cloud[:, 0], cloud[:, 1]
@@ -127,3 +129,18 @@ def compute_mae(pred, gt, mask=None, init=(0, 0)):
     a = np.abs(diff[np.isfinite(diff)]).astype(np.float64)
     return {"dx": dx, "dy": dy, "trace": trace, "muu": muu, "muv": muv, "b": b, "rdsm": rdsm, "diff": diff,
             "mean": float(a.mean()), "median": float(np.median(a))}
+
+
+def shift_diff_totals(pred, gt, dx, dy, b, threads=256, max_blocks=1024):
+    """(sum |diff|, finite count) of snerf_dsm_shift_diff, bit for bit (csrc/dsm.hip shift_diff_kernel, diff_total_kernel):
+    rv = f32(f64(pred[j + dy, i + dx]) + b), d = rv - g in fp32 with g = 0 where gt < -500; every thread adds |f64(d)| and 1 of
+    its finite cells in ascending grid-stride order, the tree sums a workgroup, one thread sums the workgroups serially"""
+    pred, gt = np.asarray(pred, np.float32), np.asarray(gt, np.float32)
+    rv = (_shifted(pred.astype(np.float64), dx, dy) + np.float64(b)).astype(np.float32)
+    d = rv - np.where(gt < np.float32(-500.0), np.float32(0.0), gt)
+    ok = np.isfinite(d)
+    grid = RN.blocks_for(d.size, threads, max_blocks)
+    with np.errstate(invalid="ignore"):
+        s = RN.tree(RN.grid_stride_sums(np.abs(d.astype(np.float64)), ok, grid, threads))
+    c = RN.tree(RN.grid_stride_sums(np.ones(d.size), ok, grid, threads))
+    return RN.serial_sum(s), RN.serial_sum(c)

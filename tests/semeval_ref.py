@@ -2,6 +2,8 @@
 spec (the reference's semantic/components/metrics.py:11-87): what csrc/semeval.hip must accumulate for one image."""
 import numpy as np
 
+from tests import reduce_numpy as RN
+
 
 def stats(pred, gt, n_classes, car_idx=-1, gt_no_cars=None, gt_non_corrupted=None, weights=None, beta=None):
     """-> dict(conf (C, C) int64 [gt][pred], errors [4] (None where the target is absent), rays, car_rays, out_of_range,
@@ -27,6 +29,33 @@ def stats(pred, gt, n_classes, car_idx=-1, gt_no_cars=None, gt_non_corrupted=Non
         bsum = float(np.sum(np.sum(w * b, axis=1)[car]))
     return {"conf": conf, "errors": errors, "rays": n, "car_rays": int(car.sum()), "out_of_range": int((~ok).sum()),
             "beta_car_sum": bsum}
+
+
+def beta_car_sum_in_kernel_order(gt, car_idx, weights, beta, threads=256, max_grid=2048):
+    """beta_car_sum of ONE snerf_semeval_accumulate call into a zeroed accumulator, bit for bit (csrc/semeval.hip, reduce.h).
+    fma((double)w, (double)b, acc) of fp32 w and b has an exact fp64 product: one fp64 addition of float64(w) * float64(b).
+      - workgroup b of the grid takes the tiles (256 rays) b, b + grid, ...;
+      - thread t takes the flat elements t, t + 256, ... of a tile's (rays, S) block in ascending order and skips the rays
+        whose target is not the car class (a tile without a car ray is skipped whole: the same sum);
+      - the 256-way tree gives partial[b]; the reduce launch sums the partials strided over 256 threads, then the tree."""
+    g = np.asarray(gt).reshape(-1).astype(np.int64)
+    n = g.shape[0]
+    w = np.asarray(weights, np.float32).reshape(n, -1)
+    S = w.shape[1]
+    prod = (w.astype(np.float64) * np.asarray(beta, np.float32).reshape(n, S).astype(np.float64)).reshape(-1)
+    car = np.repeat(g == car_idx, S)
+    grid = RN.blocks_for(n, threads, max_grid)
+    tiles = -(-n // threads)
+    t = np.arange(threads)
+    acc = np.zeros((grid, threads))
+    for j in range(-(-tiles // grid)):                       # the workgroups' j-th tile
+        tile = np.arange(grid) + j * grid
+        for m in range(S):                                   # the threads' m-th element of it: S * 256 elements a full tile
+            e = tile[:, None] * (threads * S) + m * threads + t[None, :]
+            ok = e < n * S
+            ec = np.where(ok, e, 0)
+            acc = np.where(ok & car[ec], acc + prod[ec], acc)
+    return float(RN.strided_sum(RN.tree(acc), threads))
 
 
 def accuracy(errors, n):

@@ -237,6 +237,23 @@ def test_apply_shift_and_median_rule():
         assert D.nanmedian_numpy(torch.from_numpy(a).to(DEV)) == float(np.median(a[np.isfinite(a)]))
 
 
+@pytest.mark.parametrize("shape", ((37, 53), (520, 521)))
+def test_shift_diff_totals_are_the_restated_summation_order_bit_for_bit(shape):
+    """snerf_dsm_shift_diff's (sum |diff|, count) against tests/dsm_numpy.py shift_diff_totals as bits; (520, 521) has more
+    than 1024 x 256 cells, so the grid-stride loop runs"""
+    D = _dsm()
+    rng = np.random.default_rng(shape[0])
+    pred = (rng.standard_normal(shape) * 2.0 ** rng.integers(-8, 9, shape)).astype(np.float32)
+    pred[rng.random(shape) < 0.05] = np.nan
+    gt = (rng.standard_normal(shape) * 30).astype(np.float32)
+    gt[rng.random(shape) < 0.05] = -9999.0
+    want = N.shift_diff_totals(pred, gt, 3, -2, 0.37)
+    _, _, totals = D._shift_diff(torch.from_numpy(pred).to(DEV), torch.from_numpy(gt).to(DEV), 3, -2, 0.37)
+    got = totals.cpu().numpy()
+    print(f"{shape}: kernel {got.tolist()!r}, restated {want!r}")
+    assert np.array_equal(got.view(np.int64), np.array(want, np.float64).view(np.int64)), (got.tolist(), want)
+
+
 def _nadir(field, res, xoff, yoff, z_top=500.0):
     """one nadir ray per cell centre of `field` (rows from the north), with the depth that puts its end point on the field"""
     h, w = field.shape

@@ -121,6 +121,39 @@ def test_streaming_chunks_equal_one_call_and_runs_are_bit_identical():
     assert torch.equal(run([0, 1000, 77_777, 200_000, 200_001, n]), chunked)
 
 
+def _order_case(n, S, seed):
+    """three classes, car = 1 on about a third of the rays and on none of rays [200, 560) (a whole tile of 256 without a car);
+    weights and beta of either sign with magnitudes spread over 2^-20 ... 2^20, so that the order shows in the low bits"""
+    rng = np.random.default_rng(seed)
+    gt = rng.integers(0, 3, n)
+    gt[200:560] = np.where(gt[200:560] == 1, 0, gt[200:560])
+    draw = lambda: (rng.uniform(1.0, 2.0, (n, S)) * 2.0 ** rng.integers(-20, 21, (n, S)) *                # noqa: E731
+                    rng.choice((-1.0, 1.0), (n, S))).astype(np.float32)
+    return gt, draw(), draw()
+
+
+def test_beta_sum_is_the_restated_summation_order_bit_for_bit():
+    """beta_car_sum against tests/semeval_ref.py beta_car_sum_in_kernel_order as int64 bits: n = 600 (three tiles, the last
+    ragged; fewer partials than threads), 257 * 256 + 17 (258 partials: the strided part of the reduce launch) and
+    2048 * 256 + 256 + 40 (more tiles than the grid cap: a workgroup walks two tiles).  A plain np.sum of the same products
+    must differ from the restated value in at least one case, or the inputs could not tell one order from another."""
+    S_ = _S()
+    told_apart = False
+    for k, (n, S) in enumerate(((600, 5), (257 * 256 + 17, 2), (2048 * 256 + 256 + 40, 1))):
+        gt, w, b = _order_case(n, S, 40 + k)
+        assert not (gt[200:560] == 1).any() and (gt[:200] == 1).any() and (gt[560:] == 1).any()
+        want = R.beta_car_sum_in_kernel_order(gt, 1, w, b)
+        plain = float(np.sum((w.astype(np.float64) * b.astype(np.float64))[gt == 1]))
+        told_apart |= plain != want
+        acc = S_.SemanticEvalAccumulator(3, 1, DEV)
+        acc.add(torch.zeros(n, dtype=torch.int64, device=DEV), torch.from_numpy(gt).to(DEV),
+                weights=torch.from_numpy(w).to(DEV), beta=torch.from_numpy(b).to(DEV)[..., None])
+        got = acc._read()["beta_car_sum"]
+        print(f"n = {n}, S = {S}: kernel {got!r}, restated {want!r}, np.sum {plain!r}")
+        assert np.float64(got).view(np.int64) == np.float64(want).view(np.int64), (n, S, got, want)
+    assert told_apart
+
+
 def test_out_of_range_labels_are_refused():
     S_ = _S()
     pred = torch.zeros(100, dtype=torch.int64, device=DEV)
@@ -253,6 +286,34 @@ def test_eval_semantic_images_equals_lean_inference(tmp_path):
     # the train split keeps item 0; a model without a semantic head is refused
     tr = eval_semantic_images(pipe.cfgs, pipe.renderer, pipe.models, images, 5, 4, split="train")
     assert [k for k in tr if k.startswith("img_")] == ["img_0", "img_1", "img_2"]
+
+
+def test_the_three_lean_evaluators_render_the_same_chunks():
+    """a frame of 2 * chunk + 3 rays (a ragged last chunk) with the jitter pinned for the whole frame: lean_inference,
+    lean_frame_maps and lean_semantic_eval go through util.render_chunks and give bit-identical rgb, depth and labels"""
+    from snerf_amd.eval.utils.util import lean_inference
+    from snerf_amd.eval.utils.vismaps import lean_frame_maps
+    S_ = _S()
+    chunk = 500
+    O, pipe = _setup(chunk=chunk)
+    n = 2 * chunk + 3
+    img = _image(O, n, 70, "x")
+    opts = {"perturb_rand": torch.rand(n, 16, generator=torch.Generator().manual_seed(5)).to(DEV)}
+    args = (pipe.cfgs, pipe.renderer, pipe.models, img["rays"], img["extras"])
+    res = lean_inference(*args, render_options=opts)
+    maps = lean_frame_maps(*args, products=("rgb", "depth"), render_options=opts)
+    assert torch.equal(maps["rgb"], res["rgb_coarse"]) and torch.equal(maps["depth"], res["depth_coarse"])
+
+    class Recording(S_.SemanticEvalAccumulator):
+        def add(self, pred, *a, **kw):
+            self.labels = getattr(self, "labels", []) + [pred.clone()]
+            return super().add(pred, *a, **kw)
+
+    acc = S_.lean_semantic_eval(*args, img["semantic"], car_cls_idx=4, render_options=opts, acc=Recording(5, 4, DEV))
+    assert [t.numel() for t in acc.labels] == [chunk, chunk, 3]
+    assert torch.equal(torch.cat(acc.labels), res["semantic_label_coarse"])
+    st = R.stats(res["semantic_label_coarse"].cpu(), img["semantic"].cpu(), 5, 4)
+    assert np.array_equal(acc.counts(), st["conf"]) and acc._read()["rays"] == n
 
 
 def test_model_without_semantic_head_is_refused():
