@@ -527,7 +527,7 @@ int snerf_ray_bounds(const float* const* rays, const long long* n_rows, int n_ar
  * center_range (device): c[3], range -- out + 9 of snerf_ray_bounds.  stride >= 8 with bounds, >= 3 without. */
 int snerf_normalize_rows(float* rows, long long n, int stride, int bounds, const float* center_range, void* stream);
 
-/* ---- world clouds: rays + depth -> UTM (east, north, alt) (eval/utils/dsm.py get_utm_cloud, baseline/dataset/satnerf_dataset.py
+/* ---- world clouds: rays + depth -> UTM (east, north, alt), and UTM points back into the scene (eval/utils/dsm.py get_utm_cloud, baseline/dataset/satnerf_dataset.py
  * get_latlonalt_from_nerf_prediction, StandardNormalization.denormalize, framework/util/conversions.py) ----------------------
  * One launch, one thread per point, every step fp64 with one rounding per operation (no contraction):
  *   1. xyz_n = o + d * depth, the fp32 ray columns 0..2 / 3..5 and the fp32 depth widened first (rays.double());
@@ -542,16 +542,29 @@ int snerf_normalize_rows(float* rows, long long n, int stride, int bounds, const
  * at its initial value means no finite point; [4] += points whose east, north or alt is not finite (written as they come,
  * left out of the bounds); [5..7] reserved.  n = 0 is legal and launches nothing.
  * Refused without touching the device: null pointers (lla_out excepted), n outside [0, 2^31], ray_stride < 6, a range that is not
- * positive and finite, a centre that is not finite, lon0 outside [-pi, pi], south other than 0 / 1. */
+ * positive and finite, a centre that is not finite, lon0 outside [-pi, pi], south other than 0 / 1, a direction other than the
+ * two below, and SNERF_GEO_TO_SCENE given to snerf_geo_cloud.
+ *
+ * params->direction selects the way through the same steps:
+ *   SNERF_GEO_TO_WORLD (0): scene -> world, the steps above.
+ *   SNERF_GEO_TO_SCENE (1): world -> scene, snerf_geo_points only.  Its input array (`xyz_n` in the prototype) holds (n, 3) fp64
+ *     (east, north, alt) in the zone of lon0 / south; per point
+ *       1. the utm package's to_latlon series (the same constants; restated, parity with the package UNPINNED) -> lat, lon (degrees);
+ *       2. latlon_to_ecef_custom(lat, lon, alt);
+ *       3. xyz_n = (ECEF - centre) / range, two roundings per component (normalize_xyz on an fp64 tensor).
+ *     enu_out receives xyz_n (n, 3) fp64; lla_out, when not NULL, (lat deg, lon deg, alt).  stats as above over the OUTPUT: [0..3]
+ *     the bounds of scene x and scene y, [4] += points whose xyz_n is not finite. */
+#define SNERF_GEO_TO_WORLD 0
+#define SNERF_GEO_TO_SCENE 1
 typedef struct SnerfGeoParams {
   double centre[3];
   double range;
   double lon0;
-  int south, reserved;
+  int south, direction;
 } SnerfGeoParams;
 int snerf_geo_cloud(const float* rays, int ray_stride, const float* depth, long long n, const SnerfGeoParams* params,
                     double* enu_out, double* lla_out, unsigned long long* stats, void* stream);
-/* the same kernel entered at step 2: xyz_n (n, 3) fp64 normalised points */
+/* direction 0: the same kernel entered at step 2, xyz_n (n, 3) fp64 normalised points; direction 1: world -> scene, see above */
 int snerf_geo_points(const double* xyz_n, long long n, const SnerfGeoParams* params, double* enu_out, double* lla_out,
                      unsigned long long* stats, void* stream);
 

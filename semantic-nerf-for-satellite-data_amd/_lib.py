@@ -138,9 +138,10 @@ class SnerfRayImage(C.Structure):
 
 
 class SnerfGeoParams(C.Structure):
-    _fields_ = [("centre", C.c_double * 3), ("range", C.c_double), ("lon0", C.c_double), ("south", C.c_int), ("reserved", C.c_int)]
+    _fields_ = [("centre", C.c_double * 3), ("range", C.c_double), ("lon0", C.c_double), ("south", C.c_int), ("direction", C.c_int)]
 
 
+GEO_TO_WORLD, GEO_TO_SCENE = 0, 1                                # SnerfGeoParams.direction (snerf_geo_points; snerf_geo_cloud: 0 only)
 GEO_STATS_INIT = (2 ** 64 - 1, 0, 2 ** 64 - 1, 0, 0, 0, 0, 0)   # include/snerf_hip.h: the caller's initial stats words
 
 

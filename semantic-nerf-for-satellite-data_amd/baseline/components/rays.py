@@ -1,7 +1,11 @@
 """Ray construction of the scene loaders -- mirror of baseline/components/rays.py.  satnerf_construct builds the rays of
 every image of a split in ONE launch of csrc/satrays.hip (snerf_rpc_rays): per pixel, rpcm localisation at max_alt and at
 min_alt, custom ECEF in fp64, and the un-normalised fp32 row [o(3), d(3), near = 0, far] that the reference returns after
-`.type(FloatTensor)`."""
+`.type(FloatTensor)`.
+
+nadir_construct casts one VERTICAL ray per cell of a map lattice (a DsmGrid of eval/utils/dsm.py): from the cell centre at max_alt
+straight down to min_alt, taken into the scene by GeoFrame.to_scene (csrc/geo.hip, direction 1).  The
+reference has no counterpart; its rays are already normalised, ready for the renderer."""
 import numpy as np
 import torch
 
@@ -66,3 +70,51 @@ def raise_on_failures(fails: torch.Tensor, names=None):
         who = names[k] if names is not None else f"#{k}"
         raise LocalizationError(f"image {who}: {int(f[k])} pixels did not converge in 100 RPC localisation iterations "
                                 "(rpcm: MaxLocalizationIterationsError)")
+
+
+def nadir_cell_centres(grid, device=None):
+    """(east (H, W), north (H, W)) fp64 tensors on `device` (default: the CPU) of the cell centres of `grid` -- a DsmGrid, or a
+    window of one as eval/utils/dsm.py grid_struct makes it.  Cell (j, i) of the window has its centre at
+    E = xoff + (ioff + i + 1/2) res, N = yoff - (joff + j + 1/2) res: row 0 is the north edge, the convention of csrc/lattice.h."""
+    from ...eval.utils.dsm import grid_struct
+    g = grid_struct(grid)
+    i = torch.arange(g.out_w, dtype=torch.float64, device=device) + float(g.ioff)
+    j = torch.arange(g.out_h, dtype=torch.float64, device=device) + float(g.joff)
+    east = g.xoff + (i + 0.5) * g.res
+    north = g.yoff - (j + 0.5) * g.res
+    return east.reshape(1, -1).expand(g.out_h, g.out_w), north.reshape(-1, 1).expand(g.out_h, g.out_w)
+
+
+def nadir_construct(grid, geo, min_alt, max_alt, device=None, want_bounds=False):
+    """One vertical ray per cell of `grid` (see nadir_cell_centres), row-major over the lattice: (H * W, 8) fp32, contiguous,
+    [o(3), d(3), near = 0, far] in `geo`'s normalised scene coordinates -- o is the cell centre at max_alt, o + far * d the cell
+    centre at min_alt.  The 2 H W points (E, N, max_alt), (E, N, min_alt) go through ONE GeoFrame.to_scene launch; d = p_bot -
+    p_top and its norm are fp64 torch ops on the device, rounded once to fp32.  `want_bounds`: also return the GeoBounds of the
+    points' scene x / y (a lattice inside the normalised box stays within about [-1, 1])."""
+    from ...eval.utils.dsm import grid_struct
+    min_alt, max_alt = float(min_alt), float(max_alt)
+    if not min_alt < max_alt:
+        raise ValueError(f"nadir_construct: min_alt = {min_alt} must lie below max_alt = {max_alt}")
+    g = grid_struct(grid)
+    if g.out_h <= 0 or g.out_w <= 0:
+        raise ValueError(f"nadir_construct: the lattice is empty ({g.out_h} x {g.out_w} cells)")
+    device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    east, north = (t.reshape(-1) for t in nadir_cell_centres(g, device))
+    cells = east.shape[0]
+    pts = torch.empty((2, cells, 3), dtype=torch.float64, device=device)
+    pts[:, :, 0] = east
+    pts[:, :, 1] = north
+    pts[0, :, 2] = max_alt
+    pts[1, :, 2] = min_alt
+    xyz, bounds = geo.to_scene(pts.reshape(-1, 3))
+    top, bot = xyz[:cells], xyz[cells:]
+    d = bot - top
+    norm = torch.linalg.vector_norm(d, dim=1, keepdim=True)
+    rays = torch.cat([top, d / norm, torch.zeros_like(norm), norm], 1).to(torch.float32).contiguous()
+    return (rays, bounds) if want_bounds else rays
+
+
+def nadir_extras(sun_elevation_deg: float, sun_azimuth_deg: float, t, n_rays: int, device=None) -> torch.Tensor:
+    """(n_rays, 4) fp32 extras of nadir rays, the loaders' columns: the sun direction and the constant embedding index `t`"""
+    sun = construct_sun_dir(sun_elevation_deg, sun_azimuth_deg, n_rays)
+    return torch.hstack([sun, float(t) * torch.ones(n_rays, 1)]).to(device).contiguous()

@@ -1,11 +1,14 @@
 // World clouds on the device: a frame's rays and depth (or normalised end points) to metric (east, north, alt) UTM points and,
 // optionally, (lat, lon, alt) -- the reference's get_xyz_from_nerf_prediction, StandardNormalization.denormalize,
 // ecef_to_latlon_custom and utm.from_latlon (its eval/utils/dsm.py get_utm_cloud path), which it runs in numpy on the host.
-// The spec is stated in include/snerf_hip.h; DESIGN.md section 5h gives the arithmetic contract.
+// The way back (SnerfGeoParams.direction = 1, snerf_geo_points only): UTM (east, north, alt) -> lat / lon (utm.to_latlon) -> custom
+// ECEF -> normalised scene coordinates, the reference's convert_utm_to_local, for casting a vertical ray per map cell.
+// The spec is stated in include/snerf_hip.h; DESIGN.md sections 5h and 5l give the arithmetic contracts.
 //   - one launch, one point per thread (the workgroups stride over the points), every step fp64 and evaluated operation by
 //     operation as torch / numpy do: no fused multiply-adds in this file;
-//   - the east / north bounds the DSM grid needs are folded in the same launch: per wave with shuffles, per workgroup through
-//     LDS, then ONE 64-bit integer atomic min / max per workgroup and bound on an order-preserving integer key of the double.
+//   - the east / north bounds the DSM grid needs (direction 1: the bounds of scene x / y) are folded in the same launch: per wave
+//     with shuffles, per workgroup through LDS, then ONE 64-bit integer atomic min / max per workgroup and bound on an
+//     order-preserving integer key of the double.
 //     Min and max are exact and commute, so the bounds do not depend on the grid or on the order the workgroups arrive in;
 //   - a point that is not finite is written as it comes, left out of the bounds and counted.
 // No allocation and no host synchronisation; both entries run on the caller's stream.
@@ -69,18 +72,120 @@ __device__ __forceinline__ void latlon_to_utm(double lat, double lon, double lon
   *north = nn;
 }
 
+// utm.to_latlon's constants: _E = (1 - sqrt(1 - E)) / (1 + sqrt(1 - E)) and the footpoint-latitude coefficients P2 .. P5.
+// UTM_SQRT_1ME is the double nearest sqrt(1 - E) (sqrt is not a constant expression); the rest is evaluated in the package's order
+constexpr double UTM_SQRT_1ME = 0.9966471893303066;
+static_assert(UTM_SQRT_1ME * UTM_SQRT_1ME > (1.0 - UTM_E) * (1.0 - 1e-15) && UTM_SQRT_1ME * UTM_SQRT_1ME < (1.0 - UTM_E) * (1.0 + 1e-15),
+              "UTM_SQRT_1ME is sqrt(1 - UTM_E)");
+constexpr double UTM_E1 = (1.0 - UTM_SQRT_1ME) / (1.0 + UTM_SQRT_1ME);
+constexpr double UTM_E1_2 = UTM_E1 * UTM_E1;
+constexpr double UTM_E1_3 = UTM_E1_2 * UTM_E1;
+constexpr double UTM_E1_4 = UTM_E1_3 * UTM_E1;
+constexpr double UTM_E1_5 = UTM_E1_4 * UTM_E1;
+constexpr double UTM_P2 = 3.0 / 2.0 * UTM_E1 - 27.0 / 32.0 * UTM_E1_3 + 269.0 / 512.0 * UTM_E1_5;
+constexpr double UTM_P3 = 21.0 / 16.0 * UTM_E1_2 - 55.0 / 32.0 * UTM_E1_4;
+constexpr double UTM_P4 = 151.0 / 96.0 * UTM_E1_3 - 417.0 / 128.0 * UTM_E1_5;
+constexpr double UTM_P5 = 1097.0 / 512.0 * UTM_E1_4;
+
+// utm.to_latlon's series for a point at (east, north) metres in the zone of central meridian lon0 (radians) -> degrees
+__device__ __forceinline__ void utm_to_latlon(double east, double north, double lon0, int south, double* lat, double* lon) {
+  const double x = east - 500000.0;
+  double y = north;
+  if (south) y -= 10000000.0;
+  const double m = y / UTM_K0;
+  const double mu = m / (UTM_R * UTM_M1);
+  const double p = mu + UTM_P2 * sin(2.0 * mu) + UTM_P3 * sin(4.0 * mu) + UTM_P4 * sin(6.0 * mu) + UTM_P5 * sin(8.0 * mu);
+  const double ps = sin(p), pc = cos(p);
+  const double pt = ps / pc;
+  const double pt2 = pt * pt;
+  const double pt4 = pt2 * pt2;
+  const double eps = 1.0 - UTM_E * (ps * ps);
+  const double n = UTM_R / sqrt(eps);
+  const double r = (1.0 - UTM_E) / eps;
+  const double c = UTM_E_P2 * (pc * pc);
+  const double c2 = c * c;
+  const double d = x / (n * UTM_K0);
+  const double d2 = d * d;
+  const double d3 = d2 * d;
+  const double d4 = d3 * d;
+  const double d5 = d4 * d;
+  const double d6 = d5 * d;
+  // the d^6 term stands outside the bracket that pt / r multiplies, as in the package
+  const double lat_rad = p - (pt / r) * (d2 / 2.0 - d4 / 24.0 * (5.0 + 3.0 * pt2 + 10.0 * c - 4.0 * c2 - 9.0 * UTM_E_P2)) +
+                         d6 / 720.0 * (61.0 + 90.0 * pt2 + 298.0 * c + 45.0 * pt4 - 252.0 * UTM_E_P2 - 3.0 * c2);
+  const double lon_rad = (d - d3 / 6.0 * (1.0 + 2.0 * pt2 + c) +
+                          d5 / 120.0 * (5.0 - 2.0 * c + 28.0 * pt2 - 3.0 * c2 + 8.0 * UTM_E_P2 + 24.0 * pt4)) / pc;
+  *lat = lat_rad * (180.0 / M_PI);
+  *lon = utm_wrap(lon_rad + lon0) * (180.0 / M_PI);
+}
+
 constexpr unsigned long long KEY_MIN_IDENTITY = ~0ull;   // what the host writes into the two minimum words
 constexpr unsigned long long KEY_MAX_IDENTITY = 0ull;    // ... and into the two maximum words
 
-// rays != nullptr: step 1 (end points from the rays) first; else the points come in as xyz_n
+// The bounds of a launch's output, shared by both directions: every thread offers its points' first two components (east /
+// north, or scene x / y), then finish() folds them per wave, per workgroup and into the caller's stats words.
+struct GeoFold {
+  unsigned long long k_amin = KEY_MIN_IDENTITY, k_amax = KEY_MAX_IDENTITY, k_bmin = KEY_MIN_IDENTITY, k_bmax = KEY_MAX_IDENTITY;
+  unsigned int bad = 0;
+
+  __device__ __forceinline__ void add(double a, double b, double c) {
+    if (__builtin_isfinite(a) && __builtin_isfinite(b) && __builtin_isfinite(c)) {
+      const unsigned long long ka = order_key(a), kb = order_key(b);
+      k_amin = OpMin()(k_amin, ka);
+      k_amax = OpMax()(k_amax, ka);
+      k_bmin = OpMin()(k_bmin, kb);
+      k_bmax = OpMax()(k_bmax, kb);
+    } else {
+      ++bad;
+    }
+  }
+
+  // every thread of the workgroup calls this once, after its loop has ended
+  __device__ __forceinline__ void finish(unsigned long long* __restrict__ stats) {
+    __shared__ unsigned long long red[4][GEO_WAVES];
+    __shared__ unsigned int red_bad[GEO_WAVES];
+    // wave64 butterflies (every lane takes part: the loop has ended for the whole wave)
+    k_amin = wave_reduce(k_amin, OpMin());
+    k_amax = wave_reduce(k_amax, OpMax());
+    k_bmin = wave_reduce(k_bmin, OpMin());
+    k_bmax = wave_reduce(k_bmax, OpMax());
+    bad = wave_reduce(bad, OpSum());
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+      red[0][wave] = k_amin;
+      red[1][wave] = k_amax;
+      red[2][wave] = k_bmin;
+      red[3][wave] = k_bmax;
+      red_bad[wave] = bad;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+      for (int w = 1; w < GEO_WAVES; ++w) {
+        k_amin = OpMin()(k_amin, red[0][w]);
+        k_amax = OpMax()(k_amax, red[1][w]);
+        k_bmin = OpMin()(k_bmin, red[2][w]);
+        k_bmax = OpMax()(k_bmax, red[3][w]);
+        bad += red_bad[w];
+      }
+      // a workgroup without a finite point holds the identities: nothing to fold
+      if (k_amin != KEY_MIN_IDENTITY) {
+        atomicMin(&stats[0], k_amin);
+        atomicMax(&stats[1], k_amax);
+        atomicMin(&stats[2], k_bmin);
+        atomicMax(&stats[3], k_bmax);
+      }
+      if (bad) atomicAdd(&stats[4], (unsigned long long)bad);
+    }
+  }
+};
+
+// direction 0, scene -> world.  rays != nullptr: step 1 (end points from the rays) first; else the points come in as xyz_n
 __global__ __launch_bounds__(GEO_THREADS) void geo_cloud_kernel(const float* __restrict__ rays, int ray_stride,
                                                                 const float* __restrict__ depth, const double* __restrict__ xyz_n,
                                                                 long long n, SnerfGeoParams p, double* __restrict__ enu_out,
                                                                 double* __restrict__ lla_out, unsigned long long* __restrict__ stats) {
-  __shared__ unsigned long long red[4][GEO_WAVES];
-  __shared__ unsigned int red_bad[GEO_WAVES];
-  unsigned long long k_emin = KEY_MIN_IDENTITY, k_emax = KEY_MAX_IDENTITY, k_nmin = KEY_MIN_IDENTITY, k_nmax = KEY_MAX_IDENTITY;
-  unsigned int bad = 0;
+  GeoFold fold;
   for (long long i = (long long)blockIdx.x * GEO_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * GEO_THREADS) {
     double q[3];
     if (rays != nullptr) {
@@ -111,49 +216,38 @@ __global__ __launch_bounds__(GEO_THREADS) void geo_cloud_kernel(const float* __r
       l[1] = lon;
       l[2] = alt;
     }
-    if (__builtin_isfinite(east) && __builtin_isfinite(north) && __builtin_isfinite(alt)) {
-      const unsigned long long ke = order_key(east), kn = order_key(north);
-      k_emin = OpMin()(k_emin, ke);
-      k_emax = OpMax()(k_emax, ke);
-      k_nmin = OpMin()(k_nmin, kn);
-      k_nmax = OpMax()(k_nmax, kn);
-    } else {
-      ++bad;
-    }
+    fold.add(east, north, alt);
   }
-  // wave64 butterflies (every lane takes part: the loop above has ended for the whole wave)
-  k_emin = wave_reduce(k_emin, OpMin());
-  k_emax = wave_reduce(k_emax, OpMax());
-  k_nmin = wave_reduce(k_nmin, OpMin());
-  k_nmax = wave_reduce(k_nmax, OpMax());
-  bad = wave_reduce(bad, OpSum());
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-    red[0][wave] = k_emin;
-    red[1][wave] = k_emax;
-    red[2][wave] = k_nmin;
-    red[3][wave] = k_nmax;
-    red_bad[wave] = bad;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
+  fold.finish(stats);
+}
+
+// direction 1, world -> scene: enu (n, 3) (east, north, alt) -> lat / lon (utm.to_latlon) -> custom ECEF -> normalised points
+__global__ __launch_bounds__(GEO_THREADS) void geo_scene_kernel(const double* __restrict__ enu, long long n, SnerfGeoParams p,
+                                                                double* __restrict__ xyz_out, double* __restrict__ lla_out,
+                                                                unsigned long long* __restrict__ stats) {
+  GeoFold fold;
+  for (long long i = (long long)blockIdx.x * GEO_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * GEO_THREADS) {
+    const double east = enu[3 * i], north = enu[3 * i + 1], alt = enu[3 * i + 2];
+    double lat, lon, x[3];
+    utm_to_latlon(east, north, p.lon0, p.south, &lat, &lon);
+    latlon_to_ecef(lat, lon, alt, &x[0], &x[1], &x[2]);
+    // normalize: (xyz - centre) / range, two roundings per component (the inverse of denormalize on an fp64 tensor)
+    double q[3];
 #pragma unroll
-    for (int w = 1; w < GEO_WAVES; ++w) {
-      k_emin = OpMin()(k_emin, red[0][w]);
-      k_emax = OpMax()(k_emax, red[1][w]);
-      k_nmin = OpMin()(k_nmin, red[2][w]);
-      k_nmax = OpMax()(k_nmax, red[3][w]);
-      bad += red_bad[w];
+    for (int k = 0; k < 3; ++k) q[k] = __ddiv_rn(__dsub_rn(x[k], p.centre[k]), p.range);
+    double* o = xyz_out + 3 * i;
+    o[0] = q[0];
+    o[1] = q[1];
+    o[2] = q[2];
+    if (lla_out != nullptr) {
+      double* l = lla_out + 3 * i;
+      l[0] = lat;
+      l[1] = lon;
+      l[2] = alt;
     }
-    // a workgroup without a finite point holds the identities: nothing to fold
-    if (k_emin != KEY_MIN_IDENTITY) {
-      atomicMin(&stats[0], k_emin);
-      atomicMax(&stats[1], k_emax);
-      atomicMin(&stats[2], k_nmin);
-      atomicMax(&stats[3], k_nmax);
-    }
-    if (bad) atomicAdd(&stats[4], (unsigned long long)bad);
+    fold.add(q[0], q[1], q[2]);
   }
+  fold.finish(stats);
 }
 
 static int geo_launch(const char* who, const float* rays, int ray_stride, const float* depth, const double* xyz_n, long long n,
@@ -165,10 +259,19 @@ static int geo_launch(const char* who, const float* rays, int ray_stride, const 
     if (!__builtin_isfinite(params->centre[k])) { set_error("%s: centre[%d] is not finite", who, k); return SNERF_ERR_BAD_DESC; }
   if (!(params->lon0 >= -M_PI && params->lon0 <= M_PI)) { set_error("%s: central meridian %g rad outside [-pi, pi]", who, params->lon0); return SNERF_ERR_BAD_DESC; }
   if (params->south != 0 && params->south != 1) { set_error("%s: south = %d", who, params->south); return SNERF_ERR_BAD_DESC; }
+  // world -> scene starts from points: only snerf_geo_points (rays == nullptr) offers it
+  if (params->direction != SNERF_GEO_TO_WORLD && (params->direction != SNERF_GEO_TO_SCENE || rays != nullptr)) {
+    set_error("%s: direction = %d", who, params->direction);
+    return SNERF_ERR_BAD_DESC;
+  }
   if (n == 0) return SNERF_OK;
   if (!enu_out) { set_error("%s: null pointer", who); return SNERF_ERR_NULL; }
-  hipLaunchKernelGGL(geo_cloud_kernel, dim3(blocks_for(n, GEO_THREADS, GEO_MAX_GRID)), dim3(GEO_THREADS), 0, (hipStream_t)stream, rays, ray_stride, depth, xyz_n, n,
-                     *params, enu_out, lla_out, stats);
+  const dim3 grid(blocks_for(n, GEO_THREADS, GEO_MAX_GRID)), block(GEO_THREADS);
+  if (params->direction == SNERF_GEO_TO_SCENE)
+    hipLaunchKernelGGL(geo_scene_kernel, grid, block, 0, (hipStream_t)stream, xyz_n, n, *params, enu_out, lla_out, stats);
+  else
+    hipLaunchKernelGGL(geo_cloud_kernel, grid, block, 0, (hipStream_t)stream, rays, ray_stride, depth, xyz_n, n, *params, enu_out,
+                       lla_out, stats);
   SNERF_LAUNCH_CHECK();
   return SNERF_OK;
 }

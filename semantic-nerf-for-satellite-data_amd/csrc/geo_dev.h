@@ -1,5 +1,6 @@
 // Geodetic conversions of the custom ECEF system on the device (the reference's framework/util/conversions.py), shared by the
-// ray builder (satrays.hip) and the world-cloud kernel (geo.hip).  fp64, evaluated operation by operation as numpy does.
+// ray builder (satrays.hip) and the world-cloud kernels (geo.hip: ecef_to_latlon on the way to the world, latlon_to_ecef on the way
+// back into the scene).  fp64, evaluated operation by operation as numpy does.
 #pragma once
 #include "common.h"
 

@@ -9,7 +9,14 @@ Files under `output_dp`/ortho/{split}/:
     top_alt.png/.tif, dsm.png/.tif       the top-surface altitude and the mean DSM: float32 in the .tif (NaN = no data), JET
                                          between the plane's own bounds in the .png (NaN as the colormap treats it: as 0)
     vote_share.png/.tif                  the winning class's share of a cell's votes: float32, BONE in the .png
-GeoTIFFs carry ModelPixelScale, ModelTiepoint and, with the scene's zone, a GeoKeyDirectory (img_utils.save_geotiff)."""
+GeoTIFFs carry ModelPixelScale, ModelTiepoint and, with the scene's zone, a GeoKeyDirectory (img_utils.save_geotiff).
+
+export_nadir writes the map rendered from above (eval/utils/ortho.py nadir_products) by the same writers
+and rules.  Files under `output_dp`/nadir/:
+    rgb.png/.tif, albedo.png/.tif        the nadir ortho-image under the chosen sun and the albedo: uint8
+    sun.png/.tif, beta.png/.tif          the shadow map and the uncertainty: float32 in the .tif, BONE in the .png
+    dsm.png/.tif                         the rendered surface altitude, every cell filled: float32 in the .tif, JET in the .png
+    label.png/.tif                       the class seen from above (a semantic model only): ids in the .tif, the palette in the .png"""
 import os
 
 import numpy as np
@@ -20,7 +27,7 @@ from ..framework.util import colormaps, img_utils
 from ..framework.visualize import to_uint8_image
 from ..parallel import world
 from .utils import vismaps
-from .utils.ortho import NO_LABEL, ortho_products
+from .utils.ortho import NO_LABEL, nadir_products, ortho_products
 
 
 def _png(fp, chw_u8):
@@ -67,6 +74,38 @@ def export_ortho(cfgs, renderer, models, images, output_dp, split="test", palett
         if "vote_share" in prod:
             planes.append(("vote_share", colormaps.COLORMAP_BONE))
         for key, cmap in planes:
+            plane = prod[key]
+            stats = vismaps.plane_minmax(plane, vismaps.new_stats(plane.device), "user")
+            _png(fp(key + ".png"), vismaps.colormap(plane, colormaps.table(cmap, plane.device), stats, "user"))
+            img_utils.save_geotiff(fp(key + ".tif"), plane, grid, zone_string)
+    return dict(prod, files=files)
+
+
+@torch.no_grad()
+def export_nadir(cfgs, renderer, models, output_dp, palette=None, zone_string=None, **kwargs):
+    """nadir_products(cfgs, renderer, models, **kwargs), written to `output_dp`/nadir/.  `palette`: (K, 3) uint8, default
+    colormaps.DEFAULT_PALETTE.  `zone_string`: the GeoTIFFs' UTM zone, default the zone of the GeoFrame in use.  Every rank
+    computes the products (with sharded=True each renders its share of the lattice); only rank 0 writes.  Returns the products
+    plus "files": {name: path}."""
+    prod = nadir_products(cfgs, renderer, models, **kwargs)
+    if zone_string is None:
+        g = kwargs.get("geo") or getattr(kwargs.get("dataset"), "geo", None)
+        zone_string = getattr(g, "zone_string", None)
+    grid = prod["grid"]
+    out_dp = os.path.join(output_dp, "nadir")
+    files = {}
+    if world()[0] == 0:
+        os.makedirs(out_dp, exist_ok=True)
+        fp = lambda name: files.setdefault(name, os.path.join(out_dp, name))      # noqa: E731
+        for key in ("rgb", "albedo"):
+            u8 = to_uint8_image(prod[key])
+            _png(fp(key + ".png"), u8)
+            img_utils.save_geotiff(fp(key + ".tif"), u8.permute(1, 2, 0).contiguous(), grid, zone_string)
+        if "label" in prod:
+            pal = colormaps.DEFAULT_PALETTE if palette is None else palette
+            _png(fp("label.png"), label_colors(prod["label"], pal))
+            img_utils.save_geotiff(fp("label.tif"), prod["label"], grid, zone_string)
+        for key, cmap in (("dsm", colormaps.COLORMAP_JET), ("sun", colormaps.COLORMAP_BONE), ("beta", colormaps.COLORMAP_BONE)):
             plane = prod[key]
             stats = vismaps.plane_minmax(plane, vismaps.new_stats(plane.device), "user")
             _png(fp(key + ".png"), vismaps.colormap(plane, colormaps.table(cmap, plane.device), stats, "user"))

@@ -16,10 +16,15 @@ winner belongs to the image of the call ([index0, index0 + n)), so a fused map g
 Votes -- every point adds 1 to votes[label][cell] over the same window (integer atomic add); finish_votes gives the argmax
 (the lowest class on a tie, 255 for a cell without a vote) and the winner's share of the cell's votes.
 
-ortho_products walks a set of images and returns the fused map; eval/ortho.py writes it (PNG and GeoTIFF).
+ortho_products walks a set of images and returns the fused map; eval/ortho.py writes it (PNG and GeoTIFF).  A splatted map has
+cells no view's point reaches, and its occlusion is "the highest point wins".
+
+nadir_products asks the model instead: one vertical ray per cell of the lattice
+(baseline/components/rays.py nadir_construct, through GeoFrame.to_scene), rendered under a chosen sun -- a DSM without holes, a
+true nadir ortho-image, the shadow map and the top-surface label, with occlusion resolved by the renderer.
 
 Out of scope: map-space accuracy against a ground-truth class raster (the US3D classes of dsm_cls_fp are not the scene's
-label set), finite-sigma splats, occlusion reasoning beyond the highest point, RPC tags."""
+label set), finite-sigma splats, slanted or perspective map cameras, sweeps over several suns (callers loop), RPC tags."""
 import torch
 
 from ... import _lib
@@ -212,3 +217,113 @@ def ortho_products(cfgs, renderer, models, images, geo=None, roi=None, resolutio
         res.update(bad_labels=bad_labels, max_votes=max_votes)
     res["bad_points"] = bad_points
     return res
+
+
+def window_grid(grid):
+    """the lattice of a window as a DsmGrid of its own: a DsmGrid as it is, a _lib.SnerfDsmGrid (dsm.grid_struct) by its window"""
+    if isinstance(grid, D.DsmGrid):
+        return grid
+    return D.DsmGrid(grid.xoff + grid.ioff * grid.res, grid.yoff - grid.joff * grid.res, grid.res, grid.out_w, grid.out_h)
+
+
+def _nadir_defaults(dataset, geo, roi, gt, water_mask, ignore_mask, min_alt, max_alt, sun_elevation, sun_azimuth):
+    """what a loaded dataset (baseline/dataset/satnerf_dataset.py) supplies when the caller does not: its GeoFrame, its "dsm"
+    entry (roi, gt, masks), the altitude range of the split's images and the sun of the first one"""
+    if dataset is not None:
+        geo = dataset.geo if geo is None else geo
+        entry = dataset.dsm or {}
+        if roi is None and gt is None:
+            roi, gt = entry.get("roi"), entry.get("gt")
+            water_mask = entry.get("water_mask") if water_mask is None else water_mask
+            ignore_mask = entry.get("ignore_mask") if ignore_mask is None else ignore_mask
+        min_alt = min(it["alt_min"] for it in dataset.items) if min_alt is None else min_alt
+        max_alt = max(it["alt_max"] for it in dataset.items) if max_alt is None else max_alt
+        sun_elevation = float(dataset.metas[0]["sun_elevation"]) if sun_elevation is None else sun_elevation
+        sun_azimuth = float(dataset.metas[0]["sun_azimuth"]) if sun_azimuth is None else sun_azimuth
+    missing = [k for k, v in (("geo", geo), ("min_alt", min_alt), ("max_alt", max_alt), ("sun_elevation", sun_elevation),
+                              ("sun_azimuth", sun_azimuth)) if v is None]
+    if missing:
+        raise ValueError(f"nadir_products: pass {', '.join(missing)} (or a loaded dataset= to take them from)")
+    return geo, roi, gt, water_mask, ignore_mask, min_alt, max_alt, sun_elevation, sun_azimuth
+
+
+@torch.no_grad()
+def nadir_products(cfgs, renderer, models, geo=None, grid=None, roi=None, min_alt=None, max_alt=None, sun_elevation=None,
+                   sun_azimuth=None, t=0, render_options={}, sharded=False, gt=None, water_mask=None, ignore_mask=None,
+                   dataset=None):
+    """The map of the lattice rendered from above: one vertical ray per cell (rays.nadir_construct between `max_alt` and
+    `min_alt` metres, through `geo`, a GeoFrame), extras of the sun at (`sun_elevation`, `sun_azimuth`) degrees and the
+    embedding index `t`.  The grid: `grid` (a DsmGrid, or a window of one from dsm.grid_struct), else the ROI grid of `roi`
+    (a DsmGrid or the roi_txt meta), else a ValueError.  `dataset` (a loaded SatNeRFDataset) supplies what is not given: its
+    geo, its "dsm" entry (roi, gt, masks), the min / max of its images' alt_min / alt_max, the sun of its first image.
+
+    ONE walk of util.render_chunks over the rays (`sharded`: over this rank's frame_shard of them, the results all-gathered as
+    sharded_lean_inference does): the per-ray results are copied, albedo / sun / beta folded by vismaps.fold_chunk; no
+    frame-sized per-sample tensor exists.  `render_options` as everywhere in evaluation ({"perturb": 0} for a repeatable map).
+
+    Returns {"grid": DsmGrid (of the window), "dsm": (H, W) f32 -- the altitude of geo.cloud(rays, depth), every cell filled --,
+    "rgb": (3, H, W) f32, "albedo": (3, H, W) f32, "sun": (H, W) f32 (the shadow map), "beta": (H, W) f32[, "label": (H, W) u8
+    (a model with classes; 255 for a label beyond 254)], "rays": the (H W, 8) nadir rays, "planimetric_error": the largest
+    |east / north of the cloud - cell centre| in metres (the self-check of the ray construction), "scene_bounds": GeoBounds of
+    the lattice's scene x / y (to_scene's stats)[, "mae": {"mean", "median"} of dsm.compute_mae(dsm, gt, water_mask,
+    ignore_mask), with `gt` (H, W)]}."""
+    from ... import ops, parallel
+    from ...baseline.components import rays as R
+    from . import vismaps
+    from .util import render_chunks, result_buffers, shard_options
+    geo, roi, gt, water_mask, ignore_mask, min_alt, max_alt, sun_elevation, sun_azimuth = _nadir_defaults(
+        dataset, geo, roi, gt, water_mask, ignore_mask, min_alt, max_alt, sun_elevation, sun_azimuth)
+    if grid is None:
+        if roi is None:
+            raise ValueError("nadir_products: pass grid= or roi= (the lattice to render)")
+        grid = roi if isinstance(roi, D.DsmGrid) else D.roi_grid(roi)
+    g = grid_struct(grid)
+    h, w = g.out_h, g.out_w
+    n = _cells(g)
+    model = models["coarse"]
+    n_classes = model.spec.n_classes
+    dev = next(model.parameters()).device
+    rays, bounds = R.nadir_construct(g, geo, min_alt, max_alt, device=dev, want_bounds=True)
+    extras = R.nadir_extras(sun_elevation, sun_azimuth, t, n, dev)
+
+    lo, hi = parallel.frame_shard(n) if sharded else (0, n)
+    m = hi - lo
+    S = cfgs.pipeline.n_samples
+    keys = ("rgb", "depth") + (("semantic_label",) if n_classes else ()) + ("weights", "albedo", "sun", "beta")
+    loc = {"rgb": torch.empty((m, 3), dtype=torch.float32, device=dev), "depth": torch.empty(m, dtype=torch.float32, device=dev),
+           "albedo": torch.empty((3, m), dtype=torch.float32, device=dev), "sun": torch.empty(m, dtype=torch.float32, device=dev),
+           "beta": torch.empty(m, dtype=torch.float32, device=dev)}
+    if n_classes:
+        loc["label"] = torch.empty(m, dtype=torch.int64, device=dev)
+    if m:
+        ops.release_workspaces()
+        bufs = result_buffers(keys, min(cfgs.pipeline.render_chunk_size, m), S, n_classes, dev)
+        planes = {"albedo_map": loc["albedo"], "sun_map": loc["sun"], "beta_map": loc["beta"]}
+        stats = vismaps.new_stats(dev)
+        for i, k, sl in render_chunks(cfgs, renderer, models, rays[lo:hi], extras[lo:hi], bufs,
+                                      shard_options(render_options, lo, hi, n)):
+            loc["rgb"][i:i + k].copy_(sl["rgb_coarse"])
+            loc["depth"][i:i + k].copy_(sl["depth_coarse"])
+            if n_classes:
+                loc["label"][i:i + k].copy_(sl["semantic_label_coarse"])
+            vismaps.fold_chunk(planes, stats, i, m, k, S, weights=sl["weights_coarse"], albedo=sl["albedo_coarse"],
+                               sun=sl["sun_coarse"], beta=sl["beta_coarse"])
+    if sharded:
+        loc["albedo"] = loc["albedo"].t().contiguous()
+        loc = {key: parallel.allgather_rows(v, n) for key, v in loc.items()}
+        loc["albedo"] = loc["albedo"].t().contiguous()
+
+    cloud, _ = geo.cloud(rays, loc["depth"])
+    east, north = (c.reshape(-1) for c in R.nadir_cell_centres(g, dev))
+    off = torch.maximum((cloud[:, 0] - east).abs().max(), (cloud[:, 1] - north).abs().max())
+    out = {"grid": window_grid(grid), "dsm": cloud[:, 2].to(torch.float32).reshape(h, w),
+           "rgb": loc["rgb"].t().contiguous().reshape(3, h, w), "albedo": loc["albedo"].reshape(3, h, w),
+           "sun": loc["sun"].reshape(h, w), "beta": loc["beta"].reshape(h, w), "rays": rays,
+           "planimetric_error": float(off), "scene_bounds": bounds}
+    if n_classes:
+        lab = loc["label"]
+        out["label"] = torch.where((lab >= 0) & (lab < NO_LABEL), lab, torch.full_like(lab, NO_LABEL)).to(torch.uint8).reshape(h, w)
+    if gt is not None:
+        mae = D.compute_mae(out["dsm"], gt, water_mask=water_mask, ignore_mask=ignore_mask)
+        out["mae"] = {"mean": mae["mean"], "median": mae["median"]}
+    return out

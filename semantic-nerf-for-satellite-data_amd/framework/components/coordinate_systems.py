@@ -6,8 +6,10 @@ for training is an error, not a silent switch to ECEF.
 GeoFrame takes a loaded scene's predictions back to the world for EVALUATION: normalised ECEF end points -> ECEF -> lat / lon /
 alt -> UTM (east, north, alt), one launch of csrc/geo.hip per frame, which also folds the east / north bounds the DSM grid
 needs (the reference: satnerf_dataset.py:156-206, normalization.py:50-58, conversions.py:61-83,111-150, eval/utils/dsm.py:18-36,
-all numpy on the host).  The UTM series is the `utm` package's, restated; the package is not part of this build, so parity with
-it is UNPINNED.  DIVERGENCE: the zone is the scene's (root.json "zone_string"), where the reference's
+all numpy on the host).  GeoFrame.to_scene is the way back, UTM (east, north, alt) -> lat / lon -> ECEF -> normalised scene
+coordinates (the reference's conversions.py:7-24 convert_utm_to_local), the same entry point with `direction` = 1: it is what
+casts a vertical ray per map cell (baseline/components/rays.py nadir_construct).  Both UTM series are the
+`utm` package's, restated; the package is not part of this build, so parity with it is UNPINNED (DESIGN.md sections 5h, 5l).  DIVERGENCE: the zone is the scene's (root.json "zone_string"), where the reference's
 get_utm_cloud lets `utm` pick it from the first point -- the same zone unless a scene straddles a zone edge."""
 import ctypes as C
 import struct
@@ -20,7 +22,8 @@ from ..util.conversions import split_zone_string, zone_central_meridian, zone_is
 
 CUSTOM_ECEF = "custom_ecef"
 
-GeoBounds = namedtuple("GeoBounds", "xmin xmax ymin ymax")     # east / north extremes of a cloud's finite points (floats)
+# east / north extremes of a cloud's finite points (floats); of to_scene's output: its scene x / y extremes
+GeoBounds = namedtuple("GeoBounds", "xmin xmax ymin ymax")
 
 
 def init_coordinate_system(cfgs) -> str:
@@ -48,14 +51,15 @@ def decode_geo_stats(words):
 
 
 class GeoFrame:
-    """normalised scene coordinates -> UTM, from a StandardNormalization (centre, range) and a zone string ("17R")"""
+    """normalised scene coordinates -> UTM (cloud, points) and back (to_scene), from a StandardNormalization (centre, range) and
+    a zone string ("17R")"""
 
     def __init__(self, normalization, zone_string: str):
         center, rng = normalization.calculate_center_range()
         number, _ = split_zone_string(zone_string)
         self.zone_string = zone_string
         self.params = _lib.SnerfGeoParams((C.c_double * 3)(*[float(v) for v in center]), float(rng), zone_central_meridian(number),
-                                          int(zone_is_south(zone_string)), 0)
+                                          int(zone_is_south(zone_string)), _lib.GEO_TO_WORLD)
 
     @staticmethod
     def _outputs(n, dev, want_lla):
@@ -96,4 +100,20 @@ class GeoFrame:
         xyz_n = xyz_n.double().contiguous()
         out = self._outputs(xyz_n.shape[0], xyz_n.device, want_lla)
         _lib.call("snerf_geo_points", xyz_n, xyz_n.shape[0], self.params, *out)
+        return self._result(*out)
+
+    def to_scene(self, enu, want_lla=False):
+        """UTM points (N, 3) (east, north, alt) in the frame's zone -> (xyz_n (N, 3) f64 normalised scene coordinates[, lla
+        (N, 3) f64 (lat deg, lon deg, alt)], GeoBounds of scene x / y); the inverse of `points`, computed in fp64 (an fp32 input
+        is widened first).  Raises ValueError naming the count when points are not finite."""
+        if not (torch.is_tensor(enu) and enu.is_cuda):
+            raise ValueError("GeoFrame runs on the device: pass CUDA tensors")
+        if enu.dim() != 2 or enu.shape[1] != 3:
+            raise ValueError("GeoFrame.to_scene: (N, 3) points")
+        enu = enu.double().contiguous()
+        # the frame keeps its forward params: the inverse call uses a copy
+        p = _lib.SnerfGeoParams.from_buffer_copy(self.params)
+        p.direction = _lib.GEO_TO_SCENE
+        out = self._outputs(enu.shape[0], enu.device, want_lla)
+        _lib.call("snerf_geo_points", enu, enu.shape[0], p, *out)
         return self._result(*out)

@@ -1,9 +1,12 @@
-"""UTM helpers -- mirror of framework/util/conversions.py:104-150 (utm_from_latlon, utm_from_lonlat, split_zone_string,
-zonestring_to_hemisphere) on device tensors.  The reference hands numpy arrays to the `utm` package; this build does not carry
-it, so the package's from_latlon series is restated here (fp64 torch ops on the tensors' device, the operation order of
-csrc/geo.hip) -- parity with the package is UNPINNED, see DESIGN.md section 5h.  The evaluation path does not go through this
-module: a frame's cloud is one launch of csrc/geo.hip (framework/components/coordinate_systems.py GeoFrame); these functions
-serve callers that already hold lat / lon.
+"""UTM helpers -- mirror of framework/util/conversions.py:7-40,104-150 (utm_from_latlon, utm_from_lonlat, latlon_from_utm,
+lonlat_from_utm, convert_utm_to_local, convert_local_to_utm, split_zone_string, zonestring_to_hemisphere) on device tensors.  The
+reference hands numpy arrays to the `utm` package; this build does not carry it, so the package's from_latlon series is restated
+here (fp64 torch ops on the tensors' device, the operation order of csrc/geo.hip) -- parity with the package is UNPINNED, see
+DESIGN.md section 5h.  The evaluation path does not go through utm_from_latlon: a frame's cloud is one launch of csrc/geo.hip
+(framework/components/coordinate_systems.py GeoFrame); it serves callers that already hold lat / lon.
+
+The way back (UTM -> lat / lon -> scene) exists on the device only: latlon_from_utm, lonlat_from_utm and the two convert_*
+functions are launches of csrc/geo.hip (snerf_geo_points) on CUDA tensors, a CPU tensor is an error.
 
 With zone_string=None the zone number comes from the FIRST point, int((lon + 180) / 6) % 60 + 1, and the letter from the first
 latitude (bands C..X of 8 degrees from 80 S, X reaching 84 N), as the package picks them.  NOT handled: the package's
@@ -90,3 +93,48 @@ def utm_from_latlon(lats, lons, zone_string=None):
 
 def utm_from_lonlat(lons, lats, zone_string=None):
     return utm_from_latlon(lats, lons, zone_string)
+
+
+def _zone_frame(zone_string):
+    """a GeoFrame of the zone alone (centre 0, range 1): its lat / lon do not depend on a scene's normalisation"""
+    from ..components.coordinate_systems import GeoFrame
+
+    class _Unit:
+        @staticmethod
+        def calculate_center_range():
+            return (0.0, 0.0, 0.0), 1.0
+    return GeoFrame(_Unit, zone_string)
+
+
+def latlon_from_utm(easts, norths, zone_string):
+    """(lats, lons) in degrees of the UTM points (easts, norths) of `zone_string` (utm.to_latlon); CUDA tensors in, fp64
+    tensors of the inputs' shape out"""
+    if not (torch.is_tensor(easts) and easts.is_cuda and torch.is_tensor(norths) and norths.is_cuda):
+        raise ValueError("latlon_from_utm runs on the device: pass CUDA tensors")
+    if easts.shape != norths.shape:
+        raise ValueError(f"latlon_from_utm: easts {tuple(easts.shape)} and norths {tuple(norths.shape)} differ in shape")
+    e, n = easts.double().reshape(-1), norths.double().reshape(-1)
+    _, lla, _ = _zone_frame(zone_string).to_scene(torch.stack([e, n, torch.zeros_like(e)], 1), want_lla=True)
+    return lla[:, 0].reshape(easts.shape), lla[:, 1].reshape(easts.shape)
+
+
+def lonlat_from_utm(easts, norths, zone_string):
+    lats, lons = latlon_from_utm(easts, norths, zone_string)
+    return lons, lats
+
+
+def _dataset_geo(dataset):
+    geo = getattr(dataset, "geo", None)
+    if geo is None:
+        raise ValueError("the dataset carries no GeoFrame (`geo`): load a scene with a zone_string")
+    return geo
+
+
+def convert_utm_to_local(dataset, utm_points):
+    """un-normalised UTM (N, 3) (east, north, alt) -> the loaded dataset's normalised scene coordinates (N, 3) f64"""
+    return _dataset_geo(dataset).to_scene(utm_points)[0]
+
+
+def convert_local_to_utm(dataset, xyz):
+    """normalised scene coordinates (N, 3) -> un-normalised UTM (N, 3) f64 (east, north, alt)"""
+    return _dataset_geo(dataset).points(xyz)[0]
