@@ -44,6 +44,12 @@ extern "C" {
 #define SNERF_FLAG_SC_PASS 2u /* solar-correction variant: sample points on o + sun_d*z, evaluate only the
                                  trunk + sigma + sun-visibility branch and return weights/transparency/sun
                                  (semantic/components/rendering.py:59-78) */
+#define SNERF_FLAG_RELIGHT 4u /* relight: re-render the chunk a finished inference main pass left in `workspace` under another sun
+                                 (and t / t_s) WITHOUT re-running positions, encoding, the trunk, sigma or the rgb / semantic / beta
+                                 heads -- only the extras columns [sun | t | t_s], the sun block of the first head layer, the
+                                 sun-visibility layers, the sky colour and the composite are run again (about a tenth of a pass's
+                                 matrix work).  Every result has the bits a full pass under that sun gives.  Not with SNERF_FLAG_TRAIN or
+                                 SNERF_FLAG_SC_PASS (SNERF_ERR_BAD_DESC).  Contract: see snerf_forward */
 
 /* Arithmetic of the dense contractions.  With NONE of the arithmetic bits set a pass runs the default, SNERF_FLAG_F16X2
  * (the same for C and Python callers); the two bits exclude each other. */
@@ -170,7 +176,21 @@ int snerf_unpack_grads(const SnerfDesc* desc, const float* packed_grads, const S
  * Replaces BaseRenderer.render_rays/sample_rays (framework/components/rendering.py:84-157),
  * RSSemanticRendering._model_rendering (semantic/components/rendering.py:18-80; one call per pass),
  * inference + RSSemanticNeRF.forward (semantic/models/rs_semantic.py:8-128,260-340;
- * baseline/models/satnerf.py:8-98,203-255) and convert_sigmas (framework/util/rendering.py:4-34). */
+ * baseline/models/satnerf.py:8-98,203-255) and convert_sigmas (framework/util/rendering.py:4-34).
+ *
+ * With SNERF_FLAG_RELIGHT the call is a RELIGHT of a base pass.  The base pass is the last library call that wrote `workspace`
+ * (the same pointer); it must have been an inference main pass (neither SNERF_FLAG_TRAIN nor SNERF_FLAG_SC_PASS) with the
+ * identical descriptor apart from the RELIGHT bit -- hence the same n_rays, n_samples and arithmetic -- and the same packed
+ * parameters.  The relight reads in->sun_d, in->sun_stride, in->t and in->t_s (t_s where the descriptor needs it) and ignores
+ * rays, xyz, z_vals, z_steps and u.  It may fill any SnerfOutputs pointer a main pass can fill; out->z_vals is copied from the
+ * workspace.  snerf_workspace_bytes(desc | RELIGHT) == snerf_workspace_bytes(desc).  It overwrites only the extras columns, the sun
+ * block of the first head layer, the sun-visibility activations and pre-activations and the tile counters: any number of relights
+ * may follow one base pass, each as if it were the first.
+ * Refused on the host before any launch (SNERF_ERR_BAD_DESC): a workspace the library has not seen a pass write; one whose last
+ * pass was a training, solar-correction or backward pass; a base pass with another descriptor; out->beta when the base pass was
+ * asked for no beta (it may then have skipped the beta block of the first head layer).  The library remembers per workspace
+ * ADDRESS which pass it queued last (host side, the 256 addresses noted last): this guards against mis-sequenced calls.  It cannot
+ * know that the caller overwrote, freed or reallocated the buffer in between -- keeping the bytes intact is the caller's part. */
 int snerf_forward(const SnerfDesc* desc, const float* packed_params, const SnerfInputs* in,
                   const SnerfOutputs* out, void* workspace, size_t workspace_bytes, void* stream);
 

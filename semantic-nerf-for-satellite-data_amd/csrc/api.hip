@@ -200,6 +200,10 @@ int make_plan(const SnerfDesc* d, Plan* pl) {
   p.tau = d->t_dim; p.C = d->n_classes;
   p.siren = d->siren != 0; p.sem_sigmoid = d->sem_sigmoid != 0;
   p.train = (d->flags & SNERF_FLAG_TRAIN) != 0; p.sc = (d->flags & SNERF_FLAG_SC_PASS) != 0;
+  p.relight = (d->flags & SNERF_FLAG_RELIGHT) != 0;
+  // A relight reuses what an INFERENCE MAIN pass left: a training workspace has another layout, the solar-correction pass samples along
+  // the sun ray itself (nothing of it survives a new sun).  The plan of a relight is otherwise that of its base pass, sizes included.
+  if (p.relight && (p.train || p.sc)) return bad("SNERF_FLAG_RELIGHT cannot be combined with SNERF_FLAG_TRAIN or SNERF_FLAG_SC_PASS (a relight follows an inference main pass)");
   p.skip_mask = d->skip_mask;
   const bool sem = p.C > 0;
   const bool sbeta = sem && d->use_separate_beta_for_s;
@@ -336,17 +340,22 @@ static void build_tables(const Plan& p, const SnerfParams* w, TableBuilder& tb) 
 // check is best effort in both directions -- a mismatch on an address evicted since goes unnoticed, and a buffer the CALLER filled (a
 // clone of packed parameters) at an address last noted under the other setting is refused wrongly.  Both need the switch to change inside
 // one process, which only tests do; a process that keeps one setting never sees either.
+// A workspace's note also says WHICH pass wrote it last: a relight (SNERF_FLAG_RELIGHT) reuses the tensors of an inference main pass and
+// is refused on anything else.  The note is taken when a call is queued, so it guards against mis-sequenced calls; it cannot know that
+// the caller overwrote the buffer itself.
 namespace {
-struct BufNote { const void* p; bool composed; };
+enum PassKind { PASS_NONE = 0, PASS_MAIN_INFER, PASS_TRAIN, PASS_SC, PASS_BACKWARD };   // PASS_NONE: a packed parameter buffer
+struct BufNote { const void* p; bool composed; int kind; SnerfDesc desc; bool no_beta; };
 constexpr int NOTE_MAX = 256;
 BufNote g_notes[NOTE_MAX];
 int g_n_notes = 0, g_note_next = 0;
 std::mutex g_note_mu;
-void note_plan(const void* buf, bool composed) {
+void note_plan(const void* buf, bool composed, int kind = PASS_NONE, const SnerfDesc* desc = nullptr, bool no_beta = false) {
   std::lock_guard<std::mutex> lk(g_note_mu);
-  for (int i = 0; i < g_n_notes; ++i) if (g_notes[i].p == buf) { g_notes[i].composed = composed; return; }
-  if (g_n_notes < NOTE_MAX) g_notes[g_n_notes++] = {buf, composed};
-  else { g_notes[g_note_next] = {buf, composed}; g_note_next = (g_note_next + 1) % NOTE_MAX; }   // oldest first
+  BufNote n{buf, composed, kind, desc ? *desc : SnerfDesc{}, no_beta};
+  for (int i = 0; i < g_n_notes; ++i) if (g_notes[i].p == buf) { g_notes[i] = n; return; }
+  if (g_n_notes < NOTE_MAX) g_notes[g_n_notes++] = n;
+  else { g_notes[g_note_next] = n; g_note_next = (g_note_next + 1) % NOTE_MAX; }   // oldest first
 }
 int check_plan_note(const void* buf, bool composed, const char* who, const char* what) {
   std::lock_guard<std::mutex> lk(g_note_mu);
@@ -358,6 +367,41 @@ int check_plan_note(const void* buf, bool composed, const char* who, const char*
     }
   return SNERF_OK;
 }
+// the descriptor fields that make two passes the same pass: everything, bar the RELIGHT bit and the spelling of the default arithmetic
+bool same_pass_desc(SnerfDesc a, SnerfDesc b) {
+  a.flags &= ~(SNERF_FLAG_RELIGHT | SNERF_FLAG_F16X2); b.flags &= ~(SNERF_FLAG_RELIGHT | SNERF_FLAG_F16X2);
+  return a.n_rays == b.n_rays && a.n_samples == b.n_samples && a.fc_units == b.fc_units && a.fc_layers == b.fc_layers &&
+         a.feat_last == b.feat_last && a.skip_mask == b.skip_mask && a.n_freq == b.n_freq && a.siren == b.siren && a.t_dim == b.t_dim &&
+         a.n_classes == b.n_classes && a.sem_sigmoid == b.sem_sigmoid && a.use_tj_instead_of_beta == b.use_tj_instead_of_beta &&
+         a.use_tj_for_s == b.use_tj_for_s && a.use_separate_beta_for_s == b.use_separate_beta_for_s &&
+         a.use_separate_tj_for_semantic == b.use_separate_tj_for_semantic && a.flags == b.flags;
+}
+// A relight's base pass: the workspace's last noted pass must be an inference main pass of the same descriptor, and one that computed
+// the beta block if this relight hands out beta.
+int check_relight_note(const void* workspace, const SnerfDesc* d, bool want_beta) {
+  std::lock_guard<std::mutex> lk(g_note_mu);
+  const BufNote* n = nullptr;
+  for (int i = 0; i < g_n_notes; ++i) if (g_notes[i].p == workspace) n = &g_notes[i];
+  if (!n || n->kind == PASS_NONE) {
+    set_error("snerf_forward(SNERF_FLAG_RELIGHT): no base pass -- the library has not seen an inference main pass write this workspace");
+    return SNERF_ERR_BAD_DESC;
+  }
+  if (n->kind != PASS_MAIN_INFER) {
+    set_error("snerf_forward(SNERF_FLAG_RELIGHT): the workspace's last pass was a %s pass, not an inference main pass",
+              n->kind == PASS_TRAIN ? "training (SNERF_FLAG_TRAIN)" : n->kind == PASS_SC ? "solar-correction (SNERF_FLAG_SC_PASS)" : "backward");
+    return SNERF_ERR_BAD_DESC;
+  }
+  if (!same_pass_desc(n->desc, *d)) {
+    set_error("snerf_forward(SNERF_FLAG_RELIGHT): the descriptor differs from the base pass's (base %d rays x %d samples, flags %u; this call %d x %d, flags %u)",
+              n->desc.n_rays, n->desc.n_samples, n->desc.flags, d->n_rays, d->n_samples, d->flags);
+    return SNERF_ERR_BAD_DESC;
+  }
+  if (want_beta && n->no_beta) {
+    set_error("snerf_forward(SNERF_FLAG_RELIGHT): beta is asked of a base pass that was asked for no beta and skipped the beta block of the first head layer");
+    return SNERF_ERR_BAD_DESC;
+  }
+  return SNERF_OK;
+}
 }  // namespace
 
 static int check_inputs(const Plan& p, const SnerfInputs* in) {
@@ -365,6 +409,7 @@ static int check_inputs(const Plan& p, const SnerfInputs* in) {
   if (!in->sun_d || in->sun_stride < 3) { set_error("sun_d (N,3) with stride >= 3 is required"); return SNERF_ERR_NULL; }
   if (!in->t) { set_error("t (N,tau) is required"); return SNERF_ERR_NULL; }
   if (p.x_ts >= 0 && !in->t_s) { set_error("t_s is required with use_separate_tj_for_semantic"); return SNERF_ERR_NULL; }
+  if (p.relight) return SNERF_OK;   // positions and depths are the base pass's
   if (in->xyz) {
     if (!in->z_vals) { set_error("explicit xyz needs explicit z_vals"); return SNERF_ERR_NULL; }
   } else {
@@ -456,7 +501,12 @@ int snerf_forward(const SnerfDesc* desc, const float* packed_params, const Snerf
   if (((uintptr_t)workspace & 255) || ((uintptr_t)packed_params & 255)) { set_error("workspace and packed params must be 256-byte aligned"); return SNERF_ERR_WORKSPACE; }
   RC(check_inputs(p, in));
   RC(check_plan_note(packed_params, p.compose_feats, "snerf_forward", "packed parameter buffer"));
-  note_plan(workspace, p.compose_feats);
+  if (p.relight) {   // every refusal before any launch; the note stays the base pass's, so relights chain
+    RC(check_plan_note(workspace, p.compose_feats, "snerf_forward", "workspace"));
+    RC(check_relight_note(workspace, desc, out->beta != nullptr));
+  } else {
+    note_plan(workspace, p.compose_feats, p.train ? PASS_TRAIN : p.sc ? PASS_SC : PASS_MAIN_INFER, desc, skips_beta_block(p, out->beta != nullptr));
+  }
   return forward_bsp(p, packed_params, in, out, workspace, (hipStream_t)stream);
 }
 
@@ -471,6 +521,7 @@ int snerf_backward(const SnerfDesc* desc, const float* packed_params, const Sner
   RC(check_inputs(p, in));
   RC(check_plan_note(packed_params, p.compose_feats, "snerf_backward", "packed parameter buffer"));
   RC(check_plan_note(workspace, p.compose_feats, "snerf_backward", "workspace"));
+  note_plan(workspace, p.compose_feats, PASS_BACKWARD, desc);
   return backward_bsp(p, packed_params, in, gout, packed_grads, d_t, d_t_s, workspace, (hipStream_t)stream);
 }
 

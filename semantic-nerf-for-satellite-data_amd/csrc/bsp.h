@@ -270,6 +270,9 @@ struct EncodeArgs;
 namespace bsp {
 // x = o + d z, gamma(x) (or raw x) as planes [P][Ep]; the [sun | t | t_s] block as columns [fa_col0, +16) of the [P][FA] tensor
 int launch_encode_bsp(const EncodeArgs& a, char* pe, int* Epe, char* fa, int* Efa, int fa_col0, int pl, hipStream_t st);
+// relight (SNERF_FLAG_RELIGHT): the extras block alone -- planes and block exponents of columns [fa_col0, +16) for every row block, the
+// bits launch_encode_bsp writes for the same sun_d / t / t_s (one device function serves both); clears a.zero like it
+int launch_relight_extras(const EncodeArgs& a, char* fa, int* Efa, int fa_col0, int pl, hipStream_t st);
 int launch_zero_cols(char* base, size_t pitch, size_t width_bytes, int rows, hipStream_t st);   // width_bytes % 16 == 0
 // [rows][32] fp32 -> 256-row partial column sums (+ planes [rows][32] and one exponent per 128 rows when planes != null)
 int launch_colsum32_bsp(const float* in, int rows, float* partial, char* planes, int* E, int pl, hipStream_t st);

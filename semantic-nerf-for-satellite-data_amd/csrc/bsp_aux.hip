@@ -294,6 +294,36 @@ __device__ __forceinline__ float extras_value(const EncodeArgs& a, int n, int c)
   return 0.f;
 }
 
+// The extras block [sun | t | t_s] of one 128-point row block, in two steps that the encode kernel and the relight kernel share: a
+// thread's part of the block's |max| (over the rays the block touches), and one point's 16 columns split into planes under the
+// block's scale.  A relight writes the bits a full pass writes for the same inputs because it runs these two functions.
+__device__ __forceinline__ float extras_absmax_part(const EncodeArgs& a, long long p0, int npts, int t) {
+  const int n0 = (int)((unsigned)p0 / (unsigned)a.S), n1 = (int)((unsigned)(p0 + npts - 1) / (unsigned)a.S);
+  float me = 0.f;
+  for (int i = t; i < (n1 - n0 + 1) * 16; i += 256) me = fmaxf(me, fabsf(extras_value(a, n0 + (i >> 4), i & 15)));
+  return me;
+}
+// 16 fp32 values times `sc` -> one 16-column group at d: [hi(16) | lo(16)], one plane: hi only
+__device__ __forceinline__ void store_group16(char* d, const float (&v)[16], float sc, int npl) {
+  u32x4 hi, lo;
+  float h8[8];
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) h8[j] = v[8 * half + j];
+    split8(h8, sc, hi, lo);
+    *reinterpret_cast<u32x4*>(d + 16 * half) = hi;
+    if (npl == 2) *reinterpret_cast<u32x4*>(d + 32 + 16 * half) = lo;
+  }
+}
+__device__ __forceinline__ void extras_store_point(const EncodeArgs& a, char* fa, int fa_col0, int npl, long long point, float sc) {
+  const int n = (int)((unsigned)point / (unsigned)a.S);
+  float v[16];
+#pragma unroll
+  for (int j = 0; j < 16; ++j) v[j] = extras_value(a, n, j);
+  store_group16(fa + (size_t)point * a.FA * 2 * npl + g16_off(fa_col0, npl), v, sc, npl);
+}
+
 struct EncodeBsp {
   EncodeArgs a;                 // pe / fa fields unused here
   char* pe; int* Epe;           // planes [P][Ep]
@@ -317,10 +347,7 @@ __global__ __launch_bounds__(256) void encode_bsp_kernel(EncodeBsp g) {
       point_xyz(a, p0 + i, x);
       mx = fmaxf(mx, fmaxf(fabsf(x[0]), fmaxf(fabsf(x[1]), fabsf(x[2]))));
     }
-  if (g.fa != nullptr) {
-    const int n0 = (int)((unsigned)p0 / (unsigned)a.S), n1 = (int)((unsigned)(p0 + npts - 1) / (unsigned)a.S);
-    for (int i = t; i < (n1 - n0 + 1) * 16; i += 256) me = fmaxf(me, fabsf(extras_value(a, n0 + (i >> 4), i & 15)));
-  }
+  if (g.fa != nullptr) me = extras_absmax_part(a, p0, npts, t);
   const int e_pe = a.F > 0 ? 13 : exp_of_maxbits(__float_as_uint(block_max_256(mx, sm)));
   const int e_x = g.fa != nullptr ? exp_of_maxbits(__float_as_uint(block_max_256(me, sm))) : 0;
   if (t == 0) {
@@ -332,48 +359,28 @@ __global__ __launch_bounds__(256) void encode_bsp_kernel(EncodeBsp g) {
   for (int item = t; item < npts * ngrp; item += 256) {
     const int pl = item / ngrp, grp = item - pl * ngrp;
     const long long point = p0 + pl;
+    if (grp >= gpe) { extras_store_point(a, g.fa, g.fa_col0, g.pl, point, s_x); continue; }
     float v[16];
-    char* d;
-    float sc;
-    if (grp < gpe) {
-      float x[3];
-      point_xyz(a, point, x);
+    float x[3];
+    point_xyz(a, point, x);
 #pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        const int col = 16 * grp + j;
-        float r = 0.f;
-        if (a.F > 0) {
-          if (col < 6 * a.F) {
-            const int k = col / 6, q = col - 6 * k, c = q >= 3 ? q - 3 : q;
-            const float xc = c == 0 ? x[0] : (c == 1 ? x[1] : x[2]);
-            float s, co;
-            sincos_acc((float)(1 << k) * xc, &s, &co);
-            r = q >= 3 ? co : s;
-          }
-        } else if (col < 3) {
-          r = col == 0 ? x[0] : (col == 1 ? x[1] : x[2]);
+    for (int j = 0; j < 16; ++j) {
+      const int col = 16 * grp + j;
+      float r = 0.f;
+      if (a.F > 0) {
+        if (col < 6 * a.F) {
+          const int k = col / 6, q = col - 6 * k, c = q >= 3 ? q - 3 : q;
+          const float xc = c == 0 ? x[0] : (c == 1 ? x[1] : x[2]);
+          float s, co;
+          sincos_acc((float)(1 << k) * xc, &s, &co);
+          r = q >= 3 ? co : s;
         }
-        v[j] = r;
+      } else if (col < 3) {
+        r = col == 0 ? x[0] : (col == 1 ? x[1] : x[2]);
       }
-      d = g.pe + (size_t)point * a.Ep * 2 * g.pl + (size_t)grp * 32 * g.pl;
-      sc = s_pe;
-    } else {
-      const int n = (int)((unsigned)point / (unsigned)a.S);
-#pragma unroll
-      for (int j = 0; j < 16; ++j) v[j] = extras_value(a, n, j);
-      d = g.fa + (size_t)point * a.FA * 2 * g.pl + g16_off(g.fa_col0, g.pl);
-      sc = s_x;
+      v[j] = r;
     }
-    u32x4 hi, lo;
-    float h8[8];
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) h8[j] = v[8 * half + j];
-      split8(h8, sc, hi, lo);
-      *reinterpret_cast<u32x4*>(d + 16 * half) = hi;
-      if (g.pl == 2) *reinterpret_cast<u32x4*>(d + 32 + 16 * half) = lo;
-    }
+    store_group16(g.pe + (size_t)point * a.Ep * 2 * g.pl + (size_t)grp * 32 * g.pl, v, s_pe, g.pl);
   }
 }
 
@@ -385,6 +392,36 @@ int launch_encode_bsp(const EncodeArgs& a, char* pe, int* Epe, char* fa, int* Ef
   EncodeBsp g{a, pe, Epe, fa, Efa, fa_col0, pl};
   const long long P = (long long)a.N * a.S;
   hipLaunchKernelGGL(encode_bsp_kernel, dim3((unsigned)((P + 127) / 128)), dim3(256), 0, st, g);
+  SNERF_LAUNCH_CHECK();
+  return SNERF_OK;
+}
+
+// ---- relight: the extras block alone ---------------------------------------------------------------------------------------------
+// Rewrites columns [fa_col0, fa_col0 + 16) of the [P][FA] tensor of a finished inference pass -- planes AND the block exponents of
+// that column block, for every 128-point row block -- from a new sun_d (and t / t_s): the whole block, because a new sun can move
+// the block's |max| and with it the exponent under which the t columns lie.  Clears the pass's tile counters like the encode kernel.
+struct RelightExtras { EncodeArgs a; char* fa; int* Efa; int fa_col0; int pl; };
+__global__ __launch_bounds__(256) void relight_extras_kernel(RelightExtras g) {
+  __shared__ float sm[4];
+  const EncodeArgs& a = g.a;
+  const int rb = blockIdx.x, t = threadIdx.x;
+  if (rb == 0) for (int i = t; i < a.zero_n; i += 256) a.zero[i] = 0u;
+  const long long P = (long long)a.N * a.S;
+  const long long p0 = (long long)rb * 128;
+  const int npts = (int)min((long long)128, P - p0);
+  const int e_x = exp_of_maxbits(__float_as_uint(block_max_256(extras_absmax_part(a, p0, npts, t), sm)));
+  if (t == 0) g.Efa[(size_t)rb * ncb_of(a.FA) + (g.fa_col0 >> 7)] = e_x;
+  const float s_x = pow2f(e_x);
+  for (int pl = t; pl < npts; pl += 256) extras_store_point(a, g.fa, g.fa_col0, g.pl, p0 + pl, s_x);
+}
+int launch_relight_extras(const EncodeArgs& a, char* fa, int* Efa, int fa_col0, int pl, hipStream_t st) {
+  if (!fa || !Efa || (fa_col0 & 127) || (a.FA & 15) || a.Xp != 16 || fa_col0 + 16 > a.FA || a.N <= 0 || a.S <= 0 || !a.sun_d || !a.t || (pl != 1 && pl != 2)) {
+    set_error("relight extras: extras block of 16 columns at a multiple of 128 inside the [P][FA] tensor");
+    return SNERF_ERR_BAD_DESC;
+  }
+  RelightExtras g{a, fa, Efa, fa_col0, pl};
+  const long long P = (long long)a.N * a.S;
+  hipLaunchKernelGGL(relight_extras_kernel, dim3((unsigned)((P + 127) / 128)), dim3(256), 0, st, g);
   SNERF_LAUNCH_CHECK();
   return SNERF_OK;
 }

@@ -67,89 +67,100 @@ int forward_bsp(const Plan& p, const float* pk, const SnerfInputs* in, const Sne
   auto launch_kc = [&](bsp::KcArgs& g) { g.rev = kcq & 1; g.tile_ctr = kcq < KCQ_SLOTS ? ws.i(p.o_kcq) + 16 * kcq++ : nullptr; return bsp::launch_kc(g, st); };
   const int P = p.P, W = p.W, H = p.H;
   float* z = ws.f(p.o_z);
-  // 1. depths
-  if (in->z_vals) SNERF_HIP_CHECK(hipMemcpyAsync(z, in->z_vals, sizeof(float) * P, hipMemcpyDeviceToDevice, st));
-  else RC(launch_sample_z(in->rays, in->z_steps, in->u, z, p.N, p.S, st));
-  if (out->z_vals) SNERF_HIP_CHECK(hipMemcpyAsync(out->z_vals, z, sizeof(float) * P, hipMemcpyDeviceToDevice, st));
-  // 2. positions + encoding + extras, written as planes with their block exponents
+  const int act = p.siren ? ACT_SIN : ACT_RELU;
+  const bool fused = p.fuse_trunk && bsp::trunk_fusion_enabled();
+  const bool feats_launch = !p.compose_feats && (!fused || p.train);   // feats_from_xyz as a launch of its own
+  const size_t EB = 2 * (size_t)p.pl;   // bytes per element of a plane tensor
+  // The extras block [sun | t | t_s] of the [feats or h_last | extras] tensor, as both its writers take it
   EncodeArgs ea;
-  ea.rays = in->xyz ? nullptr : in->rays; ea.xyz = in->xyz; ea.z = z;
   ea.sun_d = in->sun_d; ea.sun_stride = in->sun_stride; ea.t = in->t; ea.t_s = in->t_s;
-  ea.dir_is_sun = (p.sc && !in->xyz) ? 1 : 0;
   ea.N = p.N; ea.S = p.S; ea.F = p.F; ea.Ep = p.Ep;
   ea.FA = p.FA; ea.W = p.Wf; ea.Xp = p.Xp; ea.x_sun = p.x_sun; ea.x_t = p.x_t; ea.x_ts = p.x_ts; ea.tau = p.tau;
   ea.zero = ws.u(p.o_kcq); ea.zero_n = KCQ_SLOTS * 16;
-  RC(bsp::launch_encode_bsp(ea, ws.c(p.pe.o), ws.i(p.pe.e), ws.c(p.fa.o), ws.i(p.fa.e), p.Wf, p.pl, st));
-  const size_t EB = 2 * (size_t)p.pl;   // bytes per element of a plane tensor
-  if (p.Wf > W)   // pad columns between feats and extras (narrow test networks only): zero planes, read against zero weights
-    RC(bsp::launch_zero_cols(ws.c(p.fa.o) + (size_t)W * EB, (size_t)p.FA * EB, (size_t)(p.Wf - W) * EB, P, st));
-  // 3. trunk (rs_semantic.py:325-334)
-  const int act = p.siren ? ACT_SIN : ACT_RELU;
-  const bool fused = p.fuse_trunk && bsp::trunk_fusion_enabled();
-  if (fused) {   // one persistent launch, the activation tile resident in LDS (bsp_trunk.hip); inference: only the last layer's planes + sigma's partials leave
-    bsp::TrunkArgs g;
-    g.pe = ws.c(p.pe.o); g.Epe = ws.i(p.pe.e); g.P = P; g.W = W; g.L = p.L; g.skip_mask = p.skip_mask;
-    // feats (rs_semantic.py:338) rides as one more layer of an inference pass, entry L: written into the first W columns of the
-    // [feats | sun | t | t_s] tensor.  (One plane: fuse_trunk holds only with p.pl == 1.)
-    const bool fused_feats = !p.train;
-    for (int i = 0; i < p.L + (fused_feats ? 1 : 0); ++i) {
-      const WOp w = wop(p, pk, i < p.L ? p.wj_tr[i] : p.wj_fs);
-      g.Wp[i] = w.W; g.EW[i] = w.EW; g.w_bytes[i] = w.bytes; g.K[i] = w.K;
-      g.bias[i] = pk + (i < p.L ? p.b_tr[i] : p.b_fs);
-      g.w0[i] = i == 0 ? 30.f : 1.f;
-    }
-    if (fused_feats) { g.F = ws.c(p.fa.o); g.EF = ws.i(p.fa.e); g.ldf = p.fa.ld; }
-    for (int i = 0; i < p.L && p.train; ++i) {   // training (feats stays a launch of its own): every layer's planes and sign words leave for the backward pass
-      g.H[i] = ws.c(p.h[i].o); g.EH[i] = ws.i(p.h[i].e); g.Hsign[i] = ws.u(p.h[i].s);
-    }
-    g.nd_w = pk + p.w_fs + (size_t)W * W; g.nd_out = ws.f(p.o_sigpart); g.nd_stride = p.Pp;
-    g.tile_ctr = ws.i(p.o_kcq) + 16 * kcq++;
-    RC(bsp::launch_trunk(g, p.train, st));
-  }
-  for (int i = 0; i < p.L && !fused; ++i) {
-    bsp::KcArgs g;
-    const bool skip = (p.skip_mask >> i) & 1u;
-    if (i == 0) ws.a(g, p.pe, p.Ep);
-    else if (skip) { ws.a(g, p.pe, p.Ep); ws.a2(g, p.h[i - 1]); }   // [gamma | h]
-    else ws.a(g, p.h[i - 1], W);
-    weights(g, p, pk, p.wj_tr[i]);
-    g.I = P; g.J = W; g.K = p.k_tr[i];
-    ws.out(g, p.h[i]);   // (inference: h[i] alternates between two buffers, api.hip: plan_bsp)
-    g.bias = pk + p.b_tr[i]; g.act = act; g.w0 = (p.siren && i == 0) ? 30.f : 1.f;
-    if (i == p.L - 1 && p.nd_sig) {   // sigma's 1-wide projection rides in this launch's epilogue (bsp_kc.hip: NDOT)
+  if (p.relight) {
+    // Relight (SNERF_FLAG_RELIGHT; api.hip has checked that the workspace holds an inference main pass of this plan): z, the
+    // [feats or h_last] columns of fa, sigma's partials / buffer, the rgb / semantic / beta blocks of h1 and the final layers'
+    // partials / buffer are the base pass's.  None of the launches below writes them: fa is a tensor of its own (not one of the
+    // two alternating trunk buffers), the head launch writes the sun block's columns of h1 only and folds no finals.  What a new
+    // sun changes is the extras block (whole: its |max|, hence the exponent of the t columns, may move), then everything from the
+    // first head layer's sun block on.  Each launch keeps the tile direction (rev) and the counter slot it has in the full pass.
+    if (out->z_vals) SNERF_HIP_CHECK(hipMemcpyAsync(out->z_vals, z, sizeof(float) * P, hipMemcpyDeviceToDevice, st));
+    RC(bsp::launch_relight_extras(ea, ws.c(p.fa.o), ws.i(p.fa.e), p.Wf, p.pl, st));
+    kcq = (fused ? 1 : p.L) + (feats_launch ? 1 : 0);
+  } else {
+    // 1. depths
+    if (in->z_vals) SNERF_HIP_CHECK(hipMemcpyAsync(z, in->z_vals, sizeof(float) * P, hipMemcpyDeviceToDevice, st));
+    else RC(launch_sample_z(in->rays, in->z_steps, in->u, z, p.N, p.S, st));
+    if (out->z_vals) SNERF_HIP_CHECK(hipMemcpyAsync(out->z_vals, z, sizeof(float) * P, hipMemcpyDeviceToDevice, st));
+    // 2. positions + encoding + extras, written as planes with their block exponents
+    ea.rays = in->xyz ? nullptr : in->rays; ea.xyz = in->xyz; ea.z = z;
+    ea.dir_is_sun = (p.sc && !in->xyz) ? 1 : 0;
+    RC(bsp::launch_encode_bsp(ea, ws.c(p.pe.o), ws.i(p.pe.e), ws.c(p.fa.o), ws.i(p.fa.e), p.Wf, p.pl, st));
+    if (p.Wf > W)   // pad columns between feats and extras (narrow test networks only): zero planes, read against zero weights
+      RC(bsp::launch_zero_cols(ws.c(p.fa.o) + (size_t)W * EB, (size_t)p.FA * EB, (size_t)(p.Wf - W) * EB, P, st));
+    // 3. trunk (rs_semantic.py:325-334)
+    if (fused) {   // one persistent launch, the activation tile resident in LDS (bsp_trunk.hip); inference: only the last layer's planes + sigma's partials leave
+      bsp::TrunkArgs g;
+      g.pe = ws.c(p.pe.o); g.Epe = ws.i(p.pe.e); g.P = P; g.W = W; g.L = p.L; g.skip_mask = p.skip_mask;
+      // feats (rs_semantic.py:338) rides as one more layer of an inference pass, entry L: written into the first W columns of the
+      // [feats | sun | t | t_s] tensor.  (One plane: fuse_trunk holds only with p.pl == 1.)
+      const bool fused_feats = !p.train;
+      for (int i = 0; i < p.L + (fused_feats ? 1 : 0); ++i) {
+        const WOp w = wop(p, pk, i < p.L ? p.wj_tr[i] : p.wj_fs);
+        g.Wp[i] = w.W; g.EW[i] = w.EW; g.w_bytes[i] = w.bytes; g.K[i] = w.K;
+        g.bias[i] = pk + (i < p.L ? p.b_tr[i] : p.b_fs);
+        g.w0[i] = i == 0 ? 30.f : 1.f;
+      }
+      if (fused_feats) { g.F = ws.c(p.fa.o); g.EF = ws.i(p.fa.e); g.ldf = p.fa.ld; }
+      for (int i = 0; i < p.L && p.train; ++i) {   // training (feats stays a launch of its own): every layer's planes and sign words leave for the backward pass
+        g.H[i] = ws.c(p.h[i].o); g.EH[i] = ws.i(p.h[i].e); g.Hsign[i] = ws.u(p.h[i].s);
+      }
       g.nd_w = pk + p.w_fs + (size_t)W * W; g.nd_out = ws.f(p.o_sigpart); g.nd_stride = p.Pp;
+      g.tile_ctr = ws.i(p.o_kcq) + 16 * kcq++;
+      RC(bsp::launch_trunk(g, p.train, st));
     }
-    RC(launch_kc(g));
+    for (int i = 0; i < p.L && !fused; ++i) {
+      bsp::KcArgs g;
+      const bool skip = (p.skip_mask >> i) & 1u;
+      if (i == 0) ws.a(g, p.pe, p.Ep);
+      else if (skip) { ws.a(g, p.pe, p.Ep); ws.a2(g, p.h[i - 1]); }   // [gamma | h]
+      else ws.a(g, p.h[i - 1], W);
+      weights(g, p, pk, p.wj_tr[i]);
+      g.I = P; g.J = W; g.K = p.k_tr[i];
+      ws.out(g, p.h[i]);   // (inference: h[i] alternates between two buffers, api.hip: plan_bsp)
+      g.bias = pk + p.b_tr[i]; g.act = act; g.w0 = (p.siren && i == 0) ? 30.f : 1.f;
+      if (i == p.L - 1 && p.nd_sig) {   // sigma's 1-wide projection rides in this launch's epilogue (bsp_kc.hip: NDOT)
+        g.nd_w = pk + p.w_fs + (size_t)W * W; g.nd_out = ws.f(p.o_sigpart); g.nd_stride = p.Pp;
+      }
+      RC(launch_kc(g));
+    }
+    const PlaneT& hl = p.h[p.L - 1];
+    if (!p.nd_sig) {  // sigma pre-activation (rs_semantic.py:337) -> 32-wide fp32 buffer, column 0
+      bsp::KcArgs g;
+      ws.a(g, hl, W); weights(g, p, pk, p.wj_sig);
+      g.I = P; g.J = NARROW; g.K = W; g.Cf = ws.f(p.o_sigo); g.bias = pk + p.b_fs + W;
+      RC(bsp::launch_kc_narrow(g, st));
+    }
+    // Composed plans (Plan::compose_feats) run no feats layer: h[L - 1] IS columns [0, W) of the [. | sun | t | t_s] tensor, and the first
+    // head layer below multiplies it by W_c = W_h1[:, :W] W_f with the bias b_c that the pack built.
+    if (feats_launch) {  // feats (rs_semantic.py:338), written into the first W columns of the [feats | sun | t | t_s] tensor
+      bsp::KcArgs g;
+      ws.a(g, hl, W); weights(g, p, pk, p.wj_fs);
+      g.I = P; g.J = W; g.K = W; ws.out(g, p.fa); g.bias = pk + p.b_fs;
+      RC(launch_kc(g));
+    }
   }
-  const PlaneT& hl = p.h[p.L - 1];
-  if (!p.nd_sig) {  // sigma pre-activation (rs_semantic.py:337) -> 32-wide fp32 buffer, column 0
-    bsp::KcArgs g;
-    ws.a(g, hl, W); weights(g, p, pk, p.wj_sig);
-    g.I = P; g.J = NARROW; g.K = W; g.Cf = ws.f(p.o_sigo); g.bias = pk + p.b_fs + W;
-    RC(bsp::launch_kc_narrow(g, st));
-  }
-  // Composed plans (Plan::compose_feats) run no feats layer: h[L - 1] IS columns [0, W) of the [. | sun | t | t_s] tensor, and the first
-  // head layer below multiplies it by W_c = W_h1[:, :W] W_f with the bias b_c that the pack built.
-  if (!p.compose_feats && (!fused || p.train)) {  // feats (rs_semantic.py:338), written into the first W columns of the [feats | sun | t | t_s] tensor
-    bsp::KcArgs g;
-    ws.a(g, hl, W); weights(g, p, pk, p.wj_fs);
-    g.I = P; g.J = W; g.K = W; ws.out(g, p.fa); g.bias = pk + p.b_fs;
-    RC(launch_kc(g));
-  }
-  const int r0 = p.sc ? p.sun_col : 0;
-  {  // first layer of every head in one GEMM (sc pass: sun-visibility block only)
+  const int r0 = (p.sc || p.relight) ? p.sun_col : 0;
+  {  // first layer of every head in one GEMM (sc pass, relight: sun-visibility block only; a relight writes it at its column of the main pass's h1)
     bsp::KcArgs g;
     ws.a(g, p.fa, p.FA); weights(g, p, pk, p.wj_h1, r0);
-    g.I = P; g.J = p.h1w; g.K = p.FA; ws.out(g, p.h1);
+    g.I = P; g.J = p.relight ? H : p.h1w; g.K = p.FA; ws.out(g, p.h1, p.relight ? p.sun_col : 0);
     g.bias = pk + (p.compose_feats ? p.o_bc : p.b_h1) + r0; g.act = act; g.w0 = 1.f;
-    if (p.nd_fin) {   // the heads' final layers (block-diagonal [32][KF]: block b's rows read only block b's 256 columns) in this launch's epilogue
+    if (p.nd_fin && !p.relight) {   // (a relight folds no finals: the base pass's partials are what its composite reads)   // the heads' final layers (block-diagonal [32][KF]: block b's rows read only block b's 256 columns) in this launch's epilogue
       g.nd_w = pk + p.w_fin; g.nd_ldw = p.KF; g.nd_omax = ND_FIN; g.nd_out = ws.f(p.o_finpart); g.nd_stride = p.Pp;
       auto blk = [&](int b, int col, int n) { if (b >= 0) { g.nd_rows[b] = n; g.nd_row0[b] = col; } };
       blk(p.blk_rgb, Plan::col_rgb, 3); blk(p.blk_sem, Plan::col_sem, p.C); blk(p.blk_beta, Plan::col_beta, 1); blk(p.blk_sbeta, Plan::col_sbeta, 1);
-      // A frame that asks for no beta (full-frame inference: rgb / depth / labels -- eval/extract_pointcloud.py:66-79) does not compute the
-      // beta block: a quarter of this launch.  Only with the finals folded (each block's final rows read its own tile only; the 32-wide
-      // final launch would contract the unwritten columns) and when beta is this pass's only use of the block.
-      if (!p.train && H == 256 && p.blk_beta >= 0 && out->beta == nullptr && !p.rgb_t && p.blk_sbeta < 0) g.tj_skip = p.blk_beta;
+      if (skips_beta_block(p, out->beta != nullptr)) g.tj_skip = p.blk_beta;   // (plan.h)
     }
     RC(launch_kc(g));
   }
@@ -170,7 +181,7 @@ int forward_bsp(const Plan& p, const float* pk, const SnerfInputs* in, const Sne
     g.I = P; g.J = NARROW; g.K = H; g.Cf = ws.f(p.o_suno); g.bias = pk + p.b_s4;
     RC(bsp::launch_kc_narrow(g, st));
   }
-  if (!p.sc && !p.nd_fin) {  // last layer of rgb / beta / beta_s / semantic heads: block-diagonal [32][KF]
+  if (!p.sc && !p.nd_fin && !p.relight) {  // last layer of rgb / beta / beta_s / semantic heads: block-diagonal [32][KF]
     bsp::KcArgs g;
     ws.a(g, p.h1, p.KF); weights(g, p, pk, p.wj_fin);
     g.I = P; g.J = NARROW; g.K = p.KF; g.Cf = ws.f(p.o_fino); g.bias = pk + p.b_fin;

@@ -29,6 +29,7 @@ struct Plan {
   int N = 0, S = 0, P = 0, Pp = 0;
   int W = 0, H = 0, L = 0, E = 0, Ep = 0, F = 0, tau = 0, C = 0;
   bool siren = false, train = false, sc = false, sem_sigmoid = false;
+  bool relight = false;   // SNERF_FLAG_RELIGHT: the sun-dependent launches alone, on the workspace of a finished inference main pass (same layout)
   unsigned skip_mask = 0;
   // extras columns appended to the feats buffer: [sun(3) | t(tau) | t_s(tau)] padded to 4
   int x_sun = 0, x_t = 3, x_ts = -1, Xp = 0, FA = 0;
@@ -99,6 +100,14 @@ struct Plan {
   int comp_blocks = 0;
   size_t ws_bytes = 0;
 };
+
+// A frame that asks for no beta (full-frame inference: rgb / depth / labels -- eval/extract_pointcloud.py:66-79) does not compute the
+// beta block of the fused first head layer: a quarter of that launch.  Only with the finals folded (each block's final rows read
+// its own tile only; the 32-wide final launch would contract the unwritten columns) and when beta is the pass's only use of the block.
+// (bsp_pass.hip: KcArgs::tj_skip; api.hip notes it per workspace: a relight cannot hand out a beta its base pass never computed.)
+inline bool skips_beta_block(const Plan& p, bool want_beta) {
+  return p.nd_fin && !p.train && p.H == 256 && p.blk_beta >= 0 && !want_beta && !p.rgb_t && p.blk_sbeta < 0;
+}
 
 constexpr int KCQ_SLOTS = 64;
 struct DwSplit { int ns = 1; int k_split = 32; };

@@ -16,7 +16,15 @@ and rules.  Files under `output_dp`/nadir/:
     rgb.png/.tif, albedo.png/.tif        the nadir ortho-image under the chosen sun and the albedo: uint8
     sun.png/.tif, beta.png/.tif          the shadow map and the uncertainty: float32 in the .tif, BONE in the .png
     dsm.png/.tif                         the rendered surface altitude, every cell filled: float32 in the .tif, JET in the .png
-    label.png/.tif                       the class seen from above (a semantic model only): ids in the .tif, the palette in the .png"""
+    label.png/.tif                       the class seen from above (a semantic model only): ids in the .tif, the palette in the .png
+
+export_sun_sweep writes that map under a list of suns (eval/utils/ortho.py nadir_sun_sweep), again by the same
+writers and rules.  Files under `output_dp`/nadir/sweep/:
+    rgb_{k:03d}.png/.tif                 the nadir ortho-image under sun k: uint8
+    sun_{k:03d}.png/.tif                 the shadow map under sun k: float32 in the .tif, BONE in the .png
+    lit_share.png/.tif                   the mean of the shadow maps -- the share of the suns that light a cell: float32, BONE
+    suns.json                            [{"index", "elevation_deg", "azimuth_deg"}], the suns in order"""
+import json
 import os
 
 import numpy as np
@@ -27,7 +35,7 @@ from ..framework.util import colormaps, img_utils
 from ..framework.visualize import to_uint8_image
 from ..parallel import world
 from .utils import vismaps
-from .utils.ortho import NO_LABEL, nadir_products, ortho_products
+from .utils.ortho import NO_LABEL, nadir_products, nadir_sun_sweep, ortho_products
 
 
 def _png(fp, chw_u8):
@@ -40,6 +48,13 @@ def label_colors(label, palette):
     lut = torch.zeros((256, 3), dtype=torch.uint8)
     lut[:min(len(pal), NO_LABEL)] = pal[:NO_LABEL]
     return lut.to(label.device)[label.long()].permute(2, 0, 1).contiguous()
+
+
+def _scalar_plane(fp, name, plane, cmap, grid, zone_string):
+    """a float32 plane as `name`.png (`cmap` between the plane's own bounds) and `name`.tif"""
+    stats = vismaps.plane_minmax(plane, vismaps.new_stats(plane.device), "user")
+    _png(fp(name + ".png"), vismaps.colormap(plane, colormaps.table(cmap, plane.device), stats, "user"))
+    img_utils.save_geotiff(fp(name + ".tif"), plane, grid, zone_string)
 
 
 @torch.no_grad()
@@ -74,10 +89,7 @@ def export_ortho(cfgs, renderer, models, images, output_dp, split="test", palett
         if "vote_share" in prod:
             planes.append(("vote_share", colormaps.COLORMAP_BONE))
         for key, cmap in planes:
-            plane = prod[key]
-            stats = vismaps.plane_minmax(plane, vismaps.new_stats(plane.device), "user")
-            _png(fp(key + ".png"), vismaps.colormap(plane, colormaps.table(cmap, plane.device), stats, "user"))
-            img_utils.save_geotiff(fp(key + ".tif"), plane, grid, zone_string)
+            _scalar_plane(fp, key, prod[key], cmap, grid, zone_string)
     return dict(prod, files=files)
 
 
@@ -106,8 +118,32 @@ def export_nadir(cfgs, renderer, models, output_dp, palette=None, zone_string=No
             _png(fp("label.png"), label_colors(prod["label"], pal))
             img_utils.save_geotiff(fp("label.tif"), prod["label"], grid, zone_string)
         for key, cmap in (("dsm", colormaps.COLORMAP_JET), ("sun", colormaps.COLORMAP_BONE), ("beta", colormaps.COLORMAP_BONE)):
-            plane = prod[key]
-            stats = vismaps.plane_minmax(plane, vismaps.new_stats(plane.device), "user")
-            _png(fp(key + ".png"), vismaps.colormap(plane, colormaps.table(cmap, plane.device), stats, "user"))
-            img_utils.save_geotiff(fp(key + ".tif"), plane, grid, zone_string)
+            _scalar_plane(fp, key, prod[key], cmap, grid, zone_string)
+    return dict(prod, files=files)
+
+
+@torch.no_grad()
+def export_sun_sweep(cfgs, renderer, models, output_dp, zone_string=None, **kwargs):
+    """nadir_sun_sweep(cfgs, renderer, models, **kwargs), written to `output_dp`/nadir/sweep/ by export_nadir's writers and rules:
+    per sun k rgb_{k:03d} and sun_{k:03d} -- the files export_nadir writes as rgb and sun under that sun --, lit_share, and
+    suns.json.  `zone_string`: the GeoTIFFs' UTM zone, default the zone of the GeoFrame in use.  Every rank computes the products
+    (with sharded=True each renders its share of the lattice); only rank 0 writes.  Returns the products plus "files"."""
+    prod = nadir_sun_sweep(cfgs, renderer, models, **kwargs)
+    if zone_string is None:
+        g = kwargs.get("geo") or getattr(kwargs.get("dataset"), "geo", None)
+        zone_string = getattr(g, "zone_string", None)
+    grid = prod["grid"]
+    out_dp = os.path.join(output_dp, "nadir", "sweep")
+    files = {}
+    if world()[0] == 0:
+        os.makedirs(out_dp, exist_ok=True)
+        fp = lambda name: files.setdefault(name, os.path.join(out_dp, name))      # noqa: E731
+        for k in range(len(prod["suns"])):
+            u8 = to_uint8_image(prod["rgb"][k])
+            _png(fp(f"rgb_{k:03d}.png"), u8)
+            img_utils.save_geotiff(fp(f"rgb_{k:03d}.tif"), u8.permute(1, 2, 0).contiguous(), grid, zone_string)
+            _scalar_plane(fp, f"sun_{k:03d}", prod["sun"][k], colormaps.COLORMAP_BONE, grid, zone_string)
+        _scalar_plane(fp, "lit_share", prod["lit_share"], colormaps.COLORMAP_BONE, grid, zone_string)
+        with open(fp("suns.json"), "w") as f:
+            json.dump([{"index": k, "elevation_deg": el, "azimuth_deg": az} for k, (el, az) in enumerate(prod["suns"])], f, indent=1)
     return dict(prod, files=files)

@@ -24,7 +24,10 @@ nadir_products asks the model instead: one vertical ray p
 true nadir ortho-image, the shadow map and the top-surface label, with occlusion resolved by the renderer.
 
 Out of scope: map-space accuracy against a ground-truth class raster (the US3D classes of dsm_cls_fp are not the scene's
-label set), finite-sigma splats, slanted or perspective map cameras, sweeps over several suns (callers loop), RPC tags."""
+label set), finite-sigma splats, slanted or perspective map cameras, RPC tags.
+
+nadir_sun_sweep renders that map under a list of suns in one walk: per chunk one full pass and one relight
+per further sun -- the shadow maps of a day, or the scene lit as each of its acquisitions saw it."""
 import torch
 
 from ... import _lib
@@ -247,6 +250,40 @@ def _nadir_defaults(dataset, geo, roi, gt, water_mask, ignore_mask, min_alt, max
     return geo, roi, gt, water_mask, ignore_mask, min_alt, max_alt, sun_elevation, sun_azimuth
 
 
+def _nadir_lattice(who, models, geo, grid, roi, min_alt, max_alt):
+    """the lattice of a nadir map and its rays: -> (grid, its SnerfDsmGrid, rays (H W, 8), the GeoBounds of its scene x / y)"""
+    from ...baseline.components import rays as R
+    if grid is None:
+        if roi is None:
+            raise ValueError(f"{who}: pass grid= or roi= (the lattice to render)")
+        grid = roi if isinstance(roi, D.DsmGrid) else D.roi_grid(roi)
+    g = grid_struct(grid)
+    dev = next(models["coarse"].parameters()).device
+    rays, bounds = R.nadir_construct(g, geo, min_alt, max_alt, device=dev, want_bounds=True)
+    return grid, g, rays, bounds
+
+
+def _nadir_finish(grid, g, geo, rays, bounds, loc, n_classes, gt, water_mask, ignore_mask):
+    """the products of a nadir walk that do not depend on the sun, from the frame's per-ray results `loc` (depth (n), albedo (3, n),
+    beta (n)[, label (n) int64]): grid, dsm, albedo, beta, rays, planimetric_error, scene_bounds[, label][, mae]"""
+    from ...baseline.components import rays as R
+    h, w = g.out_h, g.out_w
+    dev = rays.device
+    cloud, _ = geo.cloud(rays, loc["depth"])
+    east, north = (c.reshape(-1) for c in R.nadir_cell_centres(g, dev))
+    off = torch.maximum((cloud[:, 0] - east).abs().max(), (cloud[:, 1] - north).abs().max())
+    out = {"grid": window_grid(grid), "dsm": cloud[:, 2].to(torch.float32).reshape(h, w),
+           "albedo": loc["albedo"].reshape(3, h, w), "beta": loc["beta"].reshape(h, w), "rays": rays,
+           "planimetric_error": float(off), "scene_bounds": bounds}
+    if n_classes:
+        lab = loc["label"]
+        out["label"] = torch.where((lab >= 0) & (lab < NO_LABEL), lab, torch.full_like(lab, NO_LABEL)).to(torch.uint8).reshape(h, w)
+    if gt is not None:
+        mae = D.compute_mae(out["dsm"], gt, water_mask=water_mask, ignore_mask=ignore_mask)
+        out["mae"] = {"mean": mae["mean"], "median": mae["median"]}
+    return out
+
+
 @torch.no_grad()
 def nadir_products(cfgs, renderer, models, geo=None, grid=None, roi=None, min_alt=None, max_alt=None, sun_elevation=None,
                    sun_azimuth=None, t=0, render_options={}, sharded=False, gt=None, water_mask=None, ignore_mask=None,
@@ -273,17 +310,12 @@ def nadir_products(cfgs, renderer, models, geo=None, grid=None, roi=None, min_al
     from .util import render_chunks, result_buffers, shard_options
     geo, roi, gt, water_mask, ignore_mask, min_alt, max_alt, sun_elevation, sun_azimuth = _nadir_defaults(
         dataset, geo, roi, gt, water_mask, ignore_mask, min_alt, max_alt, sun_elevation, sun_azimuth)
-    if grid is None:
-        if roi is None:
-            raise ValueError("nadir_products: pass grid= or roi= (the lattice to render)")
-        grid = roi if isinstance(roi, D.DsmGrid) else D.roi_grid(roi)
-    g = grid_struct(grid)
+    grid, g, rays, bounds = _nadir_lattice("nadir_products", models, geo, grid, roi, min_alt, max_alt)
     h, w = g.out_h, g.out_w
     n = _cells(g)
     model = models["coarse"]
     n_classes = model.spec.n_classes
-    dev = next(model.parameters()).device
-    rays, bounds = R.nadir_construct(g, geo, min_alt, max_alt, device=dev, want_bounds=True)
+    dev = rays.device
     extras = R.nadir_extras(sun_elevation, sun_azimuth, t, n, dev)
 
     lo, hi = parallel.frame_shard(n) if sharded else (0, n)
@@ -313,17 +345,90 @@ def nadir_products(cfgs, renderer, models, geo=None, grid=None, roi=None, min_al
         loc = {key: parallel.allgather_rows(v, n) for key, v in loc.items()}
         loc["albedo"] = loc["albedo"].t().contiguous()
 
-    cloud, _ = geo.cloud(rays, loc["depth"])
-    east, north = (c.reshape(-1) for c in R.nadir_cell_centres(g, dev))
-    off = torch.maximum((cloud[:, 0] - east).abs().max(), (cloud[:, 1] - north).abs().max())
-    out = {"grid": window_grid(grid), "dsm": cloud[:, 2].to(torch.float32).reshape(h, w),
-           "rgb": loc["rgb"].t().contiguous().reshape(3, h, w), "albedo": loc["albedo"].reshape(3, h, w),
-           "sun": loc["sun"].reshape(h, w), "beta": loc["beta"].reshape(h, w), "rays": rays,
-           "planimetric_error": float(off), "scene_bounds": bounds}
+    out = _nadir_finish(grid, g, geo, rays, bounds, loc, n_classes, gt, water_mask, ignore_mask)
+    out["rgb"] = loc["rgb"].t().contiguous().reshape(3, h, w)
+    out["sun"] = loc["sun"].reshape(h, w)
+    return out
+
+
+def sweep_suns(suns, dataset=None, who="nadir_sun_sweep"):
+    """the suns of a sweep as a list of (elevation_deg, azimuth_deg) floats: `suns`, else those of the images of a loaded
+    dataset's split, in split order; an empty list (or neither) is a ValueError"""
+    if suns is None and dataset is not None:
+        suns = [(m["sun_elevation"], m["sun_azimuth"]) for m in dataset.metas]
+    suns = [(float(el), float(az)) for el, az in (suns or ())]
+    if not suns:
+        raise ValueError(f"{who}: no sun -- pass suns=[(elevation_deg, azimuth_deg), ...] (or a loaded dataset= to take its images' suns)")
+    return suns
+
+
+@torch.no_grad()
+def nadir_sun_sweep(cfgs, renderer, models, suns=None, geo=None, grid=None, roi=None, min_alt=None, max_alt=None, t=0,
+                    render_options={}, sharded=False, gt=None, water_mask=None, ignore_mask=None, dataset=None):
+    """nadir_products under K suns in ONE walk over the lattice's rays (util.relight_chunks): per chunk a full pass under suns[0]
+    and a relight per further sun, which re-runs only the sun-visibility branch, the sky colour and the composite on the chunk the
+    workspace holds.  `suns`: (elevation_deg, azimuth_deg) pairs; None with a loaded `dataset`: the suns of
+    the split's images in split order.  The lattice, `geo`, the altitudes, `t`, `sharded`, `gt` and the masks as for
+    nadir_products, which `dataset` supplies likewise.
+
+    Returns the products of nadir_products that do not depend on the sun ("grid", "dsm", "albedo", "beta"[, "label"], "rays",
+    "planimetric_error", "scene_bounds"[, "mae"]) and "suns": the list, "rgb": (K, 3, H, W) f32, "sun": (K, H, W) f32 (the
+    shadow maps, folded by vismaps.fold_chunk), "lit_share": (H, W) f32 -- the mean of the K shadow maps, summed in fp64 in sun
+    order and rounded once.  Map k has the bits of nadir_products under sun k, given the same depths ({"perturb": 0}): the jitter
+    is drawn once per chunk and shared by the suns."""
+    from ... import ops, parallel
+    from ...baseline.components import rays as R
+    from . import vismaps
+    from .util import relight_chunks, result_buffers, shard_options
+    suns = sweep_suns(suns, dataset)
+    geo, roi, gt, water_mask, ignore_mask, min_alt, max_alt, _, _ = _nadir_defaults(
+        dataset, geo, roi, gt, water_mask, ignore_mask, min_alt, max_alt, suns[0][0], suns[0][1])
+    grid, g, rays, bounds = _nadir_lattice("nadir_sun_sweep", models, geo, grid, roi, min_alt, max_alt)
+    h, w = g.out_h, g.out_w
+    n = _cells(g)
+    K = len(suns)
+    n_classes = models["coarse"].spec.n_classes
+    dev = rays.device
+    extras = R.nadir_extras(suns[0][0], suns[0][1], t, n, dev)
+
+    lo, hi = parallel.frame_shard(n) if sharded else (0, n)
+    m = hi - lo
+    S = cfgs.pipeline.n_samples
+    keys = ("rgb", "depth") + (("semantic_label",) if n_classes else ()) + ("weights", "albedo", "sun", "beta")
+    loc = {"depth": torch.empty(m, dtype=torch.float32, device=dev), "albedo": torch.empty((3, m), dtype=torch.float32, device=dev),
+           "beta": torch.empty(m, dtype=torch.float32, device=dev)}
     if n_classes:
-        lab = loc["label"]
-        out["label"] = torch.where((lab >= 0) & (lab < NO_LABEL), lab, torch.full_like(lab, NO_LABEL)).to(torch.uint8).reshape(h, w)
-    if gt is not None:
-        mae = D.compute_mae(out["dsm"], gt, water_mask=water_mask, ignore_mask=ignore_mask)
-        out["mae"] = {"mean": mae["mean"], "median": mae["median"]}
+        loc["label"] = torch.empty(m, dtype=torch.int64, device=dev)
+    rgb = torch.empty((K, m, 3), dtype=torch.float32, device=dev)
+    sun = torch.empty((K, m), dtype=torch.float32, device=dev)
+    if m:
+        ops.release_workspaces()
+        bufs = result_buffers(keys, min(cfgs.pipeline.render_chunk_size, m), S, n_classes, dev)
+        stats = vismaps.new_stats(dev)
+        for i, k, s, sl in relight_chunks(cfgs, renderer, models, rays[lo:hi], extras[lo:hi], suns, bufs,
+                                          shard_options(render_options, lo, hi, n)):
+            rgb[s, i:i + k].copy_(sl["rgb_coarse"])
+            if s == 0:      # what no sun changes: taken from the base pass
+                loc["depth"][i:i + k].copy_(sl["depth_coarse"])
+                if n_classes:
+                    loc["label"][i:i + k].copy_(sl["semantic_label_coarse"])
+                vismaps.fold_chunk({"albedo_map": loc["albedo"], "sun_map": sun[0], "beta_map": loc["beta"]}, stats, i, m, k, S,
+                                   weights=sl["weights_coarse"], albedo=sl["albedo_coarse"], sun=sl["sun_coarse"], beta=sl["beta_coarse"])
+            else:
+                vismaps.fold_chunk({"sun_map": sun[s]}, stats, i, m, k, S, weights=sl["weights_coarse"], sun=sl["sun_coarse"])
+    if sharded:
+        loc["albedo"] = loc["albedo"].t().contiguous()
+        loc = {key: parallel.allgather_rows(v, n) for key, v in loc.items()}
+        loc["albedo"] = loc["albedo"].t().contiguous()
+        rgb = torch.stack([parallel.allgather_rows(rgb[s].contiguous(), n) for s in range(K)])
+        sun = torch.stack([parallel.allgather_rows(sun[s].contiguous(), n) for s in range(K)])
+
+    out = _nadir_finish(grid, g, geo, rays, bounds, loc, n_classes, gt, water_mask, ignore_mask)
+    out["suns"] = suns
+    out["rgb"] = rgb.permute(0, 2, 1).contiguous().reshape(K, 3, h, w)
+    out["sun"] = sun.reshape(K, h, w)
+    total = torch.zeros((h, w), dtype=torch.float64, device=dev)
+    for s in range(K):      # in sun order, fp64; one rounding at the end
+        total += out["sun"][s].double()
+    out["lit_share"] = (total / K).to(torch.float32)
     return out

@@ -105,6 +105,74 @@ def lean_inference(cfgs, renderer, models, rays, extras, keys=("rgb_coarse", "de
     return out
 
 
+def sun_extras(extras, sun, device=None):
+    """`extras` (n, 4) with its sun columns replaced by the direction of `sun` = (elevation_deg, azimuth_deg): the reference's
+    convention (baseline/components/rays.py construct_sun_dir: fp64, rounded once), the embedding index column kept"""
+    from ...baseline.components import rays as R
+    from ...framework.components.rays import extras_component_fn
+    el, az = sun
+    e = extras.clone()
+    extras_component_fn(e, "sun_d", R.construct_sun_dir(float(el), float(az), 1).to(e.device))
+    return e
+
+
+def relight_chunks(cfgs, renderer, models, rays, extras, suns, buffers, render_options, frame_sized=False, show_tqdm=False):
+    """render_chunks over a list of suns, the chunk loop run ONCE: per chunk one base pass under suns[0] (render_rays_into: it
+    draws the chunk's jitter, so all suns of a sweep share their depths) and one relight per further sun (relight_rays_into on
+    the base pass's workspace: only the sun-dependent part of the pass).  `suns`: (elevation_deg, azimuth_deg) pairs; the sun
+    columns of `extras` are replaced by each in turn (sun_extras).  Yields (i, k, sun_index, views) after every pass, suns in
+    order within a chunk.  `buffers`: chunk-sized result_buffers, reused for every sun -- views = buffers[key][:k], to be consumed
+    before the next yield -- or, with frame_sized, tensors with a leading sun axis, (K, n, ...): views = buffers[key][s, i:i + k].
+    Every sun is asked for the same results, those of `buffers`."""
+    from ... import ops
+    suns = list(suns)
+    if not suns:
+        raise ValueError("relight_chunks: no sun")
+    chunk = cfgs.pipeline.render_chunk_size
+    n = rays.shape[0]
+    model = models["coarse"]
+    packed = ops.pack_params(model.spec, dict(model.named_parameters()))
+    ws = None
+    steps = range(0, n, chunk)
+    if show_tqdm:
+        from tqdm import tqdm
+        steps = tqdm(steps)
+    for i in steps:
+        k = min(chunk, n - i)
+        opts = _chunk_options(render_options, i, chunk, n)
+        opts["packed_params"] = packed
+        ex = extras[i:i + chunk]
+        for s, sun in enumerate(suns):
+            views = {key: v[s, i:i + k] if frame_sized else v[:k] for key, v in buffers.items()}
+            opts["workspace"] = ws
+            if s == 0:
+                ws = renderer.render_rays_into(models, rays[i:i + chunk], sun_extras(ex, sun), views, opts)
+            else:
+                ws = renderer.relight_rays_into(models, sun_extras(ex, sun), views, opts)
+            yield i, k, s, views
+
+
+@torch.no_grad()
+def lean_relight(cfgs, renderer, models, rays, extras, suns, keys=("rgb_coarse",), render_options={}, show_tqdm=False):
+    """lean_inference under every sun of `suns` ((elevation_deg, azimuth_deg) pairs) for the cost of one walk plus the
+    sun-dependent part per further sun: each result of `keys` stacked over the suns, (K, N, ...).  Entry k has the bits of
+    lean_inference with the sun columns of `extras` set to sun k -- given the same depths, i.e. {"perturb": 0} or a pinned
+    "perturb_rand" (the jitter is drawn once per chunk, by the base pass, and shared by the suns)."""
+    from ... import ops
+    for k in keys:
+        if _bare(k) not in _KEY_SHAPES or _bare(k).endswith("_sc"):
+            raise KeyError(f"lean_relight: '{k}' is not a result of the main pass")
+    suns = list(suns)
+    if not suns:
+        raise ValueError("lean_relight: no sun")
+    ops.release_workspaces()
+    one = result_buffers(keys, 0, cfgs.pipeline.n_samples, models["coarse"].spec.n_classes, rays.device)
+    out = {k: torch.empty((len(suns), rays.shape[0]) + tuple(v.shape[1:]), dtype=v.dtype, device=v.device) for k, v in one.items()}
+    for _ in relight_chunks(cfgs, renderer, models, rays, extras, suns, out, render_options, frame_sized=True, show_tqdm=show_tqdm):
+        pass
+    return out
+
+
 PER_RAY_RESULTS = ("rgb", "depth", "semantic_label", "semantic_logits")   # (N, ...) results: what a frame / point cloud is made of
 
 

@@ -68,6 +68,19 @@ class BaseRenderer:
             bare[k[:-len("_coarse")]] = v
         return fused_model_rendering_into(self, models, "coarse", rays, extras, opts, bare)
 
+    @torch.no_grad()
+    def relight_rays_into(self, models: dict, extras: torch.Tensor, out: dict, render_options={}):
+        """The rays render_rays_into rendered last into render_options['workspace'] (the workspace it returned), under the sun of
+        `extras`: only the sun-dependent part of the pass runs again, on the base pass's depths, and every result has the bits
+        render_rays_into gives under that sun.  `out` as for render_rays_into, main-pass results only.  Returns the workspace."""
+        from ...semantic.components.rendering import fused_model_relighting_into
+        bare = {}
+        for k, v in out.items():
+            if not k.endswith("_coarse"):
+                raise KeyError(f"relight_rays_into: result keys end in '_coarse', got '{k}'")
+            bare[k[:-len("_coarse")]] = v
+        return fused_model_relighting_into(self, models, "coarse", extras, dict(render_options) if render_options else {}, bare)
+
     @abc.abstractmethod
     def _model_rendering(self, models: dict, typ: str, cfgs, rays, extras, xyz, z_vals, rays_d, epoch=None,
                          progress=1.0, render_options=None) -> dict:

@@ -394,12 +394,12 @@ def output_keys(spec: ModelSpec, sc_pass: bool) -> list:
     return keys
 
 
-def _forward_setup(spec, pin, t, t_s, flags):
-    """What both forward entries do before they allocate: S from the inputs, the descriptor, the workspace size, contiguous
-    t / t_s and the inputs struct.  Returns (S, desc, workspace bytes, tc, tsc, launch); launch(packed, so, ws) is the
-    snerf_forward call on the workspace tensor `ws`."""
-    S = (pin.z_vals.shape[1] if pin.z_vals is not None else
-         (pin.u.shape[1] if pin.u is not None else pin.z_steps.shape[0]))
+def _forward_setup(spec, pin, t, t_s, flags, n_samples=None):
+    """What every forward entry does before it allocates: S from the inputs (`n_samples`: a relight, whose inputs carry no depths),
+    the descriptor, the workspace size, contiguous t / t_s and the inputs struct.  Returns (S, desc, workspace bytes, tc, tsc,
+    launch); launch(packed, so, ws) is the snerf_forward call on the workspace tensor `ws`."""
+    S = int(n_samples) if n_samples is not None else (
+        pin.z_vals.shape[1] if pin.z_vals is not None else (pin.u.shape[1] if pin.u is not None else pin.z_steps.shape[0]))
     d = spec.desc(t.shape[0], S, flags)
     nbytes = _lib.call_size("snerf_workspace_bytes", d)
     _check_dev(t, "t")
@@ -515,6 +515,25 @@ def render_pass(spec: ModelSpec, params: dict, pin: PassInputs, t: torch.Tensor,
     return out
 
 
+def _outputs_struct(who, spec, out, N, S, sc_pass=False):
+    """SnerfOutputs of the *_into entries: every tensor of `out` checked (a result of this pass; on the GPU; contiguous, of the pass's
+    shape and dtype) and bound; every other pointer stays NULL"""
+    allowed = set(output_keys(spec, sc_pass)) | {"z_vals"} | ({"semantic_label"} if spec.n_classes > 0 and not sc_pass else set())
+    so = _lib.SnerfOutputs()
+    for k, v in out.items():
+        if k not in allowed:
+            raise KeyError(f"{who}: '{k}' is not a result of this pass (have {sorted(allowed)})")
+        want = (N,) if k == "semantic_label" else ((N, S) if k == "z_vals" else _OUT_SHAPES[k](N, S, spec.n_classes))
+        if tuple(v.shape) != tuple(want) or not v.is_contiguous():
+            raise ValueError(f"{who}: out['{k}'] must be a contiguous {tuple(want)} tensor, got {tuple(v.shape)}")
+        if v.dtype != (torch.int64 if k == "semantic_label" else torch.float32):
+            raise ValueError(f"{who}: out['{k}'] has dtype {v.dtype}")
+        if not v.is_cuda:
+            raise RuntimeError(f"snerf_amd: out['{k}'] must live on the GPU (the HIP path has no CPU fallback)")
+        setattr(so, k, v.data_ptr())
+    return so
+
+
 @torch.no_grad()
 def render_pass_into(spec: ModelSpec, params: dict, pin: PassInputs, t: torch.Tensor, t_s: torch.Tensor | None,
                      out: dict, sc_pass: bool = False, packed: torch.Tensor | None = None,
@@ -528,22 +547,44 @@ def render_pass_into(spec: ModelSpec, params: dict, pin: PassInputs, t: torch.Te
     S, _, nbytes, _, _, launch = _forward_setup(spec, pin, t, t_s, _lib.FLAG_SC_PASS if sc_pass else 0)
     if workspace is None or workspace.numel() < nbytes or workspace.device != dev:
         workspace = _empty(nbytes, dtype=torch.uint8, device=dev)
-    allowed = set(output_keys(spec, sc_pass)) | {"z_vals"} | ({"semantic_label"} if spec.n_classes > 0 and not sc_pass else set())
-    so = _lib.SnerfOutputs()
-    for k, v in out.items():
-        if k not in allowed:
-            raise KeyError(f"render_pass_into: '{k}' is not a result of this pass (have {sorted(allowed)})")
-        if not v.is_cuda:
-            raise RuntimeError(f"snerf_amd: out['{k}'] must live on the GPU (the HIP path has no CPU fallback)")
-        want = (N,) if k == "semantic_label" else ((N, S) if k == "z_vals" else _OUT_SHAPES[k](N, S, spec.n_classes))
-        if tuple(v.shape) != tuple(want) or not v.is_contiguous():
-            raise ValueError(f"render_pass_into: out['{k}'] must be a contiguous {tuple(want)} tensor, got {tuple(v.shape)}")
-        if v.dtype != (torch.int64 if k == "semantic_label" else torch.float32):
-            raise ValueError(f"render_pass_into: out['{k}'] has dtype {v.dtype}")
-        setattr(so, k, v.data_ptr())
+    so = _outputs_struct("render_pass_into", spec, out, N, S, sc_pass)
     if packed is None:
         packed = pack_params(spec, params)
     launch(packed, so, workspace)
+    return workspace
+
+
+@torch.no_grad()
+def relight_pass_into(spec: ModelSpec, params: dict, sun_d: torch.Tensor, t: torch.Tensor, t_s: torch.Tensor | None, out: dict,
+                      workspace: torch.Tensor, packed: torch.Tensor | None = None, n_samples: int | None = None) -> torch.Tensor:
+    """The chunk that `workspace` holds, under another sun: `workspace` is the tensor the BASE pass returned -- the last
+    render_pass_into main pass on it, with this spec, these parameters and the same number of rays and samples.  Only what depends on
+    the sun runs again (the extras columns, the sun block of the first head layer, the sun-visibility layers, the sky colour, the
+    composite: snerf_forward under SNERF_FLAG_RELIGHT); positions, encoding, the trunk, sigma and the other heads are the base
+    pass's, and so are the depths.  Every result has the bits of a full pass under `sun_d` (N, 3).  `t` / `t_s` as in the base pass
+    (or others: the extras block is rewritten whole).  `out` as for render_pass_into (main-pass keys); N comes from `t`, S from
+    `n_samples` or from the shape of a per-sample result tensor in `out`.  Any number of relights may follow one base pass; the
+    library refuses a workspace whose last pass was not such a base pass (RuntimeError with its message), but cannot know that the
+    caller wrote into the tensor itself.  Returns the workspace."""
+    N = t.shape[0]
+    S = n_samples
+    for k, v in out.items():      # a per-sample result names S: (N, S) or (N, S, c)
+        if S is None and k in ("weights", "transparency", "sigmas", "z_vals", "albedo", "sun", "sky", "beta", "beta_semantic") and v.dim() >= 2:
+            S = v.shape[1]
+    if S is None:
+        raise ValueError("relight_pass_into: pass n_samples= (no per-sample result tensor in `out` to take it from)")
+    so = _outputs_struct("relight_pass_into", spec, out, N, int(S))
+    if workspace is None:
+        raise ValueError("relight_pass_into: workspace= must be the tensor the base pass returned")
+    pin = PassInputs(sun_d=sun_d)      # (held, with tc / tsc, until the launch is queued: they own the contiguous copies)
+    _, _, nbytes, tc, tsc, launch = _forward_setup(spec, pin, t, t_s, _lib.FLAG_RELIGHT, n_samples=S)
+    if workspace.numel() < nbytes or workspace.device != t.device:
+        raise ValueError(f"relight_pass_into: the workspace holds {workspace.numel()} bytes on {workspace.device}, the base pass of "
+                         f"{N} x {S} needs {nbytes} on {t.device}")
+    if packed is None:
+        packed = pack_params(spec, params)
+    launch(packed, so, workspace)
+    del pin, tc, tsc
     return workspace
 
 

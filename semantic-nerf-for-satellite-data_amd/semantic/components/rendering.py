@@ -119,6 +119,36 @@ def fused_model_rendering_into(renderer, models, typ, rays, extras, render_optio
     return ws
 
 
+@torch.no_grad()
+def fused_model_relighting_into(renderer, models, typ, extras, render_options, out: dict):
+    """The chunk that render_options["workspace"] holds -- the workspace fused_model_rendering_into returned for its main pass --
+    under the sun (and embedding index) of `extras`: ops.relight_pass_into, which re-runs only what depends on the sun.  `out` takes
+    the main pass's keys; a solar-correction key ('weights_sc', ...) is a KeyError: that pass samples along the sun ray itself and
+    leaves nothing a new sun could reuse.  Returns the workspace."""
+    opts = render_options or {}
+    for k in out:
+        if k in _SC_KEYS:
+            raise KeyError(f"fused_model_relighting_into: '{k}' belongs to the solar-correction pass, which cannot be relit "
+                           "(it samples along the sun ray); render it with fused_model_rendering_into")
+    ws = opts.get("workspace")
+    if ws is None:
+        raise ValueError("fused_model_relighting_into: render_options['workspace'] must be the workspace of the base pass")
+    model = models[typ]
+    allowed = set(ops.output_keys(model.spec, False)) | {"z_vals"} | ({"semantic_label"} if model.spec.n_classes > 0 else set())
+    for k in out:
+        if k not in allowed:
+            raise KeyError(f"fused_model_relighting_into: '{k}' is not a result of the main pass (have {sorted(allowed)})")
+    sun_d = extras_component_fn(extras, "sun_d")
+    ts = extras_component_fn(extras, "ts").squeeze(-1).long()
+    rays_t = ops.embed_rows(models["t"], ts)
+    rays_t_s = ops.embed_rows(models["t_s"], ts) if "t_s" in models else None
+    params = dict(model.named_parameters())
+    packed = opts.get("packed_params")
+    if packed is None:
+        packed = ops.pack_params(model.spec, params)
+    return ops.relight_pass_into(model.spec, params, sun_d, rays_t, rays_t_s, out, ws, packed=packed, n_samples=renderer.N_samples)
+
+
 class RSSemanticRendering(BaseRenderer):
     def __init__(self, cfgs, inference=rs_semantic_inference):
         super().__init__(cfgs)
