@@ -50,6 +50,11 @@ extern "C" {
                                  sun-visibility layers, the sky colour and the composite are run again (about a tenth of a pass's
                                  matrix work).  Every result has the bits a full pass under that sun gives.  Not with SNERF_FLAG_TRAIN or
                                  SNERF_FLAG_SC_PASS (SNERF_ERR_BAD_DESC).  Contract: see snerf_forward */
+#define SNERF_FLAG_EMBED_GRAD  16u /* embedding-only backward: snerf_backward writes d_t / d_t_s and NOTHING else -- it stops where the
+                                 gradient of the transient embedding is complete (no weight-gradient launch, no sun-visibility chain,
+                                 no trunk), and packed_grads may be NULL.  Valid only together with SNERF_FLAG_TRAIN and never with
+                                 SNERF_FLAG_RELIGHT (SNERF_ERR_BAD_DESC); combines with SNERF_FLAG_SC_PASS and either arithmetic flag.
+                                 snerf_forward and every size ignore the bit.  Contract: see snerf_backward */
 
 /* Arithmetic of the dense contractions.  With NONE of the arithmetic bits set a pass runs the default, SNERF_FLAG_F16X2
  * (the same for C and Python callers); the two bits exclude each other. */
@@ -210,7 +215,17 @@ int snerf_embedding_backward(const long long* idx, const float* d_rows, int n, i
 /* Backward of one pass (what autograd does in the reference for the ops above): consumes the
  * activations that snerf_forward(SNERF_FLAG_TRAIN) left in `workspace`, ACCUMULATES parameter
  * gradients into packed_grads (caller zeroes it once per step) and writes d loss / d t (N,tau)
- * [and d t_s] when those pointers are non-NULL. */
+ * [and d t_s] when those pointers are non-NULL.
+ *
+ * With SNERF_FLAG_EMBED_GRAD the call computes d_t / d_t_s ALONE (fitting the embedding of an unseen image with the network frozen).
+ * packed_grads may be NULL; it is never read or written, and no parameter gradient is computed.  At least one of d_t, d_t_s must be
+ * non-NULL (SNERF_ERR_NULL).  What is written into d_t / d_t_s equals, element for element, what the full backward of the same
+ * forward under the same cotangents writes there: the main pass runs the composite backward, the plane conversion of the final
+ * layers' gradient, the one dX launch into the first head layer's pre-activation gradient and the narrow launch into the extras
+ * columns with its per-ray sums -- the full pass's launches with the full pass's operands -- and stops; the solar-correction pass
+ * (SNERF_FLAG_SC_PASS) zeroes d_t / d_t_s and launches nothing else.  The bit need not have been set in the forward:
+ * snerf_forward(TRAIN | EMBED_GRAD) is snerf_forward(TRAIN) bit for bit, snerf_workspace_bytes is the same with and without it, and the
+ * host may decide at backward time.  As after any backward, the workspace's activations are spent. */
 int snerf_backward(const SnerfDesc* desc, const float* packed_params, const SnerfInputs* in,
                    const SnerfOutGrads* gout, float* packed_grads, float* d_t, float* d_t_s,
                    void* workspace, size_t workspace_bytes, void* stream);

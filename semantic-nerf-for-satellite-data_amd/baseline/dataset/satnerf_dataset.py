@@ -63,6 +63,12 @@ def t_indices(names, split):
     return [0] + [VAL_T_INDEX.get(get_file_id(name), 0) for name in names[1:]]
 
 
+def unlisted_test_views(names):
+    """the names (files or ids, in order) that VAL_T_INDEX does not list: as test views they fall back to row 0 of the embedding
+    table, another image's appearance -- the views whose embedding a caller fits instead (eval/utils/embedding.py)"""
+    return [name for name in names if get_file_id(name) not in VAL_T_INDEX]
+
+
 def refuse_unsupported(cfgs):
     init_coordinate_system(cfgs)
     pc = cfgs.pipeline

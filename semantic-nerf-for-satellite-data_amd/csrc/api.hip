@@ -201,6 +201,9 @@ int make_plan(const SnerfDesc* d, Plan* pl) {
   p.siren = d->siren != 0; p.sem_sigmoid = d->sem_sigmoid != 0;
   p.train = (d->flags & SNERF_FLAG_TRAIN) != 0; p.sc = (d->flags & SNERF_FLAG_SC_PASS) != 0;
   p.relight = (d->flags & SNERF_FLAG_RELIGHT) != 0;
+  p.embed_grad = (d->flags & SNERF_FLAG_EMBED_GRAD) != 0;
+  // The embedding-only backward follows a training forward: it reads the activations that one keeps.  Sizes and forward are the TRAIN plan's.
+  if (p.embed_grad && (p.relight || !p.train)) return bad("SNERF_FLAG_EMBED_GRAD is valid only together with SNERF_FLAG_TRAIN, and not with SNERF_FLAG_RELIGHT (it selects the backward of a training pass)");
   // A relight reuses what an INFERENCE MAIN pass left: a training workspace has another layout, the solar-correction pass samples along
   // the sun ray itself (nothing of it survives a new sun).  The plan of a relight is otherwise that of its base pass, sizes included.
   if (p.relight && (p.train || p.sc)) return bad("SNERF_FLAG_RELIGHT cannot be combined with SNERF_FLAG_TRAIN or SNERF_FLAG_SC_PASS (a relight follows an inference main pass)");
@@ -367,9 +370,11 @@ int check_plan_note(const void* buf, bool composed, const char* who, const char*
     }
   return SNERF_OK;
 }
-// the descriptor fields that make two passes the same pass: everything, bar the RELIGHT bit and the spelling of the default arithmetic
+// the descriptor fields that make two passes the same pass: everything, bar the RELIGHT bit, the spelling of the default arithmetic and
+// the EMBED_GRAD bit (which only selects how much of the backward runs: it may be set at backward time alone)
 bool same_pass_desc(SnerfDesc a, SnerfDesc b) {
-  a.flags &= ~(SNERF_FLAG_RELIGHT | SNERF_FLAG_F16X2); b.flags &= ~(SNERF_FLAG_RELIGHT | SNERF_FLAG_F16X2);
+  const unsigned ignore = SNERF_FLAG_RELIGHT | SNERF_FLAG_F16X2 | SNERF_FLAG_EMBED_GRAD;
+  a.flags &= ~ignore; b.flags &= ~ignore;
   return a.n_rays == b.n_rays && a.n_samples == b.n_samples && a.fc_units == b.fc_units && a.fc_layers == b.fc_layers &&
          a.feat_last == b.feat_last && a.skip_mask == b.skip_mask && a.n_freq == b.n_freq && a.siren == b.siren && a.t_dim == b.t_dim &&
          a.n_classes == b.n_classes && a.sem_sigmoid == b.sem_sigmoid && a.use_tj_instead_of_beta == b.use_tj_instead_of_beta &&
@@ -515,7 +520,9 @@ int snerf_backward(const SnerfDesc* desc, const float* packed_params, const Sner
   Plan p;
   RC(make_plan(desc, &p));
   if (!p.train) { set_error("snerf_backward needs the SnerfDesc used for the SNERF_FLAG_TRAIN forward"); return SNERF_ERR_BAD_DESC; }
-  if (!packed_params || !gout || !packed_grads || !workspace) { set_error("snerf_backward: null argument"); return SNERF_ERR_NULL; }
+  // (SNERF_FLAG_EMBED_GRAD: packed_grads is neither read nor written and may be NULL)
+  if (!packed_params || !gout || (!packed_grads && !p.embed_grad) || !workspace) { set_error("snerf_backward: null argument"); return SNERF_ERR_NULL; }
+  if (p.embed_grad && !d_t && !d_t_s) { set_error("snerf_backward(SNERF_FLAG_EMBED_GRAD): d_t and d_t_s are both NULL -- nothing to compute"); return SNERF_ERR_NULL; }
   if (workspace_bytes < p.ws_bytes) { set_error("snerf_backward: workspace too small (%zu < %zu)", workspace_bytes, p.ws_bytes); return SNERF_ERR_WORKSPACE; }
   if (((uintptr_t)workspace & 255) || ((uintptr_t)packed_params & 255) || ((uintptr_t)packed_grads & 255)) { set_error("workspace and packed buffers must be 256-byte aligned"); return SNERF_ERR_WORKSPACE; }
   RC(check_inputs(p, in));

@@ -229,7 +229,9 @@ struct BwdRegions {
   int ld_cs1 = 0;   // composed: cs_fin and cs_sun are column ranges of ONE [tiles][h1w] region (row 0 of it becomes g_c, the bias gradient of the composed layer)
   struct Layer { DwMat w, w_gamma; float* cs; } tr[SNERF_MAX_LAYERS];   // w_gamma: skip layers; cs: the dX launch into layer i - 1
 };
-void take_regions(const Plan& p, RQ& rq, BwdRegions& r) {
+// `embed_only` (SNERF_FLAG_EMBED_GRAD): the two regions of the launches that lie between the cotangents and d t -- the 256-row partials
+// of d fin and the column-sum partials of the dX launch into dz1[:, :KF] -- and nothing else.
+void take_regions(const Plan& p, RQ& rq, BwdRegions& r, bool embed_only = false) {
   // `split_rows`: the rows the split count is chosen for when they differ from the slab's (the [W + 32][W] matrix of feats + sigma:
   // its wide launch covers W rows -- counting the 32 sigma rows as a third row tile gave it 43 splits, 172 workgroups for 256 CUs)
   auto dw = [&](int rows, int ldw, int cols, bool narrow_rows, int split_rows = 0) {
@@ -243,6 +245,13 @@ void take_regions(const Plan& p, RQ& rq, BwdRegions& r) {
   auto cs = [&](int width) { return rq.take((size_t)((p.P + 127) / 128) * cs_ld(width)); };
   auto nar = [&]() { return rq.take((size_t)((p.P + 255) / 256) * NARROW); };
   const int W = p.W, H = p.H;
+  if (embed_only) {
+    if (p.sc) return;
+    r.nar_fin = nar();
+    if (p.compose_feats) { r.ld_cs1 = cs_ld(p.h1w); r.cs_fin = cs(p.h1w); }
+    else r.cs_fin = cs(p.KF);
+    return;
+  }
   if (!p.sc) { r.nar_fin = nar(); r.w_fin = dw(NARROW, p.KF, p.KF, true); if (!p.compose_feats) r.cs_fin = cs(p.KF); }
   r.nar_sun = nar(); r.w_s4 = dw(NARROW, H, H, true); r.w_s3 = dw(H, H, H, false); r.w_s2 = dw(H, H, H, false);   // one slab region per matrix
   r.cs_s3 = cs(H); r.cs_s2 = cs(H);
@@ -278,11 +287,16 @@ int backward_bsp(const Plan& p, const float* pk, const SnerfInputs* in, const Sn
                  void* workspace, hipStream_t st) {
   const Ws ws{(char*)workspace};
   const int P = p.P, W = p.W, H = p.H;
+  // SNERF_FLAG_EMBED_GRAD: d_t / d_t_s alone.  t enters at the extras columns of the first head layer and the density does not depend
+  // on it, so the pass ends where transient_grads() has run: composite backward, planes of d fin, the dX launch into dz1[:, :KF], the
+  // narrow launch into d extras, the per-ray sums -- the launches of the full pass with the operands of the full pass, hence its bits.
+  // gp may be NULL and is never touched: no reduction is queued, none is run.
+  const bool embed = p.embed_grad;
   int kcq = 0;     // (the counters are cleared by the composite backward kernel, the first launch of this pass)
   auto launch_kc = [&](bsp::KcArgs& g) { g.rev = kcq & 1; g.tile_ctr = kcq < KCQ_SLOTS ? ws.i(p.o_kcq) + 16 * kcq++ : nullptr; return bsp::launch_kc(g, st); };
   RQ rq{ws.f(p.o_rq), p.rq_floats};
   BwdRegions r;
-  take_regions(p, rq, r);
+  take_regions(p, rq, r, embed);
   if (rq.over) { set_error("reduction arena too small (plan / pass mismatch)"); return SNERF_ERR_WORKSPACE; }
   // activation derivative in a dX epilogue, rebuilt from the stored activation h (column col0 of it): siren
   // w0 * sign(cos) * sqrt(1 - h^2) with h's sign words; relu: h > 0
@@ -310,6 +324,11 @@ int backward_bsp(const Plan& p, const float* pk, const SnerfInputs* in, const Sn
     return red_add_col(rq.col, part, (P + 255) / 256, NARROW, NARROW, gout);
   };
   float* dsig = ws.f(p.o_dsig); float* dfin = ws.f(p.o_dfin); float* dsun = ws.f(p.o_dsun);
+  if (embed && p.sc) {   // the sun-visibility block reads [feats | sun_d] only: zeros, as transient_grads() below writes them, and no launch besides
+    if (d_t) RC(launch_zero_bytes(d_t, (size_t)p.N * p.tau * sizeof(float), st));
+    if (d_t_s && p.x_ts >= 0) RC(launch_zero_bytes(d_t_s, (size_t)p.N * p.tau * sizeof(float), st));
+    return SNERF_OK;
+  }
   // 0. composite backward -> gradients of the 32-wide pre-activations (+ sky MLP grads)
   CompBwdArgs b;
   CompArgs& c = b.f;
@@ -321,10 +340,10 @@ int backward_bsp(const Plan& p, const float* pk, const SnerfInputs* in, const Sn
   b.g_rgb = go->rgb; b.g_depth = go->depth; b.g_weights = go->weights; b.g_transparency = go->transparency;
   b.g_albedo = go->albedo; b.g_sun = go->sun; b.g_sky = go->sky; b.g_beta = go->beta; b.g_sigmas = go->sigmas;
   b.g_beta_s = go->beta_semantic; b.g_logits = go->semantic_logits;
-  b.d_sigo = dsig; b.d_fino = dfin; b.d_suno = dsun; b.sky_slab = p.sc ? nullptr : ws.f(p.o_skyslab);
+  b.d_sigo = dsig; b.d_fino = dfin; b.d_suno = dsun; b.sky_slab = (p.sc || embed) ? nullptr : ws.f(p.o_skyslab);
   b.zero = ws.u(p.o_kcq); b.zero_n = KCQ_SLOTS * 16;
   RC(launch_composite_bwd(b, st));
-  if (!p.sc)
+  if (!p.sc && !embed)
     RC(red_add_col(rq.col, ws.f(p.o_skyslab), p.comp_blocks * 4, (size_t)p.sky_floats, p.sky_floats, gp + p.sky));
 
 
@@ -332,9 +351,12 @@ int backward_bsp(const Plan& p, const float* pk, const SnerfInputs* in, const Sn
   const int sun_col = p.sc ? 0 : p.sun_col;
   if (!p.sc) {
     // 1. final head layers: bias gradient + planes of dfin, dW, then dz1[:, :KF] = (dfin . W_fin) * act'
-    RC(narrow_grad(dfin, r.nar_fin, p.pdfin, gp + p.b_fin));
-    RC(dw_gemm(r.w_fin, p.pdfin, NARROW, true, p.h1, 0, p.KF));
-    RC(dw_reduce(r.w_fin, (size_t)NARROW * p.KF, gp + p.w_fin));
+    if (embed) RC(bsp::launch_colsum32_bsp(dfin, P, r.nar_fin, ws.c(p.pdfin.o), ws.i(p.pdfin.e), p.pl, st));   // narrow_grad's plane conversion, its bias sums left in the arena
+    else {
+      RC(narrow_grad(dfin, r.nar_fin, p.pdfin, gp + p.b_fin));
+      RC(dw_gemm(r.w_fin, p.pdfin, NARROW, true, p.h1, 0, p.KF));
+      RC(dw_reduce(r.w_fin, (size_t)NARROW * p.KF, gp + p.w_fin));
+    }
     bsp::KcArgs g;
     ws.a(g, p.pdfin, NARROW); weights(g, p, pk, p.wj_tfin);
     g.I = P; g.J = p.KF; g.K = NARROW; ws.out(g, dz1);
@@ -342,9 +364,9 @@ int backward_bsp(const Plan& p, const float* pk, const SnerfInputs* in, const Sn
     colsum(g, r.cs_fin, p.KF);
     if (p.compose_feats) g.ldcs = r.ld_cs1;
     RC(launch_kc(g));
-    if (!p.compose_feats) RC(bias_from_colsum(r.cs_fin, p.KF, gp + p.b_h1));
+    if (!p.compose_feats && !embed) RC(bias_from_colsum(r.cs_fin, p.KF, gp + p.b_h1));
   }
-  {  // 2. sun visibility chain: output layer, layer 3, layer 2
+  if (!embed) {  // 2. sun visibility chain: output layer, layer 3, layer 2
     RC(narrow_grad(dsun, r.nar_sun, p.pdsun, gp + p.b_s4));
     RC(dw_gemm(r.w_s4, p.pdsun, NARROW, true, p.s3, 0, H));
     RC(dw_reduce(r.w_s4, (size_t)NARROW * H, gp + p.w_s4));
@@ -394,6 +416,7 @@ int backward_bsp(const Plan& p, const float* pk, const SnerfInputs* in, const Sn
     }
     return (int)SNERF_OK;
   };
+  if (embed) return transient_grads();   // (it reads dz1 in [k_lo, k_lo + k_n), inside [0, KF): the sun block's columns are unwritten in this pass)
   PlaneT dz_cur = p.dza.view(W);   // dz of the trunk layers, [P][W], in dza and dzb in turn (dz1 is dead by then)
   PlaneT dz_nxt = p.dzb.view(W);
   // The density branch carries a gradient only if one reaches weights / transparency (/ sigmas, depth, rgb, logits in the main

@@ -30,6 +30,7 @@ struct Plan {
   int W = 0, H = 0, L = 0, E = 0, Ep = 0, F = 0, tau = 0, C = 0;
   bool siren = false, train = false, sc = false, sem_sigmoid = false;
   bool relight = false;   // SNERF_FLAG_RELIGHT: the sun-dependent launches alone, on the workspace of a finished inference main pass (same layout)
+  bool embed_grad = false;   // SNERF_FLAG_EMBED_GRAD: snerf_backward writes d_t / d_t_s alone (bsp_pass.hip); forward and every size as without it
   unsigned skip_mask = 0;
   // extras columns appended to the feats buffer: [sun(3) | t(tau) | t_s(tau)] padded to 4
   int x_sun = 0, x_t = 3, x_ts = -1, Xp = 0, FA = 0;

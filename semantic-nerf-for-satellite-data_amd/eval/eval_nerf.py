@@ -10,7 +10,12 @@ per-image entries and the means are written to `output_dp`/results.json with the
 DIVERGENCES: the per-image "mae" entry holds the MAE dict's numbers as floats (the DSM and the registered DSM are dropped);
 its means are taken over those floats.  PSNR and SSIM means are, as in the reference, the means of the formatted strings.
 No GeoTIFF is written (`epoch` named the reference's DSM files and is accepted for its signature only).  If no image has a
-"dsm" entry the MAE keys are absent; a split that mixes images with and without one is refused."""
+"dsm" entry the MAE keys are absent; a split that mixes images with and without one is refused.
+
+ADDITION: `fit_embedding` (NeRF-W's protocol for a view without a row in the embedding table; eval/utils/embedding.py): per image
+the transient vector is fitted on a region of its pixels with the network frozen, the WHOLE frame is rendered with it and every
+key above comes from that render; the entry gains "psnr_heldout" (the region's complement) and "t_fit", and the vectors are
+written to `output_dp`/t_fit.json.  None (the default) changes nothing."""
 import json
 import math
 import os
@@ -39,13 +44,17 @@ def _mae_floats(mae):
 
 
 @torch.no_grad()
-def eval_nerf_images(cfgs, renderer, models, images, output_dp=None, split="test", epoch=-1, sharded=False):
+def eval_nerf_images(cfgs, renderer, models, images, output_dp=None, split="test", epoch=-1, sharded=False, fit_embedding=None):
     """images: a sequence of dicts with the reference's item keys ("name", "rays", "extras", "rgbs", optional "w", "h") and
     the optional "dsm" entry of validation_step.  On the test split item 0 is skipped (it is also a training view,
     eval_nerf.py:52-55).  Returns the dict written to results.json: {name: {["mae": {...},] "psnr": "{:.2f}",
     "ssim": "{:.3f}"}, ["MAE (Mean)", "MAE (Median)",] "PSNR (Mean)", "SSIM (Mean)"}.  With sharded=True every rank renders
-    its share of each frame and computes the same values; only rank 0 writes the file."""
+    its share of each frame and computes the same values; only rank 0 writes the file.
+    fit_embedding: None, or a dict of fit_image_embedding's keyword arguments (missing ones: embedding.FIT_DEFAULTS) plus "region":
+    "left" (default: fit on the columns [0, w // 2), "psnr_heldout" on the others) or "all" (no held-out key).  Every rank fits the
+    same vector from the same seed (no collective), so it works as it is under sharded=True."""
     from .utils.dsm import compute_dsm_and_mae
+    from .utils import embedding
     start = 1 if split == "test" else 0
     todo = list(images)[start:]
     if not todo:
@@ -57,13 +66,20 @@ def eval_nerf_images(cfgs, renderer, models, images, output_dp=None, split="test
     stats_fp = os.path.join(output_dp, "results.json") if output_dp is not None else None
     if stats_fp is not None:
         os.makedirs(output_dp, exist_ok=True)
-    per_image, d = {}, {}
+    per_image, d, vectors = {}, {}, {}
+    region, fit_kw = embedding.fit_options(fit_embedding) if fit_embedding is not None else (None, None)
     for img in todo:
         rays = img["rays"].reshape(-1, img["rays"].shape[-1])
         extras = img["extras"].reshape(-1, img["extras"].shape[-1]) if img.get("extras") is not None else None
         rgbs = img["rgbs"].reshape(-1, 3)
         W, H = _w_h(img, rays.shape[0])
-        results = infer(cfgs, renderer, models, rays, extras, keys=("rgb_coarse", "depth_coarse"))
+        if region is None:
+            results = infer(cfgs, renderer, models, rays, extras, keys=("rgb_coarse", "depth_coarse"))
+        else:
+            fit, fit_mask, t_fit = embedding.fit_for_image(cfgs, renderer, models, img, rays, extras, W, H, region, fit_kw)
+            vectors[img["name"]] = [float(v) for v in fit["t"].cpu()]
+            results = infer(cfgs, renderer, models, rays, extras, keys=("rgb_coarse", "depth_coarse"),
+                            render_options=embedding.vector_options(fit))
         rgb = results["rgb_coarse"]
         entry = {}
         if img.get("dsm") is not None:
@@ -77,6 +93,10 @@ def eval_nerf_images(cfgs, renderer, models, images, output_dp=None, split="test
         ssim_ = metrics.ssim(rgb.view(1, 3, H, W), rgbs.reshape(1, 3, H, W))
         entry["psnr"] = "{:.2f}".format(float(psnr_))
         entry["ssim"] = "{:.3f}".format(float(ssim_))
+        if region is not None:
+            if region == "left":
+                entry["psnr_heldout"] = "{:.2f}".format(float(metrics.psnr(rgb, rgbs, valid_mask=~fit_mask)))
+            entry["t_fit"] = t_fit
         per_image[img["name"]] = entry
         n = len(per_image)
         d = dict(per_image)
@@ -88,4 +108,7 @@ def eval_nerf_images(cfgs, renderer, models, images, output_dp=None, split="test
         if stats_fp is not None and world()[0] == 0:
             with open(stats_fp, "w") as f:
                 json.dump(d, f, indent=4)
+            if region is not None:
+                with open(os.path.join(output_dp, "t_fit.json"), "w") as f:
+                    json.dump(vectors, f, indent=4)
     return d

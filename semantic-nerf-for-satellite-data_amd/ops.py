@@ -410,7 +410,9 @@ def _forward_setup(spec, pin, t, t_s, flags, n_samples=None):
 
 
 class _RenderPass(torch.autograd.Function):
-    """forward = snerf_forward, backward = snerf_backward (+ snerf_unpack_grads)."""
+    """forward = snerf_forward, backward = snerf_backward (+ snerf_unpack_grads).  A backward in which no parameter needs a
+    gradient (frozen network, the leaf is t / t_s: fitting an image's embedding) is the library's embedding-only backward,
+    SNERF_FLAG_EMBED_GRAD: d_t / d_t_s with the bits of the full backward, no gradient buffer, no unpack."""
 
     @staticmethod
     def forward(ctx, spec, pin, sc_pass, need_grad, packed, names, t, t_s, *params):
@@ -466,9 +468,15 @@ class _RenderPass(torch.autograd.Function):
         if not live:
             return (None,) * (8 + len(ctx.names))
         dev = ctx.tc.device
-        pg = torch.zeros(_lib.call_size("snerf_grad_floats", d), dtype=torch.float32, device=dev)   # the fp32 region only: the backward touches nothing else
         d_t = _poison(torch.empty_like(ctx.tc))
         d_ts = _poison(torch.empty_like(ctx.tsc)) if ctx.tsc is not None else None
+        if not any(ctx.needs_input_grad[8:]) and _sinks_for(ctx.param_like) is None:
+            de = _lib.SnerfDesc.from_buffer_copy(d)
+            de.flags |= _lib.FLAG_EMBED_GRAD
+            _lib.call("snerf_backward", de, ctx.packed, ctx.pin.struct(ctx.tc, ctx.tsc), go, None, d_t, d_ts, ctx.lease.t, ctx.nbytes)
+            ctx.lease.release()
+            return (None, None, None, None, None, None, d_t, d_ts) + (None,) * len(ctx.names)
+        pg = torch.zeros(_lib.call_size("snerf_grad_floats", d), dtype=torch.float32, device=dev)   # the fp32 region only: the backward touches nothing else
         _lib.call("snerf_backward", d, ctx.packed, ctx.pin.struct(ctx.tc, ctx.tsc), go, pg, d_t, d_ts, ctx.lease.t, ctx.nbytes)
         like = dict(zip(ctx.names, ctx.param_like))
         ctx.lease.release()

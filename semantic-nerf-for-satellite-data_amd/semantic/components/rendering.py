@@ -29,6 +29,20 @@ def _side_stream(device):
     return _SIDE_STREAMS[key]
 
 
+def transient_rows(models, name, ts, opts):
+    """The rays' rows of the transient embedding `name` ("t" / "t_s"): models[name](ts), or -- render_options["t_vector"] /
+    ["t_s_vector"], a (tau,) fp32 GPU tensor -- that ONE vector for every ray, whatever `ts` says (an image without a row of its
+    own: eval/utils/embedding.py fits one).  The vector goes through the same Function as a (1, tau) table under a zero index, so
+    its gradient is snerf_embedding_backward's fixed-order sum over the rays."""
+    v = opts.get(name + "_vector")
+    if v is None:
+        return ops.embed_rows(models[name], ts)
+    tau = models[name].weight.shape[1]
+    if v.dim() != 1 or v.shape[0] != tau or v.dtype != torch.float32 or not v.is_cuda:
+        raise ValueError(f"render_options['{name}_vector'] must be a ({tau},) float32 GPU tensor, got {tuple(v.shape)} {v.dtype} on {v.device}")
+    return ops._EmbedRows.apply(v.view(1, tau), torch.zeros_like(ts))
+
+
 def fused_model_rendering(renderer, models, typ, rays, extras, render_options, inference_func, default_inference):
     if inference_func is not default_inference:
         raise NotImplementedError(
@@ -38,8 +52,8 @@ def fused_model_rendering(renderer, models, typ, rays, extras, render_options, i
     opts = render_options or {}
     sun_d = extras_component_fn(extras, "sun_d")
     ts = extras_component_fn(extras, "ts").squeeze(-1).long()
-    rays_t = ops.embed_rows(models["t"], ts)
-    rays_t_s = ops.embed_rows(models["t_s"], ts) if "t_s" in models else None
+    rays_t = transient_rows(models, "t", ts, opts)
+    rays_t_s = transient_rows(models, "t_s", ts, opts) if "t_s" in models else None
     model = models[typ]
     params = dict(model.named_parameters())
     packed = opts.get("packed_params")
@@ -96,8 +110,8 @@ def fused_model_rendering_into(renderer, models, typ, rays, extras, render_optio
     opts = render_options or {}
     sun_d = extras_component_fn(extras, "sun_d")
     ts = extras_component_fn(extras, "ts").squeeze(-1).long()
-    rays_t = ops.embed_rows(models["t"], ts)
-    rays_t_s = ops.embed_rows(models["t_s"], ts) if "t_s" in models else None
+    rays_t = transient_rows(models, "t", ts, opts)
+    rays_t_s = transient_rows(models, "t_s", ts, opts) if "t_s" in models else None
     model = models[typ]
     params = dict(model.named_parameters())
     packed = opts.get("packed_params")
@@ -140,8 +154,8 @@ def fused_model_relighting_into(renderer, models, typ, extras, render_options, o
             raise KeyError(f"fused_model_relighting_into: '{k}' is not a result of the main pass (have {sorted(allowed)})")
     sun_d = extras_component_fn(extras, "sun_d")
     ts = extras_component_fn(extras, "ts").squeeze(-1).long()
-    rays_t = ops.embed_rows(models["t"], ts)
-    rays_t_s = ops.embed_rows(models["t_s"], ts) if "t_s" in models else None
+    rays_t = transient_rows(models, "t", ts, opts)
+    rays_t_s = transient_rows(models, "t_s", ts, opts) if "t_s" in models else None
     params = dict(model.named_parameters())
     packed = opts.get("packed_params")
     if packed is None:
