@@ -23,7 +23,14 @@ writers and rules.  Files under `output_dp`/nadir/sweep/:
     rgb_{k:03d}.png/.tif                 the nadir ortho-image under sun k: uint8
     sun_{k:03d}.png/.tif                 the shadow map under sun k: float32 in the .tif, BONE in the .png
     lit_share.png/.tif                   the mean of the shadow maps -- the share of the suns that light a cell: float32, BONE
-    suns.json                            [{"index", "elevation_deg", "azimuth_deg"}], the suns in order"""
+    suns.json                            [{"index", "elevation_deg", "azimuth_deg"}], the suns in order
+
+export_shadow_check runs the sweep and holds its learned shadow maps to the shadows its own DSM casts (eval/utils/shadow.py
+shadow_check).  Files under `output_dp`/nadir/shadow/:
+    cast_{k:03d}.png/.tif                the shadow the rendered DSM casts under sun k: 0 shadowed, 1 lit, 255 unknown in the .tif;
+                                         black / white / grey in the .png
+    disagree_{k:03d}.png                 where the thresholded learned shadow map and the cast mask differ: white; left-out cells grey
+    shadow_check.json                    the suns, per sun the 8 raw words and the figures derived from them, bias and threshold"""
 import json
 import os
 
@@ -36,6 +43,7 @@ from ..framework.visualize import to_uint8_image
 from ..parallel import world
 from .utils import vismaps
 from .utils.ortho import NO_LABEL, nadir_products, nadir_sun_sweep, ortho_products
+from .utils.shadow import METRICS, UNKNOWN, shadow_check
 
 
 def _png(fp, chw_u8):
@@ -147,3 +155,44 @@ def export_sun_sweep(cfgs, renderer, models, output_dp, zone_string=None, **kwar
         with open(fp("suns.json"), "w") as f:
             json.dump([{"index": k, "elevation_deg": el, "azimuth_deg": az} for k, (el, az) in enumerate(prod["suns"])], f, indent=1)
     return dict(prod, files=files)
+
+
+def _mask_png(fp, mask):
+    """a 0 / 1 / 255 mask as a grey PNG: 0 black, 1 white, 255 (unknown / left out) mid-grey"""
+    lut = torch.zeros(256, dtype=torch.uint8)
+    lut[1], lut[UNKNOWN] = 255, 128
+    _png(fp, lut.to(mask.device)[mask.long()].unsqueeze(0).expand(3, -1, -1))
+
+
+@torch.no_grad()
+def export_shadow_check(cfgs, renderer, models, output_dp, zone_string=None, bias=0.0, threshold=0.5, **kwargs):
+    """nadir_sun_sweep(cfgs, renderer, models, **kwargs) and shadow_check on its products (with the sweep's gt / masks when it was
+    given them), written to `output_dp`/nadir/shadow/: per sun k cast_{k:03d}.png/.tif and disagree_{k:03d}.png, and
+    shadow_check.json.  `zone_string`: the GeoTIFFs' UTM zone, default the zone of the GeoFrame in use.  Every rank computes the
+    products; only rank 0 writes.  Returns the sweep's products, "shadow_check": the check's result, and "files"."""
+    prod = nadir_sun_sweep(cfgs, renderer, models, **kwargs)
+    ds = kwargs.get("dataset")
+    entry = (getattr(ds, "dsm", None) or {}) if kwargs.get("gt") is None and kwargs.get("roi") is None else {}
+    masks = {k: kwargs.get(k) if kwargs.get(k) is not None else entry.get(k) for k in ("gt", "water_mask", "ignore_mask")}
+    chk = shadow_check(prod, bias=bias, threshold=threshold, **masks)
+    if zone_string is None:
+        g = kwargs.get("geo") or getattr(ds, "geo", None)
+        zone_string = getattr(g, "zone_string", None)
+    grid = prod["grid"]
+    out_dp = os.path.join(output_dp, "nadir", "shadow")
+    files = {}
+    if world()[0] == 0:
+        os.makedirs(out_dp, exist_ok=True)
+        fp = lambda name: files.setdefault(name, os.path.join(out_dp, name))      # noqa: E731
+        for k in range(len(chk["suns"])):
+            _mask_png(fp(f"cast_{k:03d}.png"), chk["cast_model"][k])
+            img_utils.save_geotiff(fp(f"cast_{k:03d}.tif"), chk["cast_model"][k], grid, zone_string)
+            _mask_png(fp(f"disagree_{k:03d}.png"), chk["disagree"][k])
+        doc = {"bias": bias, "threshold": threshold,
+               "suns": [{"index": k, "elevation_deg": el, "azimuth_deg": az} for k, (el, az) in enumerate(chk["suns"])]}
+        for key in ("agreement_model", "agreement_gt"):
+            if key in chk:
+                doc[key] = [dict({m: a[m] for m in METRICS}, words=a["words"]) for a in chk[key]]
+        with open(fp("shadow_check.json"), "w") as f:
+            json.dump(doc, f, indent=1)
+    return dict(prod, shadow_check=chk, files=files)
