@@ -283,7 +283,10 @@ size_t snerf_loss_workspace_bytes(const SnerfLossCfg* cfg);
 int snerf_loss_partial(const SnerfLossCfg* cfg, const SnerfLossIn* in, float* totals, void* workspace,
                        size_t workspace_bytes, void* stream);
 /* n_rays_global = number of rays the means run over (sum over ranks), or 0 = use the ray count that snerf_loss_partial
- * summed into `totals` (all-reduced with the other sums, so unequal shards are handled); grads are scaled by grad_scale.
+ * summed into `totals` (all-reduced with the other sums, so unequal shards are handled); grads are scaled by grad_scale, as the
+ * last multiplication (terms are not).  Data parallelism: partial on every rank with n_rays > 0, totals summed over the ranks, finish
+ * with n_rays_global = 0 on each of them == the single-GPU terms and each rank's rows of its gradients; a rank without rays makes no
+ * call (n_rays <= 0 is refused) and adds zeros.  NULL members of SnerfLossGrads are skipped.
  * A label outside [0, n_classes) that is not ignore_index makes the CE term NaN (torch raises there). */
 int snerf_loss_finish(const SnerfLossCfg* cfg, const SnerfLossIn* in, const float* totals, float n_rays_global,
                       float grad_scale, float* terms, const SnerfLossGrads* grads, void* stream);

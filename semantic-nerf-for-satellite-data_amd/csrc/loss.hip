@@ -156,7 +156,7 @@ __global__ __launch_bounds__(256) void loss_finish_kernel(SnerfLossCfg c, SnerfL
       }
       if (c.has_sc && g.sun_sc) {
         const float v = in.sun_sc[p];
-        g.sun_sc[p] = gs * (c.sc_lambda / (3.f * Ng)) * (-2.f * (in.transparency_sc[p] - v) - in.weights_sc[p]);
+        g.sun_sc[p] = gs * ((c.sc_lambda / (3.f * Ng)) * (-2.f * (in.transparency_sc[p] - v) - in.weights_sc[p]));   // gs last, as everywhere: one rounding
       }
     }
     if (lane == 0) {
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(256) void loss_finish_kernel(SnerfLossCfg c, SnerfL
       }
       if (g.depth && c.has_depth) {
         const float w = in.depth_weights ? in.depth_weights[ray] : 1.f;
-        g.depth[ray] = gs * (c.ds_lambda / 3.f) / Ng * 2.f * w * (in.depth[ray] - in.gt_depth[ray]);
+        g.depth[ray] = gs * ((c.ds_lambda / 3.f) / Ng * 2.f * w * (in.depth[ray] - in.gt_depth[ray]));
       }
     }
     if (g.semantic_logits && C > 0) {

@@ -290,3 +290,149 @@ def test_autograd_grad_contract_with_flat_adam():
     for p, g in zip(params, grads):
         if g is not None:
             assert max_abs(p.grad.cpu(), g.cpu()) <= 1e-6 * max(1e-12, float(g.abs().max()))
+
+
+# ---- snerf_adam_step at bucket size, called directly ---------------------------------------------------------------------------------
+ADAM_GRID = 2048 * 256 * 4            # floats one pass of the capped grid covers (2048 blocks x 256 threads x float4)
+ADAM_N = ADAM_GRID + 1028             # + a second grid-stride pass of 257 float4: one past a wavefront-aligned 256
+ADAM_GUARD = 64
+# the ABI takes floats: all three evaluations (kernel, torch fp32, numpy fp64) get the SAME hyperparameters, the fp32 values.  With
+# the decimal doubles torch's host-side 1 - beta2 (0.001 rounded to fp32) and the kernel's 1.f - 0.999f differ by 1.3e-5 relative:
+# an offset in exp_avg_sq that the bias correction (computed from the same beta2 on each side) cancels in the step itself.
+ADAM_LR, ADAM_B1, ADAM_B2, ADAM_EPS = (float(np.float32(x)) for x in (5e-4, 0.9, 0.999, 1e-8))
+
+
+@pytest.fixture(scope="module")
+def adam_inputs():
+    """params ~ randn, three gradients: magnitudes log-uniform over 1e-12 .. 1e3, one sign per element, one element in 16 an exact zero
+    on every step; the second grid-stride pass (the last 1,028 elements) carries distinct values of its own"""
+    g = torch.Generator().manual_seed(77)
+    p0 = torch.randn(ADAM_N, generator=g)
+    sign = torch.where(torch.rand(ADAM_N, generator=g) < 0.5, -1.0, 1.0)
+    zero = torch.arange(ADAM_N) % 16 == 5
+    zero[ADAM_GRID:] = False             # the second pass carries its own values
+    grads = []
+    for step in range(3):
+        mag = 10.0 ** (torch.rand(ADAM_N, generator=g, dtype=torch.float64) * 15.0 - 12.0)
+        gr = (mag.float() * sign)
+        gr[zero] = 0.0
+        tail = torch.arange(1028, dtype=torch.float32)
+        gr[ADAM_GRID:] = (1.0 + tail / 1028.0) * 10.0 ** (step - 2) * torch.where(tail % 2 == 0, 1.0, -1.0)
+        grads.append(gr)
+    assert len(set(grads[0][ADAM_GRID:].tolist())) == 1028
+    return p0, grads, zero
+
+
+def _adam_ref64(p, m, v, g, t):
+    """torch.optim.Adam's formulas (single tensor, no weight decay, no amsgrad) in fp64, in place on numpy arrays"""
+    m *= ADAM_B1
+    m += (1.0 - ADAM_B1) * g
+    v *= ADAM_B2
+    v += (1.0 - ADAM_B2) * g * g
+    bc1, bc2 = 1.0 - ADAM_B1 ** t, 1.0 - ADAM_B2 ** t
+    p -= (ADAM_LR / bc1) * m / (np.sqrt(v) / np.sqrt(bc2) + ADAM_EPS)
+
+
+def _rel_dist(a, ref):
+    """max |a - ref| / |ref| over the elements where ref != 0; where ref == 0, a must be 0"""
+    a, ref = np.asarray(a, dtype=np.float64), np.asarray(ref, dtype=np.float64)
+    nz = ref != 0
+    assert not a[~nz].any()
+    return float((np.abs(a[nz] - ref[nz]) / np.abs(ref[nz])).max())
+
+
+@pytest.fixture(scope="module")
+def adam_reference(adam_inputs):
+    p0, grads, _ = adam_inputs
+    return adam_reference_distances(p0, grads)
+
+
+def adam_reference_distances(p0, grads):
+    """-> (fp64 states after each step [(p, m, v)], the max relative distance of torch.optim.Adam in fp32 on the CPU from them: (m, v))"""
+    p, m, v = p0.double().numpy().copy(), np.zeros(ADAM_N), np.zeros(ADAM_N)
+    tp = torch.nn.Parameter(p0.clone())
+    opt = torch.optim.Adam([tp], lr=ADAM_LR, betas=(ADAM_B1, ADAM_B2), eps=ADAM_EPS, weight_decay=0)
+    states, dm, dv = [], 0.0, 0.0
+    for t, gr in enumerate(grads, 1):
+        _adam_ref64(p, m, v, gr.double().numpy(), t)
+        states.append((p.copy(), m.copy(), v.copy()))
+        tp.grad = gr.clone()
+        opt.step()
+        st = opt.state[tp]
+        dm = max(dm, _rel_dist(st["exp_avg"].numpy(), m))
+        dv = max(dv, _rel_dist(st["exp_avg_sq"].numpy(), v))
+        assert np.allclose(tp.detach().numpy(), p, rtol=2e-6, atol=1e-7)
+    return states, (dm, dv)
+
+
+def _guarded(src):
+    """a device buffer of src's values with ADAM_GUARD guard floats behind it"""
+    b = torch.full((src.numel() + ADAM_GUARD,), -7.25, device=DEV)
+    b[:src.numel()] = src.to(DEV)
+    return b
+
+
+def _adam_call(bufs, step, grad_scale=1.0):
+    from snerf_amd import _lib
+    p, g, m, v = bufs
+    _lib.call("snerf_adam_step", p, g, m, v, ADAM_N, ADAM_LR, ADAM_B1, ADAM_B2, ADAM_EPS, step, grad_scale)
+    for b in bufs:
+        assert bool((b[ADAM_N:] == -7.25).all()), "guard floats behind an Adam buffer were written"
+    return [b[:ADAM_N].cpu() for b in (p, m, v)]
+
+
+def test_adam_step_at_bucket_size_against_fp64(adam_inputs, adam_reference):
+    """snerf_adam_step on 2,097,152 + 1,028 floats -- one full pass of the capped 2048 x 256 float4 grid and a second grid-stride pass,
+    as every training step on the 2.83 M-float bucket takes -- for three steps against torch's formulas in numpy fp64.
+    params: rtol 2e-6, atol 1e-7 (the bar of test_fused_adam_matches_torch_adam).  exp_avg / exp_avg_sq: 4 x the max relative
+    distance of torch.optim.Adam (fp32, CPU) from the same fp64 reference on the same inputs -- both are fp32 evaluations of one
+    formula, differing in contraction and in where the host scalars round.  Measured: torch 1.61e-07 (exp_avg) and 2.75e-07
+    (exp_avg_sq), so the bars are 6.45e-07 and 1.10e-06; the kernel measured 2.31e-07 and 2.71e-07 (params: 5.8e-07 max abs).
+    Elements whose gradient is 0 on every step keep zero state and the bits of their parameter; guard floats stay untouched."""
+    p0, grads, zero = adam_inputs
+    states, (dm, dv) = adam_reference
+    print(f"torch fp32 Adam vs fp64: exp_avg {dm:.3e}, exp_avg_sq {dv:.3e} (bars: 4 x)")
+    bufs = [_guarded(p0), _guarded(grads[0]), _guarded(torch.zeros(ADAM_N)), _guarded(torch.zeros(ADAM_N))]
+    for t, gr in enumerate(grads, 1):
+        bufs[1][:ADAM_N] = gr.to(DEV)
+        p, m, v = _adam_call(bufs, t)
+        rp, rm, rv = states[t - 1]
+        km, kv = _rel_dist(m.numpy(), rm), _rel_dist(v.numpy(), rv)
+        print(f"step {t}: kernel vs fp64: exp_avg {km:.3e}, exp_avg_sq {kv:.3e}, params max abs {float(np.abs(p.numpy() - rp).max()):.3e}")
+        assert np.allclose(p.numpy(), rp, rtol=2e-6, atol=1e-7)
+        assert km <= 4 * dm and kv <= 4 * dv, (km, dm, kv, dv)
+        assert torch.equal(p[zero].view(torch.int32), p0[zero].view(torch.int32))
+        assert not m[zero].any() and not v[zero].any()
+
+
+def test_adam_grad_scale_at_bucket_size(adam_inputs, adam_reference):
+    """grad_scale = 2^-7 on g is, bit for bit in params and both moments, grad_scale = 1 on g * 2^-7; grad_scale = 1/3 meets the bars of
+    test_adam_step_at_bucket_size_against_fp64 against the fp64 reference fed g / 3.  Both as a fourth step on the state three
+    steps have built."""
+    p0, grads, zero = adam_inputs
+    states, (dm, dv) = adam_reference
+    start = [_guarded(p0), _guarded(grads[0]), _guarded(torch.zeros(ADAM_N)), _guarded(torch.zeros(ADAM_N))]
+    for t, gr in enumerate(grads, 1):
+        start[1][:ADAM_N] = gr.to(DEV)
+        _adam_call(start, t)
+    g4 = grads[1]
+    a = [b.clone() for b in start]
+    a[1][:ADAM_N] = g4.to(DEV)
+    got_a = _adam_call(a, 4, grad_scale=2.0 ** -7)
+    b = [x.clone() for x in start]
+    b[1][:ADAM_N] = (g4 * 2.0 ** -7).to(DEV)
+    got_b = _adam_call(b, 4, grad_scale=1.0)
+    for x, y in zip(got_a, got_b):
+        assert torch.equal(x.view(torch.int32), y.view(torch.int32))
+    assert not torch.equal(got_a[0], start[0][:ADAM_N].cpu())
+    third = float(np.float32(1.0 / 3.0))
+    c = [x.clone() for x in start]
+    c[1][:ADAM_N] = g4.to(DEV)
+    p, m, v = _adam_call(c, 4, grad_scale=third)
+    # the reference continues from the KERNEL's state after three steps (fp32 values, exact in fp64): the fourth step alone is compared
+    rp, rm, rv = (x[:ADAM_N].double().cpu().numpy().copy() for x in (start[0], start[2], start[3]))
+    _adam_ref64(rp, rm, rv, g4.double().numpy() * third, 4)
+    km, kv = _rel_dist(m.numpy(), rm), _rel_dist(v.numpy(), rv)
+    print(f"grad_scale 1/3: kernel vs fp64: exp_avg {km:.3e}, exp_avg_sq {kv:.3e}")
+    assert np.allclose(p.numpy(), rp, rtol=2e-6, atol=1e-7)
+    assert km <= 4 * dm and kv <= 4 * dv, (km, dm, kv, dv)

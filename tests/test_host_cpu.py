@@ -138,6 +138,71 @@ def test_two_rank_gloo_gradient_allreduce_and_sharding(tmp_path):
         assert p.wait(timeout=240) == 0
 
 
+_WORKER_N = r"""
+import sys
+sys.path.insert(0, {root!r})
+import torch, torch.distributed as dist
+from snerf_amd import parallel
+rank, world, dev = parallel.init_distributed(backend="gloo")
+assert world == {world} and dev.type == "cpu" and torch.get_num_threads() == 1
+ps = [torch.nn.Parameter(torch.zeros(s)) for s in ((3, 5), (7,), (2, 2, 2))]
+for i, p in enumerate(ps):
+    p.grad = torch.full_like(p, float(rank + 1) * (i + 1))
+buf = parallel.allreduce_gradients(ps)
+for i, p in enumerate(ps):
+    assert torch.equal(p.grad, torch.full_like(p, world * (world + 1) / 2 * (i + 1))), p.grad
+assert buf.numel() == 15 + 7 + 8
+# the 16 totals of the fused loss between its two phases
+t = torch.arange(16, dtype=torch.float32) * (rank + 1)
+assert torch.equal(parallel.allreduce_sum_(t), torch.arange(16, dtype=torch.float32) * (world * (world + 1) / 2))
+from snerf_amd.framework.datasets import GpuRayBank
+bank = GpuRayBank.synthetic(512, seed=1)
+mine = bank.batch(3, 64, rank, world)["rays"]
+gathered = [torch.empty_like(mine) for _ in range(world)]
+dist.all_gather(gathered, mine)
+assert torch.equal(torch.cat(gathered, 0), bank.batch(3, 64)["rays"])
+# rank-sharded full-frame inference: ragged tails and empty shards (n = 9: 2, 2, 2, 2, 1, 0, 0, 0; n = 1: seven empty ones)
+from snerf_amd.eval.utils.util import shard_and_gather
+for n in (1001, 64, 9, 1):
+    def rows(lo, hi, n=n):
+        idx = torch.arange(lo, hi)
+        return {{"rgb_coarse": torch.stack([idx.float(), idx.float() * 2, idx.float() + 0.5], 1), "depth_coarse": idx.float() / 7,
+                "semantic_label_coarse": idx % 5, "weights_coarse": idx.float()[:, None].repeat(1, 4)}}
+    got = shard_and_gather(rows, n)
+    want = rows(0, n)
+    lo, hi = got["_rows"]
+    assert (lo, hi) == parallel.frame_shard(n) and hi - lo == max(0, min(-(-n // world), n - rank * -(-n // world)))
+    for k in ("rgb_coarse", "depth_coarse", "semantic_label_coarse"):
+        assert got[k].dtype == want[k].dtype and torch.equal(got[k], want[k]), (n, k)
+    assert torch.equal(got["weights_coarse"], want["weights_coarse"][lo:hi])
+# the split the sharded-loss tests use (tests/loss_shards_ref.py ROWS[4])
+from tests import loss_shards_ref
+assert [parallel.frame_shard(9, r, world) for r in range(world)] == loss_shards_ref.ROWS[4][3] == loss_shards_ref.frame_bounds(9, world)
+assert parallel.frame_shard(9) == loss_shards_ref.ROWS[4][3][rank]
+dist.barrier()
+print("rank", rank, "ok")
+"""
+
+
+def test_eight_rank_gloo_sharding(tmp_path):
+    """the world-2 checks above at the world size of the 8-GPU presets: the bucket sum, the 16-float totals vector, the bank's
+    shards in rank order, frame_shard / shard_and_gather with ragged and empty shards"""
+    world = 8
+    script = tmp_path / "w8.py"
+    script.write_text(_WORKER_N.format(root=ROOT, world=world))
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29677", WORLD_SIZE=str(world), CUDA_VISIBLE_DEVICES="",
+               HIP_VISIBLE_DEVICES="", OMP_NUM_THREADS="1")
+    procs = [subprocess.Popen([sys.executable, str(script)], env=dict(env, RANK=str(r), LOCAL_RANK=str(r)), cwd=ROOT)
+             for r in range(world)]
+    try:
+        codes = [p.wait(timeout=240) for p in procs]
+    finally:
+        for p in procs:
+            if p.poll() is None:
+                p.kill()
+    assert codes == [0] * world, codes
+
+
 def test_model_forward_is_fused_only():
     """the per-point nn.Module forward is not a fallback path: it refuses to run"""
     import types
