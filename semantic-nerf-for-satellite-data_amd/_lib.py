@@ -213,6 +213,9 @@ def _signatures():
         "snerf_normalize_rows": (i, (p, ll, i, i, p, st)),
         "snerf_geo_cloud": (i, (p, i, p, ll, P(SnerfGeoParams), p, p, p, st)),
         "snerf_geo_points": (i, (p, ll, P(SnerfGeoParams), p, p, p, st)),
+        # suns_host is a HOST table (a ctypes array): void*, as the RPC tables
+        "snerf_shadow_cast": (i, (p, i, i, p, i, d, d, p, p, st)),
+        "snerf_shadow_agreement": (i, (p, p, p, ll, i, d, p, st)),
         "snerf_profile_begin": (i, ()),
         "snerf_profile_end": (i, (P(SnerfProfile),)),
         "snerf_test_set_kc_grid": (i, (i,)),
@@ -229,20 +232,8 @@ SIGNATURES = _signatures()
 EXPORTED_SYMBOLS = tuple(SIGNATURES)
 
 
-def _shadow_signatures():
-    i, ll, d, p, st = C.c_int, C.c_longlong, C.c_double, C.c_void_p, c_stream
-    return {
-        # suns_host is a HOST table (a ctypes array): void*, as the RPC tables
-        "snerf_shadow_cast": (i, (p, i, i, p, i, d, d, p, p, st)),
-        "snerf_shadow_agreement": (i, (p, p, p, ll, i, d, p, st)),
-    }
-
-
-# the cast-shadow entries: one row per prototype of include/snerf_shadow.h in that header's order (tests/test_shadow_cpu.py compares
-# the two).  A table of its own because SIGNATURES is include/snerf_hip.h, symbol for symbol; lib() applies both, call() serves both.
-SHADOW_SIGNATURES = _shadow_signatures()
-SHADOW_MAX_SUNS = 64       # include/snerf_shadow.h SNERF_SHADOW_MAX_SUNS
-SHADOW_UNKNOWN = 255       # include/snerf_shadow.h SNERF_SHADOW_UNKNOWN
+SHADOW_MAX_SUNS = 64       # include/snerf_hip.h SNERF_SHADOW_MAX_SUNS
+SHADOW_UNKNOWN = 255       # include/snerf_hip.h SNERF_SHADOW_UNKNOWN
 
 ORTHO_MAX_RADIUS = 7       # include/snerf_hip.h SNERF_ORTHO_MAX_RADIUS
 ORTHO_MAX_CLASSES = 255    # include/snerf_hip.h SNERF_ORTHO_MAX_CLASSES
@@ -252,8 +243,8 @@ ORTHO_NO_LABEL = 255       # include/snerf_hip.h SNERF_ORTHO_NO_LABEL
 # stream follows them)
 _PLANS = {name: (tuple(float if t in (C.c_float, C.c_double) else None if issubclass(t, (C.c_void_p, C._Pointer)) else int
                        for t in args if t is not c_stream), c_stream in args)
-          for name, (_, args) in {**SIGNATURES, **SHADOW_SIGNATURES}.items()}
-assert all(c_stream not in args[:-1] for _, args in {**SIGNATURES, **SHADOW_SIGNATURES}.values())
+          for name, (_, args) in SIGNATURES.items()}
+assert all(c_stream not in args[:-1] for _, args in SIGNATURES.values())
 
 _lib = None
 
@@ -272,7 +263,7 @@ def lib():
     # owns torch's device context and streams (loading ours first brings up a second runtime that then
     # reports "no ROCm-capable device").
     L = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**SIGNATURES, **SHADOW_SIGNATURES}.items():
+    for name, (restype, argtypes) in SIGNATURES.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, list(argtypes)
     if L.snerf_version() != ABI_VERSION:

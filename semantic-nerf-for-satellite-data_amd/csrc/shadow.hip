@@ -1,6 +1,6 @@
 // Cast shadows on the DSM lattice: the shadow a height field casts under a sun (one Amanatides-Woo march per cell and sun), and
 // the agreement of a learned shadow map with the cast mask (integer counts and quantised integer sums).  The spec is
-// include/snerf_shadow.h and DESIGN.md section 5o.
+// the cast-shadow section of include/snerf_hip.h and DESIGN.md section 5o.
 //   - the march is fp64, evaluated operation by operation (no fused multiply-adds in this file), and uses only + - * /,
 //     comparisons and integer work: the host evaluates every transcendental, so tests/shadow_numpy.py reproduces it bit for bit.
 //     Plain operators under `fp contract(off)`, NOT __dadd_rn / __dmul_rn: those are header inlines compiled under the build's
@@ -12,7 +12,7 @@
 //     independent of the launch order.
 // No allocation, no copy and no host synchronisation; both entries run on the caller's stream.
 #include "reduce.h"
-#include "../../include/snerf_shadow.h"
+#include "../../include/snerf_hip.h"
 
 #pragma clang fp contract(off)
 

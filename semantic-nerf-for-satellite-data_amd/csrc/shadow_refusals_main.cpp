@@ -1,7 +1,7 @@
 // Stand-alone host program over the refusal paths of snerf_shadow_cast / snerf_shadow_agreement (shadow.hip): every call below is
 // refused by the argument checks, so no kernel launch is reached and no GPU is needed.  Built with ASAN + UBSAN on the host code
 // (`make shadow-refusals`); exits 0 when every call came back with the expected code and message.  CPU machines only.
-#include "../../include/snerf_shadow.h"
+#include "../../include/snerf_hip.h"
 
 #include <cmath>
 #include <cstdarg>

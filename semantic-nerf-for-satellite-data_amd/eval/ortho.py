@@ -65,6 +65,41 @@ def _scalar_plane(fp, name, plane, cmap, grid, zone_string):
     img_utils.save_geotiff(fp(name + ".tif"), plane, grid, zone_string)
 
 
+def _color_plane(fp, name, chw, grid, zone_string):
+    """a float32 colour plane (3, H, W) as uint8 `name`.png and `name`.tif"""
+    u8 = to_uint8_image(chw)
+    _png(fp(name + ".png"), u8)
+    img_utils.save_geotiff(fp(name + ".tif"), u8.permute(1, 2, 0).contiguous(), grid, zone_string)
+
+
+def _label_plane(fp, name, label, palette, grid, zone_string):
+    """a uint8 class plane as `name`.png (the colours of `palette`, default colormaps.DEFAULT_PALETTE) and `name`.tif (the ids)"""
+    _png(fp(name + ".png"), label_colors(label, colormaps.DEFAULT_PALETTE if palette is None else palette))
+    img_utils.save_geotiff(fp(name + ".tif"), label, grid, zone_string)
+
+
+def _zone(zone_string, kwargs, geo=None):
+    """the GeoTIFFs' UTM zone: `zone_string`, else the zone of the GeoFrame in use -- the products' geo=, their dataset's, or `geo`"""
+    if zone_string is None:
+        zone_string = getattr(kwargs.get("geo") or getattr(kwargs.get("dataset"), "geo", None) or geo, "zone_string", None)
+    return zone_string
+
+
+def _writer(*dirs):
+    """-> (files, fp): on rank 0 the directory os.path.join(*dirs) exists and fp(name) is the path of `name` in it, entered into
+    `files`; on every other rank fp is None -- only rank 0 writes"""
+    out_dp = os.path.join(*dirs)
+    files = {}
+    if world()[0] != 0:
+        return files, None
+    os.makedirs(out_dp, exist_ok=True)
+    return files, lambda name: files.setdefault(name, os.path.join(out_dp, name))
+
+
+def _sun_rows(suns):
+    return [{"index": k, "elevation_deg": el, "azimuth_deg": az} for k, (el, az) in enumerate(suns)]
+
+
 @torch.no_grad()
 def export_ortho(cfgs, renderer, models, images, output_dp, split="test", palette=None, zone_string=None, **kwargs):
     """ortho_products(cfgs, renderer, models, images, **kwargs) of the split's images, written to `output_dp`/ortho/{split}/.
@@ -76,23 +111,14 @@ def export_ortho(cfgs, renderer, models, images, output_dp, split="test", palett
     if not todo:
         raise ValueError(f"no {split} image to export")
     prod = ortho_products(cfgs, renderer, models, todo, **kwargs)
-    if zone_string is None:
-        g = kwargs.get("geo") or (todo[0].get("dsm") or {}).get("geo")
-        zone_string = getattr(g, "zone_string", None)
+    zone_string = _zone(zone_string, kwargs, (todo[0].get("dsm") or {}).get("geo"))
     grid = prod["grid"]
-    out_dp = os.path.join(output_dp, "ortho", split)
-    files = {}
-    if world()[0] == 0:
-        os.makedirs(out_dp, exist_ok=True)
-        fp = lambda name: files.setdefault(name, os.path.join(out_dp, name))      # noqa: E731
-        rgb8 = to_uint8_image(torch.nan_to_num(prod["rgb"], nan=0.0))
-        _png(fp("rgb.png"), rgb8)
-        img_utils.save_geotiff(fp("rgb.tif"), rgb8.permute(1, 2, 0).contiguous(), grid, zone_string)
-        pal = colormaps.DEFAULT_PALETTE if palette is None else palette
+    files, fp = _writer(output_dp, "ortho", split)
+    if fp:
+        _color_plane(fp, "rgb", torch.nan_to_num(prod["rgb"], nan=0.0), grid, zone_string)
         for key in ("label_top", "label_vote"):
             if key in prod:
-                _png(fp(key + ".png"), label_colors(prod[key], pal))
-                img_utils.save_geotiff(fp(key + ".tif"), prod[key], grid, zone_string)
+                _label_plane(fp, key, prod[key], palette, grid, zone_string)
         planes = [("top_alt", colormaps.COLORMAP_JET), ("dsm", colormaps.COLORMAP_JET)]
         if "vote_share" in prod:
             planes.append(("vote_share", colormaps.COLORMAP_BONE))
@@ -108,23 +134,14 @@ def export_nadir(cfgs, renderer, models, output_dp, palette=None, zone_string=No
     computes the products (with sharded=True each renders its share of the lattice); only rank 0 writes.  Returns the products
     plus "files": {name: path}."""
     prod = nadir_products(cfgs, renderer, models, **kwargs)
-    if zone_string is None:
-        g = kwargs.get("geo") or getattr(kwargs.get("dataset"), "geo", None)
-        zone_string = getattr(g, "zone_string", None)
+    zone_string = _zone(zone_string, kwargs)
     grid = prod["grid"]
-    out_dp = os.path.join(output_dp, "nadir")
-    files = {}
-    if world()[0] == 0:
-        os.makedirs(out_dp, exist_ok=True)
-        fp = lambda name: files.setdefault(name, os.path.join(out_dp, name))      # noqa: E731
+    files, fp = _writer(output_dp, "nadir")
+    if fp:
         for key in ("rgb", "albedo"):
-            u8 = to_uint8_image(prod[key])
-            _png(fp(key + ".png"), u8)
-            img_utils.save_geotiff(fp(key + ".tif"), u8.permute(1, 2, 0).contiguous(), grid, zone_string)
+            _color_plane(fp, key, prod[key], grid, zone_string)
         if "label" in prod:
-            pal = colormaps.DEFAULT_PALETTE if palette is None else palette
-            _png(fp("label.png"), label_colors(prod["label"], pal))
-            img_utils.save_geotiff(fp("label.tif"), prod["label"], grid, zone_string)
+            _label_plane(fp, "label", prod["label"], palette, grid, zone_string)
         for key, cmap in (("dsm", colormaps.COLORMAP_JET), ("sun", colormaps.COLORMAP_BONE), ("beta", colormaps.COLORMAP_BONE)):
             _scalar_plane(fp, key, prod[key], cmap, grid, zone_string)
     return dict(prod, files=files)
@@ -137,23 +154,16 @@ def export_sun_sweep(cfgs, renderer, models, output_dp, zone_string=None, **kwar
     suns.json.  `zone_string`: the GeoTIFFs' UTM zone, default the zone of the GeoFrame in use.  Every rank computes the products
     (with sharded=True each renders its share of the lattice); only rank 0 writes.  Returns the products plus "files"."""
     prod = nadir_sun_sweep(cfgs, renderer, models, **kwargs)
-    if zone_string is None:
-        g = kwargs.get("geo") or getattr(kwargs.get("dataset"), "geo", None)
-        zone_string = getattr(g, "zone_string", None)
+    zone_string = _zone(zone_string, kwargs)
     grid = prod["grid"]
-    out_dp = os.path.join(output_dp, "nadir", "sweep")
-    files = {}
-    if world()[0] == 0:
-        os.makedirs(out_dp, exist_ok=True)
-        fp = lambda name: files.setdefault(name, os.path.join(out_dp, name))      # noqa: E731
+    files, fp = _writer(output_dp, "nadir", "sweep")
+    if fp:
         for k in range(len(prod["suns"])):
-            u8 = to_uint8_image(prod["rgb"][k])
-            _png(fp(f"rgb_{k:03d}.png"), u8)
-            img_utils.save_geotiff(fp(f"rgb_{k:03d}.tif"), u8.permute(1, 2, 0).contiguous(), grid, zone_string)
+            _color_plane(fp, f"rgb_{k:03d}", prod["rgb"][k], grid, zone_string)
             _scalar_plane(fp, f"sun_{k:03d}", prod["sun"][k], colormaps.COLORMAP_BONE, grid, zone_string)
         _scalar_plane(fp, "lit_share", prod["lit_share"], colormaps.COLORMAP_BONE, grid, zone_string)
         with open(fp("suns.json"), "w") as f:
-            json.dump([{"index": k, "elevation_deg": el, "azimuth_deg": az} for k, (el, az) in enumerate(prod["suns"])], f, indent=1)
+            json.dump(_sun_rows(prod["suns"]), f, indent=1)
     return dict(prod, files=files)
 
 
@@ -175,21 +185,15 @@ def export_shadow_check(cfgs, renderer, models, output_dp, zone_string=None, bia
     entry = (getattr(ds, "dsm", None) or {}) if kwargs.get("gt") is None and kwargs.get("roi") is None else {}
     masks = {k: kwargs.get(k) if kwargs.get(k) is not None else entry.get(k) for k in ("gt", "water_mask", "ignore_mask")}
     chk = shadow_check(prod, bias=bias, threshold=threshold, **masks)
-    if zone_string is None:
-        g = kwargs.get("geo") or getattr(ds, "geo", None)
-        zone_string = getattr(g, "zone_string", None)
+    zone_string = _zone(zone_string, kwargs)
     grid = prod["grid"]
-    out_dp = os.path.join(output_dp, "nadir", "shadow")
-    files = {}
-    if world()[0] == 0:
-        os.makedirs(out_dp, exist_ok=True)
-        fp = lambda name: files.setdefault(name, os.path.join(out_dp, name))      # noqa: E731
+    files, fp = _writer(output_dp, "nadir", "shadow")
+    if fp:
         for k in range(len(chk["suns"])):
             _mask_png(fp(f"cast_{k:03d}.png"), chk["cast_model"][k])
             img_utils.save_geotiff(fp(f"cast_{k:03d}.tif"), chk["cast_model"][k], grid, zone_string)
             _mask_png(fp(f"disagree_{k:03d}.png"), chk["disagree"][k])
-        doc = {"bias": bias, "threshold": threshold,
-               "suns": [{"index": k, "elevation_deg": el, "azimuth_deg": az} for k, (el, az) in enumerate(chk["suns"])]}
+        doc = {"bias": bias, "threshold": threshold, "suns": _sun_rows(chk["suns"])}
         for key in ("agreement_model", "agreement_gt"):
             if key in chk:
                 doc[key] = [dict({m: a[m] for m in METRICS}, words=a["words"]) for a in chk[key]]

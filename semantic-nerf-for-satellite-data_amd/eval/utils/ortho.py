@@ -284,112 +284,26 @@ def _nadir_finish(grid, g, geo, rays, bounds, loc, n_classes, gt, water_mask, ig
     return out
 
 
-@torch.no_grad()
-def nadir_products(cfgs, renderer, models, geo=None, grid=None, roi=None, min_alt=None, max_alt=None, sun_elevation=None,
-                   sun_azimuth=None, t=0, render_options={}, sharded=False, gt=None, water_mask=None, ignore_mask=None,
-                   dataset=None):
-    """The map of the lattice rendered from above: one vertical ray per cell (rays.nadir_construct between `max_alt` and
-    `min_alt` metres, through `geo`, a GeoFrame), extras of the sun at (`sun_elevation`, `sun_azimuth`) degrees and the
-    embedding index `t`.  The grid: `grid` (a DsmGrid, or a window of one from dsm.grid_struct), else the ROI grid of `roi`
-    (a DsmGrid or the roi_txt meta), else a ValueError.  `dataset` (a loaded SatNeRFDataset) supplies what is not given: its
-    geo, its "dsm" entry (roi, gt, masks), the min / max of its images' alt_min / alt_max, the sun of its first image.
-
-    ONE walk of util.render_chunks over the rays (`sharded`: over this rank's frame_shard of them, the results all-gathered as
-    sharded_lean_inference does): the per-ray results are copied, albedo / sun / beta folded by vismaps.fold_chunk; no
-    frame-sized per-sample tensor exists.  `render_options` as everywhere in evaluation ({"perturb": 0} for a repeatable map).
-
-    Returns {"grid": DsmGrid (of the window), "dsm": (H, W) f32 -- the altitude of geo.cloud(rays, depth), every cell filled --,
-    "rgb": (3, H, W) f32, "albedo": (3, H, W) f32, "sun": (H, W) f32 (the shadow map), "beta": (H, W) f32[, "label": (H, W) u8
-    (a model with classes; 255 for a label beyond 254)], "rays": the (H W, 8) nadir rays, "planimetric_error": the largest
-    |east / north of the cloud - cell centre| in metres (the self-check of the ray construction), "scene_bounds": GeoBounds of
-    the lattice's scene x / y (to_scene's stats)[, "mae": {"mean", "median"} of dsm.compute_mae(dsm, gt, water_mask,
-    ignore_mask), with `gt` (H, W)]}."""
-    from ... import ops, parallel
-    from ...baseline.components import rays as R
-    from . import vismaps
-    from .util import render_chunks, result_buffers, shard_options
-    geo, roi, gt, water_mask, ignore_mask, min_alt, max_alt, sun_elevation, sun_azimuth = _nadir_defaults(
-        dataset, geo, roi, gt, water_mask, ignore_mask, min_alt, max_alt, sun_elevation, sun_azimuth)
-    grid, g, rays, bounds = _nadir_lattice("nadir_products", models, geo, grid, roi, min_alt, max_alt)
-    h, w = g.out_h, g.out_w
-    n = _cells(g)
-    model = models["coarse"]
-    n_classes = model.spec.n_classes
-    dev = rays.device
-    extras = R.nadir_extras(sun_elevation, sun_azimuth, t, n, dev)
-
-    lo, hi = parallel.frame_shard(n) if sharded else (0, n)
-    m = hi - lo
-    S = cfgs.pipeline.n_samples
-    keys = ("rgb", "depth") + (("semantic_label",) if n_classes else ()) + ("weights", "albedo", "sun", "beta")
-    loc = {"rgb": torch.empty((m, 3), dtype=torch.float32, device=dev), "depth": torch.empty(m, dtype=torch.float32, device=dev),
-           "albedo": torch.empty((3, m), dtype=torch.float32, device=dev), "sun": torch.empty(m, dtype=torch.float32, device=dev),
-           "beta": torch.empty(m, dtype=torch.float32, device=dev)}
-    if n_classes:
-        loc["label"] = torch.empty(m, dtype=torch.int64, device=dev)
-    if m:
-        ops.release_workspaces()
-        bufs = result_buffers(keys, min(cfgs.pipeline.render_chunk_size, m), S, n_classes, dev)
-        planes = {"albedo_map": loc["albedo"], "sun_map": loc["sun"], "beta_map": loc["beta"]}
-        stats = vismaps.new_stats(dev)
-        for i, k, sl in render_chunks(cfgs, renderer, models, rays[lo:hi], extras[lo:hi], bufs,
-                                      shard_options(render_options, lo, hi, n)):
-            loc["rgb"][i:i + k].copy_(sl["rgb_coarse"])
-            loc["depth"][i:i + k].copy_(sl["depth_coarse"])
-            if n_classes:
-                loc["label"][i:i + k].copy_(sl["semantic_label_coarse"])
-            vismaps.fold_chunk(planes, stats, i, m, k, S, weights=sl["weights_coarse"], albedo=sl["albedo_coarse"],
-                               sun=sl["sun_coarse"], beta=sl["beta_coarse"])
-    if sharded:
-        loc["albedo"] = loc["albedo"].t().contiguous()
-        loc = {key: parallel.allgather_rows(v, n) for key, v in loc.items()}
-        loc["albedo"] = loc["albedo"].t().contiguous()
-
-    out = _nadir_finish(grid, g, geo, rays, bounds, loc, n_classes, gt, water_mask, ignore_mask)
-    out["rgb"] = loc["rgb"].t().contiguous().reshape(3, h, w)
-    out["sun"] = loc["sun"].reshape(h, w)
-    return out
-
-
-def sweep_suns(suns, dataset=None, who="nadir_sun_sweep"):
-    """the suns of a sweep as a list of (elevation_deg, azimuth_deg) floats: `suns`, else those of the images of a loaded
-    dataset's split, in split order; an empty list (or neither) is a ValueError"""
-    if suns is None and dataset is not None:
-        suns = [(m["sun_elevation"], m["sun_azimuth"]) for m in dataset.metas]
-    suns = [(float(el), float(az)) for el, az in (suns or ())]
-    if not suns:
-        raise ValueError(f"{who}: no sun -- pass suns=[(elevation_deg, azimuth_deg), ...] (or a loaded dataset= to take its images' suns)")
-    return suns
-
-
-@torch.no_grad()
-def nadir_sun_sweep(cfgs, renderer, models, suns=None, geo=None, grid=None, roi=None, min_alt=None, max_alt=None, t=0,
-                    render_options={}, sharded=False, gt=None, water_mask=None, ignore_mask=None, dataset=None):
-    """nadir_products under K suns in ONE walk over the lattice's rays (util.relight_chunks): per chunk a full pass under suns[0]
-    and a relight per further sun, which re-runs only the sun-visibility branch, the sky colour and the composite on the chunk the
-    workspace holds (DESIGN.md section 5m).  `suns`: (elevation_deg, azimuth_deg) pairs; None with a loaded `dataset`: the suns of
-    the split's images in split order.  The lattice, `geo`, the altitudes, `t`, `sharded`, `gt` and the masks as for
-    nadir_products, which `dataset` supplies likewise.
-
-    Returns the products of nadir_products that do not depend on the sun ("grid", "dsm", "albedo", "beta"[, "label"], "rays",
-    "planimetric_error", "scene_bounds"[, "mae"]) and "suns": the list, "rgb": (K, 3, H, W) f32, "sun": (K, H, W) f32 (the
-    shadow maps, folded by vismaps.fold_chunk), "lit_share": (H, W) f32 -- the mean of the K shadow maps, summed in fp64 in sun
-    order and rounded once.  Map k has the bits of nadir_products under sun k, given the same depths ({"perturb": 0}): the jitter
-    is drawn once per chunk and shared by the suns."""
+def _nadir_walk(who, cfgs, renderer, models, suns, geo, grid, roi, min_alt, max_alt, t, render_options, sharded, gt, water_mask,
+                ignore_mask, dataset):
+    """The one walk behind nadir_products (its K = 1 case) and nadir_sun_sweep, whose docstrings state the arguments: the defaults
+    and the lattice, ONE walk of util.relight_chunks over the rays under the K >= 1 `suns` ((elevation_deg, azimuth_deg) pairs; the
+    first may hold None for what `dataset` supplies), the per-ray copies and the folds, the sharded gather and _nadir_finish.
+    Returns _nadir_finish's products and "suns": the list, "rgb": (K, 3, H, W) f32, "sun": (K, H, W) f32."""
     from ... import ops, parallel
     from ...baseline.components import rays as R
     from . import vismaps
     from .util import relight_chunks, result_buffers, shard_options
-    suns = sweep_suns(suns, dataset)
-    geo, roi, gt, water_mask, ignore_mask, min_alt, max_alt, _, _ = _nadir_defaults(
+    geo, roi, gt, water_mask, ignore_mask, min_alt, max_alt, el, az = _nadir_defaults(
         dataset, geo, roi, gt, water_mask, ignore_mask, min_alt, max_alt, suns[0][0], suns[0][1])
-    grid, g, rays, bounds = _nadir_lattice("nadir_sun_sweep", models, geo, grid, roi, min_alt, max_alt)
+    suns = [(el, az)] + suns[1:]
+    grid, g, rays, bounds = _nadir_lattice(who, models, geo, grid, roi, min_alt, max_alt)
     h, w = g.out_h, g.out_w
     n = _cells(g)
     K = len(suns)
     n_classes = models["coarse"].spec.n_classes
     dev = rays.device
-    extras = R.nadir_extras(suns[0][0], suns[0][1], t, n, dev)
+    extras = R.nadir_extras(el, az, t, n, dev)
 
     lo, hi = parallel.frame_shard(n) if sharded else (0, n)
     m = hi - lo
@@ -427,8 +341,65 @@ def nadir_sun_sweep(cfgs, renderer, models, suns=None, geo=None, grid=None, roi=
     out["suns"] = suns
     out["rgb"] = rgb.permute(0, 2, 1).contiguous().reshape(K, 3, h, w)
     out["sun"] = sun.reshape(K, h, w)
-    total = torch.zeros((h, w), dtype=torch.float64, device=dev)
-    for s in range(K):      # in sun order, fp64; one rounding at the end
-        total += out["sun"][s].double()
-    out["lit_share"] = (total / K).to(torch.float32)
+    return out
+
+
+@torch.no_grad()
+def nadir_products(cfgs, renderer, models, geo=None, grid=None, roi=None, min_alt=None, max_alt=None, sun_elevation=None,
+                   sun_azimuth=None, t=0, render_options={}, sharded=False, gt=None, water_mask=None, ignore_mask=None,
+                   dataset=None):
+    """The map of the lattice rendered from above: one vertical ray per cell (rays.nadir_construct between `max_alt` and
+    `min_alt` metres, through `geo`, a GeoFrame), extras of the sun at (`sun_elevation`, `sun_azimuth`) degrees and the
+    embedding index `t`.  The grid: `grid` (a DsmGrid, or a window of one from dsm.grid_struct), else the ROI grid of `roi`
+    (a DsmGrid or the roi_txt meta), else a ValueError.  `dataset` (a loaded SatNeRFDataset) supplies what is not given: its
+    geo, its "dsm" entry (roi, gt, masks), the min / max of its images' alt_min / alt_max, the sun of its first image.
+
+    ONE walk of util.relight_chunks over the rays, under the one sun (`sharded`: over this rank's frame_shard of them, the
+    results all-gathered as sharded_lean_inference does): the per-ray results are copied, albedo / sun / beta folded by
+    vismaps.fold_chunk; no frame-sized per-sample tensor exists.  `render_options` as everywhere in evaluation ({"perturb": 0} for a repeatable map).
+
+    Returns {"grid": DsmGrid (of the window), "dsm": (H, W) f32 -- the altitude of geo.cloud(rays, depth), every cell filled --,
+    "rgb": (3, H, W) f32, "albedo": (3, H, W) f32, "sun": (H, W) f32 (the shadow map), "beta": (H, W) f32[, "label": (H, W) u8
+    (a model with classes; 255 for a label beyond 254)], "rays": the (H W, 8) nadir rays, "planimetric_error": the largest
+    |east / north of the cloud - cell centre| in metres (the self-check of the ray construction), "scene_bounds": GeoBounds of
+    the lattice's scene x / y (to_scene's stats)[, "mae": {"mean", "median"} of dsm.compute_mae(dsm, gt, water_mask,
+    ignore_mask), with `gt` (H, W)]}."""
+    out = _nadir_walk("nadir_products", cfgs, renderer, models, [(sun_elevation, sun_azimuth)], geo, grid, roi, min_alt, max_alt, t,
+                      render_options, sharded, gt, water_mask, ignore_mask, dataset)
+    del out["suns"]
+    out["rgb"], out["sun"] = out["rgb"][0], out["sun"][0]
+    return out
+
+
+def sweep_suns(suns, dataset=None, who="nadir_sun_sweep"):
+    """the suns of a sweep as a list of (elevation_deg, azimuth_deg) floats: `suns`, else those of the images of a loaded
+    dataset's split, in split order; an empty list (or neither) is a ValueError"""
+    if suns is None and dataset is not None:
+        suns = [(m["sun_elevation"], m["sun_azimuth"]) for m in dataset.metas]
+    suns = [(float(el), float(az)) for el, az in (suns or ())]
+    if not suns:
+        raise ValueError(f"{who}: no sun -- pass suns=[(elevation_deg, azimuth_deg), ...] (or a loaded dataset= to take its images' suns)")
+    return suns
+
+
+@torch.no_grad()
+def nadir_sun_sweep(cfgs, renderer, models, suns=None, geo=None, grid=None, roi=None, min_alt=None, max_alt=None, t=0,
+                    render_options={}, sharded=False, gt=None, water_mask=None, ignore_mask=None, dataset=None):
+    """nadir_products under K suns in ONE walk over the lattice's rays (util.relight_chunks): per chunk a full pass under suns[0]
+    and a relight per further sun, which re-runs only the sun-visibility branch, the sky colour and the composite on the chunk the
+    workspace holds (DESIGN.md section 5m).  `suns`: (elevation_deg, azimuth_deg) pairs; None with a loaded `dataset`: the suns of
+    the split's images in split order.  The lattice, `geo`, the altitudes, `t`, `sharded`, `gt` and the masks as for
+    nadir_products, which `dataset` supplies likewise.
+
+    Returns the products of nadir_products that do not depend on the sun ("grid", "dsm", "albedo", "beta"[, "label"], "rays",
+    "planimetric_error", "scene_bounds"[, "mae"]) and "suns": the list, "rgb": (K, 3, H, W) f32, "sun": (K, H, W) f32 (the
+    shadow maps, folded by vismaps.fold_chunk), "lit_share": (H, W) f32 -- the mean of the K shadow maps, summed in fp64 in sun
+    order and rounded once.  Map k has the bits of nadir_products under sun k, given the same depths ({"perturb": 0}): the jitter
+    is drawn once per chunk and shared by the suns."""
+    out = _nadir_walk("nadir_sun_sweep", cfgs, renderer, models, sweep_suns(suns, dataset), geo, grid, roi, min_alt, max_alt, t,
+                      render_options, sharded, gt, water_mask, ignore_mask, dataset)
+    total = torch.zeros_like(out["sun"][0], dtype=torch.float64)
+    for plane in out["sun"]:      # in sun order, fp64; one rounding at the end
+        total += plane.double()
+    out["lit_share"] = (total / len(out["suns"])).to(torch.float32)
     return out

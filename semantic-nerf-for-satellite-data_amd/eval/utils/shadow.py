@@ -1,6 +1,6 @@
 """Cast shadows on the map: the shadow a DSM casts under a sun, and how far a model's learned shadow maps agree with it -- the
 question the S-NeRF / Sat-NeRF irradiance model raises (do the learned shadows follow from the learned geometry?) as a number.
-The reference has no counterpart; the spec is include/snerf_shadow.h, the stages are the kernels of
+The reference has no counterpart; the spec is include/snerf_hip.h, the stages are the kernels of
 csrc/shadow.hip, torch is plumbing.  All functions take and return device tensors; there is no CPU fallback.
 
 cast_shadows marches, per cell and sun, from the cell towards the sun over the height field (an Amanatides-Woo walk in cell
@@ -130,7 +130,7 @@ def shadow_agreement(sun_maps, lit, valid=None, threshold=0.5):
     is predicted lit when its value >= `threshold`; cells with lit == 255, with `valid` ((H, W), 0 = leave out) zero or with a value
     that is not finite are left out.  Returns one dict per sun: "n" (cells counted), "left_out", "accuracy", "iou_shadow" (of the
     shadow class: both shadow / either shadow), "mean_sun_lit" / "mean_sun_shadow" (the mean learned value over the cast-lit /
-    cast-shadowed cells, from sums quantised to 2^-24) and "words", the 8 raw u64 words of include/snerf_shadow.h.  Derived on the
+    cast-shadowed cells, from sums quantised to 2^-24) and "words", the 8 raw u64 words of include/snerf_hip.h.  Derived on the
     host from the integer words; an empty denominator gives NaN."""
     return [agreement_metrics(row) for row in agreement_words(sun_maps, lit, valid, threshold).cpu().tolist()]
 

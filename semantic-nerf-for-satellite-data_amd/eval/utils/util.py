@@ -3,6 +3,7 @@ from collections import defaultdict
 
 import torch
 
+from ...framework.components.rendering import bare_key as _bare
 
 _PER_RAY_OPTIONS = ("perturb_rand", "given_z_vals")   # (N, S) tensors a caller may pin for the whole frame
 
@@ -42,10 +43,6 @@ _KEY_SHAPES = {  # per-ray trailing shape of the render_rays results (S = n_samp
 }
 
 
-def _bare(key):
-    return key[:-len("_coarse")] if key.endswith("_coarse") else key
-
-
 def result_buffers(keys, rows, S, n_classes, device) -> dict:
     """uninitialised render_rays_into result tensors of `rows` rays for the results `keys` (with or without the `_coarse`
     postfix), under their `_coarse` names"""
@@ -67,22 +64,9 @@ def render_chunks(cfgs, renderer, models, rays, extras, buffers, render_options,
     is the chunks' order.  A caller allocates its buffers after ops.release_workspaces(): full-frame inference has its own
     memory profile, and the idle TRAINING workspaces (8-20 GB each, held outside torch's allocator by the lease pool) go back
     to torch first, so that the frame's tensors and the inference workspace can use that memory."""
-    from ... import ops
-    chunk = cfgs.pipeline.render_chunk_size
-    n = rays.shape[0]
-    model = models["coarse"]
-    packed = ops.pack_params(model.spec, dict(model.named_parameters()))
-    ws = None
-    steps = range(0, n, chunk)
-    if show_tqdm:
-        from tqdm import tqdm
-        steps = tqdm(steps)
-    for i in steps:
-        k = min(chunk, n - i)
-        views = {key: v[i:i + k] if frame_sized else v[:k] for key, v in buffers.items()}
-        opts = _chunk_options(render_options, i, chunk, n)
-        opts["packed_params"], opts["workspace"] = packed, ws
-        ws = renderer.render_rays_into(models, rays[i:i + chunk], extras[i:i + chunk] if extras is not None else None, views, opts)
+    if frame_sized:      # a sun axis of one: the same memory
+        buffers = {key: v[None] for key, v in buffers.items()}
+    for i, k, _, views in relight_chunks(cfgs, renderer, models, rays, extras, (None,), buffers, render_options, frame_sized, show_tqdm):
         yield i, k, views
 
 
@@ -123,7 +107,9 @@ def relight_chunks(cfgs, renderer, models, rays, extras, suns, buffers, render_o
     columns of `extras` are replaced by each in turn (sun_extras).  Yields (i, k, sun_index, views) after every pass, suns in
     order within a chunk.  `buffers`: chunk-sized result_buffers, reused for every sun -- views = buffers[key][:k], to be consumed
     before the next yield -- or, with frame_sized, tensors with a leading sun axis, (K, n, ...): views = buffers[key][s, i:i + k].
-    Every sun is asked for the same results, those of `buffers`."""
+    Every sun is asked for the same results, those of `buffers`.  A sun of None stands for `extras` as they are, None included:
+    render_chunks is the walk under that one sun.  The walk owns the pack of the weights (once), the workspace carried from pass
+    to pass, the chunk steps and the per-chunk options."""
     from ... import ops
     suns = list(suns)
     if not suns:
@@ -141,14 +127,15 @@ def relight_chunks(cfgs, renderer, models, rays, extras, suns, buffers, render_o
         k = min(chunk, n - i)
         opts = _chunk_options(render_options, i, chunk, n)
         opts["packed_params"] = packed
-        ex = extras[i:i + chunk]
+        ex = extras[i:i + chunk] if extras is not None else None
         for s, sun in enumerate(suns):
             views = {key: v[s, i:i + k] if frame_sized else v[:k] for key, v in buffers.items()}
             opts["workspace"] = ws
+            e = ex if sun is None else sun_extras(ex, sun)
             if s == 0:
-                ws = renderer.render_rays_into(models, rays[i:i + chunk], sun_extras(ex, sun), views, opts)
+                ws = renderer.render_rays_into(models, rays[i:i + chunk], e, views, opts)
             else:
-                ws = renderer.relight_rays_into(models, sun_extras(ex, sun), views, opts)
+                ws = renderer.relight_rays_into(models, e, views, opts)
             yield i, k, s, views
 
 

@@ -35,6 +35,18 @@ def z_steps_on(device, n: int) -> torch.Tensor:
     return t
 
 
+def bare_key(key: str) -> str:
+    return key[:-len("_coarse")] if key.endswith("_coarse") else key
+
+
+def _bare_results(who: str, out: dict) -> dict:
+    """`out` under its keys without the '_coarse' postfix, which every key must carry"""
+    for k in out:
+        if not k.endswith("_coarse"):
+            raise KeyError(f"{who}: result keys end in '_coarse', got '{k}'")
+    return {bare_key(k): v for k, v in out.items()}
+
+
 class BaseRenderer:
     def __init__(self, cfgs) -> None:
         super().__init__()
@@ -61,12 +73,7 @@ class BaseRenderer:
         opts = dict(render_options) if render_options else {}
         if "perturb_rand" not in opts and opts.get("perturb", 1.0) > 0:
             opts["perturb_rand"] = torch.rand(rays.shape[0], self.N_samples, device=rays.device, dtype=torch.float32)
-        bare = {}
-        for k, v in out.items():
-            if not k.endswith("_coarse"):
-                raise KeyError(f"render_rays_into: result keys end in '_coarse', got '{k}'")
-            bare[k[:-len("_coarse")]] = v
-        return fused_model_rendering_into(self, models, "coarse", rays, extras, opts, bare)
+        return fused_model_rendering_into(self, models, "coarse", rays, extras, opts, _bare_results("render_rays_into", out))
 
     @torch.no_grad()
     def relight_rays_into(self, models: dict, extras: torch.Tensor, out: dict, render_options={}):
@@ -74,12 +81,8 @@ class BaseRenderer:
         `extras`: only the sun-dependent part of the pass runs again, on the base pass's depths, and every result has the bits
         render_rays_into gives under that sun.  `out` as for render_rays_into, main-pass results only.  Returns the workspace."""
         from ...semantic.components.rendering import fused_model_relighting_into
-        bare = {}
-        for k, v in out.items():
-            if not k.endswith("_coarse"):
-                raise KeyError(f"relight_rays_into: result keys end in '_coarse', got '{k}'")
-            bare[k[:-len("_coarse")]] = v
-        return fused_model_relighting_into(self, models, "coarse", extras, dict(render_options) if render_options else {}, bare)
+        return fused_model_relighting_into(self, models, "coarse", extras, dict(render_options) if render_options else {},
+                                           _bare_results("relight_rays_into", out))
 
     @abc.abstractmethod
     def _model_rendering(self, models: dict, typ: str, cfgs, rays, extras, xyz, z_vals, rays_d, epoch=None,

@@ -43,6 +43,21 @@ def transient_rows(models, name, ts, opts):
     return ops._EmbedRows.apply(v.view(1, tau), torch.zeros_like(ts))
 
 
+def _pass_operands(models, model, extras, opts):
+    """what the fused entry points hand to a pass of `model`: -> (sun_d, rays_t, rays_t_s, params, packed) -- the sun columns of
+    `extras`, the rays' transient rows (launched before the pack), the parameters, and their pack (render_options["packed_params"],
+    else packed here)"""
+    sun_d = extras_component_fn(extras, "sun_d")
+    ts = extras_component_fn(extras, "ts").squeeze(-1).long()
+    rays_t = transient_rows(models, "t", ts, opts)
+    rays_t_s = transient_rows(models, "t_s", ts, opts) if "t_s" in models else None
+    params = dict(model.named_parameters())
+    packed = opts.get("packed_params")
+    if packed is None:
+        packed = ops.pack_params(model.spec, params)
+    return sun_d, rays_t, rays_t_s, params, packed
+
+
 def fused_model_rendering(renderer, models, typ, rays, extras, render_options, inference_func, default_inference):
     if inference_func is not default_inference:
         raise NotImplementedError(
@@ -50,15 +65,8 @@ def fused_model_rendering(renderer, models, typ, rays, extras, render_options, i
             "fused HIP pass (snerf_forward); a foreign per-sample inference callable has nothing to plug into")
     cfgs = renderer.cfgs
     opts = render_options or {}
-    sun_d = extras_component_fn(extras, "sun_d")
-    ts = extras_component_fn(extras, "ts").squeeze(-1).long()
-    rays_t = transient_rows(models, "t", ts, opts)
-    rays_t_s = transient_rows(models, "t_s", ts, opts) if "t_s" in models else None
     model = models[typ]
-    params = dict(model.named_parameters())
-    packed = opts.get("packed_params")
-    if packed is None:
-        packed = ops.pack_params(model.spec, params)
+    sun_d, rays_t, rays_t_s, params, packed = _pass_operands(models, model, extras, opts)
     pin = ops.PassInputs(sun_d=sun_d, rays=rays, z_vals=opts.get("given_z_vals"),
                          z_steps=z_steps_on(rays.device, renderer.N_samples), u=opts.get("perturb_rand"))
     do_sc = cfgs.pipeline.sc_lambda > 0
@@ -108,15 +116,8 @@ def fused_model_rendering_into(renderer, models, typ, rays, extras, render_optio
     the given tensors.  The solar-correction pass runs only if one of its three results is asked for -- a point-cloud
     or image render (rgb / depth / label) does half the work of render_rays."""
     opts = render_options or {}
-    sun_d = extras_component_fn(extras, "sun_d")
-    ts = extras_component_fn(extras, "ts").squeeze(-1).long()
-    rays_t = transient_rows(models, "t", ts, opts)
-    rays_t_s = transient_rows(models, "t_s", ts, opts) if "t_s" in models else None
     model = models[typ]
-    params = dict(model.named_parameters())
-    packed = opts.get("packed_params")
-    if packed is None:
-        packed = ops.pack_params(model.spec, params)
+    sun_d, rays_t, rays_t_s, params, packed = _pass_operands(models, model, extras, opts)
     main_out = {k: v for k, v in out.items() if k not in _SC_KEYS}
     sc_out = {_SC_KEYS[k]: v for k, v in out.items() if k in _SC_KEYS}
     ws = opts.get("workspace")
@@ -152,14 +153,7 @@ def fused_model_relighting_into(renderer, models, typ, extras, render_options, o
     for k in out:
         if k not in allowed:
             raise KeyError(f"fused_model_relighting_into: '{k}' is not a result of the main pass (have {sorted(allowed)})")
-    sun_d = extras_component_fn(extras, "sun_d")
-    ts = extras_component_fn(extras, "ts").squeeze(-1).long()
-    rays_t = transient_rows(models, "t", ts, opts)
-    rays_t_s = transient_rows(models, "t_s", ts, opts) if "t_s" in models else None
-    params = dict(model.named_parameters())
-    packed = opts.get("packed_params")
-    if packed is None:
-        packed = ops.pack_params(model.spec, params)
+    sun_d, rays_t, rays_t_s, params, packed = _pass_operands(models, model, extras, opts)
     return ops.relight_pass_into(model.spec, params, sun_d, rays_t, rays_t_s, out, ws, packed=packed, n_samples=renderer.N_samples)
 
 

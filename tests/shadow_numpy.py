@@ -1,4 +1,4 @@
-"""NumPy restatement of the cast-shadow entries (tests only), written from include/snerf_shadow.h: the Amanatides-Woo march over a
+"""NumPy restatement of the cast-shadow entries (tests only), written from include/snerf_hip.h: the Amanatides-Woo march over a
 height field in fp64, vectorised over the cells with a Python loop over the march steps, and the integer words of the agreement.
 The kernel uses only fp64 + - * / and comparisons, one rounding per operation, so every array here is held to the kernels BIT FOR
 BIT by tests/test_gpu_shadow.py (numpy evaluates `h0 + rise * t` as two ufunc calls: no contraction); tests/test_shadow_cpu.py

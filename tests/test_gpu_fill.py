@@ -84,6 +84,9 @@ POINTERS = {
     "snerf_normalize_rows": {"rows": "inout", "center_range": "in"},
     "snerf_geo_cloud": {"rays": "in", "depth": "in", "params": "in", "enu_out": "out", "lla_out": "out", "stats": "acc"},
     "snerf_geo_points": {"xyz_n": "in", "params": "in", "enu_out": "out", "lla_out": "out", "stats": "acc"},
+    # the fill test of these two is tests/test_gpu_shadow.py test_no_output_depends_on_bytes_the_library_did_not_write
+    "snerf_shadow_cast": {"dsm": "in", "suns_host": "in", "lit_out": "out", "dist_out": "out"},
+    "snerf_shadow_agreement": {"sun": "in", "lit": "in", "valid": "in", "acc": "acc"},
 }
 # entries with no device pointer to classify: sizes, version, error text; and the hooks the issue excepts
 _NO_POINTERS = ("snerf_version", "snerf_last_error", "snerf_packed_floats", "snerf_grad_floats", "snerf_workspace_bytes",

@@ -1,4 +1,4 @@
-"""Cast shadows on the map (include/snerf_shadow.h, csrc/shadow.hip, eval/utils/shadow.py, eval/ortho.py export_shadow_check;
+"""Cast shadows on the map (include/snerf_hip.h, csrc/shadow.hip, eval/utils/shadow.py, eval/ortho.py export_shadow_check;
 DESIGN.md section 5o) on an MI355X.  The kernels do only fp64 + - * / and integer work, so every comparison with the numpy
 restatement (tests/shadow_numpy.py, itself held to a brute-force formulation by tests/test_shadow_cpu.py) is bit for bit:
 torch.equal on `lit`, the fp32 bit patterns on `dist`, the integer words of the agreement."""

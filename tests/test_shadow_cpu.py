@@ -1,5 +1,6 @@
-"""CPU-side checks of the cast-shadow entries (include/snerf_shadow.h, csrc/shadow.hip, eval/utils/shadow.py; DESIGN.md section
-5o): the second header against its binding table, every refusal of both entries (none reaches a launch), the Python refusals,
+"""CPU-side checks of the cast-shadow entries (include/snerf_hip.h, csrc/shadow.hip, eval/utils/shadow.py; DESIGN.md section
+5o): the header's constants against the binding (tests/test_abi_cpu.py compares the prototypes with their rows, as for every
+entry), every refusal of both entries (none reaches a launch), the Python refusals,
 sun_rows against construct_sun_dir, and the numpy restatement (tests/shadow_numpy.py, the oracle of tests/test_gpu_shadow.py)
 against an independent brute-force formulation."""
 import ctypes as C
@@ -12,46 +13,17 @@ import pytest
 import torch
 
 from tests import shadow_numpy as SN
-from tests.test_abi_cpu import _c_type, _table_type
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "snerf_shadow.h")
+HEADER = os.path.join(ROOT, "include", "snerf_hip.h")
 
 
-def _shadow_prototypes():
-    """include/snerf_shadow.h without comments and preprocessor lines -> {symbol: (return type, [(type, name)])}, in its order"""
-    src = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    src = re.sub(r"^\s*#.*$", "", src, flags=re.M)
-    protos = {}
-    for ret, name, params in re.findall(r"([\w \*]+?)\b(snerf_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", src):
-        params = [re.fullmatch(r"\s*(.*?)(\w+)\s*", p).groups() for p in params.split(",")]
-        protos[name] = (_c_type(ret), [(_c_type(t), n) for t, n in params])
-    return protos
-
-
-def test_second_header_matches_its_table_and_the_first_is_untouched():
+def test_header_constants_match_the_binding():
     from snerf_amd import _lib
-    protos = _shadow_prototypes()
-    assert list(protos) == list(_lib.SHADOW_SIGNATURES) == ["snerf_shadow_cast", "snerf_shadow_agreement"]
-    L = _lib.lib()
-    for name, (ret, params) in protos.items():
-        restype, argtypes = _lib.SHADOW_SIGNATURES[name]
-        assert _table_type(restype) == ret, (name, restype, ret)
-        assert len(argtypes) == len(params), (name, len(argtypes), len(params))
-        for k, (t, (want, pname)) in enumerate(zip(argtypes, params)):
-            got = _table_type(t)
-            assert got == want or (want[0] == "pointer" and got == ("pointer", None)), (name, k, pname, t, want)
-            assert (t is _lib.c_stream) == (pname == "stream"), (name, k, pname, t)
-        fn = getattr(L, name)                                           # exported, and lib() applied the table
-        assert fn.restype is restype and tuple(fn.argtypes) == tuple(argtypes), name
-        assert name in _lib._PLANS and name not in _lib.SIGNATURES and name not in _lib.EXPORTED_SYMBOLS
     src = open(HEADER).read()
-    assert '#include "snerf_hip.h"' in src
+    assert _lib.lib().snerf_version() == _lib.ABI_VERSION == 6
     assert int(re.search(r"#define SNERF_SHADOW_MAX_SUNS (\d+)", src).group(1)) == _lib.SHADOW_MAX_SUNS == 64
     assert int(re.search(r"#define SNERF_SHADOW_UNKNOWN (\d+)", src).group(1)) == _lib.SHADOW_UNKNOWN == 255
-    assert len(_lib.SIGNATURES) == 49 and L.snerf_version() == _lib.ABI_VERSION == 6
-    assert "shadow" not in open(os.path.join(ROOT, "include", "snerf_hip.h")).read()
 
 
 DUMMY = 4096        # a non-null address no refusal path dereferences

@@ -41,7 +41,7 @@ def city(n, seed=0):
 
 
 def torch_cast(dsm, rows, bias, z_top):
-    """the march of include/snerf_shadow.h on K x H x W fp64 tensors: lit (K, H, W) u8"""
+    """the march of include/snerf_hip.h on K x H x W fp64 tensors: lit (K, H, W) u8"""
     dev = dsm.device
     h, w = dsm.shape
     K = len(rows)
