@@ -4,7 +4,7 @@ from typing import List, Literal, Optional, Union
 
 import numpy as np
 import torch
-from pydantic import BaseModel
+from pydantic import BaseModel, model_validator
 
 from ...framework.datasets import GpuRayBank
 from ..components.loss import SNerfLoss, SatNerfLoss, DepthLoss
@@ -35,6 +35,19 @@ class NeRFConfig(BaseModel):
     fc_skips: List[int] = [4]
     ray_subsampling_activated: Union[bool, int] = False
     ray_subsampling_amount: float = 1.0
+
+    @model_validator(mode="after")
+    def _check_n_importance(self):
+        """n_importance fine samples per ray are merged with the n_samples coarse ones (ops.resample_z): the pdf is over the
+        interior weights, and a ray holds at most 1024 samples (include/snerf_resample.h: snerf_resample_z)"""
+        if self.n_importance < 0:
+            raise ValueError(f"n_importance must be >= 0, got {self.n_importance}")
+        if self.n_importance > 0:
+            if self.n_samples < 3:
+                raise ValueError(f"n_importance > 0 needs n_samples >= 3, got n_samples = {self.n_samples}")
+            if self.n_samples + self.n_importance > 1024:
+                raise ValueError(f"n_samples + n_importance must be <= 1024, got {self.n_samples} + {self.n_importance}")
+        return self
 
 
 class SNeRFConfig(NeRFConfig):

@@ -82,6 +82,10 @@ def fit_image_embedding(cfgs, renderer, models, rays, extras, rgbs, *, fit_mask=
     of iterate 0 .. steps on the fit subset], "best_step": index of the returned iterate, "rays": size of the subset}.
     render_options: "packed_params" (the packed weights, else packed here once) and "t_s_vector" (instead of the t_s init)."""
     opts = render_options or {}
+    if getattr(renderer, "N_importance", 0) > 0:
+        # the fit builds its own PassInputs on the stratified depths: it would fit on other depths than the frame is rendered with
+        raise NotImplementedError("fit_image_embedding: n_importance > 0 is not supported (the fit runs on the n_samples stratified "
+                                  "depths, the render on the resampled ones); fit with n_importance = 0")
     steps = int(steps)
     if steps < 0:
         raise ValueError("steps must be >= 0")

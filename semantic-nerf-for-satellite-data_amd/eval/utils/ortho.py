@@ -31,6 +31,7 @@ per further sun -- the shadow maps of a day, or the scene lit as each of its acq
 import torch
 
 from ... import _lib
+from ...framework.components.rendering import n_render_samples
 from . import dsm as D
 from .dsm import grid_struct, new_stats      # the lattice plumbing is the DSM's
 
@@ -307,7 +308,7 @@ def _nadir_walk(who, cfgs, renderer, models, suns, geo, grid, roi, min_alt, max_
 
     lo, hi = parallel.frame_shard(n) if sharded else (0, n)
     m = hi - lo
-    S = cfgs.pipeline.n_samples
+    S = n_render_samples(cfgs.pipeline)
     keys = ("rgb", "depth") + (("semantic_label",) if n_classes else ()) + ("weights", "albedo", "sun", "beta")
     loc = {"depth": torch.empty(m, dtype=torch.float32, device=dev), "albedo": torch.empty((3, m), dtype=torch.float32, device=dev),
            "beta": torch.empty(m, dtype=torch.float32, device=dev)}

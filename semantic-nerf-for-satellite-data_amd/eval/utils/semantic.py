@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from ... import _lib, parallel
+from ...framework.components.rendering import n_render_samples
 
 _NCOUNT = (C.sizeof(_lib.SnerfSemevalAcc) - 8) // 8        # u64 fields before the fp64 beta sum
 _MAXC = _lib.SEMEVAL_MAX_CLASSES
@@ -210,7 +211,7 @@ def lean_semantic_eval(cfgs, renderer, models, rays, extras, semantic, semantic_
         if t is not None and t.shape[0] != n:
             raise ValueError(f"{what} has {t.shape[0]} rows for {n} rays")
     ops.release_workspaces()
-    bufs = result_buffers(("semantic_label", "weights", "beta"), min(cfgs.pipeline.render_chunk_size, n), cfgs.pipeline.n_samples,
+    bufs = result_buffers(("semantic_label", "weights", "beta"), min(cfgs.pipeline.render_chunk_size, n), n_render_samples(cfgs.pipeline),
                           Cn, rays.device)
     for i, k, v in render_chunks(cfgs, renderer, models, rays, extras, bufs, render_options):
         acc.add(v["semantic_label_coarse"], semantic[i:i + k], _slice(semantic_no_cars, i, i + k),

@@ -3,9 +3,9 @@ from collections import defaultdict
 
 import torch
 
-from ...framework.components.rendering import bare_key as _bare
+from ...framework.components.rendering import bare_key as _bare, n_render_samples
 
-_PER_RAY_OPTIONS = ("perturb_rand", "given_z_vals")   # (N, S) tensors a caller may pin for the whole frame
+_PER_RAY_OPTIONS = ("perturb_rand", "given_z_vals", "importance_rand")   # (N, S) / (N, S') / (N, Ni) tensors a caller may pin for the whole frame
 
 
 def _chunk_options(render_options, i, chunk, n):
@@ -34,7 +34,7 @@ def batched_inference(cfgs, renderer, models, rays, extras, render_options={}, e
     return {k: (v[0] if len(v) == 1 else torch.cat(v, 0)) for k, v in parts.items()}
 
 
-_KEY_SHAPES = {  # per-ray trailing shape of the render_rays results (S = n_samples, C = classes)
+_KEY_SHAPES = {  # per-ray trailing shape of the render_rays results (S = n_render_samples: n_samples + n_importance, C = classes)
     "rgb": lambda S, C: (3,), "depth": lambda S, C: (), "weights": lambda S, C: (S,), "transparency": lambda S, C: (S,),
     "albedo": lambda S, C: (S, 3), "sun": lambda S, C: (S, 1), "sky": lambda S, C: (S, 3), "beta": lambda S, C: (S, 1),
     "sigmas": lambda S, C: (S,), "beta_semantic": lambda S, C: (S, 1), "semantic_logits": lambda S, C: (C,),
@@ -83,7 +83,7 @@ def lean_inference(cfgs, renderer, models, rays, extras, keys=("rgb_coarse", "de
         if _bare(k) not in _KEY_SHAPES:
             raise KeyError(f"lean_inference: unknown result '{k}'")
     ops.release_workspaces()
-    out = result_buffers(keys, rays.shape[0], cfgs.pipeline.n_samples, models["coarse"].spec.n_classes, rays.device)
+    out = result_buffers(keys, rays.shape[0], n_render_samples(cfgs.pipeline), models["coarse"].spec.n_classes, rays.device)
     for _ in render_chunks(cfgs, renderer, models, rays, extras, out, render_options, frame_sized=True, show_tqdm=show_tqdm):
         pass
     return out
@@ -153,7 +153,7 @@ def lean_relight(cfgs, renderer, models, rays, extras, suns, keys=("rgb_coarse",
     if not suns:
         raise ValueError("lean_relight: no sun")
     ops.release_workspaces()
-    one = result_buffers(keys, 0, cfgs.pipeline.n_samples, models["coarse"].spec.n_classes, rays.device)
+    one = result_buffers(keys, 0, n_render_samples(cfgs.pipeline), models["coarse"].spec.n_classes, rays.device)
     out = {k: torch.empty((len(suns), rays.shape[0]) + tuple(v.shape[1:]), dtype=v.dtype, device=v.device) for k, v in one.items()}
     for _ in relight_chunks(cfgs, renderer, models, rays, extras, suns, out, render_options, frame_sized=True, show_tqdm=show_tqdm):
         pass
@@ -189,7 +189,7 @@ def sharded_lean_inference(cfgs, renderer, models, rays, extras, keys=("rgb_coar
 
     def rows(lo, hi):
         if hi == lo:      # more ranks than rays: contribute nothing (a zero-ray launch has no defined result)
-            return result_buffers(keys, 0, cfgs.pipeline.n_samples, models["coarse"].spec.n_classes, rays.device)
+            return result_buffers(keys, 0, n_render_samples(cfgs.pipeline), models["coarse"].spec.n_classes, rays.device)
         return lean_inference(cfgs, renderer, models, rays[lo:hi], extras[lo:hi] if extras is not None else None, keys=keys,
                               render_options=shard_options(render_options, lo, hi, n), show_tqdm=show_tqdm)
     return shard_and_gather(rows, n)

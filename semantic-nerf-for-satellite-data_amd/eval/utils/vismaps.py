@@ -12,6 +12,7 @@ import torch
 
 from ... import _lib, parallel
 from ...framework.components.coordinate_systems import key_to_double
+from ...framework.components.rendering import n_render_samples
 
 # product -> (render results it needs, per-ray inputs it needs)
 PRODUCTS = {
@@ -186,7 +187,7 @@ def lean_frame_maps(cfgs, renderer, models, rays, extras, rgbs=None, semantic=No
     products = tuple(products)
     keys = _needs(products, model, rgbs, semantic, palette)
     n, dev = rays.shape[0], rays.device
-    S, Cn = cfgs.pipeline.n_samples, model.spec.n_classes
+    S, Cn = n_render_samples(cfgs.pipeline), model.spec.n_classes
     for t, what in ((rgbs, "rgbs"), (semantic, "semantic")):
         if t is not None and t.shape[0] != n:
             raise ValueError(f"{what} has {t.shape[0]} rows for {n} rays")

@@ -2,7 +2,11 @@
 
 Stratified sampling (reference sample_rays, :84-116) is fused into the HIP pass: render_rays only
 draws the jitter tensor (the reference calls torch.rand_like with perturb=1.0 on every call, train
-and eval alike) and hands it down; z_vals / xyz never materialise on the host side."""
+and eval alike) and hands it down; z_vals / xyz never materialise on the host side.
+
+With `n_importance` > 0 (the reference's sample_pdf, :8-51, which its BaseRenderer never calls) a render first runs a proposal
+pass on the stratified depths and resamples them on the device (ops.resample_z); everything else then runs on the merged
+n_samples + n_importance depths through the `given_z_vals` seam."""
 import abc
 import functools
 
@@ -47,11 +51,25 @@ def _bare_results(who: str, out: dict) -> dict:
     return {bare_key(k): v for k, v in out.items()}
 
 
+def n_render_samples(pipeline_cfg) -> int:
+    """S' = n_samples + n_importance: the samples per ray of every rendering pass and the columns of every per-sample result.
+    THE place that names it: the renderer and everything that sizes a buffer for its results ask here."""
+    return int(pipeline_cfg.n_samples) + max(int(getattr(pipeline_cfg, "n_importance", 0) or 0), 0)
+
+
 class BaseRenderer:
     def __init__(self, cfgs) -> None:
         super().__init__()
         self.cfgs = cfgs
         self.N_samples = cfgs.pipeline.n_samples
+        self.n_render_samples = n_render_samples(cfgs.pipeline)
+        self.N_importance = self.n_render_samples - self.N_samples
+
+    def _importance_depths(self, models, rays, extras, opts):
+        """n_importance > 0 and no depths given: opts["given_z_vals"] = the merged depths of a proposal pass (no gradient)"""
+        if self.N_importance > 0 and opts.get("given_z_vals") is None:
+            from ...semantic.components.rendering import importance_depths
+            importance_depths(self, models, "coarse", rays, extras, opts)
 
     def render_rays(self, models: dict, rays: torch.Tensor, extras: torch.Tensor, epoch=None, progress=1.0,
                     render_options={}):
@@ -59,6 +77,7 @@ class BaseRenderer:
         opts = dict(render_options) if render_options else {}
         if "perturb_rand" not in opts and opts.get("perturb", 1.0) > 0:
             opts["perturb_rand"] = torch.rand(rays.shape[0], self.N_samples, device=rays.device, dtype=torch.float32)
+        self._importance_depths(models, rays, extras, opts)
         model_results = self._model_rendering(models, "coarse", self.cfgs, rays, extras, None, None, rays_d,
                                               epoch=epoch, progress=progress, render_options=opts)
         # "_coarse" postfix as in the reference (no fine network is ever built)
@@ -73,6 +92,7 @@ class BaseRenderer:
         opts = dict(render_options) if render_options else {}
         if "perturb_rand" not in opts and opts.get("perturb", 1.0) > 0:
             opts["perturb_rand"] = torch.rand(rays.shape[0], self.N_samples, device=rays.device, dtype=torch.float32)
+        self._importance_depths(models, rays, extras, opts)
         return fused_model_rendering_into(self, models, "coarse", rays, extras, opts, _bare_results("render_rays_into", out))
 
     @torch.no_grad()

@@ -634,3 +634,29 @@ def sample_z(rays: torch.Tensor, z_steps: torch.Tensor, u: torch.Tensor | None) 
     z = _empty((N, S), dtype=torch.float32, device=rays.device)
     _lib.call("snerf_sample_z", rays.contiguous(), z_steps.contiguous(), u.contiguous() if u is not None else None, z, N, S)
     return z
+
+
+def resample_z(z: torch.Tensor, weights: torch.Tensor, n_importance: int, u: torch.Tensor | None = None, return_fine: bool = False):
+    """importance resampling of the depths -- snerf_resample_z (the reference's sample_pdf, framework/components/rendering.py:8-51,
+    and the sort of the merged depths): `n_importance` fine samples per ray from the pdf that a proposal pass's `weights` (N, S)
+    define over the midpoints of the coarse depths `z` (N, S), merged with `z` -> (N, S + n_importance), non-decreasing along a
+    ray.  `u` (N, n_importance) are the uniforms; None = the reference's det=True (a regular grid).  With `return_fine` also the
+    fine samples alone, (N, n_importance) in u's order.  One launch on the current stream, no synchronisation; the result
+    carries no gradient (sample_pdf's callers detach it)."""
+    _check_dev(z, "z")
+    _check_dev(weights, "weights")
+    Ni = int(n_importance)
+    if z.dim() != 2 or tuple(weights.shape) != tuple(z.shape):
+        raise ValueError(f"resample_z: z and weights must both be (N, S), got {tuple(z.shape)} and {tuple(weights.shape)}")
+    N, S = z.shape
+    if u is not None:
+        _check_dev(u, "u")
+        if tuple(u.shape) != (N, Ni):
+            raise ValueError(f"resample_z: u must be (N, n_importance) = {(N, Ni)}, got {tuple(u.shape)}")
+    for name, v in (("z", z), ("weights", weights), ("u", u)):
+        if v is not None and not v.is_contiguous():
+            raise ValueError(f"resample_z: '{name}' must be contiguous")
+    z_out = _empty((N, max(S + Ni, 0)), dtype=torch.float32, device=z.device)
+    z_fine = _empty((N, max(Ni, 0)), dtype=torch.float32, device=z.device) if return_fine else None
+    _lib.call("snerf_resample_z", z.detach(), weights.detach(), u.detach() if u is not None else None, z_out, z_fine, N, S, Ni)
+    return (z_out, z_fine) if return_fine else z_out

@@ -58,6 +58,41 @@ def _pass_operands(models, model, extras, opts):
     return sun_d, rays_t, rays_t_s, params, packed
 
 
+@torch.no_grad()
+def importance_depths(renderer, models, typ, rays, extras, opts: dict):
+    """The depths of a render with n_importance > 0, left in opts["given_z_vals"]: a PROPOSAL pass -- the inference main pass on
+    the stratified depths (opts["perturb_rand"]), asked for its weights and depths alone -- and ops.resample_z, which draws
+    n_importance fine samples per ray from those weights and merges them with the coarse depths: (N, n_samples + n_importance),
+    no gradient (sample_pdf's callers detach the samples).  The uniforms are opts["importance_rand"] (N, n_importance); absent,
+    they are drawn when opts["perturb"] (default 1.0) > 0 and are the regular grid of the reference's det=True otherwise, as in
+    NeRF.  Two launches more than the pass itself, all on the current stream: nothing waits for the host.  The pack of the
+    weights is left in opts["packed_params"] for the passes that follow; an inference workspace given in opts["workspace"] is
+    used and handed on, otherwise one is leased for the length of the pass."""
+    model = models[typ]
+    spec = model.spec
+    N, S, Ni, dev = rays.shape[0], renderer.N_samples, renderer.N_importance, rays.device
+    sun_d, rays_t, rays_t_s, params, packed = _pass_operands(models, model, extras, opts)
+    opts["packed_params"] = packed
+    out = {"weights": ops._empty((N, S), dtype=torch.float32, device=dev), "z_vals": ops._empty((N, S), dtype=torch.float32, device=dev)}
+    pin = ops.PassInputs(sun_d=sun_d, rays=rays, z_steps=z_steps_on(dev, S), u=opts.get("perturb_rand"))
+    ws, lease = opts.get("workspace"), None
+    if ws is None and "workspace" not in opts:      # a training render: the lease pool, like the passes that follow
+        with torch.cuda.device(dev):
+            lease = ops.lease_workspace(dev, ops._lib.call_size("snerf_workspace_bytes", spec.desc(N, S)))
+        ws = lease.t
+    elif ws is None:                                # the first chunk of a walk: sized for the rendering pass that follows
+        ws = ops._empty(ops._lib.call_size("snerf_workspace_bytes", spec.desc(N, S + Ni)), dtype=torch.uint8, device=dev)
+    ws = ops.render_pass_into(spec, params, pin, rays_t, rays_t_s, out, packed=packed, workspace=ws)
+    if lease is not None:
+        lease.release()      # stream order makes the reuse safe
+    else:
+        opts["workspace"] = ws
+    u = opts.get("importance_rand")
+    if u is None and opts.get("perturb", 1.0) > 0:
+        u = torch.rand(N, Ni, device=dev, dtype=torch.float32)
+    opts["given_z_vals"] = ops.resample_z(out["z_vals"], out["weights"], Ni, u)
+
+
 def fused_model_rendering(renderer, models, typ, rays, extras, render_options, inference_func, default_inference):
     if inference_func is not default_inference:
         raise NotImplementedError(
@@ -154,7 +189,7 @@ def fused_model_relighting_into(renderer, models, typ, extras, render_options, o
         if k not in allowed:
             raise KeyError(f"fused_model_relighting_into: '{k}' is not a result of the main pass (have {sorted(allowed)})")
     sun_d, rays_t, rays_t_s, params, packed = _pass_operands(models, model, extras, opts)
-    return ops.relight_pass_into(model.spec, params, sun_d, rays_t, rays_t_s, out, ws, packed=packed, n_samples=renderer.N_samples)
+    return ops.relight_pass_into(model.spec, params, sun_d, rays_t, rays_t_s, out, ws, packed=packed, n_samples=renderer.n_render_samples)
 
 
 class RSSemanticRendering(BaseRenderer):
