@@ -55,6 +55,14 @@ extern "C" {
                                  no trunk), and packed_grads may be NULL.  Valid only together with SNERF_FLAG_TRAIN and never with
                                  SNERF_FLAG_RELIGHT (SNERF_ERR_BAD_DESC); combines with SNERF_FLAG_SC_PASS and either arithmetic flag.
                                  snerf_forward and every size ignore the bit.  Contract: see snerf_backward */
+#define SNERF_FLAG_GEOMETRY  32u /* geometry-only inference pass: depths (sampled, in->z_vals or in->xyz), the encoding, the trunk, sigma and
+                                 the composite -- no head launch at all.  Produces depth, weights, transparency, sigmas and z_vals with the
+                                 bits of the plain inference pass of the same descriptor and inputs; any other non-NULL SnerfOutputs
+                                 pointer is refused by name before any launch.  in->sun_d, in->t and in->t_s are not read and may be NULL.
+                                 Not with SNERF_FLAG_TRAIN, SNERF_FLAG_SC_PASS, SNERF_FLAG_RELIGHT or SNERF_FLAG_EMBED_GRAD
+                                 (SNERF_ERR_BAD_DESC); either arithmetic flag.  snerf_workspace_bytes plans only what the pass writes
+                                 (strictly less than the plain inference pass); a larger workspace is accepted.  A workspace a geometry
+                                 pass wrote last holds no head tensors: a relight on it is refused */
 
 /* Arithmetic of the dense contractions.  With NONE of the arithmetic bits set a pass runs the default, SNERF_FLAG_F16X2
  * (the same for C and Python callers); the two bits exclude each other. */
@@ -128,7 +136,8 @@ typedef struct SnerfInputs {
 } SnerfInputs;
 
 /* Result tensors = the dict returned by inference() (rs_semantic.py:111-128); any pointer may be NULL.
- * With SNERF_FLAG_SC_PASS only weights / transparency / sun are produced. */
+ * With SNERF_FLAG_SC_PASS only weights / transparency / sun are produced; with SNERF_FLAG_GEOMETRY only depth / weights /
+ * transparency / sigmas / z_vals may be asked for. */
 typedef struct SnerfOutputs {
   float* rgb;             /* (N,3)  */
   float* depth;           /* (N)    */

@@ -114,9 +114,15 @@ static void plan_bsp(Plan& p) {
   };
   const bool keep_c = p.train && p.siren;
   p.h1w = p.sc ? p.H : p.N1;
+  // A geometry pass (SNERF_FLAG_GEOMETRY) plans only what it writes: the depths, the encoding, the two trunk buffers, sigma's partials or
+  // buffer and the tile counters.  Its last trunk layer leaves into the trunk buffer whose turn it is, also in a composed plan (whose
+  // full pass sends it into the [h_last | extras] tensor): there is no head to read it.
+  const bool geo = p.geometry;
   p.o_z = wtake(((size_t)p.P + 4) * 4);
-  p.o_T = wtake((size_t)p.P * 4);
-  p.o_rgbraw = wtake((size_t)p.N * 3 * 4);
+  if (!geo) {
+    p.o_T = wtake((size_t)p.P * 4);
+    p.o_rgbraw = wtake((size_t)p.N * 3 * 4);
+  }
   p.pe = tensor(p.Ep);
   if (p.train) {
     for (int i = 0; i < p.L - (p.compose_feats ? 1 : 0); ++i) p.h[i] = tensor(p.W, keep_c);
@@ -126,17 +132,19 @@ static void plan_bsp(Plan& p) {
     a.o = planes(p.W); b.o = planes(p.W); a.e = etab(p.W); b.e = etab(p.W);
     for (int i = 0; i < p.L; ++i) p.h[i] = (i & 1) ? b : a;
   }
-  p.fa = tensor(p.FA);
-  if (p.compose_feats) {
+  if (!geo) p.fa = tensor(p.FA);
+  if (p.compose_feats && !geo) {
     // The last trunk layer stores its planes where feats went: columns [0, W) of the [P][FA] tensor, so that the first head layer reads
     // [h_last | extras] as it read [feats | extras] -- no pass over memory added.  h[L - 1] is that tensor at leading dimension FA
     // (its sign words, for a SIREN training pass, are laid out for FA columns).
     p.h[p.L - 1] = p.fa;
     p.h[p.L - 1].s = keep_c ? wtake(bsp::sign_words(Pp, p.FA) * 4) : 0;
   }
-  p.h1 = tensor(p.h1w, keep_c);
-  p.s2 = tensor(p.H, keep_c);
-  p.s3 = tensor(p.H, keep_c);
+  if (!geo) {
+    p.h1 = tensor(p.h1w, keep_c);
+    p.s2 = tensor(p.H, keep_c);
+    p.s3 = tensor(p.H, keep_c);
+  }
   // the narrow projections: folded into the producing SIREN launch's epilogue where its width is whole 256-column tiles (partial sums
   // per wave, summed by the composite), otherwise a 32-wide fp32 buffer written by a launch of their own
   p.nd_sig = p.siren && p.W % 256 == 0 && p.W <= 1024;
@@ -144,13 +152,15 @@ static void plan_bsp(Plan& p) {
   p.nd_fin = !p.sc && p.siren && p.H == 256 && p.C <= ND_FIN;   // one 256-column tile per head block, at most ND_FIN outputs per block
   {  // bsp_trunk.hip: the shapes it is written for (launch_trunk checks them again)
     bool ok = p.pl == 1 && p.siren && p.nd_sig && p.W == 512 && p.Ep == 64 && p.L >= 3 && p.L <= bsp::TR_MAXL &&
-              !(p.skip_mask & 1u) && (p.skip_mask >> (p.L - 1)) == 0u && !bsp::trunk_dma_in_final_layer(p.L, p.skip_mask, /*feats_fused=*/!p.train);   // (bsp_pass.hip: fused_feats)
+              !(p.skip_mask & 1u) && (p.skip_mask >> (p.L - 1)) == 0u && !bsp::trunk_dma_in_final_layer(p.L, p.skip_mask, /*feats_fused=*/!p.train && !geo);   // (bsp_pass.hip: fused_feats)
     for (int i = 0; ok && i < p.L; ++i) ok = p.k_tr[i] == (i == 0 ? 64 : (((p.skip_mask >> i) & 1u) ? 576 : 512));
     p.fuse_trunk = ok;
   }
   if (p.nd_sig) p.o_sigpart = wtake((size_t)4 * (p.W / 256) * Pp * 4); else p.o_sigo = wtake(Pp * NARROW * 4);
-  if (p.nd_sun) p.o_sunpart = wtake((size_t)4 * (p.H / 256) * Pp * 4); else p.o_suno = wtake(Pp * NARROW * 4);
-  if (p.nd_fin) p.o_finpart = wtake((size_t)4 * (p.KF / 256) * ND_FIN * Pp * 4); else if (!p.sc) p.o_fino = wtake(Pp * NARROW * 4);
+  if (!geo) {
+    if (p.nd_sun) p.o_sunpart = wtake((size_t)4 * (p.H / 256) * Pp * 4); else p.o_suno = wtake(Pp * NARROW * 4);
+    if (p.nd_fin) p.o_finpart = wtake((size_t)4 * (p.KF / 256) * ND_FIN * Pp * 4); else if (!p.sc) p.o_fino = wtake(Pp * NARROW * 4);
+  }
   p.o_kcq = wtake((size_t)KCQ_SLOTS * 64);
   p.comp_blocks = composite_bwd_blocks(p.N);
   if (p.train) {
@@ -202,6 +212,11 @@ int make_plan(const SnerfDesc* d, Plan* pl) {
   p.train = (d->flags & SNERF_FLAG_TRAIN) != 0; p.sc = (d->flags & SNERF_FLAG_SC_PASS) != 0;
   p.relight = (d->flags & SNERF_FLAG_RELIGHT) != 0;
   p.embed_grad = (d->flags & SNERF_FLAG_EMBED_GRAD) != 0;
+  p.geometry = (d->flags & SNERF_FLAG_GEOMETRY) != 0;
+  // A geometry pass is an inference pass of its own kind: nothing of it is kept for a backward, it samples along the camera ray, and it
+  // leaves no head tensor a relight could reuse.
+  if (p.geometry && (p.train || p.sc || p.relight || p.embed_grad))
+    return bad("SNERF_FLAG_GEOMETRY cannot be combined with SNERF_FLAG_TRAIN, SNERF_FLAG_SC_PASS, SNERF_FLAG_RELIGHT or SNERF_FLAG_EMBED_GRAD (it is an inference pass without heads)");
   // The embedding-only backward follows a training forward: it reads the activations that one keeps.  Sizes and forward are the TRAIN plan's.
   if (p.embed_grad && (p.relight || !p.train)) return bad("SNERF_FLAG_EMBED_GRAD is valid only together with SNERF_FLAG_TRAIN, and not with SNERF_FLAG_RELIGHT (it selects the backward of a training pass)");
   // A relight reuses what an INFERENCE MAIN pass left: a training workspace has another layout, the solar-correction pass samples along
@@ -344,10 +359,11 @@ static void build_tables(const Plan& p, const SnerfParams* w, TableBuilder& tb) 
 // clone of packed parameters) at an address last noted under the other setting is refused wrongly.  Both need the switch to change inside
 // one process, which only tests do; a process that keeps one setting never sees either.
 // A workspace's note also says WHICH pass wrote it last: a relight (SNERF_FLAG_RELIGHT) reuses the tensors of an inference main pass and
-// is refused on anything else.  The note is taken when a call is queued, so it guards against mis-sequenced calls; it cannot know that
+// is refused on anything else -- a geometry pass (SNERF_FLAG_GEOMETRY) included, which is noted as a kind of its own: it leaves no head
+// tensor.  The note is taken when a call is queued, so it guards against mis-sequenced calls; it cannot know that
 // the caller overwrote the buffer itself.
 namespace {
-enum PassKind { PASS_NONE = 0, PASS_MAIN_INFER, PASS_TRAIN, PASS_SC, PASS_BACKWARD };   // PASS_NONE: a packed parameter buffer
+enum PassKind { PASS_NONE = 0, PASS_MAIN_INFER, PASS_TRAIN, PASS_SC, PASS_BACKWARD, PASS_GEOMETRY };   // PASS_NONE: a packed parameter buffer
 struct BufNote { const void* p; bool composed; int kind; SnerfDesc desc; bool no_beta; };
 constexpr int NOTE_MAX = 256;
 BufNote g_notes[NOTE_MAX];
@@ -371,7 +387,8 @@ int check_plan_note(const void* buf, bool composed, const char* who, const char*
   return SNERF_OK;
 }
 // the descriptor fields that make two passes the same pass: everything, bar the RELIGHT bit, the spelling of the default arithmetic and
-// the EMBED_GRAD bit (which only selects how much of the backward runs: it may be set at backward time alone)
+// the EMBED_GRAD bit (which only selects how much of the backward runs: it may be set at backward time alone).  The GEOMETRY bit IS part
+// of the identity: such a pass leaves another workspace.
 bool same_pass_desc(SnerfDesc a, SnerfDesc b) {
   const unsigned ignore = SNERF_FLAG_RELIGHT | SNERF_FLAG_F16X2 | SNERF_FLAG_EMBED_GRAD;
   a.flags &= ~ignore; b.flags &= ~ignore;
@@ -393,7 +410,8 @@ int check_relight_note(const void* workspace, const SnerfDesc* d, bool want_beta
   }
   if (n->kind != PASS_MAIN_INFER) {
     set_error("snerf_forward(SNERF_FLAG_RELIGHT): the workspace's last pass was a %s pass, not an inference main pass",
-              n->kind == PASS_TRAIN ? "training (SNERF_FLAG_TRAIN)" : n->kind == PASS_SC ? "solar-correction (SNERF_FLAG_SC_PASS)" : "backward");
+              n->kind == PASS_TRAIN ? "training (SNERF_FLAG_TRAIN)" : n->kind == PASS_SC ? "solar-correction (SNERF_FLAG_SC_PASS)" :
+              n->kind == PASS_GEOMETRY ? "geometry (SNERF_FLAG_GEOMETRY)" : "backward");
     return SNERF_ERR_BAD_DESC;
   }
   if (!same_pass_desc(n->desc, *d)) {
@@ -411,9 +429,11 @@ int check_relight_note(const void* workspace, const SnerfDesc* d, bool want_beta
 
 static int check_inputs(const Plan& p, const SnerfInputs* in) {
   if (!in) { set_error("null inputs"); return SNERF_ERR_NULL; }
-  if (!in->sun_d || in->sun_stride < 3) { set_error("sun_d (N,3) with stride >= 3 is required"); return SNERF_ERR_NULL; }
-  if (!in->t) { set_error("t (N,tau) is required"); return SNERF_ERR_NULL; }
-  if (p.x_ts >= 0 && !in->t_s) { set_error("t_s is required with use_separate_tj_for_semantic"); return SNERF_ERR_NULL; }
+  if (!p.geometry) {   // (a geometry pass reads none of the three: they may be NULL)
+    if (!in->sun_d || in->sun_stride < 3) { set_error("sun_d (N,3) with stride >= 3 is required"); return SNERF_ERR_NULL; }
+    if (!in->t) { set_error("t (N,tau) is required"); return SNERF_ERR_NULL; }
+    if (p.x_ts >= 0 && !in->t_s) { set_error("t_s is required with use_separate_tj_for_semantic"); return SNERF_ERR_NULL; }
+  }
   if (p.relight) return SNERF_OK;   // positions and depths are the base pass's
   if (in->xyz) {
     if (!in->z_vals) { set_error("explicit xyz needs explicit z_vals"); return SNERF_ERR_NULL; }
@@ -502,6 +522,16 @@ int snerf_forward(const SnerfDesc* desc, const float* packed_params, const Snerf
   Plan p;
   RC(make_plan(desc, &p));
   if (!packed_params || !out || !workspace) { set_error("snerf_forward: null argument"); return SNERF_ERR_NULL; }
+  if (p.geometry) {   // no head runs: a result of one cannot be handed out
+    const struct { const void* ptr; const char* name; } heads[] = {
+        {out->rgb, "rgb"}, {out->albedo, "albedo"}, {out->sun, "sun"}, {out->sky, "sky"}, {out->beta, "beta"},
+        {out->beta_semantic, "beta_semantic"}, {out->semantic_logits, "semantic_logits"}, {out->semantic_label, "semantic_label"}};
+    for (const auto& h : heads)
+      if (h.ptr) {
+        set_error("snerf_forward(SNERF_FLAG_GEOMETRY): out->%s is not a result of a geometry pass (depth, weights, transparency, sigmas, z_vals)", h.name);
+        return SNERF_ERR_BAD_DESC;
+      }
+  }
   if (workspace_bytes < p.ws_bytes) { set_error("snerf_forward: workspace too small (%zu < %zu)", workspace_bytes, p.ws_bytes); return SNERF_ERR_WORKSPACE; }
   if (((uintptr_t)workspace & 255) || ((uintptr_t)packed_params & 255)) { set_error("workspace and packed params must be 256-byte aligned"); return SNERF_ERR_WORKSPACE; }
   RC(check_inputs(p, in));
@@ -510,7 +540,7 @@ int snerf_forward(const SnerfDesc* desc, const float* packed_params, const Snerf
     RC(check_plan_note(workspace, p.compose_feats, "snerf_forward", "workspace"));
     RC(check_relight_note(workspace, desc, out->beta != nullptr));
   } else {
-    note_plan(workspace, p.compose_feats, p.train ? PASS_TRAIN : p.sc ? PASS_SC : PASS_MAIN_INFER, desc, skips_beta_block(p, out->beta != nullptr));
+    note_plan(workspace, p.compose_feats, p.train ? PASS_TRAIN : p.sc ? PASS_SC : p.geometry ? PASS_GEOMETRY : PASS_MAIN_INFER, desc, skips_beta_block(p, out->beta != nullptr));
   }
   return forward_bsp(p, packed_params, in, out, workspace, (hipStream_t)stream);
 }

@@ -268,7 +268,9 @@ void uncompose_jobs(SgTable& tb, const float* G, const float* gc, const float* w
 }  // namespace bsp
 struct EncodeArgs;
 namespace bsp {
-// x = o + d z, gamma(x) (or raw x) as planes [P][Ep]; the [sun | t | t_s] block as columns [fa_col0, +16) of the [P][FA] tensor
+// x = o + d z, gamma(x) (or raw x) as planes [P][Ep]; the [sun | t | t_s] block as columns [fa_col0, +16) of the [P][FA] tensor.
+// fa == null (the geometry pass, SNERF_FLAG_GEOMETRY): the planes of pe alone -- the same bits -- and a.sun_d / a.t / a.t_s are not
+// dereferenced (unless a.dir_is_sun, the solar-correction pass, which always has an fa); a.zero is cleared either way
 int launch_encode_bsp(const EncodeArgs& a, char* pe, int* Epe, char* fa, int* Efa, int fa_col0, int pl, hipStream_t st);
 // relight (SNERF_FLAG_RELIGHT): the extras block alone -- planes and block exponents of columns [fa_col0, +16) for every row block, the
 // bits launch_encode_bsp writes for the same sun_d / t / t_s (one device function serves both); clears a.zero like it

@@ -69,7 +69,7 @@ int forward_bsp(const Plan& p, const float* pk, const SnerfInputs* in, const Sne
   float* z = ws.f(p.o_z);
   const int act = p.siren ? ACT_SIN : ACT_RELU;
   const bool fused = p.fuse_trunk && bsp::trunk_fusion_enabled();
-  const bool feats_launch = !p.compose_feats && (!fused || p.train);   // feats_from_xyz as a launch of its own
+  const bool feats_launch = !p.geometry && !p.compose_feats && (!fused || p.train);   // feats_from_xyz as a launch of its own
   const size_t EB = 2 * (size_t)p.pl;   // bytes per element of a plane tensor
   // The extras block [sun | t | t_s] of the [feats or h_last | extras] tensor, as both its writers take it
   EncodeArgs ea;
@@ -95,8 +95,10 @@ int forward_bsp(const Plan& p, const float* pk, const SnerfInputs* in, const Sne
     // 2. positions + encoding + extras, written as planes with their block exponents
     ea.rays = in->xyz ? nullptr : in->rays; ea.xyz = in->xyz; ea.z = z;
     ea.dir_is_sun = (p.sc && !in->xyz) ? 1 : 0;
-    RC(bsp::launch_encode_bsp(ea, ws.c(p.pe.o), ws.i(p.pe.e), ws.c(p.fa.o), ws.i(p.fa.e), p.Wf, p.pl, st));
-    if (p.Wf > W)   // pad columns between feats and extras (narrow test networks only): zero planes, read against zero weights
+    // (a geometry pass has no [. | extras] tensor: the kernel then writes the planes of pe alone -- the same bits -- and reads none of
+    //  sun_d / t / t_s, which may be null; it still clears the tile counters)
+    RC(bsp::launch_encode_bsp(ea, ws.c(p.pe.o), ws.i(p.pe.e), p.geometry ? nullptr : ws.c(p.fa.o), p.geometry ? nullptr : ws.i(p.fa.e), p.Wf, p.pl, st));
+    if (p.Wf > W && !p.geometry)   // pad columns between feats and extras (narrow test networks only): zero planes, read against zero weights
       RC(bsp::launch_zero_cols(ws.c(p.fa.o) + (size_t)W * EB, (size_t)p.FA * EB, (size_t)(p.Wf - W) * EB, P, st));
     // 3. trunk (rs_semantic.py:325-334)
     if (fused) {   // one persistent launch, the activation tile resident in LDS (bsp_trunk.hip); inference: only the last layer's planes + sigma's partials leave
@@ -104,7 +106,10 @@ int forward_bsp(const Plan& p, const float* pk, const SnerfInputs* in, const Sne
       g.pe = ws.c(p.pe.o); g.Epe = ws.i(p.pe.e); g.P = P; g.W = W; g.L = p.L; g.skip_mask = p.skip_mask;
       // feats (rs_semantic.py:338) rides as one more layer of an inference pass, entry L: written into the first W columns of the
       // [feats | sun | t | t_s] tensor.  (One plane: fuse_trunk holds only with p.pl == 1.)
-      const bool fused_feats = !p.train;
+      // A geometry pass drops that entry: the trunk alone, whose last layer's planes leave into h[L - 1] (api.hip plans fuse_trunk for
+      // that form: no fusion at L = 3, where the final layer would request the next tile's encoding).
+      const bool fused_feats = !p.train && !p.geometry;
+      if (!p.train && !fused_feats) { g.H[p.L - 1] = ws.c(p.h[p.L - 1].o); g.EH[p.L - 1] = ws.i(p.h[p.L - 1].e); }
       for (int i = 0; i < p.L + (fused_feats ? 1 : 0); ++i) {
         const WOp w = wop(p, pk, i < p.L ? p.wj_tr[i] : p.wj_fs);
         g.Wp[i] = w.W; g.EW[i] = w.EW; g.w_bytes[i] = w.bytes; g.K[i] = w.K;
@@ -149,6 +154,21 @@ int forward_bsp(const Plan& p, const float* pk, const SnerfInputs* in, const Sne
       g.I = P; g.J = W; g.K = W; ws.out(g, p.fa); g.bias = pk + p.b_fs;
       RC(launch_kc(g));
     }
+  }
+  if (p.geometry) {
+    // Geometry pass (SNERF_FLAG_GEOMETRY): sigma's pre-activation is complete, and nothing below serves anything but a head.  The
+    // launches above ARE the leading launches of the full pass, queued in its order, so each already has the counter slot and the
+    // tile direction (rev) it has there -- no `kcq = ...` as in the relight branch, whose launches are the full pass's trailing ones.
+    // Kept because the direction decides which rows a consumer finds in the cache when it starts (the measurement in the comment on
+    // launch_kc), not for the bits: a tile's values do not depend on the order the tiles are walked in.
+    // The composite reads z and sigma's partials / buffer alone; every head pointer of CompArgs stays null.
+    CompArgs c;
+    c.N = p.N; c.S = p.S; c.H = H; c.C = 0;
+    c.z = z; c.sigo = ws.f(p.o_sigo);
+    c.part_stride = p.Pp;
+    if (p.nd_sig) { c.sig_part = ws.f(p.o_sigpart); c.n_sig_part = 4 * (W / 256); c.sig_bias = pk + p.b_fs + W; }
+    c.o_depth = out->depth; c.o_weights = out->weights; c.o_transparency = out->transparency; c.o_sigmas = out->sigmas;
+    return launch_composite_fwd(c, st, /*geometry=*/true);
   }
   const int r0 = (p.sc || p.relight) ? p.sun_col : 0;
   {  // first layer of every head in one GEMM (sc pass, relight: sun-visibility block only; a relight writes it at its column of the main pass's h1)

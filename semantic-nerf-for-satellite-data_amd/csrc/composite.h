@@ -38,7 +38,8 @@ struct CompBwdArgs {
   unsigned* zero = nullptr; int zero_n = 0;   // words the first workgroup clears (the backward pass's tile counters)
 };
 
-int launch_composite_fwd(const CompArgs& a, hipStream_t st);
+// geometry: the instantiation that reads z and sigma's pre-activation alone (SNERF_FLAG_GEOMETRY; every head pointer of `a` may be null)
+int launch_composite_fwd(const CompArgs& a, hipStream_t st, bool geometry = false);
 int composite_bwd_blocks(int N);
 int launch_composite_bwd(const CompBwdArgs& b, hipStream_t st);
 

@@ -74,6 +74,12 @@ __device__ __forceinline__ float fin_pre(const CompArgs& a, size_t p, int col, i
   return s;
 }
 
+// GEO (SNERF_FLAG_GEOMETRY): the geometry instantiation of the SAME body -- z and sigma's pre-activation in; weights, transparency,
+// sigmas and depth out.  Everything that belongs to a head is compiled out, so suno / sun_part, fino / fin_part, sky and sun_d (null
+// in that pass) are never touched.  What remains is the full pass's statement sequence for alpha, the scan, w and
+// `acc_depth += w * zj`: the compiler contracts and orders it as there, which is what gives depth / weights / transparency the full
+// pass's bits (a restated loop may contract differently).
+template <bool GEO>
 __global__ __launch_bounds__(256) void composite_fwd_kernel(CompArgs a) {
   const int lane = threadIdx.x & 63;
   const int wave_g = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -81,7 +87,7 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(CompArgs a) {
   const int S = a.S, C = a.C;
   for (int ray = wave_g; ray < a.N; ray += nwaves) {
     float k[3] = {0.f, 0.f, 0.f};
-    if (!a.sc) {
+    if (!GEO && !a.sc) {
       float hu[MAX_SKY_UNITS];
       const float* sd = a.sun_d + (size_t)ray * a.sun_stride;
       sky_forward(a.sky, a.H, sd[0], sd[1], sd[2], lane, hu, k);
@@ -108,41 +114,51 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(CompArgs a) {
       const float T = carryT * excl;
       carryT = carryT * __shfl(incl, 63, 64);
       const float w = alpha * T;
-      const float v = sigmoid_f(narrow_pre(a.suno, a.sun_part, a.sun_bias, a.n_sun_part, a.part_stride, p));
+      const float v = GEO ? 0.f : sigmoid_f(narrow_pre(a.suno, a.sun_part, a.sun_bias, a.n_sun_part, a.part_stride, p));
       if (valid) {
         if (a.o_weights) a.o_weights[p] = w;
         if (a.o_transparency) a.o_transparency[p] = T;
-        if (a.o_sun) a.o_sun[p] = v;
-        if (a.save_T) a.save_T[p] = T;
+        if (!GEO && a.o_sun) a.o_sun[p] = v;
+        if (!GEO && a.save_T) a.save_T[p] = T;
       }
-      if (a.sc) continue;
-      float al[3];
+      if (!GEO && a.sc) continue;
+      float al[3] = {0.f, 0.f, 0.f};
+      if (!GEO) {
 #pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        al[c] = sigmoid_f(fin_pre(a, p, Plan::col_rgb + c, 0, c)) * 1.002f - 0.001f;
-        const float irr = v + (1.f - v) * k[c];
-        if (valid) acc_rgb[c] += (w * al[c]) * irr;
+        for (int c = 0; c < 3; ++c) {
+          al[c] = sigmoid_f(fin_pre(a, p, Plan::col_rgb + c, 0, c)) * 1.002f - 0.001f;
+          const float irr = v + (1.f - v) * k[c];
+          if (valid) acc_rgb[c] += (w * al[c]) * irr;
+        }
       }
-      const float beta = a.o_beta ? softplus_f(fin_pre(a, p, Plan::col_beta, 2, 0)) : 0.f;   // (not computed when nobody asked: bsp_pass.hip, tj_skip)
+      const float beta = (!GEO && a.o_beta) ? softplus_f(fin_pre(a, p, Plan::col_beta, 2, 0)) : 0.f;   // (not computed when nobody asked: bsp_pass.hip, tj_skip)
       if (valid) {
         acc_depth += w * zj;
         if (a.o_sigmas) a.o_sigmas[p] = sigma;
-        if (a.o_beta) a.o_beta[p] = beta;
-        if (a.o_albedo) { a.o_albedo[p * 3 + 0] = al[0]; a.o_albedo[p * 3 + 1] = al[1]; a.o_albedo[p * 3 + 2] = al[2]; }
-        if (a.o_sky) { a.o_sky[p * 3 + 0] = k[0]; a.o_sky[p * 3 + 1] = k[1]; a.o_sky[p * 3 + 2] = k[2]; }
-        if (a.o_beta_s && a.has_sbeta) a.o_beta_s[p] = softplus_f(fin_pre(a, p, Plan::col_sbeta, 3, 0));
+        if (!GEO) {
+          if (a.o_beta) a.o_beta[p] = beta;
+          if (a.o_albedo) { a.o_albedo[p * 3 + 0] = al[0]; a.o_albedo[p * 3 + 1] = al[1]; a.o_albedo[p * 3 + 2] = al[2]; }
+          if (a.o_sky) { a.o_sky[p * 3 + 0] = k[0]; a.o_sky[p * 3 + 1] = k[1]; a.o_sky[p * 3 + 2] = k[2]; }
+          if (a.o_beta_s && a.has_sbeta) a.o_beta_s[p] = softplus_f(fin_pre(a, p, Plan::col_sbeta, 3, 0));
+        }
       }
+      if (!GEO) {
 #pragma unroll
-      for (int c = 0; c < MAX_CLASSES; ++c) {
-        if (c < C) {
-          const float pre = fin_pre(a, p, Plan::col_sem + c, 1, c);
-          const float q = a.sem_sigmoid ? sigmoid_f(pre) : pre;
-          if (valid) acc_log[c] += w * q;
+        for (int c = 0; c < MAX_CLASSES; ++c) {
+          if (c < C) {
+            const float pre = fin_pre(a, p, Plan::col_sem + c, 1, c);
+            const float q = a.sem_sigmoid ? sigmoid_f(pre) : pre;
+            if (valid) acc_log[c] += w * q;
+          }
         }
       }
     }
-    if (a.sc) continue;
+    if (!GEO && a.sc) continue;
     const float depth = wave_sum(acc_depth);
+    if (GEO) {
+      if (lane == 0 && a.o_depth) a.o_depth[ray] = depth;
+      continue;
+    }
     float rgb[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) rgb[c] = wave_sum(acc_rgb[c]);
@@ -166,9 +182,10 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(CompArgs a) {
   }
 }
 
-int launch_composite_fwd(const CompArgs& a, hipStream_t st) {
+int launch_composite_fwd(const CompArgs& a, hipStream_t st, bool geometry) {
   const int blocks = max(1, min((a.N + 3) / 4, 2048));
-  hipLaunchKernelGGL(composite_fwd_kernel, dim3(blocks), dim3(256), 0, st, a);
+  if (geometry) hipLaunchKernelGGL(composite_fwd_kernel<true>, dim3(blocks), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(composite_fwd_kernel<false>, dim3(blocks), dim3(256), 0, st, a);
   SNERF_LAUNCH_CHECK();
   return 0;
 }

@@ -18,8 +18,11 @@ def get_xyz_from_nerf_prediction(rays: torch.Tensor, depth: torch.Tensor) -> tor
 
 
 @torch.no_grad()
-def extract_pointcloud(cfgs, renderer, models, rays, extras, render_options=None, with_labels=None, sharded=False, geo=None):
+def extract_pointcloud(cfgs, renderer, models, rays, extras, render_options=None, with_labels=None, sharded=False, geo=None,
+                       with_colors=True):
     """One image -> {"xyz_n" (R,3) f64, "colors" (R,3) f32, "depth" (R) f32 [, "labels" (R) i64]}, all on the device.
+    `with_colors=False` leaves "colors" out; without labels either, the walk asks for the depth alone and runs as geometry passes
+    (eval/utils/util.py: relight_chunks) -- no head launch, the same depth bits, hence the same cloud.
     With `geo` also "xyz_utm" (R,3) f64: the un-normalised UTM (east, north, alt) cloud (GeoFrame.cloud of rays and depth).
     `sharded=False` (default) is the reference's single-device call: safe from one rank of a process group (the usual export
     inside a data-parallel run).  `sharded=True` is a COLLECTIVE: every rank of the group must call it with the same rays;
@@ -28,11 +31,12 @@ def extract_pointcloud(cfgs, renderer, models, rays, extras, render_options=None
     sem = models["coarse"].spec.n_classes > 0
     if with_labels is None:
         with_labels = sem
-    keys = ["rgb_coarse", "depth_coarse"] + (["semantic_label_coarse"] if with_labels and sem else [])
+    keys = (["rgb_coarse"] if with_colors else []) + ["depth_coarse"] + (["semantic_label_coarse"] if with_labels and sem else [])
     infer = sharded_lean_inference if sharded else lean_inference
     res = infer(cfgs, renderer, models, rays, extras, keys=keys, render_options=render_options or {})
-    out = {"xyz_n": get_xyz_from_nerf_prediction(rays, res["depth_coarse"]), "colors": res["rgb_coarse"],
-           "depth": res["depth_coarse"]}
+    out = {"xyz_n": get_xyz_from_nerf_prediction(rays, res["depth_coarse"]), "depth": res["depth_coarse"]}
+    if with_colors:
+        out["colors"] = res["rgb_coarse"]
     if "semantic_label_coarse" in res:
         out["labels"] = res["semantic_label_coarse"]
     if geo is not None:

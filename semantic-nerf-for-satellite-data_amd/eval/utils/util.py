@@ -109,11 +109,15 @@ def relight_chunks(cfgs, renderer, models, rays, extras, suns, buffers, render_o
     before the next yield -- or, with frame_sized, tensors with a leading sun axis, (K, n, ...): views = buffers[key][s, i:i + k].
     Every sun is asked for the same results, those of `buffers`.  A sun of None stands for `extras` as they are, None included:
     render_chunks is the walk under that one sun.  The walk owns the pack of the weights (once), the workspace carried from pass
-    to pass, the chunk steps and the per-chunk options."""
+    to pass, the chunk steps and the per-chunk options.
+    A single-sun walk (suns == (None,)) whose results all lie in ops.GEOMETRY_KEYS (depth, weights, transparency, sigmas, z_vals)
+    runs every chunk as a geometry pass (render_options["geometry_only"]): the same bits without the head launches.  A walk with
+    more suns never does: its base pass must leave a workspace that can be relit."""
     from ... import ops
     suns = list(suns)
     if not suns:
         raise ValueError("relight_chunks: no sun")
+    geometry_walk = suns == [None] and len(buffers) > 0 and all(_bare(key) in ops.GEOMETRY_KEYS for key in buffers)
     chunk = cfgs.pipeline.render_chunk_size
     n = rays.shape[0]
     model = models["coarse"]
@@ -127,6 +131,8 @@ def relight_chunks(cfgs, renderer, models, rays, extras, suns, buffers, render_o
         k = min(chunk, n - i)
         opts = _chunk_options(render_options, i, chunk, n)
         opts["packed_params"] = packed
+        if geometry_walk:
+            opts["geometry_only"] = True
         ex = extras[i:i + chunk] if extras is not None else None
         for s, sun in enumerate(suns):
             views = {key: v[s, i:i + k] if frame_sized else v[:k] for key, v in buffers.items()}

@@ -346,7 +346,7 @@ def unpack_grads(spec: ModelSpec, packed_grads: torch.Tensor, like: dict, accumu
 @dataclass
 class PassInputs:
     """One ray batch in either of the two seams (renderer: rays [+u]; inference(): xyz + z_vals)."""
-    sun_d: torch.Tensor                   # (N,3) (may be a strided view into extras (N,4))
+    sun_d: torch.Tensor | None = None     # (N,3) (may be a strided view into extras (N,4)); None only for a geometry pass, which reads no sun
     rays: torch.Tensor | None = None      # (N,8)
     xyz: torch.Tensor | None = None       # (N,S,3)
     z_vals: torch.Tensor | None = None    # (N,S)
@@ -364,15 +364,24 @@ class PassInputs:
                 self._keep.append(v)
                 setattr(si, name, v.data_ptr())
         sd = self.sun_d
-        _check_dev(sd, "sun_d")
-        if sd.dim() != 2 or sd.shape[1] != 3 or sd.stride(1) != 1:
-            sd = sd.contiguous()
-        self._keep.append(sd)
-        si.sun_d = sd.data_ptr()
-        si.sun_stride = sd.stride(0) if sd.shape[0] > 1 else 3
-        si.t = t.data_ptr()
+        si.sun_stride = 3
+        if sd is not None:      # (the library names a missing sun_d / t itself, for every pass but the geometry pass)
+            _check_dev(sd, "sun_d")
+            if sd.dim() != 2 or sd.shape[1] != 3 or sd.stride(1) != 1:
+                sd = sd.contiguous()
+            self._keep.append(sd)
+            si.sun_d = sd.data_ptr()
+            si.sun_stride = sd.stride(0) if sd.shape[0] > 1 else 3
+        si.t = t.data_ptr() if t is not None else None
         si.t_s = t_s.data_ptr() if t_s is not None else None
         return si
+
+    def n_rays(self) -> int:
+        """N from whichever per-ray tensor the batch carries"""
+        for v in (self.rays, self.z_vals, self.xyz, self.u, self.sun_d):
+            if v is not None:
+                return int(v.shape[0])
+        raise ValueError("PassInputs: no per-ray tensor to take the number of rays from")
 
 
 _OUT_SHAPES = {
@@ -400,10 +409,11 @@ def _forward_setup(spec, pin, t, t_s, flags, n_samples=None):
     launch); launch(packed, so, ws) is the snerf_forward call on the workspace tensor `ws`."""
     S = int(n_samples) if n_samples is not None else (
         pin.z_vals.shape[1] if pin.z_vals is not None else (pin.u.shape[1] if pin.u is not None else pin.z_steps.shape[0]))
-    d = spec.desc(t.shape[0], S, flags)
+    d = spec.desc(t.shape[0] if t is not None else pin.n_rays(), S, flags)      # (t = None: a geometry pass, which reads no embedding)
     nbytes = _lib.call_size("snerf_workspace_bytes", d)
-    _check_dev(t, "t")
-    tc = t.contiguous()
+    if t is not None:
+        _check_dev(t, "t")
+    tc = t.contiguous() if t is not None else None
     tsc = t_s.contiguous() if t_s is not None else None
     si = pin.struct(tc, tsc)
     return S, d, nbytes, tc, tsc, lambda packed, so, ws: _lib.call("snerf_forward", d, packed, si, so, ws, ws.numel())
@@ -523,10 +533,15 @@ def render_pass(spec: ModelSpec, params: dict, pin: PassInputs, t: torch.Tensor,
     return out
 
 
-def _outputs_struct(who, spec, out, N, S, sc_pass=False):
+GEOMETRY_KEYS = ("depth", "weights", "transparency", "sigmas", "z_vals")      # the results of a geometry pass (SNERF_FLAG_GEOMETRY)
+
+
+def _outputs_struct(who, spec, out, N, S, sc_pass=False, geometry=False):
     """SnerfOutputs of the *_into entries: every tensor of `out` checked (a result of this pass; on the GPU; contiguous, of the pass's
     shape and dtype) and bound; every other pointer stays NULL"""
     allowed = set(output_keys(spec, sc_pass)) | {"z_vals"} | ({"semantic_label"} if spec.n_classes > 0 and not sc_pass else set())
+    if geometry:
+        allowed = set(GEOMETRY_KEYS)
     so = _lib.SnerfOutputs()
     for k, v in out.items():
         if k not in allowed:
@@ -545,21 +560,41 @@ def _outputs_struct(who, spec, out, N, S, sc_pass=False):
 @torch.no_grad()
 def render_pass_into(spec: ModelSpec, params: dict, pin: PassInputs, t: torch.Tensor, t_s: torch.Tensor | None,
                      out: dict, sc_pass: bool = False, packed: torch.Tensor | None = None,
-                     workspace: torch.Tensor | None = None) -> torch.Tensor:
+                     workspace: torch.Tensor | None = None, geometry: bool = False) -> torch.Tensor:
     """Inference-only pass that produces ONLY the result tensors named in `out` and writes them in place:
     `out` maps result keys (output_keys(), 'semantic_label', 'z_vals') to preallocated contiguous tensors of the
     pass's shapes -- typically row slices of full-frame buffers, so a chunked render never concatenates
     (eval/utils/util.py:13-42 re-concatenates every key per chunk).  Every other SnerfOutputs pointer stays NULL and
-    the composite kernel skips it.  Returns the workspace (pass it back in for the next chunk of the same size)."""
-    N, dev = t.shape[0], t.device
-    S, _, nbytes, _, _, launch = _forward_setup(spec, pin, t, t_s, _lib.FLAG_SC_PASS if sc_pass else 0)
+    the composite kernel skips it.  Returns the workspace (pass it back in for the next chunk of the same size).
+    `geometry=True` runs the geometry pass (SNERF_FLAG_GEOMETRY): trunk, sigma and the composite, no head launch.  `out` may
+    then name GEOMETRY_KEYS only (KeyError otherwise), each with the bits of the full pass; `t`, `t_s` and `pin.sun_d` are not read
+    and may be None; a workspace made here is the smaller one of that pass (a larger one given is used as it is)."""
+    if geometry and sc_pass:
+        raise ValueError("render_pass_into: geometry=True is a main-pass variant, not one of the solar-correction pass")
+    for k in out if geometry else ():      # before anything is sized or allocated
+        if k not in GEOMETRY_KEYS:
+            raise KeyError(f"render_pass_into(geometry=True): '{k}' is not a result of a geometry pass (have {sorted(GEOMETRY_KEYS)})")
+    if t is None and not geometry:
+        raise ValueError("render_pass_into: t (N, tau) is required (only a geometry pass reads no embedding)")
+    lead = t if t is not None else next(v for v in (pin.rays, pin.z_vals, pin.xyz) if v is not None)      # (t = None: N and the device from the rays)
+    N, dev = lead.shape[0], lead.device
+    flags = _lib.FLAG_GEOMETRY if geometry else (_lib.FLAG_SC_PASS if sc_pass else 0)
+    S, _, nbytes, _, _, launch = _forward_setup(spec, pin, t, t_s, flags)
     if workspace is None or workspace.numel() < nbytes or workspace.device != dev:
         workspace = _empty(nbytes, dtype=torch.uint8, device=dev)
-    so = _outputs_struct("render_pass_into", spec, out, N, S, sc_pass)
+    so = _outputs_struct("render_pass_into", spec, out, N, S, sc_pass, geometry)
     if packed is None:
         packed = pack_params(spec, params)
     launch(packed, so, workspace)
     return workspace
+
+
+def geometry_pass_into(spec: ModelSpec, params: dict, pin: PassInputs, out: dict, packed: torch.Tensor | None = None,
+                       workspace: torch.Tensor | None = None) -> torch.Tensor:
+    """The geometry pass: render_pass_into(geometry=True) without the operands it does not read.  `out` names results of
+    GEOMETRY_KEYS -- depth (N), weights / transparency / sigmas / z_vals (N, S) -- each with the bits the full inference pass of the
+    same inputs gives; `pin` needs rays (or xyz + z_vals) and no sun_d.  Returns the workspace."""
+    return render_pass_into(spec, params, pin, None, None, out, packed=packed, workspace=workspace, geometry=True)
 
 
 @torch.no_grad()

@@ -60,8 +60,10 @@ def _pass_operands(models, model, extras, opts):
 
 @torch.no_grad()
 def importance_depths(renderer, models, typ, rays, extras, opts: dict):
-    """The depths of a render with n_importance > 0, left in opts["given_z_vals"]: a PROPOSAL pass -- the inference main pass on
-    the stratified depths (opts["perturb_rand"]), asked for its weights and depths alone -- and ops.resample_z, which draws
+    """The depths of a render with n_importance > 0, left in opts["given_z_vals"]: a PROPOSAL pass -- the geometry pass
+    (trunk, sigma, composite; no head launch and no embedding lookup) on the stratified depths (opts["perturb_rand"]), which gives
+    weights and depths with the bits of the inference main pass; opts["proposal_pass"] = "full" runs that main pass instead, asked
+    for the same two results -- and ops.resample_z, which draws
     n_importance fine samples per ray from those weights and merges them with the coarse depths: (N, n_samples + n_importance),
     no gradient (sample_pdf's callers detach the samples).  The uniforms are opts["importance_rand"] (N, n_importance); absent,
     they are drawn when opts["perturb"] (default 1.0) > 0 and are the regular grid of the reference's det=True otherwise, as in
@@ -71,18 +73,31 @@ def importance_depths(renderer, models, typ, rays, extras, opts: dict):
     model = models[typ]
     spec = model.spec
     N, S, Ni, dev = rays.shape[0], renderer.N_samples, renderer.N_importance, rays.device
-    sun_d, rays_t, rays_t_s, params, packed = _pass_operands(models, model, extras, opts)
+    proposal = opts.get("proposal_pass", "geometry")
+    if proposal not in ("geometry", "full"):
+        raise ValueError(f"render_options['proposal_pass'] must be 'geometry' or 'full', got {proposal!r}")
+    geometry = proposal == "geometry"
+    if geometry:
+        # weights and depths depend on no head: the geometry pass (SNERF_FLAG_GEOMETRY) gives their bits without the head launches, and
+        # reads neither the sun nor an embedding -- no lookup is launched for the proposal
+        sun_d = rays_t = rays_t_s = None
+        params = dict(model.named_parameters())
+        packed = opts.get("packed_params")
+        if packed is None:
+            packed = ops.pack_params(spec, params)
+    else:      # "full": the inference main pass asked for the same two results
+        sun_d, rays_t, rays_t_s, params, packed = _pass_operands(models, model, extras, opts)
     opts["packed_params"] = packed
     out = {"weights": ops._empty((N, S), dtype=torch.float32, device=dev), "z_vals": ops._empty((N, S), dtype=torch.float32, device=dev)}
     pin = ops.PassInputs(sun_d=sun_d, rays=rays, z_steps=z_steps_on(dev, S), u=opts.get("perturb_rand"))
     ws, lease = opts.get("workspace"), None
     if ws is None and "workspace" not in opts:      # a training render: the lease pool, like the passes that follow
         with torch.cuda.device(dev):
-            lease = ops.lease_workspace(dev, ops._lib.call_size("snerf_workspace_bytes", spec.desc(N, S)))
+            lease = ops.lease_workspace(dev, ops._lib.call_size("snerf_workspace_bytes", spec.desc(N, S, ops._lib.FLAG_GEOMETRY if geometry else 0)))
         ws = lease.t
     elif ws is None:                                # the first chunk of a walk: sized for the rendering pass that follows
         ws = ops._empty(ops._lib.call_size("snerf_workspace_bytes", spec.desc(N, S + Ni)), dtype=torch.uint8, device=dev)
-    ws = ops.render_pass_into(spec, params, pin, rays_t, rays_t_s, out, packed=packed, workspace=ws)
+    ws = ops.render_pass_into(spec, params, pin, rays_t, rays_t_s, out, packed=packed, workspace=ws, geometry=geometry)
     if lease is not None:
         lease.release()      # stream order makes the reuse safe
     else:
@@ -149,9 +164,25 @@ _SC_KEYS = {"weights_sc": "weights", "transparency_sc": "transparency", "sun_sc"
 def fused_model_rendering_into(renderer, models, typ, rays, extras, render_options, out: dict):
     """Inference-only twin of fused_model_rendering: writes just the results named in `out` (un-suffixed keys) into
     the given tensors.  The solar-correction pass runs only if one of its three results is asked for -- a point-cloud
-    or image render (rgb / depth / label) does half the work of render_rays."""
+    or image render (rgb / depth / label) does half the work of render_rays.
+    render_options["geometry_only"] = True runs the geometry pass instead of the main pass: `out` may then name ops.GEOMETRY_KEYS
+    only (KeyError for anything else, the solar-correction keys included), each result has the bits of the main pass, and neither
+    the sun nor an embedding is looked up."""
     opts = render_options or {}
+    if opts.get("geometry_only"):
+        for k in out:      # (before anything is looked up)
+            if k in _SC_KEYS or k not in ops.GEOMETRY_KEYS:
+                raise KeyError(f"fused_model_rendering_into(geometry_only): '{k}' is not a result of a geometry pass "
+                               f"(have {sorted(ops.GEOMETRY_KEYS)})")
     model = models[typ]
+    if opts.get("geometry_only"):
+        params = dict(model.named_parameters())
+        packed = opts.get("packed_params")
+        if packed is None:
+            packed = ops.pack_params(model.spec, params)
+        pin = ops.PassInputs(rays=rays, z_vals=opts.get("given_z_vals"), z_steps=z_steps_on(rays.device, renderer.N_samples),
+                             u=opts.get("perturb_rand"))
+        return ops.geometry_pass_into(model.spec, params, pin, out, packed=packed, workspace=opts.get("workspace"))
     sun_d, rays_t, rays_t_s, params, packed = _pass_operands(models, model, extras, opts)
     main_out = {k: v for k, v in out.items() if k not in _SC_KEYS}
     sc_out = {_SC_KEYS[k]: v for k, v in out.items() if k in _SC_KEYS}
