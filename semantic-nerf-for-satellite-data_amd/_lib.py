@@ -233,10 +233,12 @@ SIGNATURES = _signatures()
 EXPORTED_SYMBOLS = tuple(SIGNATURES)
 
 # Entries declared OUTSIDE include/snerf_hip.h, whose list of symbols is frozen at ABI 6: header -> rows in that header's order
-# (tests/test_resample_cpu.py compares them with the header as tests/test_abi_cpu.py does for the table above).  lib() and call()
+# (tests/test_resample_cpu.py and tests/test_raydist_cpu.py compare them with their headers as tests/test_abi_cpu.py does for the
+# table above).  lib() and call()
 # serve both tables alike.
 EXTENSION_SIGNATURES = {
     "snerf_resample.h": {"snerf_resample_z": (C.c_int, (C.c_void_p,) * 5 + (C.c_int,) * 3 + (c_stream,))},
+    "snerf_raydist.h": {"snerf_ray_distortion": (C.c_int, (C.c_void_p,) * 3 + (C.c_int,) * 3 + (C.c_void_p,) * 3 + (c_stream,))},
 }
 _ALL_SIGNATURES = dict(SIGNATURES)
 for _rows in EXTENSION_SIGNATURES.values():

@@ -35,6 +35,10 @@ class NeRFConfig(BaseModel):
     fc_skips: List[int] = [4]
     ray_subsampling_activated: Union[bool, int] = False
     ray_subsampling_amount: float = 1.0
+    # build extension: the weight of the distortion loss on the main pass's ray weights (0 = off: no launch,
+    # no tensor, no log key) and the epoch it starts at
+    lambda_dist: float = 0.0
+    dist_start_epoch: int = 0
 
     @model_validator(mode="after")
     def _check_n_importance(self):
@@ -47,6 +51,16 @@ class NeRFConfig(BaseModel):
                 raise ValueError(f"n_importance > 0 needs n_samples >= 3, got n_samples = {self.n_samples}")
             if self.n_samples + self.n_importance > 1024:
                 raise ValueError(f"n_samples + n_importance must be <= 1024, got {self.n_samples} + {self.n_importance}")
+        return self
+
+    @model_validator(mode="after")
+    def _check_lambda_dist(self):
+        if not self.lambda_dist >= 0:
+            raise ValueError(f"lambda_dist must be >= 0, got {self.lambda_dist}")
+        if self.dist_start_epoch < 0:
+            raise ValueError(f"dist_start_epoch must be >= 0, got {self.dist_start_epoch}")
+        if self.lambda_dist > 0 and self.n_samples + max(self.n_importance, 0) > 1024:
+            raise ValueError(f"lambda_dist > 0 needs n_samples + n_importance <= 1024, got {self.n_samples} + {self.n_importance}")
         return self
 
 

@@ -188,3 +188,41 @@ def run_plans(plans, results, typ: str = "coarse", sync: bool = True):
         total = t if total is None else total + t
         out.update({k: terms[idx[k]] for k in keys})
     return total, out
+
+
+# ---- the distortion loss on the ray weights ---------------------------------------------------------------------------------------
+# mip-NeRF 360's regulariser on a pass's weights (include/snerf_raydist.h): one launch gives every ray's value
+# summed into integer words and d / d weights; the mean over the batch's rays and the weight `lam` are applied on the device.
+class _DistortionLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, lam: float, sync: bool, z_vals, rays, weights):
+        from .ops import ray_distortion
+        d_weights, acc = ray_distortion(weights.detach().contiguous(), z_vals.detach().contiguous(), rays.detach().contiguous())
+        if sync and _dist_world() > 1:
+            from .parallel import allreduce_sum_
+            allreduce_sum_(acc)              # integer words over all ranks (4 int64): the mean is over the global batch's rays
+        a = acc[:2].to(torch.float64)
+        n = a[1]
+        term = ((a[0] * (2.0 ** -40) * float(lam)) / n).to(torch.float32)       # (float)((lam * (acc0 * 2^-40)) / acc1)
+        scale = (torch.full_like(n, float(lam)) / n).to(torch.float32)          # (float)(lam / acc1): a true division, not lam * (1 / acc1)
+        d_weights.mul_(scale)
+        ctx.grad = d_weights
+        return term
+
+    @staticmethod
+    def backward(ctx, g_total):
+        grad, ctx.grad = ctx.grad, None
+        if grad is None:
+            raise RuntimeError("snerf_amd: second backward through one distortion loss (its gradient buffer was scaled in place by the first)")
+        grad.mul_(g_total)
+        return None, None, None, None, grad
+
+
+def distortion_loss(weights, z_vals, rays, lam: float, sync: bool = True):
+    """lam * mean over the batch's rays of the distortion loss of `weights` (N, S) along `z_vals` (N, S) on `rays` (near, far in
+    columns 6 and 7): one launch, under data parallelism one all-reduce of four integer words, no host synchronisation.  Returns
+    (total, term) like fused_loss's (total, terms): `total` is differentiable w.r.t. `weights` (the depths carry no gradient),
+    `term` is the same value, detached, for the loss dict ('coarse_distortion').  Bad rays (include/snerf_raydist.h) add nothing and count
+    in the mean's denominator."""
+    total = _DistortionLoss.apply(float(lam), sync, z_vals, rays, weights)
+    return total, total.detach()

@@ -695,3 +695,33 @@ def resample_z(z: torch.Tensor, weights: torch.Tensor, n_importance: int, u: tor
     z_fine = _empty((N, max(Ni, 0)), dtype=torch.float32, device=z.device) if return_fine else None
     _lib.call("snerf_resample_z", z.detach(), weights.detach(), u.detach() if u is not None else None, z_out, z_fine, N, S, Ni)
     return (z_out, z_fine) if return_fine else z_out
+
+
+def ray_distortion(weights: torch.Tensor, z_vals: torch.Tensor, rays: torch.Tensor, per_ray: bool = False, acc: torch.Tensor | None = None):
+    """the distortion loss on a pass's weights -- snerf_ray_distortion (include/snerf_raydist.h): for
+    `weights` (N, S) composited along `z_vals` (N, S) on `rays` (N, >= 8; near and far are columns 6 and 7) ->
+    (d_weights_unit, acc[, per_ray]): d L_r / d weights (N, S) of every ray's own value, unscaled; `acc`, four int64 words
+    (the library's u64 words: [0] the sum of the rays' values in units of 2^-40, [1] the rays, [2] the bad rays, [3] unused);
+    with `per_ray` the rays' values (N,) fp64, NaN for a bad ray.  A given `acc` is accumulated into (shards of one batch), else
+    a zeroed one is made.  One launch on the current stream, no synchronisation; nothing here carries a gradient."""
+    _check_dev(weights, "weights")
+    _check_dev(z_vals, "z_vals")
+    _check_dev(rays, "rays")
+    if weights.dim() != 2 or tuple(z_vals.shape) != tuple(weights.shape):
+        raise ValueError(f"ray_distortion: weights and z_vals must both be (N, S), got {tuple(weights.shape)} and {tuple(z_vals.shape)}")
+    N, S = weights.shape
+    if rays.dim() != 2 or rays.shape[0] != N or rays.shape[1] < 8:
+        raise ValueError(f"ray_distortion: rays must be (N, >= 8) = ({N}, >= 8), got {tuple(rays.shape)}")
+    for name, v in (("weights", weights), ("z_vals", z_vals), ("rays", rays), ("acc", acc)):
+        if v is not None and not v.is_contiguous():
+            raise ValueError(f"ray_distortion: '{name}' must be contiguous")
+    if weights.device != z_vals.device or weights.device != rays.device:
+        raise ValueError(f"ray_distortion: weights, z_vals and rays must share a device, got {weights.device}, {z_vals.device}, {rays.device}")
+    if acc is None:
+        acc = torch.zeros(4, dtype=torch.int64, device=weights.device)
+    elif not acc.is_cuda or acc.device != weights.device or acc.dtype != torch.int64 or tuple(acc.shape) != (4,):
+        raise ValueError(f"ray_distortion: acc must be 4 int64 words on {weights.device}, got {tuple(acc.shape)} {acc.dtype} on {acc.device}")
+    d_weights = _empty((N, S), dtype=torch.float32, device=weights.device)
+    values = _empty((N,), dtype=torch.float64, device=weights.device) if per_ray else None
+    _lib.call("snerf_ray_distortion", weights.detach(), z_vals.detach(), rays.detach(), rays.shape[1], N, S, d_weights, values, acc)
+    return (d_weights, acc, values) if per_ray else (d_weights, acc)

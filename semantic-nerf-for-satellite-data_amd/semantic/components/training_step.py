@@ -1,6 +1,6 @@
 """Semantic training step -- mirror of semantic/components/training_step.py:10-99: which loss fires when
 (epoch < first_beta_epoch, train_steps < ds_drop, use_beta_for_s, use_car_reg_loss & epoch >= car_reg_loss_start)."""
-from ...baseline.components.training_step import color_and_depth_losses
+from ...baseline.components.training_step import color_and_depth_losses, main_pass
 from ...framework.components.training_step import BaseTrainingStep
 from .metrics import semantic_accuracy
 
@@ -8,7 +8,7 @@ from .metrics import semantic_accuracy
 class RSSemanticTrainingStep(BaseTrainingStep):
     def training_step(self, pipeline, batch, batch_idx):
         pc = pipeline.cfgs.pipeline
-        results = pipeline({"rays": batch["rgb"]["rays"], "extras": batch["rgb"]["extras"]})
+        results = main_pass(pipeline, batch)
         labels = batch["rgb"]["semantic"]
         mask = batch["rgb"].get("semantic_sparsity_mask")
         # the reference's gates and log keys; the gated modules hand over their PLANS and are evaluated with the colour loss in

@@ -1,0 +1,99 @@
+#!/usr/bin/env python3
+"""What the distortion loss costs: at the bench model (W = 512, H = 256, L = 8, C = 5), 4096 rays x 64
+samples, in the default arithmetic, the device time of
+
+    launch      the snerf_ray_distortion launch alone (ops.ray_distortion on a training pass's weights and depths)
+    loss        loss_ops.distortion_loss forward + backward: the launch, the handful of scalar launches behind it, two scalings
+    step        a training step of the bench's pipeline with lambda_dist = 0 (today's step)
+    step_dist   the same step with lambda_dist = 0.01
+
+Each figure is the median over --reps windows of --inner back-to-back calls between two device events in one process, after
+warm-up windows of the same shape; the legs alternate window by window, so that a drift of the machine falls on all of them.
+The two step legs share one pipeline, one optimiser and one ray bank: only the config key differs.  Prints one JSON line."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import bench  # noqa: E402
+from snerf_amd import loss_ops, ops  # noqa: E402
+from snerf_amd.framework.pipelines import TrainLoop, load_pipeline  # noqa: E402
+
+
+def window_ms(fn, inner):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(inner):
+        fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / inner
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rays", type=int, default=4096)
+    ap.add_argument("--samples", type=int, default=64)
+    ap.add_argument("--lam", type=float, default=0.01)
+    ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--inner", type=int, default=5)
+    ap.add_argument("--inner-launch", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=2)
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    N, S = a.rays, a.samples
+    cfgs = bench.make_cfgs(N, S, 1)
+    pipe = load_pipeline(cfgs)
+    pipe.log_metrics = False
+    loop = TrainLoop(pipe, cfgs, dev)
+    step = [0]
+    with torch.no_grad():
+        batch = loop._make_batch(0)["rgb"]
+        res = pipe({"rays": batch["rays"], "extras": batch["extras"]}, {"return_z_vals": True})
+    w, z, rays = res["weights_coarse"].contiguous(), res["z_vals_coarse"].contiguous(), batch["rays"].contiguous()
+    _, acc = ops.ray_distortion(w, z, rays)
+    words = [int(v) for v in acc.cpu()]
+    del res
+
+    def train(lam):
+        def fn():
+            cfgs.pipeline.lambda_dist = lam
+            loop.step(step[0])
+            step[0] += 1
+        return fn
+
+    def loss():
+        wg = w.requires_grad_(True)
+        total, _ = loss_ops.distortion_loss(wg, z, rays, a.lam)
+        total.backward()
+        wg.grad = None
+
+    legs = {"launch": (lambda: ops.ray_distortion(w, z, rays), a.inner_launch), "loss": (loss, a.inner_launch),
+            "step": (train(0.0), a.inner), "step_dist": (train(a.lam), a.inner)}
+    ms = {k: [] for k in legs}
+    for rep in range(a.warmup + a.reps):
+        order = list(legs.items())
+        for k, (fn, inner) in (order if rep % 2 == 0 else order[::-1]):      # no leg always follows the same neighbour
+            v = window_ms(fn, inner)
+            if rep >= a.warmup:
+                ms[k].append(v)
+    legs["step_dist"][0]()                                                    # the log of a step with the term
+    result = {"rays": N, "samples": S, "lambda_dist": a.lam, "reps": a.reps, "inner": a.inner, "inner_launch": a.inner_launch,
+              "acc_words": words, "mean_L_r": words[0] * 2.0 ** -40 / max(words[1], 1), "terms_logged": sorted(
+                  k for k in pipe.logged if k.startswith("train/coarse_"))}
+    for k, v in ms.items():
+        result[f"{k}_ms"] = round(statistics.median(v), 4)
+        result[f"{k}_ms_min_max"] = [round(min(v), 4), round(max(v), 4)]
+    result["step_dist_minus_step_ms"] = round(statistics.median(ms["step_dist"]) - statistics.median(ms["step"]), 4)
+    print(json.dumps(result))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
