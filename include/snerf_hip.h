@@ -664,6 +664,67 @@ int snerf_shadow_cast(const float* dsm, int h, int w, const double* suns_host, i
 int snerf_shadow_agreement(const float* sun, const unsigned char* lit, const unsigned char* valid, long long cells, int n_suns,
                            double threshold, unsigned long long* acc, void* stream);
 
+/* ---- per-ray kernels outside the render pass: importance resampling of the depths and the distortion
+ * loss on a ray's weights (section 5r).  One wave per ray; both are exact (fp64 operations rounded one by one, integer sums) and
+ * have a numpy restatement under tests/. ------------------------------------------------------------------------------------- */
+/* Importance resampling of the depths (sample_pdf, framework/components/rendering.py:8-51, and the sort of the merged depths its
+ * callers do): n_importance fine samples per ray, drawn from the pdf that a proposal pass's weights (N,S) define over the S - 1
+ * midpoints of the coarse depths z (N,S; fp32, non-decreasing along a ray, no NaN), merged with z into z_out (N, S + Ni).  NeRF's
+ * convention: the bins are the interval midpoints, the pdf is over the S - 2 interior weights.  u (N,Ni) are the uniforms; NULL is
+ * the reference's det=True.  z_fine (N,Ni), optional, receives the fine samples alone, in u's order.
+ *
+ * The arithmetic, per ray -- fp64, every operation rounded on its own (no fused multiply-add), sums in exact integers, so the
+ * result has no summation order and tests/resample_numpy.py reproduces every bit:
+ *   1. b[j] = 0.5 * ((double)z[j] + (double)z[j+1]),  j = 0 .. S-2
+ *   2. w' = w where w is finite and > 0, else 0; w' = min(w', 1);  m[j] = llrint((w'[j+1] + 1e-5) * 2^50) as int64,  j = 0 .. S-3
+ *      (the reference's eps = 1e-5; 2^50 keeps every prefix of real weights, sum <= 1, exactly representable in a double)
+ *   3. P[0] = 0, P[j+1] = P[j] + m[j] in int64;  T = P[S-2]
+ *   4. u_i = (double)u[n][i] where that is > 0, else +0 (NaN included), at most 1;  with u == NULL: u_i = (double)i / (double)(Ni-1),
+ *      and 0 when Ni = 1
+ *   5. t = u_i * (double)T;  k = the largest j in [0, S-3] with (double)P[j] <= t  (t == T lands in the last bin)
+ *   6. f = (t - (double)P[k]) / (double)m[k];  fine_i = (float)(b[k] + f * (b[k+1] - b[k]))
+ *   7. z_out = concatenate([z, fine]) reordered by numpy's STABLE argsort of its values: among equal values (+0 and -0 are equal)
+ *      coarse before fine, then index order.
+ * Every mass is at least 1e-5 * 2^50: no zero denominator and no special case.  This is the one deliberate difference from the
+ * reference, which sets a denominator below eps to 1 and so pins a sample that falls into a near-empty bin to the bin's left edge;
+ * here it is interpolated.  Both stay inside the same bin.
+ * One launch on `stream`; no allocation, no copy, no host synchronisation.  Refused on the host before any launch: a NULL z,
+ * weights or z_out (SNERF_ERR_NULL); n_rays < 1, n_samples < 3, n_importance < 1, n_samples + n_importance > SNERF_VIS_MAX_SAMPLES
+ * (SNERF_ERR_BAD_DESC; the limit SNERF_VIS_MAX_SAMPLES of snerf_hip.h already puts on a ray). */
+int snerf_resample_z(const float* z, const float* weights, const float* u, float* z_out, float* z_fine, int n_rays, int n_samples,
+                     int n_importance, void* stream);
+
+/* The distortion regulariser of mip-NeRF 360 on the weights (N,S) a pass composited along the depths z_vals (N,S):
+ *     L = sum_i sum_j w_i w_j |m_i - m_j| + 1/3 sum_i w_i^2 delta_i
+ * over the normalised interval midpoints m and widths delta of a ray, as the per-ray value L_r and d L_r / d weights, in O(S) per
+ * ray.  The depths carry no gradient.  `rays` (N, ray_stride) gives a ray's bounds: near = column 6, far = column 7.
+ *
+ * The arithmetic, per ray -- fp64, every operation rounded on its own (no fused multiply-add), every sum over exact int64
+ * integers, so no result depends on how a scan is spread over lanes and tests/raydist_numpy.py reproduces every bit.  Q = 2^50.
+ *   1. t_i = ((double)z_i - near) / (far - near);  delta_i = t_{i+1} - t_i for i < S-1, delta_{S-1} = 0;  m_i = t_i + 0.5 * delta_i
+ *   2. w'_i = min(max((double)w_i, 0), 1), a zero of either sign giving +0;  a_i = llrint(w'_i * Q);  b_i = llrint((w'_i * m_i) * Q)
+ *   3. exclusive prefixes in int64: A_i = sum_{j<i} a_j, B_i = sum_{j<i} b_j; the totals A_T, B_T;  Abar = (double)A / Q, Bbar alike
+ *   4. e_i = 2 * (w'_i * (m_i * Abar_i - Bbar_i)) + ((w'_i * w'_i) * delta_i) / 3;  q_i = llrint(e_i * Q);
+ *      L_int = sum_i q_i (int64, two's complement);  L_r = (double)L_int / Q
+ *   5. g_k = 2 * ((m_k * Abar_k - Bbar_k) + (Bbar'_k - m_k * Abar'_k)) + ((2/3) * w'_k) * delta_k, where
+ *      Abar'_k = (double)(A_T - A_k - a_k) / Q and Bbar'_k alike (the mass behind sample k), 2/3 the double 2.0 / 3.0;
+ *      d_weights[k] = (float)g_k; +0 where w_k < 0 or w_k > 1 (the clamp's derivative); an exact w_k = 0 keeps the formula
+ *   6. a ray is BAD when some w_i or z_i is not finite, z_{i+1} < z_i somewhere, near or far is not finite, !(far > near), or some
+ *      t_i lies outside [-1, 2].  A bad ray has a d_weights row of +0, a per-ray value of NaN (0x7ff8000000000000) and adds
+ *      nothing to the sum.
+ *   7. acc: 4 u64 words which the CALLER zeroes, accumulated with integer atomics (calls into one acc add up: the words of a batch
+ *      cut into shards equal the whole batch's):
+ *        [0] += llrint(L_r * 2^40) over the good rays (int64, two's complement)   [1] += rays of the call   [2] += bad rays
+ *        [3] reserved, not written
+ * With real weights (sum <= 1, t in [0, 1]) L_r <= 4/3, so word 0 cannot wrap below about 6e6 rays per accumulator.  The bounds
+ * on t keep every integer of one ray within int64 for any weights: |b_i| <= 2 Q, |q_i| < 2^13 Q, |A|, |B| <= 2^11 Q.
+ * d_weights (N,S) and per_ray (N, optional) are pure outputs: every element is written.
+ * One launch on `stream`; no allocation, no copy, no host synchronisation.  Refused on the host before any launch: a NULL weights,
+ * z_vals, rays, d_weights or acc (SNERF_ERR_NULL); n_rays < 1 or > 2^22, n_samples < 1 or > SNERF_VIS_MAX_SAMPLES, ray_stride < 8
+ * (SNERF_ERR_BAD_DESC). */
+int snerf_ray_distortion(const float* weights, const float* z_vals, const float* rays, int ray_stride, int n_rays, int n_samples,
+                         float* d_weights, double* per_ray, unsigned long long* acc, void* stream);
+
 /* ---- measurement hook ----------------------------------------------------------------------------
  * Between snerf_profile_begin and snerf_profile_end every GEMM launch is bracketed by HIP events on the
  * stream it is launched on; _end synchronises those events and returns, per kernel variant, the summed

@@ -217,6 +217,8 @@ def _signatures():
         # suns_host is a HOST table (a ctypes array): void*, as the RPC tables
         "snerf_shadow_cast": (i, (p, i, i, p, i, d, d, p, p, st)),
         "snerf_shadow_agreement": (i, (p, p, p, ll, i, d, p, st)),
+        "snerf_resample_z": (i, (p,) * 5 + (i,) * 3 + (st,)),
+        "snerf_ray_distortion": (i, (p,) * 3 + (i,) * 3 + (p,) * 3 + (st,)),
         "snerf_profile_begin": (i, ()),
         "snerf_profile_end": (i, (P(SnerfProfile),)),
         "snerf_test_set_kc_grid": (i, (i,)),
@@ -232,20 +234,6 @@ def _signatures():
 SIGNATURES = _signatures()
 EXPORTED_SYMBOLS = tuple(SIGNATURES)
 
-# Entries declared OUTSIDE include/snerf_hip.h, whose list of symbols is frozen at ABI 6: header -> rows in that header's order
-# (tests/test_resample_cpu.py and tests/test_raydist_cpu.py compare them with their headers as tests/test_abi_cpu.py does for the
-# table above).  lib() and call()
-# serve both tables alike.
-EXTENSION_SIGNATURES = {
-    "snerf_resample.h": {"snerf_resample_z": (C.c_int, (C.c_void_p,) * 5 + (C.c_int,) * 3 + (c_stream,))},
-    "snerf_raydist.h": {"snerf_ray_distortion": (C.c_int, (C.c_void_p,) * 3 + (C.c_int,) * 3 + (C.c_void_p,) * 3 + (c_stream,))},
-}
-_ALL_SIGNATURES = dict(SIGNATURES)
-for _rows in EXTENSION_SIGNATURES.values():
-    assert not set(_rows) & set(_ALL_SIGNATURES)
-    _ALL_SIGNATURES.update(_rows)
-
-
 SHADOW_MAX_SUNS = 64       # include/snerf_hip.h SNERF_SHADOW_MAX_SUNS
 SHADOW_UNKNOWN = 255       # include/snerf_hip.h SNERF_SHADOW_UNKNOWN
 
@@ -257,8 +245,8 @@ ORTHO_NO_LABEL = 255       # include/snerf_hip.h SNERF_ORTHO_NO_LABEL
 # stream follows them)
 _PLANS = {name: (tuple(float if t in (C.c_float, C.c_double) else None if issubclass(t, (C.c_void_p, C._Pointer)) else int
                        for t in args if t is not c_stream), c_stream in args)
-          for name, (_, args) in _ALL_SIGNATURES.items()}
-assert all(c_stream not in args[:-1] for _, args in _ALL_SIGNATURES.values())
+          for name, (_, args) in SIGNATURES.items()}
+assert all(c_stream not in args[:-1] for _, args in SIGNATURES.values())
 
 _lib = None
 
@@ -277,7 +265,7 @@ def lib():
     # owns torch's device context and streams (loading ours first brings up a second runtime that then
     # reports "no ROCm-capable device").
     L = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in _ALL_SIGNATURES.items():
+    for name, (restype, argtypes) in SIGNATURES.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, list(argtypes)
     if L.snerf_version() != ABI_VERSION:

@@ -43,7 +43,7 @@ class NeRFConfig(BaseModel):
     @model_validator(mode="after")
     def _check_n_importance(self):
         """n_importance fine samples per ray are merged with the n_samples coarse ones (ops.resample_z): the pdf is over the
-        interior weights, and a ray holds at most 1024 samples (include/snerf_resample.h: snerf_resample_z)"""
+        interior weights, and a ray holds at most 1024 samples (include/snerf_hip.h: snerf_resample_z)"""
         if self.n_importance < 0:
             raise ValueError(f"n_importance must be >= 0, got {self.n_importance}")
         if self.n_importance > 0:

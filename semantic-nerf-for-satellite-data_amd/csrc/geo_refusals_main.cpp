@@ -1,35 +1,10 @@
-// Stand-alone host program over the refusal paths of snerf_geo_cloud / snerf_geo_points (geo.hip geo_launch): every call below is
-// refused by the argument checks, so no kernel launch is reached and no GPU is needed.  Built with ASAN + UBSAN on the host code
-// (`make geo-refusals`); exits 0 when every call came back with the expected code and message.  CPU machines only.
-#include "../../include/snerf_hip.h"
+// The refusal paths of snerf_geo_cloud / snerf_geo_points (geo.hip geo_launch): see refusals_main.h.
+#include "refusals_main.h"
 
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
-
-static char g_error[512];
-
-namespace snerf {
-// the library's set_error (api.hip), which this program does not link
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_error, sizeof g_error, fmt, ap);
-  va_end(ap);
-}
-}  // namespace snerf
-
-static int failures = 0;
-
-static void expect(const char* what, int rc, int want, const char* needle) {
-  const bool ok = rc == want && (needle == nullptr || strstr(g_error, needle) != nullptr);
-  printf("%-52s rc = %d  \"%s\"%s\n", what, rc, g_error, ok ? "" : "   <-- UNEXPECTED");
-  if (!ok) ++failures;
-  g_error[0] = 0;
-}
+static void expect(const char* what, int rc, int want, const char* needle) { expect(what, rc, want, needle, nullptr); }
 
 int main() {
+  what_width = 52;
   // never dereferenced: every call is refused before a launch
   static double points[24], out[24], lla[24];
   static float rays[64], depth[8];
@@ -85,6 +60,5 @@ int main() {
   const unsigned long long init[8] = {~0ull, 0, ~0ull, 0, 0, 0, 0, 0};
   if (memcmp(stats, init, sizeof init) != 0) { printf("stats were written\n"); ++failures; }
   for (int k = 0; k < 24; ++k) if (out[k] != 0.0 || lla[k] != 0.0) { printf("outputs were written\n"); ++failures; break; }
-  printf("%s\n", failures ? "geo refusals: FAILED" : "geo refusals: ok");
-  return failures ? 1 : 0;
+  return verdict("geo");
 }

@@ -1,27 +1,24 @@
 // The distortion loss on a ray's weights (mip-NeRF 360's regulariser), value and d / d weights in one launch and O(S) per ray.
-// The spec is stated at snerf_ray_distortion in include/snerf_raydist.h and in DESIGN.md section 5r; tests/raydist_numpy.py
+// The spec is stated at snerf_ray_distortion in include/snerf_hip.h and in DESIGN.md section 5r; tests/raydist_numpy.py
 // restates it operation for operation.
 //   - every floating-point operation is fp64 and rounded on its own (no fused multiply-adds in this file: plain operators under
 //     `fp contract(off)`, see the note in shadow.hip), and every sum is over int64 masses: the result has no summation order, so
 //     it does not depend on how the scan is spread over the lanes and equals numpy's bit for bit;
-//   - one wave64 per ray, up to four rays per workgroup; a ray's midpoints m and the exclusive prefixes A, B of its masses live in
+//   - one wave64 per ray, up to four rays per workgroup (ray_wave.h); a ray's midpoints m and the exclusive prefixes A, B of its masses live in
 //     LDS (24 S bytes, 24 KB at the 1024-sample limit; the host lowers the rays per workgroup so that a workgroup stays within
 //     64 KB);
-//   - the scan: a lane sums a run of consecutive masses, the run totals are scanned across the wave with shuffles, the lane
-//     writes its run's prefixes (resample.hip's scan, for two sequences at once);
+//   - the scan: a lane sums a run of consecutive masses, the run totals are scanned across the wave (wave_scan_i64, once per sequence),
+//     the lane writes its run's prefixes;
 //   - wave barriers only: a ragged last workgroup retires its idle waves at once;
 //   - a ray's integer sums are reduced in the wave and lane 0 adds them to the caller's accumulator words with integer atomics;
 //   - vector loads and stores only, one launch, no allocation, no copy and no host synchronisation.
-#include "common.h"
-#include "../../include/snerf_raydist.h"
+#include "ray_wave.h"
+#include "../../include/snerf_hip.h"
 
 #pragma clang fp contract(off)
 
 namespace snerf {
 
-constexpr int RAYDIST_WAVE = 64;
-constexpr int RAYDIST_MAX_RAYS_PER_BLOCK = 4;
-constexpr size_t RAYDIST_MAX_LDS = 65536;
 constexpr int RAYDIST_MAX_RAYS = 1 << 22;
 constexpr double RAYDIST_Q = 1125899906842624.0;           // 2^50
 constexpr double RAYDIST_ACC_SCALE = 1099511627776.0;      // 2^40
@@ -35,19 +32,12 @@ __device__ __forceinline__ double raydist_clamp(float w) {
   return wd > 0.0 ? (wd > 1.0 ? 1.0 : wd) : 0.0;
 }
 
-__device__ __forceinline__ void raydist_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__global__ __launch_bounds__(RAYDIST_WAVE * RAYDIST_MAX_RAYS_PER_BLOCK) void ray_distortion_kernel(
+__global__ __launch_bounds__(RAY_WAVE * RAY_WAVE_MAX_RAYS_PER_BLOCK) void ray_distortion_kernel(
     const float* __restrict__ weights, const float* __restrict__ z_vals, const float* __restrict__ rays, int ray_stride, int n_rays,
     int S, float* __restrict__ d_weights, double* __restrict__ per_ray, unsigned long long* __restrict__ acc, int ray_bytes) {
   extern __shared__ __attribute__((aligned(16))) unsigned char raydist_lds[];
-  const int lane = threadIdx.x & (RAYDIST_WAVE - 1), wave = threadIdx.x / RAYDIST_WAVE;
-  const long long ray = (long long)blockIdx.x * (blockDim.x / RAYDIST_WAVE) + wave;
-  if (ray >= n_rays) return;                                   // wave-uniform; the kernel has no workgroup barrier
+  const auto [lane, wave, ray] = ray_wave_id();
+  if (ray >= n_rays) return;                                   // wave-uniform: see ray_wave.h
   double* m = reinterpret_cast<double*>(raydist_lds + (size_t)wave * ray_bytes);       // [S] midpoints
   long long* A = reinterpret_cast<long long*>(m + S);                                  // [S] exclusive prefixes of a
   long long* B = A + S;                                                                // [S] exclusive prefixes of b
@@ -59,7 +49,7 @@ __global__ __launch_bounds__(RAYDIST_WAVE * RAYDIST_MAX_RAYS_PER_BLOCK) void ray
 
   // 1. / 6. the midpoints, and whether the ray is bad
   bool bad = !(__builtin_isfinite(near_f) && __builtin_isfinite(far_f) && far_f > near_f);
-  for (int i = lane; i < S; i += RAYDIST_WAVE) {
+  for (int i = lane; i < S; i += RAY_WAVE) {
     const float w = wr[i], z0 = zr[i];
     const double t0 = ((double)z0 - near) / span;
     double delta = 0.0;
@@ -73,7 +63,7 @@ __global__ __launch_bounds__(RAYDIST_WAVE * RAYDIST_MAX_RAYS_PER_BLOCK) void ray
     m[i] = t0 + half;
   }
   if (__builtin_amdgcn_ballot_w64(bad) != 0ull) {               // wave-uniform from here on
-    for (int i = lane; i < S; i += RAYDIST_WAVE) gr[i] = 0.f;
+    for (int i = lane; i < S; i += RAY_WAVE) gr[i] = 0.f;
     if (lane == 0) {
       if (per_ray) per_ray[ray] = __builtin_nan("");
       atomicAdd(&acc[1], 1ull);
@@ -81,10 +71,10 @@ __global__ __launch_bounds__(RAYDIST_WAVE * RAYDIST_MAX_RAYS_PER_BLOCK) void ray
     }
     return;
   }
-  raydist_wave_sync();
+  ray_wave_sync();
 
   // 2. / 3. the masses and their exclusive prefixes: lane l owns the samples [l * per, l * per + per)
-  const int per = (S + RAYDIST_WAVE - 1) / RAYDIST_WAVE, j0 = lane * per;
+  const int per = (S + RAY_WAVE - 1) / RAY_WAVE, j0 = lane * per;
   long long run_a = 0, run_b = 0;
   for (int j = j0; j < j0 + per && j < S; ++j) {
     const double wc = raydist_clamp(wr[j]);
@@ -92,14 +82,8 @@ __global__ __launch_bounds__(RAYDIST_WAVE * RAYDIST_MAX_RAYS_PER_BLOCK) void ray
     run_a += llrint(wc * RAYDIST_Q);
     run_b += llrint(wm * RAYDIST_Q);
   }
-  long long incl_a = run_a, incl_b = run_b;
-#pragma unroll
-  for (int o = 1; o < RAYDIST_WAVE; o <<= 1) {
-    const long long up_a = __shfl_up(incl_a, o, RAYDIST_WAVE), up_b = __shfl_up(incl_b, o, RAYDIST_WAVE);
-    if (lane >= o) { incl_a += up_a; incl_b += up_b; }
-  }
-  const long long AT = __shfl(incl_a, RAYDIST_WAVE - 1, RAYDIST_WAVE), BT = __shfl(incl_b, RAYDIST_WAVE - 1, RAYDIST_WAVE);
-  long long pa = incl_a - run_a, pb = incl_b - run_b;           // the masses before this lane's run
+  long long AT, BT;
+  long long pa = wave_scan_i64(run_a, lane, &AT), pb = wave_scan_i64(run_b, lane, &BT);     // the masses before this lane's run
   for (int j = j0; j < j0 + per && j < S; ++j) {
     const double wc = raydist_clamp(wr[j]);
     const double wm = wc * m[j];
@@ -108,11 +92,11 @@ __global__ __launch_bounds__(RAYDIST_WAVE * RAYDIST_MAX_RAYS_PER_BLOCK) void ray
     pa += llrint(wc * RAYDIST_Q);
     pb += llrint(wm * RAYDIST_Q);
   }
-  raydist_wave_sync();
+  ray_wave_sync();
 
   // 4. / 5. the per-sample terms and the gradient
   unsigned long long qsum = 0ull;                               // two's complement: the sum of the spec's int64 q
-  for (int i = lane; i < S; i += RAYDIST_WAVE) {
+  for (int i = lane; i < S; i += RAY_WAVE) {
     const float w = wr[i];
     const double wc = raydist_clamp(w);
     const double mi = m[i];
@@ -144,7 +128,7 @@ __global__ __launch_bounds__(RAYDIST_WAVE * RAYDIST_MAX_RAYS_PER_BLOCK) void ray
     gr[i] = (w < 0.f || w > 1.f) ? 0.f : (float)g;
   }
 #pragma unroll
-  for (int o = RAYDIST_WAVE / 2; o > 0; o >>= 1) qsum += __shfl_xor(qsum, o, RAYDIST_WAVE);
+  for (int o = RAY_WAVE / 2; o > 0; o >>= 1) qsum += __shfl_xor(qsum, o, RAY_WAVE);
   if (lane == 0) {
     const double Lr = (double)(long long)qsum / RAYDIST_Q;
     if (per_ray) per_ray[ray] = Lr;
@@ -177,11 +161,9 @@ extern "C" int snerf_ray_distortion(const float* weights, const float* z_vals, c
     return SNERF_ERR_BAD_DESC;
   }
   const size_t ray_bytes = raydist_ray_bytes(n_samples);                         // <= 24 KB: at least 2 rays fit
-  size_t rays_per_block = RAYDIST_MAX_LDS / ray_bytes;
-  if (rays_per_block > (size_t)RAYDIST_MAX_RAYS_PER_BLOCK) rays_per_block = RAYDIST_MAX_RAYS_PER_BLOCK;
-  const unsigned blocks = (unsigned)(((long long)n_rays + (long long)rays_per_block - 1) / (long long)rays_per_block);
-  hipLaunchKernelGGL(ray_distortion_kernel, dim3(blocks), dim3((unsigned)(RAYDIST_WAVE * rays_per_block)), rays_per_block * ray_bytes,
-                     (hipStream_t)stream, weights, z_vals, rays, ray_stride, n_rays, n_samples, d_weights, per_ray, acc, (int)ray_bytes);
+  const RayWaveLaunch l = ray_wave_launch(n_rays, ray_bytes);
+  hipLaunchKernelGGL(ray_distortion_kernel, l.grid, l.block, l.lds_bytes, (hipStream_t)stream,
+                     weights, z_vals, rays, ray_stride, n_rays, n_samples, d_weights, per_ray, acc, (int)ray_bytes);
   SNERF_LAUNCH_CHECK();
   return SNERF_OK;
 }

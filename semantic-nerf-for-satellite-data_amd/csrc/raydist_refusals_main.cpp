@@ -1,32 +1,7 @@
-// Stand-alone host program over the refusal paths of snerf_ray_distortion (raydist.hip): every call below is refused by the argument
-// checks, so no kernel launch is reached and no GPU is needed.  Built with ASAN + UBSAN on the host code
-// (`make raydist-refusals`); exits 0 when every call came back with the expected code and message.  CPU machines only.
-#include "../../include/snerf_raydist.h"
+// The refusal paths of snerf_ray_distortion (raydist.hip): see refusals_main.h.
+#include "refusals_main.h"
 
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
-
-static char g_error[512];
-
-namespace snerf {
-// the library's set_error (api.hip), which this program does not link
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_error, sizeof g_error, fmt, ap);
-  va_end(ap);
-}
-}  // namespace snerf
-
-static int failures = 0;
-
-static void expect(const char* what, int rc, int want, const char* needle) {
-  const bool ok = rc == want && strstr(g_error, needle) != nullptr && strstr(g_error, "snerf_ray_distortion: ") == g_error;
-  printf("%-44s rc = %d  \"%s\"%s\n", what, rc, g_error, ok ? "" : "   <-- UNEXPECTED");
-  if (!ok) ++failures;
-  g_error[0] = 0;
-}
+static void expect(const char* what, int rc, int want, const char* needle) { expect(what, rc, want, needle, "snerf_ray_distortion: "); }
 
 int main() {
   // never dereferenced as device memory: every call is refused before a launch
@@ -56,6 +31,5 @@ int main() {
   for (int k = 0; k < 12; ++k) if (dw[k] != 0.f) { printf("d_weights was written\n"); ++failures; break; }
   for (int k = 0; k < 2; ++k) if (per_ray[k] != 0.0) { printf("per_ray was written\n"); ++failures; break; }
   for (int k = 0; k < 4; ++k) if (acc[k] != 0ull) { printf("acc was written\n"); ++failures; break; }
-  printf("%s\n", failures ? "raydist refusals: FAILED" : "raydist refusals: ok");
-  return failures ? 1 : 0;
+  return verdict("raydist");
 }

@@ -1,33 +1,7 @@
-// Stand-alone host program over the refusal paths of snerf_shadow_cast / snerf_shadow_agreement (shadow.hip): every call below is
-// refused by the argument checks, so no kernel launch is reached and no GPU is needed.  Built with ASAN + UBSAN on the host code
-// (`make shadow-refusals`); exits 0 when every call came back with the expected code and message.  CPU machines only.
-#include "../../include/snerf_hip.h"
+// The refusal paths of snerf_shadow_cast / snerf_shadow_agreement (shadow.hip): see refusals_main.h.
+#include "refusals_main.h"
 
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
-
-static char g_error[512];
-
-namespace snerf {
-// the library's set_error (api.hip), which this program does not link
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_error, sizeof g_error, fmt, ap);
-  va_end(ap);
-}
-}  // namespace snerf
-
-static int failures = 0;
-
-static void expect(const char* what, int rc, int want, const char* needle) {
-  const bool ok = rc == want && strstr(g_error, needle) != nullptr;
-  printf("%-44s rc = %d  \"%s\"%s\n", what, rc, g_error, ok ? "" : "   <-- UNEXPECTED");
-  if (!ok) ++failures;
-  g_error[0] = 0;
-}
+static void expect(const char* what, int rc, int want, const char* needle) { expect(what, rc, want, needle, nullptr); }
 
 int main() {
   // never dereferenced as device memory: every call is refused before a launch
@@ -82,6 +56,5 @@ int main() {
 
   for (int k = 0; k < 8; ++k) if (acc[k]) { printf("acc was written\n"); ++failures; break; }
   for (int k = 0; k < 12; ++k) if (lit[k] || dist[k] != 0.f) { printf("outputs were written\n"); ++failures; break; }
-  printf("%s\n", failures ? "shadow refusals: FAILED" : "shadow refusals: ok");
-  return failures ? 1 : 0;
+  return verdict("shadow");
 }

@@ -191,7 +191,7 @@ def run_plans(plans, results, typ: str = "coarse", sync: bool = True):
 
 
 # ---- the distortion loss on the ray weights ---------------------------------------------------------------------------------------
-# mip-NeRF 360's regulariser on a pass's weights (include/snerf_raydist.h): one launch gives every ray's value
+# mip-NeRF 360's regulariser on a pass's weights (include/snerf_hip.h snerf_ray_distortion): one launch gives every ray's value
 # summed into integer words and d / d weights; the mean over the batch's rays and the weight `lam` are applied on the device.
 class _DistortionLoss(torch.autograd.Function):
     @staticmethod
@@ -222,7 +222,7 @@ def distortion_loss(weights, z_vals, rays, lam: float, sync: bool = True):
     """lam * mean over the batch's rays of the distortion loss of `weights` (N, S) along `z_vals` (N, S) on `rays` (near, far in
     columns 6 and 7): one launch, under data parallelism one all-reduce of four integer words, no host synchronisation.  Returns
     (total, term) like fused_loss's (total, terms): `total` is differentiable w.r.t. `weights` (the depths carry no gradient),
-    `term` is the same value, detached, for the loss dict ('coarse_distortion').  Bad rays (include/snerf_raydist.h) add nothing and count
+    `term` is the same value, detached, for the loss dict ('coarse_distortion').  Bad rays (include/snerf_hip.h) add nothing and count
     in the mean's denominator."""
     total = _DistortionLoss.apply(float(lam), sync, z_vals, rays, weights)
     return total, total.detach()

@@ -698,7 +698,7 @@ def resample_z(z: torch.Tensor, weights: torch.Tensor, n_importance: int, u: tor
 
 
 def ray_distortion(weights: torch.Tensor, z_vals: torch.Tensor, rays: torch.Tensor, per_ray: bool = False, acc: torch.Tensor | None = None):
-    """the distortion loss on a pass's weights -- snerf_ray_distortion (include/snerf_raydist.h): for
+    """the distortion loss on a pass's weights -- snerf_ray_distortion (include/snerf_hip.h): for
     `weights` (N, S) composited along `z_vals` (N, S) on `rays` (N, >= 8; near and far are columns 6 and 7) ->
     (d_weights_unit, acc[, per_ray]): d L_r / d weights (N, S) of every ray's own value, unscaled; `acc`, four int64 words
     (the library's u64 words: [0] the sum of the rays' values in units of 2^-40, [1] the rays, [2] the bad rays, [3] unused);

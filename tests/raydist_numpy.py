@@ -1,4 +1,4 @@
-"""numpy restatement of snerf_ray_distortion (include/snerf_raydist.h), operation for operation: the oracle of
+"""numpy restatement of snerf_ray_distortion (include/snerf_hip.h), operation for operation: the oracle of
 tests/test_gpu_raydist.py and the object tests/test_raydist_cpu.py compares with the O(S^2) definition of the distortion loss.
 
 Every operation is fp64 and rounded on its own (numpy never contracts) and every sum is over int64 integers -- so the result has no

@@ -1,4 +1,4 @@
-"""numpy restatement of snerf_resample_z (include/snerf_resample.h), operation for operation: the oracle of
+"""numpy restatement of snerf_resample_z (include/snerf_hip.h), operation for operation: the oracle of
 tests/test_gpu_resample.py and the object tests/test_resample_cpu.py compares with the reference's sample_pdf.
 
 Every operation is fp64 and rounded on its own (numpy never contracts), the cdf is a prefix sum of int64 masses, and the merge

@@ -75,7 +75,7 @@ def test_binding_table_matches_header_prototypes():
     for every name _declared_symbols() finds; the rows stand in the header's order."""
     from snerf_amd import _lib
     protos = _header_prototypes()
-    assert sorted(protos) == _declared_symbols() == sorted(_lib.SIGNATURES) and len(protos) >= 51
+    assert sorted(protos) == _declared_symbols() == sorted(_lib.SIGNATURES) and len(protos) >= 53
     assert list(_lib.SIGNATURES) == list(protos)                    # the header's declaration order, for the whole table
     for name, (ret, params) in protos.items():
         restype, argtypes = _lib.SIGNATURES[name]

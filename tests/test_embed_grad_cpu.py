@@ -12,13 +12,15 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-# every symbol include/snerf_hip.h declares at ABI 6: those from before the flag (the flag adds none) and the two cast-shadow entries
+# every symbol include/snerf_hip.h declares at ABI 6: those from before the flag (the flag adds none), the two cast-shadow entries,
+# and the two per-ray entries snerf_resample_z and snerf_ray_distortion, whose declarations moved here from headers of their own
+# (the library exported them already: the version did not move)
 ABI6_SYMBOLS = """snerf_adam_step snerf_backward snerf_dsm_accumulate snerf_dsm_downsample2x snerf_dsm_finish
 snerf_dsm_ncc_search snerf_dsm_shift_diff snerf_dsm_workspace_bytes snerf_embedding_backward snerf_embedding_rows
 snerf_forward snerf_geo_cloud snerf_geo_points snerf_grad_floats snerf_last_error snerf_loss_finish snerf_loss_partial
 snerf_loss_workspace_bytes snerf_normalize_rows snerf_ortho_gather snerf_ortho_top snerf_ortho_votes
 snerf_ortho_votes_finish snerf_pack_params snerf_packed_floats snerf_profile_begin snerf_profile_end snerf_ray_bounds
-snerf_ray_bounds_workspace_bytes snerf_rpc_localize snerf_rpc_project snerf_rpc_rays snerf_rpc_reprojection_error
+snerf_ray_bounds_workspace_bytes snerf_ray_distortion snerf_resample_z snerf_rpc_localize snerf_rpc_project snerf_rpc_rays snerf_rpc_reprojection_error
 snerf_sample_z snerf_semeval_accumulate snerf_semeval_workspace_bytes snerf_shadow_agreement snerf_shadow_cast
 snerf_ssim snerf_ssim_workspace_bytes snerf_test_bsp_dw snerf_test_bsp_kc snerf_test_bsp_roundtrip
 snerf_test_set_kc_grid snerf_test_set_trunk_fusion snerf_unpack_grads snerf_version snerf_vis_colormap snerf_vis_fold
@@ -43,7 +45,7 @@ def test_abi_version_and_symbols_unchanged():
     assert _lib.lib().snerf_version() == _lib.ABI_VERSION == 6
     src = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
     declared = sorted(set(re.findall(r"\b(snerf_[a-z_0-9]+)\s*\(", src)))
-    assert declared == sorted(ABI6_SYMBOLS) and len(declared) == 51
+    assert declared == sorted(ABI6_SYMBOLS) and len(declared) == 53
     assert C.sizeof(_lib.SnerfDesc) == 16 * 4
 
 

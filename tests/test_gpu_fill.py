@@ -87,6 +87,10 @@ POINTERS = {
     # the fill test of these two is tests/test_gpu_shadow.py test_no_output_depends_on_bytes_the_library_did_not_write
     "snerf_shadow_cast": {"dsm": "in", "suns_host": "in", "lit_out": "out", "dist_out": "out"},
     "snerf_shadow_agreement": {"sun": "in", "lit": "in", "valid": "in", "acc": "acc"},
+    # the fill tests of these two are test_no_output_depends_on_bytes_the_library_did_not_write of tests/test_gpu_resample.py and
+    # of tests/test_gpu_raydist.py
+    "snerf_resample_z": {"z": "in", "weights": "in", "u": "in", "z_out": "out", "z_fine": "out"},
+    "snerf_ray_distortion": {"weights": "in", "z_vals": "in", "rays": "in", "d_weights": "out", "per_ray": "out", "acc": "acc"},
 }
 # entries with no device pointer to classify: sizes, version, error text; and the hooks the issue excepts
 _NO_POINTERS = ("snerf_version", "snerf_last_error", "snerf_packed_floats", "snerf_grad_floats", "snerf_workspace_bytes",

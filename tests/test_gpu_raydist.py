@@ -17,7 +17,7 @@ from tests.test_raydist_cpu import FAR, NEAR, composited, make_depths, make_rays
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
-SHAPES = [(1, 1), (5, 2), (77, 7), (130, 64), (33, 65), (9, 130), (2, 1024), (4096, 64)]
+SHAPES = [(1, 1), (5, 2), (77, 7), (130, 64), (33, 65), (9, 130), (2, 1024), (4, 700), (3, 1024), (4096, 64)]
 KINDS = 13
 
 

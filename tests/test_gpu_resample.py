@@ -14,7 +14,7 @@ from tests import resample_numpy as RN
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
-SHAPES = [(1, 3, 1), (5, 3, 7), (77, 7, 5), (130, 64, 64), (33, 65, 63), (9, 130, 200), (2, 512, 512)]
+SHAPES = [(1, 3, 1), (5, 3, 7), (77, 7, 5), (130, 64, 64), (33, 65, 63), (9, 130, 200), (2, 512, 512), (5, 1021, 3)]
 FAMILIES = 6
 
 

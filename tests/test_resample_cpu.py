@@ -1,4 +1,4 @@
-"""CPU-side checks of the depth resampling (include/snerf_resample.h snerf_resample_z, csrc/resample.hip, ops.resample_z; DESIGN.md
+"""CPU-side checks of the depth resampling (include/snerf_hip.h snerf_resample_z, csrc/resample.hip, ops.resample_z; DESIGN.md
 section 5p): the numpy restatement (tests/resample_numpy.py, the oracle of tests/test_gpu_resample.py) against the reference's
 own sample_pdf (tests/golden/resample_*.npz, recorded by tools/gen_golden_resample.py), the properties of the restatement, and
 every refusal -- of the entry point through the binding, of ops.resample_z, of the config and of fit_image_embedding.  No GPU.
@@ -184,36 +184,16 @@ def test_the_limit_is_the_visualisers_limit_on_a_ray():
     assert _lib.VIS_MAX_SAMPLES == RN.MAX_SAMPLES == 1024
 
 
-def test_extension_header_matches_its_binding_rows():
-    """include/snerf_hip.h is the frozen ABI-6 list of entry points (tests/test_embed_grad_cpu.py pins it), so the entry is declared
-    in include/snerf_resample.h and bound by _lib.EXTENSION_SIGNATURES: the same comparison tests/test_abi_cpu.py makes for the
-    main header and _lib.SIGNATURES -- every prototype of the header has a row and the reverse, in the header's order; return type,
-    parameter count and, per parameter, class, width and signedness; the stream marker exactly where the parameter is called
-    `stream`; the library exports the symbol and lib() / call() know it.  The main table and the ABI version are untouched."""
-    import re
+def test_entry_is_in_the_one_header_and_table():
+    """snerf_resample_z is declared in include/snerf_hip.h and bound by a row of _lib.SIGNATURES like every other entry, so
+    tests/test_abi_cpu.py compares the two type by type.  What that test does not pin: the parameter names (the keys of the pointer
+    roles in tests/test_gpu_fill.py and the words of the refusal messages), and that the entry came at ABI version 6."""
     from snerf_amd import _lib
-    from tests.test_abi_cpu import _c_type, _table_type
-    src = open(os.path.join(ROOT, "include", "snerf_resample.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    src = re.sub(r"^\s*#.*$", "", src, flags=re.M)
-    protos = {}
-    for ret, name, params in re.findall(r"([\w \*]+?)\b(snerf_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", src):
-        protos[name] = (_c_type(ret), [(_c_type(t), n) for t, n in (re.fullmatch(r"\s*(.*?)(\w+)\s*", p).groups() for p in params.split(","))])
-    rows = _lib.EXTENSION_SIGNATURES["snerf_resample.h"]
-    assert list(protos) == list(rows) == ["snerf_resample_z"] == sorted(set(re.findall(r"\b(snerf_[a-z_0-9]+)\s*\(", src)))
-    L = _lib.lib()
-    for name, (ret, params) in protos.items():
-        restype, argtypes = rows[name]
-        assert _table_type(restype) == ret and len(argtypes) == len(params) == 9
-        for k, (t, (want, pname)) in enumerate(zip(argtypes, params)):
-            got = _table_type(t)
-            assert got == want or (want[0] == "pointer" and got == ("pointer", None)), (name, k, pname, t, want)
-            assert (t is _lib.c_stream) == (pname == "stream"), (name, k, pname)
-        assert [n for _, n in params] == ["z", "weights", "u", "z_out", "z_fine", "n_rays", "n_samples", "n_importance", "stream"]
-        assert getattr(L, name).restype is restype and tuple(getattr(L, name).argtypes) == tuple(argtypes)
-        assert name in _lib._PLANS and name not in _lib.SIGNATURES and name not in _lib.EXPORTED_SYMBOLS
-    assert L.snerf_version() == _lib.ABI_VERSION == 6
-    assert "snerf_resample_z" not in open(os.path.join(ROOT, "include", "snerf_hip.h")).read().split("#ifndef SNERF_HIP_H")[1]
+    from tests.test_abi_cpu import _header_prototypes
+    _, params = _header_prototypes()["snerf_resample_z"]
+    assert [n for _, n in params] == ["z", "weights", "u", "z_out", "z_fine", "n_rays", "n_samples", "n_importance", "stream"]
+    assert "snerf_resample_z" in _lib.SIGNATURES and "snerf_resample_z" in _lib._PLANS
+    assert _lib.lib().snerf_version() == _lib.ABI_VERSION == 6
 
 
 def test_ops_resample_z_refusals():

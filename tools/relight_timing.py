@@ -20,18 +20,9 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from tools._timing import window_ms  # noqa: E402
 from oracle import snerf_oracle as O  # noqa: E402
 from snerf_amd import ops  # noqa: E402
-
-
-def window_ms(fn, inner):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(inner):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / inner
 
 
 def main():

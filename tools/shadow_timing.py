@@ -24,6 +24,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from tools._timing import window_ms  # noqa: E402
 from snerf_amd.eval.utils import shadow as S  # noqa: E402
 
 RES = 0.5
@@ -76,16 +77,6 @@ def torch_cast(dsm, rows, bias, z_top):
         lit = torch.where(blocked, torch.zeros_like(lit), lit)
         active = go & ~blocked
     return lit
-
-
-def window_ms(fn, inner):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(inner):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / inner
 
 
 def main():
