@@ -63,6 +63,33 @@ extern "C" {
                                  (SNERF_ERR_BAD_DESC); either arithmetic flag.  snerf_workspace_bytes plans only what the pass writes
                                  (strictly less than the plain inference pass); a larger workspace is accepted.  A workspace a geometry
                                  pass wrote last holds no head tensors: a relight on it is refused */
+#define SNERF_FLAG_DEPTH_MEDIAN  128u /* median depth: snerf_forward runs the pass exactly as without the bit, then ONE further launch on the same
+                                 stream overwrites out->depth (N) with the MEDIAN depth of each ray -- the depth at which half of the ray's
+                                 weight lies in front -- computed from the out->weights and out->z_vals the pass just wrote.  Every other
+                                 result keeps the bits of the pass without the bit.  Per ray, with w_i, z_i the fp32 values in memory
+                                 (i in [0, S)), every operation fp64 and rounded on its own, every sum in int64:
+                                   1. a w_i or z_i that is not finite, or z_{i+1} < z_i for some i: depth = quiet NaN; likewise, where
+                                      out->sigmas is non-NULL, a sigma_i the pass wrote there that is not finite (the composite maps such a
+                                      density -- a ray with a NaN origin or direction -- to zero weights, which alone would read as an empty ray);
+                                   2. wc_i = min(max((double)w_i, 0), 1), a zero of either sign giving +0;  a_i = llrint(wc_i * 2^50);
+                                   3. A_i = sum_{k<i} a_k, AT = sum a_k (<= 2^60);  AT == 0: depth = z_{S-1} (nothing on the ray: the far end);
+                                   4. j = the first index with 2 (A_j + a_j) >= AT;  j == S-1: depth = z_{S-1} (the last interval is the
+                                      reference's open-ended 1e10 one: its mass sits at its near edge);
+                                   5. else frac = (double)(AT - 2 A_j) / (double)(2 a_j), span = (double)z_{j+1} - (double)z_j,
+                                      depth = (float)((double)z_j + frac * span).  A tie gives frac = 1, i.e. z_{j+1}.
+                                 The weight is normalised by the ray's own total (a ray that does not saturate still has a median), and
+                                 each w_j is spread uniformly over [z_j, z_{j+1}], the interval whose opacity produced it
+                                 (framework/util/rendering.py convert_sigmas): the result sits about half an interval deeper than a mean
+                                 that puts w_j at z_j.  The result does not depend on how the sums are spread over the lanes.
+                                 Valid with the plain inference pass, SNERF_FLAG_GEOMETRY, SNERF_FLAG_RELIGHT (the relight's composite
+                                 rewrites weights and depth; the median launch follows it) and either arithmetic flag.  Not with
+                                 SNERF_FLAG_TRAIN, SNERF_FLAG_SC_PASS or SNERF_FLAG_EMBED_GRAD, and n_samples must be in
+                                 [1, SNERF_VIS_MAX_SAMPLES]: SNERF_ERR_BAD_DESC from the plan, hence from the size entries and both hot
+                                 calls, before any pointer is looked at; snerf_backward refuses the bit.  Needs out->depth, out->weights
+                                 and out->z_vals: a NULL one is refused by name (SNERF_ERR_NULL) before any launch.
+                                 snerf_workspace_bytes, snerf_packed_floats and snerf_grad_floats ignore the bit, and so does what a pass
+                                 leaves in its workspace: a relight, with or without the bit, may follow a base pass with or without it.
+                                 No allocation, no copy, no host synchronisation; one extra launch with the bit, none without */
 
 /* Arithmetic of the dense contractions.  With NONE of the arithmetic bits set a pass runs the default, SNERF_FLAG_F16X2
  * (the same for C and Python callers); the two bits exclude each other. */
@@ -204,7 +231,12 @@ int snerf_unpack_grads(const SnerfDesc* desc, const float* packed_grads, const S
  * pass was a training, solar-correction or backward pass; a base pass with another descriptor; out->beta when the base pass was
  * asked for no beta (it may then have skipped the beta block of the first head layer).  The library remembers per workspace
  * ADDRESS which pass it queued last (host side, the 256 addresses noted last): this guards against mis-sequenced calls.  It cannot
- * know that the caller overwrote, freed or reallocated the buffer in between -- keeping the bytes intact is the caller's part. */
+ * know that the caller overwrote, freed or reallocated the buffer in between -- keeping the bytes intact is the caller's part.
+ *
+ * With SNERF_FLAG_DEPTH_MEDIAN (inference main pass, SNERF_FLAG_GEOMETRY or SNERF_FLAG_RELIGHT) one launch follows the pass's composite
+ * on `stream` and overwrites out->depth with each ray's median depth, read off the out->weights and out->z_vals the pass wrote (spec
+ * and refusals at the flag).  out->depth, out->weights and out->z_vals must all be non-NULL (SNERF_ERR_NULL, by name, before any
+ * launch); out->sigmas is optional: where given, a ray with a sigma that is not finite gets a NaN depth instead of an empty ray's; every other result, the workspace and all sizes are those of the call without the bit. */
 int snerf_forward(const SnerfDesc* desc, const float* packed_params, const SnerfInputs* in,
                   const SnerfOutputs* out, void* workspace, size_t workspace_bytes, void* stream);
 

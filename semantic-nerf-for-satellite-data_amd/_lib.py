@@ -15,6 +15,7 @@ FLAG_SC_PASS = 2
 FLAG_RELIGHT = 4      # relight of the inference main pass that the workspace holds (include/snerf_hip.h: SNERF_FLAG_RELIGHT)
 FLAG_EMBED_GRAD = 16  # snerf_backward writes d_t / d_t_s alone, packed_grads may be NULL (include/snerf_hip.h: SNERF_FLAG_EMBED_GRAD)
 FLAG_GEOMETRY = 32    # geometry-only inference pass: trunk + sigma + composite, no head launch (include/snerf_hip.h: SNERF_FLAG_GEOMETRY)
+FLAG_DEPTH_MEDIAN = 128  # one launch behind an inference pass rewrites out->depth with the rays' median depth (include/snerf_hip.h: SNERF_FLAG_DEPTH_MEDIAN)
 # arithmetic bits of SnerfDesc.flags (include/snerf_hip.h): none set = the default, f16x2
 FLAG_F16X2 = 64       # default: fp32-class on the fp16 matrix cores, two fp16 planes of power-of-two-scaled operands, three products
 FLAG_F16X1 = 8        # reduced precision: ONE fp16 plane of the same block-scaled tensors, one product (precision = 16 / "medium" / "high")

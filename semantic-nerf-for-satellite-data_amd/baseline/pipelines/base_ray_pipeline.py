@@ -49,7 +49,9 @@ class BaseRayPipeline(Pipeline):
 
     # ---- validation (base_ray_pipeline.py:101-193) -----------------------------------------------------------
     def _val_render_options(self, split):
-        return {}
+        """render options of a validation / visualisation render: {} unless the config asks for the median depth"""
+        mode = getattr(self.cfgs.pipeline, "depth_mode", "mean")
+        return {"depth_mode": mode} if mode != "mean" else {}
 
     def _val_result_keys(self):
         """results the validation loss and metrics read (the reference renders all fifteen and keeps them)"""

@@ -23,6 +23,7 @@ class NeRFConfig(BaseModel):
     n_samples: int = 64
     use_fine_network: Union[bool, int] = False
     n_importance: int = 0
+    depth_mode: Literal["mean", "median"] = "mean"  # build extension: what validation and evaluation read as a ray's depth; training never takes it
     render_chunk_size: int = 5120
     batch_size: int = 1024
     learnrate: float = 5e-4

@@ -213,6 +213,13 @@ int make_plan(const SnerfDesc* d, Plan* pl) {
   p.relight = (d->flags & SNERF_FLAG_RELIGHT) != 0;
   p.embed_grad = (d->flags & SNERF_FLAG_EMBED_GRAD) != 0;
   p.geometry = (d->flags & SNERF_FLAG_GEOMETRY) != 0;
+  p.depth_median = (d->flags & SNERF_FLAG_DEPTH_MEDIAN) != 0;
+  // The median depth is read off the weights an INFERENCE composite wrote along the camera ray: it has no gradient (nothing of it is
+  // kept for a backward), and the solar-correction pass has no depth.  One wave holds a ray's run totals: the per-ray sample limit.
+  if (p.depth_median && (p.train || p.sc || p.embed_grad))
+    return bad("SNERF_FLAG_DEPTH_MEDIAN cannot be combined with SNERF_FLAG_TRAIN, SNERF_FLAG_SC_PASS or SNERF_FLAG_EMBED_GRAD (it rewrites the depth of an inference, geometry or relight pass)");
+  if (p.depth_median && d->n_samples > SNERF_VIS_MAX_SAMPLES)
+    return bad("SNERF_FLAG_DEPTH_MEDIAN needs n_samples in [1, SNERF_VIS_MAX_SAMPLES = 1024]");
   // A geometry pass is an inference pass of its own kind: nothing of it is kept for a backward, it samples along the camera ray, and it
   // leaves no head tensor a relight could reuse.
   if (p.geometry && (p.train || p.sc || p.relight || p.embed_grad))
@@ -388,9 +395,9 @@ int check_plan_note(const void* buf, bool composed, const char* who, const char*
 }
 // the descriptor fields that make two passes the same pass: everything, bar the RELIGHT bit, the spelling of the default arithmetic and
 // the EMBED_GRAD bit (which only selects how much of the backward runs: it may be set at backward time alone).  The GEOMETRY bit IS part
-// of the identity: such a pass leaves another workspace.
+// of the identity: such a pass leaves another workspace.  The DEPTH_MEDIAN bit is not: it changes nothing a pass leaves behind.
 bool same_pass_desc(SnerfDesc a, SnerfDesc b) {
-  const unsigned ignore = SNERF_FLAG_RELIGHT | SNERF_FLAG_F16X2 | SNERF_FLAG_EMBED_GRAD;
+  const unsigned ignore = SNERF_FLAG_RELIGHT | SNERF_FLAG_F16X2 | SNERF_FLAG_EMBED_GRAD | SNERF_FLAG_DEPTH_MEDIAN;
   a.flags &= ~ignore; b.flags &= ~ignore;
   return a.n_rays == b.n_rays && a.n_samples == b.n_samples && a.fc_units == b.fc_units && a.fc_layers == b.fc_layers &&
          a.feat_last == b.feat_last && a.skip_mask == b.skip_mask && a.n_freq == b.n_freq && a.siren == b.siren && a.t_dim == b.t_dim &&
@@ -532,6 +539,11 @@ int snerf_forward(const SnerfDesc* desc, const float* packed_params, const Snerf
         return SNERF_ERR_BAD_DESC;
       }
   }
+  if (p.depth_median) {   // the launch behind the composite reads the weights and depths that pass hands out
+    if (!out->weights) { set_error("snerf_forward(SNERF_FLAG_DEPTH_MEDIAN): out->weights is NULL (the median is computed from the weights the pass writes)"); return SNERF_ERR_NULL; }
+    if (!out->z_vals) { set_error("snerf_forward(SNERF_FLAG_DEPTH_MEDIAN): out->z_vals is NULL (the median is computed from the depths the pass writes)"); return SNERF_ERR_NULL; }
+    if (!out->depth) { set_error("snerf_forward(SNERF_FLAG_DEPTH_MEDIAN): out->depth is NULL -- nothing to compute"); return SNERF_ERR_NULL; }
+  }
   if (workspace_bytes < p.ws_bytes) { set_error("snerf_forward: workspace too small (%zu < %zu)", workspace_bytes, p.ws_bytes); return SNERF_ERR_WORKSPACE; }
   if (((uintptr_t)workspace & 255) || ((uintptr_t)packed_params & 255)) { set_error("workspace and packed params must be 256-byte aligned"); return SNERF_ERR_WORKSPACE; }
   RC(check_inputs(p, in));
@@ -542,13 +554,16 @@ int snerf_forward(const SnerfDesc* desc, const float* packed_params, const Snerf
   } else {
     note_plan(workspace, p.compose_feats, p.train ? PASS_TRAIN : p.sc ? PASS_SC : p.geometry ? PASS_GEOMETRY : PASS_MAIN_INFER, desc, skips_beta_block(p, out->beta != nullptr));
   }
-  return forward_bsp(p, packed_params, in, out, workspace, (hipStream_t)stream);
+  RC(forward_bsp(p, packed_params, in, out, workspace, (hipStream_t)stream));
+  if (p.depth_median) RC(launch_ray_median(out->weights, out->z_vals, out->sigmas, out->depth, p.N, p.S, (hipStream_t)stream));
+  return SNERF_OK;
 }
 
 int snerf_backward(const SnerfDesc* desc, const float* packed_params, const SnerfInputs* in, const SnerfOutGrads* gout,
                    float* packed_grads, float* d_t, float* d_t_s, void* workspace, size_t workspace_bytes, void* stream) {
   Plan p;
   RC(make_plan(desc, &p));
+  if (p.depth_median) { set_error("snerf_backward: SNERF_FLAG_DEPTH_MEDIAN is a bit of inference passes (the median depth has no gradient)"); return SNERF_ERR_BAD_DESC; }
   if (!p.train) { set_error("snerf_backward needs the SnerfDesc used for the SNERF_FLAG_TRAIN forward"); return SNERF_ERR_BAD_DESC; }
   // (SNERF_FLAG_EMBED_GRAD: packed_grads is neither read nor written and may be NULL)
   if (!packed_params || !gout || (!packed_grads && !p.embed_grad) || !workspace) { set_error("snerf_backward: null argument"); return SNERF_ERR_NULL; }

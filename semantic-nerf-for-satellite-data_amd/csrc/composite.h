@@ -42,5 +42,8 @@ struct CompBwdArgs {
 int launch_composite_fwd(const CompArgs& a, hipStream_t st, bool geometry = false);
 int composite_bwd_blocks(int N);
 int launch_composite_bwd(const CompBwdArgs& b, hipStream_t st);
+// raymedian.hip (SNERF_FLAG_DEPTH_MEDIAN): depth (N) = the median depth of each ray, from the weights and z_vals (N, S) a composite wrote; sigmas (N, S) or
+// null: where given, a sigma that is not finite makes the ray bad
+int launch_ray_median(const float* weights, const float* z_vals, const float* sigmas, float* depth, int n_rays, int S, hipStream_t st);
 
 }  // namespace snerf

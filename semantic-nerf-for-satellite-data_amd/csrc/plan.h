@@ -32,6 +32,7 @@ struct Plan {
   bool relight = false;   // SNERF_FLAG_RELIGHT: the sun-dependent launches alone, on the workspace of a finished inference main pass (same layout)
   bool embed_grad = false;   // SNERF_FLAG_EMBED_GRAD: snerf_backward writes d_t / d_t_s alone (bsp_pass.hip); forward and every size as without it
   bool geometry = false;   // SNERF_FLAG_GEOMETRY: depths, encoding, trunk, sigma and the composite alone (inference); the workspace holds no head tensor
+  bool depth_median = false;   // SNERF_FLAG_DEPTH_MEDIAN: one launch behind an inference pass's composite rewrites out->depth (raymedian.hip); sizes and workspace as without it
   unsigned skip_mask = 0;
   // extras columns appended to the feats buffer: [sun(3) | t(tau) | t_s(tau)] padded to 4
   int x_sun = 0, x_t = 3, x_ts = -1, Xp = 0, FA = 0;

@@ -12,13 +12,13 @@ constexpr size_t RAY_WAVE_MAX_LDS = 65536;
 
 // The launch of a kernel that keeps ray_bytes of LDS per ray: as many rays per workgroup as fit in RAY_WAVE_MAX_LDS, at most
 // RAY_WAVE_MAX_RAYS_PER_BLOCK; one wave per ray; the last workgroup may be ragged.  The caller's limits keep ray_bytes within
-// RAY_WAVE_MAX_LDS, so at least one ray fits.
+// RAY_WAVE_MAX_LDS, so at least one ray fits.  ray_bytes = 0 (raymedian.hip: a ray kept in registers) gives the full workgroup.
 struct RayWaveLaunch {
   dim3 grid, block;
   size_t lds_bytes;
 };
 static inline RayWaveLaunch ray_wave_launch(int n_rays, size_t ray_bytes) {
-  size_t rays_per_block = RAY_WAVE_MAX_LDS / ray_bytes;
+  size_t rays_per_block = ray_bytes ? RAY_WAVE_MAX_LDS / ray_bytes : (size_t)RAY_WAVE_MAX_RAYS_PER_BLOCK;
   if (rays_per_block > (size_t)RAY_WAVE_MAX_RAYS_PER_BLOCK) rays_per_block = RAY_WAVE_MAX_RAYS_PER_BLOCK;
   const unsigned blocks = (unsigned)(((long long)n_rays + (long long)rays_per_block - 1) / (long long)rays_per_block);
   return {dim3(blocks), dim3((unsigned)(RAY_WAVE * rays_per_block)), rays_per_block * ray_bytes};

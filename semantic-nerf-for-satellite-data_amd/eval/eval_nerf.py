@@ -23,7 +23,7 @@ import os
 import torch
 
 from .utils import metrics
-from .utils.util import lean_inference, sharded_lean_inference
+from .utils.util import lean_inference, sharded_lean_inference, with_depth_mode
 from ..baseline.pipelines.base_ray_pipeline import frame_w_h
 from ..parallel import world
 
@@ -44,7 +44,8 @@ def _mae_floats(mae):
 
 
 @torch.no_grad()
-def eval_nerf_images(cfgs, renderer, models, images, output_dp=None, split="test", epoch=-1, sharded=False, fit_embedding=None):
+def eval_nerf_images(cfgs, renderer, models, images, output_dp=None, split="test", epoch=-1, sharded=False, fit_embedding=None,
+                     depth_mode="mean"):
     """images: a sequence of dicts with the reference's item keys ("name", "rays", "extras", "rgbs", optional "w", "h") and
     the optional "dsm" entry of validation_step.  On the test split item 0 is skipped (it is also a training view,
     eval_nerf.py:52-55).  Returns the dict written to results.json: {name: {["mae": {...},] "psnr": "{:.2f}",
@@ -52,7 +53,11 @@ def eval_nerf_images(cfgs, renderer, models, images, output_dp=None, split="test
     its share of each frame and computes the same values; only rank 0 writes the file.
     fit_embedding: None, or a dict of fit_image_embedding's keyword arguments (missing ones: embedding.FIT_DEFAULTS) plus "region":
     "left" (default: fit on the columns [0, w // 2), "psnr_heldout" on the others) or "all" (no held-out key).  Every rank fits the
-    same vector from the same seed (no collective), so it works as it is under sharded=True."""
+    same vector from the same seed (no collective), so it works as it is under sharded=True.
+    depth_mode: "mean" (default) or "median" -- the DSM, hence every MAE, is then that of the rays' median depths
+    (SNERF_FLAG_DEPTH_MEDIAN) and the dict carries "depth_mode": "median"; at the default the key is absent.  The embedding fit, a
+    training render, never takes the mode."""
+    ro_depth = with_depth_mode({}, depth_mode, "eval_nerf_images")
     from .utils.dsm import compute_dsm_and_mae
     from .utils import embedding
     start = 1 if split == "test" else 0
@@ -74,12 +79,12 @@ def eval_nerf_images(cfgs, renderer, models, images, output_dp=None, split="test
         rgbs = img["rgbs"].reshape(-1, 3)
         W, H = _w_h(img, rays.shape[0])
         if region is None:
-            results = infer(cfgs, renderer, models, rays, extras, keys=("rgb_coarse", "depth_coarse"))
+            results = infer(cfgs, renderer, models, rays, extras, keys=("rgb_coarse", "depth_coarse"), render_options=ro_depth)
         else:
             fit, fit_mask, t_fit = embedding.fit_for_image(cfgs, renderer, models, img, rays, extras, W, H, region, fit_kw)
             vectors[img["name"]] = [float(v) for v in fit["t"].cpu()]
             results = infer(cfgs, renderer, models, rays, extras, keys=("rgb_coarse", "depth_coarse"),
-                            render_options=embedding.vector_options(fit))
+                            render_options=with_depth_mode(embedding.vector_options(fit), depth_mode))
         rgb = results["rgb_coarse"]
         entry = {}
         if img.get("dsm") is not None:
@@ -100,6 +105,8 @@ def eval_nerf_images(cfgs, renderer, models, images, output_dp=None, split="test
         per_image[img["name"]] = entry
         n = len(per_image)
         d = dict(per_image)
+        if depth_mode != "mean":
+            d["depth_mode"] = depth_mode
         if with_dsm[0]:
             d["MAE (Mean)"] = "{:.3f}".format(sum(v["mae"]["mean"] for v in per_image.values()) / n)
             d["MAE (Median)"] = "{:.3f}".format(sum(v["mae"]["median"] for v in per_image.values()) / n)

@@ -7,7 +7,7 @@ reference's un-normalised UTM cloud comes from one more launch (csrc/geo.hip); t
 import numpy as np
 import torch
 
-from .utils.util import lean_inference, sharded_lean_inference
+from .utils.util import lean_inference, sharded_lean_inference, with_depth_mode
 
 
 def get_xyz_from_nerf_prediction(rays: torch.Tensor, depth: torch.Tensor) -> torch.Tensor:
@@ -19,7 +19,7 @@ def get_xyz_from_nerf_prediction(rays: torch.Tensor, depth: torch.Tensor) -> tor
 
 @torch.no_grad()
 def extract_pointcloud(cfgs, renderer, models, rays, extras, render_options=None, with_labels=None, sharded=False, geo=None,
-                       with_colors=True):
+                       with_colors=True, depth_mode="mean"):
     """One image -> {"xyz_n" (R,3) f64, "colors" (R,3) f32, "depth" (R) f32 [, "labels" (R) i64]}, all on the device.
     `with_colors=False` leaves "colors" out; without labels either, the walk asks for the depth alone and runs as geometry passes
     (eval/utils/util.py: relight_chunks) -- no head launch, the same depth bits, hence the same cloud.
@@ -27,7 +27,9 @@ def extract_pointcloud(cfgs, renderer, models, rays, extras, render_options=None
     `sharded=False` (default) is the reference's single-device call: safe from one rank of a process group (the usual export
     inside a data-parallel run).  `sharded=True` is a COLLECTIVE: every rank of the group must call it with the same rays;
     the image is rendered in rank shards and the per-ray results gathered, so every rank returns the whole cloud
-    (eval/utils/util.py: sharded_lean_inference)."""
+    (eval/utils/util.py: sharded_lean_inference).
+    `depth_mode="median"` places every point at its ray's median depth (SNERF_FLAG_DEPTH_MEDIAN) instead of the expected depth."""
+    render_options = with_depth_mode(render_options, depth_mode, "extract_pointcloud")
     sem = models["coarse"].spec.n_classes > 0
     if with_labels is None:
         with_labels = sem

@@ -30,7 +30,10 @@ shadow_check).  Files under `output_dp`/nadir/shadow/:
     cast_{k:03d}.png/.tif                the shadow the rendered DSM casts under sun k: 0 shadowed, 1 lit, 255 unknown in the .tif;
                                          black / white / grey in the .png
     disagree_{k:03d}.png                 where the thresholded learned shadow map and the cast mask differ: white; left-out cells grey
-    shadow_check.json                    the suns, per sun the 8 raw words and the figures derived from them, bias and threshold"""
+    shadow_check.json                    the suns, per sun the 8 raw words and the figures derived from them, bias and threshold
+
+Every export hands its keyword arguments to its products function, `depth_mode="median"` among them: the altitudes and everything
+built on them are then those of the rays' median depths; at the default every file is what it was."""
 import json
 import os
 

@@ -17,7 +17,7 @@ import torch
 
 from ... import _lib, loss_ops, ops
 from ...framework.components.rays import extras_component_fn
-from ...framework.components.rendering import z_steps_on
+from ...framework.components.rendering import depth_mode_of, z_steps_on
 
 FIT_DEFAULTS = {"steps": 100, "lr": 0.05, "rays_per_fit": 4096}
 _ADAM = (0.9, 0.999, 1e-8)      # torch.optim.Adam's betas and eps
@@ -82,6 +82,9 @@ def fit_image_embedding(cfgs, renderer, models, rays, extras, rgbs, *, fit_mask=
     of iterate 0 .. steps on the fit subset], "best_step": index of the returned iterate, "rays": size of the subset}.
     render_options: "packed_params" (the packed weights, else packed here once) and "t_s_vector" (instead of the t_s init)."""
     opts = render_options or {}
+    if depth_mode_of(opts, "fit_image_embedding") != "mean":
+        raise ValueError("fit_image_embedding: render_options['depth_mode'] = 'median' is a mode of inference passes; the fit runs "
+                         "training passes, and the median depth has no gradient")
     if getattr(renderer, "N_importance", 0) > 0:
         # the fit builds its own PassInputs on the stratified depths: it would fit on other depths than the frame is rendered with
         raise NotImplementedError("fit_image_embedding: n_importance > 0 is not supported (the fit runs on the n_samples stratified "

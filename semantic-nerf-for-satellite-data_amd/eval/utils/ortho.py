@@ -138,7 +138,7 @@ def _flat(img, key):
 
 @torch.no_grad()
 def ortho_products(cfgs, renderer, models, images, geo=None, roi=None, resolution=D.RESOLUTION, radius=0, dsm_radius=1,
-                   sharded=False, grid=None, render_options={}):
+                   sharded=False, grid=None, render_options={}, depth_mode="mean"):
     """The fused map of `images` (dicts with the evaluators' keys: "rays", "extras"[, "dsm": {"geo": GeoFrame}]).
 
     Per image, in the order given: lean_inference (sharded_lean_inference with `sharded`: every rank then holds the whole
@@ -150,14 +150,16 @@ def ortho_products(cfgs, renderer, models, images, geo=None, roi=None, resolutio
     rgb, depth and labels are kept and the clouds are made again (one launch each) for the fold; nothing is rendered twice.
     Then one gather per image and the finishes.  `render_options` go to the renderer: as everywhere in evaluation it jitters the
     sample depths from torch's generator unless {"perturb": 0} (or a pinned "perturb_rand") says otherwise, so two walks give the
-    same map only from the same generator state.
+    same map only from the same generator state.  `depth_mode="median"` builds every cloud, hence every product, from the rays'
+    median depths (SNERF_FLAG_DEPTH_MEDIAN) instead of the expected depths.
 
     Returns {"grid": DsmGrid, "dsm": (H, W) f32 -- the mean DSM, the bits of dsm.rasterize on the concatenated cloud --,
     "top_alt": (H, W) f32, "top_index": (H, W) int64 (index into the concatenated rays, -1 where empty), "rgb": (3, H, W) f32
     (NaN where empty)[, "label_top": (H, W) u8, "label_vote": (H, W) u8, "vote_share": (H, W) f32], "n_points", "bad_points"
     (altitudes that are not finite or beyond +-32,768 m: left out of the top surface), "bad_labels" (labels outside the
     model's classes: no vote), "max_votes"}."""
-    from .util import lean_inference, sharded_lean_inference
+    from .util import lean_inference, sharded_lean_inference, with_depth_mode
+    render_options = with_depth_mode(render_options, depth_mode, "ortho_products")
     images = list(images)
     if not images:
         raise ValueError("ortho_products: no image")
@@ -348,7 +350,7 @@ def _nadir_walk(who, cfgs, renderer, models, suns, geo, grid, roi, min_alt, max_
 @torch.no_grad()
 def nadir_products(cfgs, renderer, models, geo=None, grid=None, roi=None, min_alt=None, max_alt=None, sun_elevation=None,
                    sun_azimuth=None, t=0, render_options={}, sharded=False, gt=None, water_mask=None, ignore_mask=None,
-                   dataset=None):
+                   dataset=None, depth_mode="mean"):
     """The map of the lattice rendered from above: one vertical ray per cell (rays.nadir_construct between `max_alt` and
     `min_alt` metres, through `geo`, a GeoFrame), extras of the sun at (`sun_elevation`, `sun_azimuth`) degrees and the
     embedding index `t`.  The grid: `grid` (a DsmGrid, or a window of one from dsm.grid_struct), else the ROI grid of `roi`
@@ -358,6 +360,8 @@ def nadir_products(cfgs, renderer, models, geo=None, grid=None, roi=None, min_al
     ONE walk of util.relight_chunks over the rays, under the one sun (`sharded`: over this rank's frame_shard of them, the
     results all-gathered as sharded_lean_inference does): the per-ray results are copied, albedo / sun / beta folded by
     vismaps.fold_chunk; no frame-sized per-sample tensor exists.  `render_options` as everywhere in evaluation ({"perturb": 0} for a repeatable map).
+    `depth_mode="median"`: the surface ("dsm", hence "mae" and "planimetric_error") is that of the rays' median depths
+    (SNERF_FLAG_DEPTH_MEDIAN); the colour, shadow and uncertainty maps do not read the depth and keep their bits.
 
     Returns {"grid": DsmGrid (of the window), "dsm": (H, W) f32 -- the altitude of geo.cloud(rays, depth), every cell filled --,
     "rgb": (3, H, W) f32, "albedo": (3, H, W) f32, "sun": (H, W) f32 (the shadow map), "beta": (H, W) f32[, "label": (H, W) u8
@@ -365,8 +369,9 @@ def nadir_products(cfgs, renderer, models, geo=None, grid=None, roi=None, min_al
     |east / north of the cloud - cell centre| in metres (the self-check of the ray construction), "scene_bounds": GeoBounds of
     the lattice's scene x / y (to_scene's stats)[, "mae": {"mean", "median"} of dsm.compute_mae(dsm, gt, water_mask,
     ignore_mask), with `gt` (H, W)]}."""
+    from .util import with_depth_mode
     out = _nadir_walk("nadir_products", cfgs, renderer, models, [(sun_elevation, sun_azimuth)], geo, grid, roi, min_alt, max_alt, t,
-                      render_options, sharded, gt, water_mask, ignore_mask, dataset)
+                      with_depth_mode(render_options, depth_mode, "nadir_products"), sharded, gt, water_mask, ignore_mask, dataset)
     del out["suns"]
     out["rgb"], out["sun"] = out["rgb"][0], out["sun"][0]
     return out
@@ -385,20 +390,21 @@ def sweep_suns(suns, dataset=None, who="nadir_sun_sweep"):
 
 @torch.no_grad()
 def nadir_sun_sweep(cfgs, renderer, models, suns=None, geo=None, grid=None, roi=None, min_alt=None, max_alt=None, t=0,
-                    render_options={}, sharded=False, gt=None, water_mask=None, ignore_mask=None, dataset=None):
+                    render_options={}, sharded=False, gt=None, water_mask=None, ignore_mask=None, dataset=None, depth_mode="mean"):
     """nadir_products under K suns in ONE walk over the lattice's rays (util.relight_chunks): per chunk a full pass under suns[0]
     and a relight per further sun, which re-runs only the sun-visibility branch, the sky colour and the composite on the chunk the
     workspace holds.  `suns`: (elevation_deg, azimuth_deg) pairs; None with a loaded `dataset`: the suns of
     the split's images in split order.  The lattice, `geo`, the altitudes, `t`, `sharded`, `gt` and the masks as for
-    nadir_products, which `dataset` supplies likewise.
+    nadir_products, which `dataset` supplies likewise, and so `depth_mode` (the surface a shadow check casts from is then the median one).
 
     Returns the products of nadir_products that do not depend on the sun ("grid", "dsm", "albedo", "beta"[, "label"], "rays",
     "planimetric_error", "scene_bounds"[, "mae"]) and "suns": the list, "rgb": (K, 3, H, W) f32, "sun": (K, H, W) f32 (the
     shadow maps, folded by vismaps.fold_chunk), "lit_share": (H, W) f32 -- the mean of the K shadow maps, summed in fp64 in sun
     order and rounded once.  Map k has the bits of nadir_products under sun k, given the same depths ({"perturb": 0}): the jitter
     is drawn once per chunk and shared by the suns."""
+    from .util import with_depth_mode
     out = _nadir_walk("nadir_sun_sweep", cfgs, renderer, models, sweep_suns(suns, dataset), geo, grid, roi, min_alt, max_alt, t,
-                      render_options, sharded, gt, water_mask, ignore_mask, dataset)
+                      with_depth_mode(render_options, depth_mode, "nadir_sun_sweep"), sharded, gt, water_mask, ignore_mask, dataset)
     total = torch.zeros_like(out["sun"][0], dtype=torch.float64)
     for plane in out["sun"]:      # in sun order, fp64; one rounding at the end
         total += plane.double()

@@ -3,9 +3,20 @@ from collections import defaultdict
 
 import torch
 
-from ...framework.components.rendering import bare_key as _bare, n_render_samples
+from ...framework.components.rendering import bare_key as _bare, depth_mode_of, n_render_samples
 
 _PER_RAY_OPTIONS = ("perturb_rand", "given_z_vals", "importance_rand")   # (N, S) / (N, S') / (N, Ni) tensors a caller may pin for the whole frame
+
+
+def with_depth_mode(render_options, depth_mode, who="depth_mode"):
+    """`render_options` for a consumer's depth_mode= argument: unchanged (the same object) at "mean", so that the default walk is the
+    walk it always was; a copy that carries {"depth_mode": "median"} otherwise.  Anything else is a ValueError."""
+    depth_mode_of({"depth_mode": depth_mode}, who)
+    if depth_mode == "mean":
+        return render_options
+    opts = dict(render_options) if render_options else {}
+    opts["depth_mode"] = depth_mode
+    return opts
 
 
 def _chunk_options(render_options, i, chunk, n):
@@ -112,8 +123,15 @@ def relight_chunks(cfgs, renderer, models, rays, extras, suns, buffers, render_o
     to pass, the chunk steps and the per-chunk options.
     A single-sun walk (suns == (None,)) whose results all lie in ops.GEOMETRY_KEYS (depth, weights, transparency, sigmas, z_vals)
     runs every chunk as a geometry pass (render_options["geometry_only"]): the same bits without the head launches.  A walk with
-    more suns never does: its base pass must leave a workspace that can be relit."""
+    more suns never does: its base pass must leave a workspace that can be relit.
+    render_options["depth_mode"] = "median" reaches every pass of the walk that writes 'depth' -- geometry passes and relights
+    included -- and the scratch tensors those passes may need (ops.render_pass_into: scratch=) are allocated for the first chunk and
+    carried in render_options["depth_scratch"], like the workspace."""
     from ... import ops
+    median = depth_mode_of(render_options, "relight_chunks") != "mean"
+    scratch = (render_options or {}).get("depth_scratch") if median else None
+    if median and scratch is None:
+        scratch = {}
     suns = list(suns)
     if not suns:
         raise ValueError("relight_chunks: no sun")
@@ -131,6 +149,8 @@ def relight_chunks(cfgs, renderer, models, rays, extras, suns, buffers, render_o
         k = min(chunk, n - i)
         opts = _chunk_options(render_options, i, chunk, n)
         opts["packed_params"] = packed
+        if median:
+            opts["depth_scratch"] = scratch
         if geometry_walk:
             opts["geometry_only"] = True
         ex = extras[i:i + chunk] if extras is not None else None

@@ -51,6 +51,18 @@ def _bare_results(who: str, out: dict) -> dict:
     return {bare_key(k): v for k, v in out.items()}
 
 
+DEPTH_MODES = ("mean", "median")
+
+
+def depth_mode_of(render_options, who: str) -> str:
+    """render_options["depth_mode"]: what 'depth' is -- "mean" (default: the expected depth sum w_i z_i) or "median" (the depth at
+    which half of the ray's weight lies in front: SNERF_FLAG_DEPTH_MEDIAN, inference passes only).  Anything else is a ValueError."""
+    mode = (render_options or {}).get("depth_mode", "mean")
+    if mode not in DEPTH_MODES:
+        raise ValueError(f"{who}: render_options['depth_mode'] must be one of {DEPTH_MODES}, got {mode!r}")
+    return mode
+
+
 def n_render_samples(pipeline_cfg) -> int:
     """S' = n_samples + n_importance: the samples per ray of every rendering pass and the columns of every per-sample result.
     THE place that names it: the renderer and everything that sizes a buffer for its results ask here."""
@@ -73,6 +85,10 @@ class BaseRenderer:
 
     def render_rays(self, models: dict, rays: torch.Tensor, extras: torch.Tensor, epoch=None, progress=1.0,
                     render_options={}):
+        if depth_mode_of(render_options, "render_rays") != "mean":
+            # render_rays is the differentiable render (ops.render_pass); the median has no gradient and rides on inference passes only
+            raise ValueError("render_rays: render_options['depth_mode'] = 'median' is a mode of the inference renders "
+                             "(render_rays_into, render_chunks, lean_inference); the training path does not take it")
         rays_d = ray_component_fn(rays, "directions")
         opts = dict(render_options) if render_options else {}
         if "perturb_rand" not in opts and opts.get("perturb", 1.0) > 0:
@@ -87,8 +103,11 @@ class BaseRenderer:
     def render_rays_into(self, models: dict, rays: torch.Tensor, extras: torch.Tensor, out: dict, render_options={}):
         """Inference-only render_rays that fills the preallocated tensors of `out` (keys as render_rays returns them,
         e.g. 'rgb_coarse', 'depth_coarse', 'semantic_label_coarse') and computes nothing else.  Returns the pass's
-        workspace buffer so that a caller can hand it back through render_options['workspace'] for the next chunk."""
+        workspace buffer so that a caller can hand it back through render_options['workspace'] for the next chunk.
+        render_options['depth_mode'] = "median" makes 'depth_coarse' the median depth (the final pass takes the flag, a proposal
+        pass does not); the scratch tensors that pass may need ride in render_options['depth_scratch'], a dict, like the workspace."""
         from ...semantic.components.rendering import fused_model_rendering_into
+        depth_mode_of(render_options, "render_rays_into")      # (before anything is drawn or launched)
         opts = dict(render_options) if render_options else {}
         if "perturb_rand" not in opts and opts.get("perturb", 1.0) > 0:
             opts["perturb_rand"] = torch.rand(rays.shape[0], self.N_samples, device=rays.device, dtype=torch.float32)
@@ -101,6 +120,7 @@ class BaseRenderer:
         `extras`: only the sun-dependent part of the pass runs again, on the base pass's depths, and every result has the bits
         render_rays_into gives under that sun.  `out` as for render_rays_into, main-pass results only.  Returns the workspace."""
         from ...semantic.components.rendering import fused_model_relighting_into
+        depth_mode_of(render_options, "relight_rays_into")
         return fused_model_relighting_into(self, models, "coarse", extras, dict(render_options) if render_options else {},
                                            _bare_results("relight_rays_into", out))
 

@@ -130,12 +130,15 @@ def output_path(run_dp, img_split, name, image_name, epoch):
 @torch.no_grad()
 def run_visualizer(pipeline, output_dp=None, split="test", epoch=-1, create_visualizers_fn=None, max_items=1000000,
                    render_options_fn=lambda pipeline, split: pipeline._val_render_options(split), palette=None, sharded=False,
-                   images=None):
+                   images=None, depth_mode="mean"):
     """The reference's run_visualizer loop over a loaded pipeline (the reference loads it from its log folder first): for every
     image of the split's `scene_images()` (or `images`), one lean_frame_maps fold of the products the visualisers name, then
     every visualiser writes {output_dp or cfgs.run.run_dp}/visualization/{split}/{name}/{image}_{epoch}.png.  Returns the
-    paths written.  With `sharded`, every rank folds its rows and rank 0 writes."""
+    paths written.  With `sharded`, every rank folds its rows and rank 0 writes.  `depth_mode="median"`: the depth and altitude
+    maps show the rays' median depths (SNERF_FLAG_DEPTH_MEDIAN), whatever the pipeline's config says; "mean" leaves the options of
+    `render_options_fn` as they are."""
     from .. import parallel
+    from ..eval.utils.util import with_depth_mode
     from ..eval.utils.vismaps import SEMANTIC_PRODUCTS, lean_frame_maps, sharded_lean_frame_maps
     assert create_visualizers_fn is not None and callable(create_visualizers_fn), \
         "create_visualizers_fn needs to be set to a function returning the visualizers that should be run"
@@ -154,7 +157,7 @@ def run_visualizer(pipeline, output_dp=None, split="test", epoch=-1, create_visu
         palette = torch.from_numpy(colormaps.DEFAULT_PALETTE)
     if palette is not None:
         palette = torch.as_tensor(palette, dtype=torch.uint8).to(dev)
-    render_options = render_options_fn(pipeline, split)
+    render_options = with_depth_mode(render_options_fn(pipeline, split), depth_mode, "run_visualizer")
     run_dp = output_dp if output_dp is not None else cfgs.run.run_dp
     fold = sharded_lean_frame_maps if sharded else lean_frame_maps
     written = []

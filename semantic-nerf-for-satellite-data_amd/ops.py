@@ -557,10 +557,47 @@ def _outputs_struct(who, spec, out, N, S, sc_pass=False, geometry=False):
     return so
 
 
+DEPTH_MODES = ("mean", "median")      # what a pass's 'depth' is: the expected depth sum w_i z_i, or the median (SNERF_FLAG_DEPTH_MEDIAN)
+
+
+def _depth_mode_flag(who, depth_mode, out, sc_pass=False):
+    """The flag bit of `depth_mode`, checked before anything is sized: an unknown mode and the median of a solar-correction pass
+    (which has no depth) are ValueErrors; the median needs 'depth' in `out` (KeyError)."""
+    if depth_mode not in DEPTH_MODES:
+        raise ValueError(f"{who}: depth_mode must be one of {DEPTH_MODES}, got {depth_mode!r}")
+    if depth_mode == "mean":
+        return 0
+    if sc_pass:
+        raise ValueError(f"{who}: depth_mode='median' is not a mode of the solar-correction pass (it has no depth)")
+    if "depth" not in out:
+        raise KeyError(f"{who}: depth_mode='median' rewrites out['depth'], which `out` does not name")
+    return _lib.FLAG_DEPTH_MEDIAN
+
+
+def _bind_median_scratch(so, out, N, S, dev, scratch):
+    """The median launch reads the weights, depths and sigmas the pass hands out (the sigmas so that a ray whose density is not finite
+    -- a NaN origin -- gets a NaN depth: the composite gives it zero weights): where `out` does not name one, bind (N, S) views of the flat
+    fp32 tensors in `scratch` ('weights' / 'z_vals' / 'sigmas'; made or grown here, so a frame walk that carries the dict allocates them for its
+    first chunk only).  Returns the views: hold them until the launch is queued."""
+    scratch = scratch if scratch is not None else {}
+    held = []
+    for k in ("weights", "z_vals", "sigmas"):
+        if k in out:
+            continue
+        buf = scratch.get(k)
+        if buf is None or buf.numel() < N * S or buf.device != dev:
+            buf = scratch[k] = _empty((N * S,), dtype=torch.float32, device=dev)
+        v = buf[:N * S].view(N, S)
+        setattr(so, k, v.data_ptr())
+        held.append(v)
+    return held
+
+
 @torch.no_grad()
 def render_pass_into(spec: ModelSpec, params: dict, pin: PassInputs, t: torch.Tensor, t_s: torch.Tensor | None,
                      out: dict, sc_pass: bool = False, packed: torch.Tensor | None = None,
-                     workspace: torch.Tensor | None = None, geometry: bool = False) -> torch.Tensor:
+                     workspace: torch.Tensor | None = None, geometry: bool = False, depth_mode: str = "mean",
+                     scratch: dict | None = None) -> torch.Tensor:
     """Inference-only pass that produces ONLY the result tensors named in `out` and writes them in place:
     `out` maps result keys (output_keys(), 'semantic_label', 'z_vals') to preallocated contiguous tensors of the
     pass's shapes -- typically row slices of full-frame buffers, so a chunked render never concatenates
@@ -568,7 +605,12 @@ def render_pass_into(spec: ModelSpec, params: dict, pin: PassInputs, t: torch.Te
     the composite kernel skips it.  Returns the workspace (pass it back in for the next chunk of the same size).
     `geometry=True` runs the geometry pass (SNERF_FLAG_GEOMETRY): trunk, sigma and the composite, no head launch.  `out` may
     then name GEOMETRY_KEYS only (KeyError otherwise), each with the bits of the full pass; `t`, `t_s` and `pin.sun_d` are not read
-    and may be None; a workspace made here is the smaller one of that pass (a larger one given is used as it is)."""
+    and may be None; a workspace made here is the smaller one of that pass (a larger one given is used as it is).
+    `depth_mode="median"` (main or geometry pass) sets SNERF_FLAG_DEPTH_MEDIAN: one launch behind the pass rewrites out['depth'] --
+    which `out` must name -- with each ray's median depth, every other result keeping its bits.  That launch reads the pass's weights
+    z_vals and sigmas: where `out` names them they are used, otherwise chunk-sized tensors of ops' own, kept in the optional `scratch` dict
+    that a caller carries from chunk to chunk."""
+    median = _depth_mode_flag("render_pass_into", depth_mode, out, sc_pass)
     if geometry and sc_pass:
         raise ValueError("render_pass_into: geometry=True is a main-pass variant, not one of the solar-correction pass")
     for k in out if geometry else ():      # before anything is sized or allocated
@@ -578,28 +620,33 @@ def render_pass_into(spec: ModelSpec, params: dict, pin: PassInputs, t: torch.Te
         raise ValueError("render_pass_into: t (N, tau) is required (only a geometry pass reads no embedding)")
     lead = t if t is not None else next(v for v in (pin.rays, pin.z_vals, pin.xyz) if v is not None)      # (t = None: N and the device from the rays)
     N, dev = lead.shape[0], lead.device
-    flags = _lib.FLAG_GEOMETRY if geometry else (_lib.FLAG_SC_PASS if sc_pass else 0)
+    flags = (_lib.FLAG_GEOMETRY if geometry else (_lib.FLAG_SC_PASS if sc_pass else 0)) | median
     S, _, nbytes, _, _, launch = _forward_setup(spec, pin, t, t_s, flags)
     if workspace is None or workspace.numel() < nbytes or workspace.device != dev:
         workspace = _empty(nbytes, dtype=torch.uint8, device=dev)
     so = _outputs_struct("render_pass_into", spec, out, N, S, sc_pass, geometry)
+    held = _bind_median_scratch(so, out, N, S, dev, scratch) if median else None
     if packed is None:
         packed = pack_params(spec, params)
     launch(packed, so, workspace)
+    del held
     return workspace
 
 
 def geometry_pass_into(spec: ModelSpec, params: dict, pin: PassInputs, out: dict, packed: torch.Tensor | None = None,
-                       workspace: torch.Tensor | None = None) -> torch.Tensor:
+                       workspace: torch.Tensor | None = None, depth_mode: str = "mean", scratch: dict | None = None) -> torch.Tensor:
     """The geometry pass: render_pass_into(geometry=True) without the operands it does not read.  `out` names results of
     GEOMETRY_KEYS -- depth (N), weights / transparency / sigmas / z_vals (N, S) -- each with the bits the full inference pass of the
-    same inputs gives; `pin` needs rays (or xyz + z_vals) and no sun_d.  Returns the workspace."""
-    return render_pass_into(spec, params, pin, None, None, out, packed=packed, workspace=workspace, geometry=True)
+    same inputs gives; `pin` needs rays (or xyz + z_vals) and no sun_d.  `depth_mode` / `scratch` as for render_pass_into.  Returns the
+    workspace."""
+    return render_pass_into(spec, params, pin, None, None, out, packed=packed, workspace=workspace, geometry=True,
+                            depth_mode=depth_mode, scratch=scratch)
 
 
 @torch.no_grad()
 def relight_pass_into(spec: ModelSpec, params: dict, sun_d: torch.Tensor, t: torch.Tensor, t_s: torch.Tensor | None, out: dict,
-                      workspace: torch.Tensor, packed: torch.Tensor | None = None, n_samples: int | None = None) -> torch.Tensor:
+                      workspace: torch.Tensor, packed: torch.Tensor | None = None, n_samples: int | None = None,
+                      depth_mode: str = "mean", scratch: dict | None = None) -> torch.Tensor:
     """The chunk that `workspace` holds, under another sun: `workspace` is the tensor the BASE pass returned -- the last
     render_pass_into main pass on it, with this spec, these parameters and the same number of rays and samples.  Only what depends on
     the sun runs again (the extras columns, the sun block of the first head layer, the sun-visibility layers, the sky colour, the
@@ -608,7 +655,9 @@ def relight_pass_into(spec: ModelSpec, params: dict, sun_d: torch.Tensor, t: tor
     (or others: the extras block is rewritten whole).  `out` as for render_pass_into (main-pass keys); N comes from `t`, S from
     `n_samples` or from the shape of a per-sample result tensor in `out`.  Any number of relights may follow one base pass; the
     library refuses a workspace whose last pass was not such a base pass (RuntimeError with its message), but cannot know that the
-    caller wrote into the tensor itself.  Returns the workspace."""
+    caller wrote into the tensor itself.  `depth_mode` / `scratch` as for render_pass_into: the median is that of the relit weights,
+    whatever the base pass's mode was.  Returns the workspace."""
+    median = _depth_mode_flag("relight_pass_into", depth_mode, out)
     N = t.shape[0]
     S = n_samples
     for k, v in out.items():      # a per-sample result names S: (N, S) or (N, S, c)
@@ -620,14 +669,15 @@ def relight_pass_into(spec: ModelSpec, params: dict, sun_d: torch.Tensor, t: tor
     if workspace is None:
         raise ValueError("relight_pass_into: workspace= must be the tensor the base pass returned")
     pin = PassInputs(sun_d=sun_d)      # (held, with tc / tsc, until the launch is queued: they own the contiguous copies)
-    _, _, nbytes, tc, tsc, launch = _forward_setup(spec, pin, t, t_s, _lib.FLAG_RELIGHT, n_samples=S)
+    _, _, nbytes, tc, tsc, launch = _forward_setup(spec, pin, t, t_s, _lib.FLAG_RELIGHT | median, n_samples=S)
     if workspace.numel() < nbytes or workspace.device != t.device:
         raise ValueError(f"relight_pass_into: the workspace holds {workspace.numel()} bytes on {workspace.device}, the base pass of "
                          f"{N} x {S} needs {nbytes} on {t.device}")
+    held = _bind_median_scratch(so, out, N, int(S), t.device, scratch) if median else None
     if packed is None:
         packed = pack_params(spec, params)
     launch(packed, so, workspace)
-    del pin, tc, tsc
+    del pin, tc, tsc, held
     return workspace
 
 

@@ -9,7 +9,7 @@ import os
 import torch
 
 from ... import ops
-from ...framework.components.rendering import BaseRenderer, z_steps_on
+from ...framework.components.rendering import BaseRenderer, depth_mode_of, z_steps_on
 from ...framework.components.rays import extras_component_fn
 from ..models.rs_semantic import inference as rs_semantic_inference
 
@@ -115,6 +115,9 @@ def fused_model_rendering(renderer, models, typ, rays, extras, render_options, i
             "fused HIP pass (snerf_forward); a foreign per-sample inference callable has nothing to plug into")
     cfgs = renderer.cfgs
     opts = render_options or {}
+    if depth_mode_of(opts, "fused_model_rendering") != "mean":
+        raise ValueError("fused_model_rendering: depth_mode = 'median' is a mode of the inference passes (fused_model_rendering_into); "
+                         "the differentiable passes do not take it")
     model = models[typ]
     sun_d, rays_t, rays_t_s, params, packed = _pass_operands(models, model, extras, opts)
     pin = ops.PassInputs(sun_d=sun_d, rays=rays, z_vals=opts.get("given_z_vals"),
@@ -160,6 +163,15 @@ def fused_model_rendering(renderer, models, typ, rays, extras, render_options, i
 _SC_KEYS = {"weights_sc": "weights", "transparency_sc": "transparency", "sun_sc": "sun"}
 
 
+def _depth_mode_kwargs(who, opts, out):
+    """depth_mode= / scratch= of an ops *_into pass that writes `out`: render_options["depth_mode"] where the pass is asked for
+    'depth' (a pass that hands out no depth has nothing to rewrite and runs as it is), with the scratch dict of
+    render_options["depth_scratch"]; {} at the default, so that a default render calls ops exactly as before."""
+    if depth_mode_of(opts, who) == "mean" or "depth" not in out:
+        return {}
+    return {"depth_mode": "median", "scratch": opts.get("depth_scratch")}
+
+
 @torch.no_grad()
 def fused_model_rendering_into(renderer, models, typ, rays, extras, render_options, out: dict):
     """Inference-only twin of fused_model_rendering: writes just the results named in `out` (un-suffixed keys) into
@@ -167,8 +179,11 @@ def fused_model_rendering_into(renderer, models, typ, rays, extras, render_optio
     or image render (rgb / depth / label) does half the work of render_rays.
     render_options["geometry_only"] = True runs the geometry pass instead of the main pass: `out` may then name ops.GEOMETRY_KEYS
     only (KeyError for anything else, the solar-correction keys included), each result has the bits of the main pass, and neither
-    the sun nor an embedding is looked up."""
+    the sun nor an embedding is looked up.
+    render_options["depth_mode"] = "median": the main (or geometry) pass takes SNERF_FLAG_DEPTH_MEDIAN where `out` names 'depth'; the
+    solar-correction pass never does."""
     opts = render_options or {}
+    depth_kw = _depth_mode_kwargs("fused_model_rendering_into", opts, out)
     if opts.get("geometry_only"):
         for k in out:      # (before anything is looked up)
             if k in _SC_KEYS or k not in ops.GEOMETRY_KEYS:
@@ -182,7 +197,7 @@ def fused_model_rendering_into(renderer, models, typ, rays, extras, render_optio
             packed = ops.pack_params(model.spec, params)
         pin = ops.PassInputs(rays=rays, z_vals=opts.get("given_z_vals"), z_steps=z_steps_on(rays.device, renderer.N_samples),
                              u=opts.get("perturb_rand"))
-        return ops.geometry_pass_into(model.spec, params, pin, out, packed=packed, workspace=opts.get("workspace"))
+        return ops.geometry_pass_into(model.spec, params, pin, out, packed=packed, workspace=opts.get("workspace"), **depth_kw)
     sun_d, rays_t, rays_t_s, params, packed = _pass_operands(models, model, extras, opts)
     main_out = {k: v for k, v in out.items() if k not in _SC_KEYS}
     sc_out = {_SC_KEYS[k]: v for k, v in out.items() if k in _SC_KEYS}
@@ -193,7 +208,7 @@ def fused_model_rendering_into(renderer, models, typ, rays, extras, render_optio
     pin = ops.PassInputs(sun_d=sun_d, rays=rays, z_vals=z, z_steps=z_steps_on(rays.device, renderer.N_samples),
                          u=opts.get("perturb_rand"))
     if main_out:
-        ws = ops.render_pass_into(model.spec, params, pin, rays_t, rays_t_s, main_out, packed=packed, workspace=ws)
+        ws = ops.render_pass_into(model.spec, params, pin, rays_t, rays_t_s, main_out, packed=packed, workspace=ws, **depth_kw)
     if sc_out:
         ws = ops.render_pass_into(model.spec, params, ops.PassInputs(sun_d=sun_d, rays=rays, z_vals=z), rays_t, rays_t_s,
                                   sc_out, sc_pass=True, packed=packed, workspace=ws)
@@ -205,8 +220,10 @@ def fused_model_relighting_into(renderer, models, typ, extras, render_options, o
     """The chunk that render_options["workspace"] holds -- the workspace fused_model_rendering_into returned for its main pass --
     under the sun (and embedding index) of `extras`: ops.relight_pass_into, which re-runs only what depends on the sun.  `out` takes
     the main pass's keys; a solar-correction key ('weights_sc', ...) is a KeyError: that pass samples along the sun ray itself and
-    leaves nothing a new sun could reuse.  Returns the workspace."""
+    leaves nothing a new sun could reuse.  render_options["depth_mode"] as for fused_model_rendering_into, whatever the base pass's
+    mode was.  Returns the workspace."""
     opts = render_options or {}
+    depth_kw = _depth_mode_kwargs("fused_model_relighting_into", opts, out)
     for k in out:
         if k in _SC_KEYS:
             raise KeyError(f"fused_model_relighting_into: '{k}' belongs to the solar-correction pass, which cannot be relit "
@@ -220,7 +237,8 @@ def fused_model_relighting_into(renderer, models, typ, extras, render_options, o
         if k not in allowed:
             raise KeyError(f"fused_model_relighting_into: '{k}' is not a result of the main pass (have {sorted(allowed)})")
     sun_d, rays_t, rays_t_s, params, packed = _pass_operands(models, model, extras, opts)
-    return ops.relight_pass_into(model.spec, params, sun_d, rays_t, rays_t_s, out, ws, packed=packed, n_samples=renderer.n_render_samples)
+    return ops.relight_pass_into(model.spec, params, sun_d, rays_t, rays_t_s, out, ws, packed=packed, n_samples=renderer.n_render_samples,
+                                 **depth_kw)
 
 
 class RSSemanticRendering(BaseRenderer):
