@@ -141,6 +141,14 @@ class SnerfRayImage(C.Structure):
                 ("n_rays", C.c_longlong), ("w", C.c_int), ("h", C.c_int)]
 
 
+class SnerfRectImage(C.Structure):
+    _fields_ = [("rpc", SnerfRpc), ("row0", C.c_longlong), ("w", C.c_int), ("h", C.c_int)]
+
+
+RECT_MAX_IMAGES = 64       # include/snerf_orthorect.h SNERF_RECT_MAX_IMAGES
+RECT_SEEN, RECT_HOLE, RECT_OUTSIDE, RECT_HIDDEN = 0, 1, 2, 3     # include/snerf_orthorect.h SNERF_RECT_*
+
+
 class SnerfGeoParams(C.Structure):
     _fields_ = [("centre", C.c_double * 3), ("range", C.c_double), ("lon0", C.c_double), ("south", C.c_int), ("direction", C.c_int)]
 
@@ -235,6 +243,18 @@ def _signatures():
 SIGNATURES = _signatures()
 EXPORTED_SYMBOLS = tuple(SIGNATURES)
 
+# Entries declared OUTSIDE include/snerf_hip.h, whose list of symbols is frozen at ABI 6: header -> rows in that header's order
+# (tests/test_orthorect_cpu.py compares them with the header as tests/test_abi_cpu.py does for the table above).  lib() and call()
+# serve both tables alike.  The SnerfRectImage table goes as void* twice: the host copy (a ctypes array), the device copy (a tensor).
+EXTENSION_SIGNATURES = {
+    "snerf_orthorect.h": {"snerf_orthorectify": (C.c_int, (C.c_void_p, C.POINTER(SnerfDsmGrid), C.c_double, C.c_int, C.c_void_p, C.c_void_p,
+                                                          C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int) + (C.c_void_p,) * 9 + (c_stream,))},
+}
+_ALL_SIGNATURES = dict(SIGNATURES)
+for _rows in EXTENSION_SIGNATURES.values():
+    assert not set(_rows) & set(_ALL_SIGNATURES)
+    _ALL_SIGNATURES.update(_rows)
+
 SHADOW_MAX_SUNS = 64       # include/snerf_hip.h SNERF_SHADOW_MAX_SUNS
 SHADOW_UNKNOWN = 255       # include/snerf_hip.h SNERF_SHADOW_UNKNOWN
 
@@ -246,8 +266,8 @@ ORTHO_NO_LABEL = 255       # include/snerf_hip.h SNERF_ORTHO_NO_LABEL
 # stream follows them)
 _PLANS = {name: (tuple(float if t in (C.c_float, C.c_double) else None if issubclass(t, (C.c_void_p, C._Pointer)) else int
                        for t in args if t is not c_stream), c_stream in args)
-          for name, (_, args) in SIGNATURES.items()}
-assert all(c_stream not in args[:-1] for _, args in SIGNATURES.values())
+          for name, (_, args) in _ALL_SIGNATURES.items()}
+assert all(c_stream not in args[:-1] for _, args in _ALL_SIGNATURES.values())
 
 _lib = None
 
@@ -266,7 +286,7 @@ def lib():
     # owns torch's device context and streams (loading ours first brings up a second runtime that then
     # reports "no ROCm-capable device").
     L = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in SIGNATURES.items():
+    for name, (restype, argtypes) in _ALL_SIGNATURES.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, list(argtypes)
     if L.snerf_version() != ABI_VERSION:

@@ -11,6 +11,7 @@
 // No allocation and no host synchronisation; every entry runs on the caller's stream.
 #include "geo_dev.h"
 #include "reduce.h"
+#include "rpc_dev.h"
 #include "../../include/snerf_hip.h"
 
 #include <stdint.h>
@@ -28,25 +29,7 @@ constexpr int NRM_THREADS = 256;
 
 static_assert(sizeof(SnerfRpc) == 1368 && sizeof(SnerfRayImage) == 1408, "snerf_amd/_lib.py mirrors these layouts");
 
-// rpcm.rpc_model.apply_poly(poly, x, y, z) with x = lat, y = lon, z = alt (RPC00B term order), evaluated in numpy's order
-__device__ __forceinline__ double rpc_poly(const double* c, double x, double y, double z) {
-  double out = 0.0;
-  out += c[0];
-  out += c[1] * y + c[2] * x + c[3] * z;
-  out += c[4] * y * x + c[5] * y * z + c[6] * x * z;
-  out += c[7] * y * y + c[8] * x * x + c[9] * z * z;
-  out += c[10] * x * y * z;
-  out += c[11] * y * y * y;
-  out += c[12] * y * x * x + c[13] * y * z * z + c[14] * y * y * x;
-  out += c[15] * x * x * x;
-  out += c[16] * x * z * z + c[17] * y * y * z + c[18] * x * x * z;
-  out += c[19] * z * z * z;
-  return out;
-}
-
-__device__ __forceinline__ double rpc_rfm(const double* num, const double* den, double x, double y, double z) {
-  return rpc_poly(num, x, y, z) / rpc_poly(den, x, y, z);
-}
+// the forward model (rpc_poly, rpc_rfm, rpc_project) and check_rpc live in rpc_dev.h: orthorect.hip projects with them too
 
 // rpcm's iterative inversion runs ONE loop for all points of a call: it updates every point until the last one has met the
 // tolerance, so a point that converged early keeps being updated.  The kernels reproduce that in two launches: the first
@@ -133,17 +116,6 @@ __device__ __forceinline__ void rpc_count(const SnerfRpc& r, double col, double 
   const int n = rpc_iterate(r, ncol, nrow, nalt, -1, &lon, &lat);
   if (n > RPC_MAX_ITERS) atomicAdd(fails, 1);
   else atomicMax(max_iters, n);
-}
-
-// rpcm RPCModel.projection: (lon, lat, alt) -> (col, row)
-__device__ __forceinline__ void rpc_project(const SnerfRpc& r, double lon, double lat, double alt, double* col, double* row) {
-  const double nlon = (lon - r.lon_offset) / r.lon_scale;
-  const double nlat = (lat - r.lat_offset) / r.lat_scale;
-  const double nalt = (alt - r.alt_offset) / r.alt_scale;
-  const double c = rpc_rfm(r.col_num, r.col_den, nlat, nlon, nalt);
-  const double w = rpc_rfm(r.row_num, r.row_den, nlat, nlon, nalt);
-  *col = c * r.col_scale + r.col_offset;
-  *row = w * r.row_scale + r.row_offset;
 }
 
 __device__ __forceinline__ void ray_pixel(const SnerfRayImage& im, const double* pixels, long long i, double* col, double* row) {
@@ -320,14 +292,6 @@ __global__ __launch_bounds__(NRM_THREADS) void normalize_rows_kernel(float* __re
 
 // one item per thread, no grid stride: n <= 2^31 at every caller
 static inline long long blocks_of(long long n, int threads) { return (n + threads - 1) / threads; }
-
-static int check_rpc(const SnerfRpc& r, const char* who, int idx) {
-  const double s[5] = {r.row_scale, r.col_scale, r.lat_scale, r.lon_scale, r.alt_scale};
-  for (double v : s)
-    if (!(v != 0.0) || !__builtin_isfinite(v)) { set_error("%s: RPC %d has a zero or non-finite scale", who, idx); return SNERF_ERR_BAD_DESC; }
-  if (r.has_inverse != 0 && r.has_inverse != 1) { set_error("%s: RPC %d has_inverse = %d", who, idx, r.has_inverse); return SNERF_ERR_BAD_DESC; }
-  return SNERF_OK;
-}
 
 }  // namespace snerf
 

@@ -32,7 +32,17 @@ shadow_check).  Files under `output_dp`/nadir/shadow/:
     disagree_{k:03d}.png                 where the thresholded learned shadow map and the cast mask differ: white; left-out cells grey
     shadow_check.json                    the suns, per sun the 8 raw words and the figures derived from them, bias and threshold
 
-Every export hands its keyword arguments to its products function, `depth_mode="median"` among them: the altitudes and everything
+export_rectified takes the scene's OWN images and labels to the map (eval/utils/orthorect.py rectify) and, given a
+model's map products on the same grid, scores them against the mosaic.  Files under `output_dp`/rectified/{split}/:
+    {name}_rgb.png/.tif                  image {name} orthorectified on the DSM: uint8, cells it does not see black
+    {name}_state.png/.tif                per cell 0 seen, 1 hole, 2 outside the image, 3 hidden by the DSM in the .tif; greys in the .png
+    {name}_label.png/.tif                the image's labels on the map (a semantic scene only): ids in the .tif (255 = not seen)
+    mosaic_rgb.png/.tif, coverage.png/.tif   the mean colour of the images that see a cell, and how many do (float32, BONE)
+    mosaic_label.png/.tif, vote_share.png/.tif   the voted class and the winner's share of the votes (a semantic scene only)
+    map_eval.json                        with model_products=: PSNR of its colour and, per label plane, the confusion matrix against
+                                         the voted labels, accuracy, mIoU and the compared cells
+
+The other exports hand their keyword arguments to their products function, `depth_mode="median"` among them: the altitudes and everything
 built on them are then those of the rays' median depths; at the default every file is what it was."""
 import json
 import os
@@ -44,9 +54,10 @@ from PIL import Image
 from ..framework.util import colormaps, img_utils
 from ..framework.visualize import to_uint8_image
 from ..parallel import world
-from .utils import vismaps
+from .utils import orthorect, vismaps
+from .utils.dsm import roi_grid
 from .utils.ortho import NO_LABEL, nadir_products, nadir_sun_sweep, ortho_products
-from .utils.shadow import METRICS, UNKNOWN, shadow_check
+from .utils.shadow import GT_HOLE_BELOW, METRICS, UNKNOWN, shadow_check
 
 
 def _png(fp, chw_u8):
@@ -168,6 +179,73 @@ def export_sun_sweep(cfgs, renderer, models, output_dp, zone_string=None, **kwar
         with open(fp("suns.json"), "w") as f:
             json.dump(_sun_rows(prod["suns"]), f, indent=1)
     return dict(prod, files=files)
+
+
+def _state_png(fp, state):
+    """a rectified image's state plane as a grey PNG: seen white, hidden mid-grey, outside dark grey, hole black"""
+    lut = torch.zeros(256, dtype=torch.uint8)
+    lut[orthorect.SEEN], lut[orthorect.HIDDEN], lut[orthorect.OUTSIDE] = 255, 128, 64
+    _png(fp, lut.to(state.device)[state.long()].unsqueeze(0).expand(3, -1, -1))
+
+
+@torch.no_grad()
+def export_rectified(cfgs, dataset, output_dp, dsm=None, split="train", model_products=None, grid=None, palette=None,
+                     zone_string=None, occlusion=True, bias=0.0):
+    """The images of a loaded `dataset` (the `split` split of a scene: baseline/dataset/satnerf_dataset.py) orthorectified on a DSM
+    (eval/utils/orthorect.py rectify), written to `output_dp`/rectified/{split}/.  `dsm` ((H, W) f32 on the
+    GPU) with its `grid` (a DsmGrid or a window of one): None takes `model_products`' "dsm" and "grid" when given, else the
+    scene's lidar ground truth on its ROI (altitudes below -500 m are holes).  A semantic dataset's labels are voted per cell.
+    `model_products`: an ortho_products or nadir_products result ON THE SAME GRID (anything else is a ValueError); with it
+    map_eval.json holds orthorect.map_agreement of its "rgb" and of each of its label planes against the mosaic.
+    Files: per image {name}_rgb, {name}_state[, {name}_label], and for the split mosaic_rgb, coverage (how many images see a cell),
+    [mosaic_label, vote_share], each as .png and .tif by the writers and rules of export_ortho; the state .tif holds 0 seen,
+    1 hole, 2 outside, 3 hidden.  Only rank 0 writes.  Returns rectify's result plus "files"[, "map_eval"]."""
+    if dataset.geo is None:
+        raise ValueError("export_rectified: the dataset carries no GeoFrame (load the scene through load_scene_banks)")
+    if dsm is None and model_products is not None:
+        dsm, grid = model_products["dsm"], model_products["grid"]
+    elif dsm is None:
+        entry = dataset.dsm
+        if not entry or "gt" not in entry:
+            raise ValueError("export_rectified: no dsm= given and the scene has no ground-truth DSM on disk")
+        gt = entry["gt"].float()
+        dsm, grid = torch.where(gt < GT_HOLE_BELOW, torch.full_like(gt, float("nan")), gt), roi_grid(entry["roi"])
+    elif grid is None:
+        if model_products is None:
+            raise ValueError("export_rectified: pass grid=, the lattice of dsm=")
+        grid = model_products["grid"]
+    n_classes = getattr(dataset, "semantic_n_classes", None) if "semantic" in dataset.t else None
+    res = orthorect.rectify(dsm, grid, dataset.geo, orthorect.dataset_images(dataset), n_classes=n_classes, occlusion=occlusion,
+                            keep_images=True, bias=bias)
+    out_grid = res["grid"]
+    if model_products is not None and orthorect.window_grid(model_products["grid"]) != out_grid:
+        raise ValueError(f"export_rectified: the model's products lie on {orthorect.window_grid(model_products['grid'])}, the DSM on {out_grid}")
+    zone_string = zone_string or dataset.geo.zone_string
+    files, fp = _writer(output_dp, "rectified", split)
+    if model_products is not None:
+        doc = {"rgb": orthorect.map_agreement(model_products["rgb"], None, res, n_classes)} if "rgb" in model_products else {}
+        if n_classes:
+            for key in ("label", "label_top", "label_vote"):
+                if key in model_products:
+                    doc[key] = orthorect.map_agreement(None, model_products[key], res, n_classes)
+        res["map_eval"] = doc
+    if fp:
+        kept = res["images"]
+        for k, it in enumerate(dataset.items):
+            _color_plane(fp, f"{it['name']}_rgb", torch.nan_to_num(kept["rgb"][k], nan=0.0), out_grid, zone_string)
+            _state_png(fp(f"{it['name']}_state.png"), kept["state"][k])
+            img_utils.save_geotiff(fp(f"{it['name']}_state.tif"), kept["state"][k], out_grid, zone_string)
+            if "label" in kept:
+                _label_plane(fp, f"{it['name']}_label", kept["label"][k], palette, out_grid, zone_string)
+        _color_plane(fp, "mosaic_rgb", torch.nan_to_num(res["rgb"], nan=0.0), out_grid, zone_string)
+        _scalar_plane(fp, "coverage", res["count"].to(torch.float32), colormaps.COLORMAP_BONE, out_grid, zone_string)
+        if "label_vote" in res:
+            _label_plane(fp, "mosaic_label", res["label_vote"], palette, out_grid, zone_string)
+            _scalar_plane(fp, "vote_share", res["vote_share"], colormaps.COLORMAP_BONE, out_grid, zone_string)
+        if "map_eval" in res:
+            with open(fp("map_eval.json"), "w") as f:
+                json.dump(res["map_eval"], f, indent=1)
+    return dict(res, files=files)
 
 
 def _mask_png(fp, mask):

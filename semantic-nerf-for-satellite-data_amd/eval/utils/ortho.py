@@ -23,8 +23,9 @@ nadir_products asks the model instead: one vertical ray p
 (baseline/components/rays.py nadir_construct, through GeoFrame.to_scene), rendered under a chosen sun -- a DSM without holes, a
 true nadir ortho-image, the shadow map and the top-surface label, with occlusion resolved by the renderer.
 
-Out of scope: map-space accuracy against a ground-truth class raster (the US3D classes of dsm_cls_fp are not the scene's
-label set), finite-sigma splats, slanted or perspective map cameras, RPC tags.
+Out of scope: finite-sigma splats, slanted or perspective map cameras, RPC tags.  Map-space accuracy is eval/utils/orthorect.py: the
+ground-truth class raster is the scene's own labels, orthorectified and voted (the US3D classes of dsm_cls_fp are not the scene's
+label set).
 
 nadir_sun_sweep renders that map under a list of suns in one walk: per chunk one full pass and one relight
 per further sun -- the shadow maps of a day, or the scene lit as each of its acquisitions saw it."""
