@@ -249,7 +249,7 @@ int snerf_sample_z(const float* rays, const float* z_steps, const float* u, floa
  * snerf_embedding_rows: rows[n][:] = table[idx[n]][:]  (forward; idx is int64 as torch hands it over).
  * snerf_embedding_backward: grad_table[v][:] += sum over the rays n with idx[n] == v of d_rows[n][:], summed in a fixed
  * order (no atomics: the gradient is bitwise reproducible, like every other one of the path).  Indices outside
- * [0, n_embed) give zero rows in the forward and are skipped in the backward (torch's nn.Embedding asserts on the device). */
+ * [0, n_embed) give NaN rows in the forward and are skipped in the backward (torch's nn.Embedding asserts on the device). */
 int snerf_embedding_rows(const float* table, int n_embed, int tau, const long long* idx, int n, float* rows, void* stream);
 int snerf_embedding_backward(const long long* idx, const float* d_rows, int n, int tau, int n_embed, float* grad_table, void* stream);
 

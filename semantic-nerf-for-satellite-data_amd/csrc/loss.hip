@@ -22,7 +22,7 @@ __device__ __forceinline__ RayLoss ray_loss(const SnerfLossCfg& c, const SnerfLo
     if (c.color_mode == 2 || c.sem_mode == 2 || c.car_reg) {
       const float w = in.weights[p];
       wb += w * in.beta[p];
-      if (c.use_sbeta) wbs += w * in.beta_semantic[p];
+      if (c.use_sbeta && c.sem_mode == 2) wbs += w * in.beta_semantic[p];   // wbs feeds the uncertainty CE alone: the one mode check_loss requires the pointer for
     }
     if (c.has_sc) {
       const float v = in.sun_sc[p];

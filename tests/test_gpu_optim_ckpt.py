@@ -121,14 +121,18 @@ def test_checkpoint_resume_continues_the_same_trajectory(tmp_path):
     assert only and all(k.startswith("fc_net") for k in only)
 
 
-@pytest.mark.parametrize("env", [{"SNERF_PREFETCH": "0"}, {"SNERF_MAX_LEAD": "0"}, {"SNERF_MAX_LEAD": "1"}, {"SNERF_MERGE_LOSSES": "0"}])
+@pytest.mark.parametrize("env", [{"SNERF_PREFETCH": "0"}, {"SNERF_MAX_LEAD": "0"}, {"SNERF_MAX_LEAD": "1"}, {"SNERF_MERGE_LOSSES": "0"},
+                                 {"SNERF_OVERLAP_SC": "0"}, {"SNERF_GRAD_SINKS": "0"}])
 def test_trainloop_host_side_switches_do_not_change_the_trajectory(env, monkeypatch):
     """Batch prefetch on a data stream, the bound on the host's lead and the merged loss call are scheduling: the same seeded steps give
     the same losses (bit for bit for the first two; the merged loss call sums its terms in one kernel instead of module by module) and
     the same weights, across an epoch boundary (a new permutation of the bank drawn by the prefetching side) and a jump in the step
-    index (a prefetched batch that is not the one asked for)."""
+    index (a prefetched batch that is not the one asked for).  So are the two-stream overlap of the main and the solar-correction pass
+    (SNERF_OVERLAP_SC=0 serialises them: bit for bit) and the gradient sinks (SNERF_GRAD_SINKS=0 hands the gradients back to autograd:
+    at the fp32-summation-order bar of test_gradient_sinks_equal_autograd_accumulation, 1e-6 of the largest magnitude)."""
     import importlib
-    from snerf_amd import loss_ops
+    from snerf_amd import loss_ops, ops
+    from snerf_amd.semantic.components import rendering
     def run():
         loop = _loop(seed=11)
         spe = loop.steps_per_epoch
@@ -143,8 +147,16 @@ def test_trainloop_host_side_switches_do_not_change_the_trajectory(env, monkeypa
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     monkeypatch.setattr(loss_ops, "_MERGE", env.get("SNERF_MERGE_LOSSES", "1") != "0")
+    monkeypatch.setattr(rendering, "OVERLAP_SC_PASS", env.get("SNERF_OVERLAP_SC", "1") != "0")      # (module constants, read at import)
+    monkeypatch.setattr(ops, "_SINKS_ON", env.get("SNERF_GRAD_SINKS", "1") != "0")
     got_l, got_w = run()
-    if "SNERF_MERGE_LOSSES" in env:
+    if "SNERF_GRAD_SINKS" in env:
+        dl = max(abs(a_ - b_) for a_, b_ in zip(base_l, got_l))
+        print(f"sinks off vs on: max |dloss| {dl:.3e}, max |dweight| {max(max_abs(a_.cpu(), b_.cpu()) for a_, b_ in zip(base_w, got_w)):.3e}")
+        assert dl <= 1e-6 * max(abs(x) for x in base_l), (base_l, got_l)
+        for a_, b_ in zip(base_w, got_w):
+            assert max_abs(a_.cpu(), b_.cpu()) <= 1e-6 * float(a_.abs().max())
+    elif "SNERF_MERGE_LOSSES" in env:
         assert np.allclose(base_l, got_l, rtol=2e-6, atol=0), (base_l, got_l)
         for a_, b_ in zip(base_w, got_w):
             assert torch.allclose(a_, b_, rtol=0, atol=2e-6)
