@@ -250,10 +250,19 @@ EXTENSION_SIGNATURES = {
     "snerf_orthorect.h": {"snerf_orthorectify": (C.c_int, (C.c_void_p, C.POINTER(SnerfDsmGrid), C.c_double, C.c_int, C.c_void_p, C.c_void_p,
                                                           C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int) + (C.c_void_p,) * 9 + (c_stream,))},
 }
+# A further table of the same kind (tests/test_orthorect_cpu.py pins the one above to its single header): the entries of
+# include/snerf_raycast.h (tests/test_raycast_cpu.py compares them with it).
+RAYCAST_SIGNATURES = {
+    "snerf_raycast.h": {"snerf_dsm_segment_hit": (C.c_int, (C.c_void_p, C.c_void_p, C.c_longlong, C.POINTER(SnerfDsmGrid), C.c_void_p,
+                                                            C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, c_stream))},
+}
 _ALL_SIGNATURES = dict(SIGNATURES)
-for _rows in EXTENSION_SIGNATURES.values():
-    assert not set(_rows) & set(_ALL_SIGNATURES)
-    _ALL_SIGNATURES.update(_rows)
+for _table in (EXTENSION_SIGNATURES, RAYCAST_SIGNATURES):
+    for _rows in _table.values():
+        assert not set(_rows) & set(_ALL_SIGNATURES)
+        _ALL_SIGNATURES.update(_rows)
+
+HIT_TOP, HIT_WALL, HIT_START, HIT_END, HIT_OUTSIDE, HIT_BAD = range(6)     # include/snerf_raycast.h SNERF_HIT_*
 
 SHADOW_MAX_SUNS = 64       # include/snerf_hip.h SNERF_SHADOW_MAX_SUNS
 SHADOW_UNKNOWN = 255       # include/snerf_hip.h SNERF_SHADOW_UNKNOWN

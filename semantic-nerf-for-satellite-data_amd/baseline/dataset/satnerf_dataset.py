@@ -206,7 +206,8 @@ class SatNeRFDataset:
 def load_scene_banks(cfgs, semantic: bool, depth: bool, device=None, seed=0) -> dict:
     """the pipeline's datasets from `run.dataset_dp`, in the order of base_ray_pipeline.py:198-244 (_handle_normalization):
     train and test rays built, normalisation parameters from both (or read from norm_params.json), both normalised, then
-    the depth set built and normalised with the same parameters.  Returns {"rgb", "rgb_test"[, "depth"]} GpuRayBanks; the
+    the depth set built and normalised with the same parameters (pipeline.depth_source: the tie points, a DSM seen through the
+    training rays -- dsm_depth_dataset.py --, or both).  Returns {"rgb", "rgb_test"[, "depth"]} GpuRayBanks; the
     test bank's `scene_images()` gives the per-image dicts of the evaluation functions."""
     from ..components.normalization import StandardNormalization
     from ...parallel import world
@@ -220,10 +221,22 @@ def load_scene_banks(cfgs, semantic: bool, depth: bool, device=None, seed=0) -> 
         norm.normalize_rays_(ds.t["rays"])
         ds.attach_normalization(norm)
     out = {"rgb": train.bank(seed=seed), "rgb_test": test.bank(seed=seed + 1)}
-    if depth:
+    source = getattr(cfgs.pipeline, "depth_source", "tie_points") if depth else None
+    if depth and source == "tie_points":
         from .satnerf_depth_dataset import SatNeRFDepthDataset
         out["depth"] = SatNeRFDepthDataset(cfgs, device).load(norm).bank(out["rgb"].semantic_n_classes, out["rgb"].car_cls_idx,
                                                                         seed=seed + 2)
+    elif depth:
+        # depth_source "dsm": the dense prior alone (a scene without points3d_fp will do); "both": the tie points' rows, then the prior's
+        from .dsm_depth_dataset import DsmDepthDataset, prior_settings
+        prior_settings(cfgs.pipeline)
+        parts = []
+        if source == "both":
+            from .satnerf_depth_dataset import SatNeRFDepthDataset
+            parts.append(SatNeRFDepthDataset(cfgs, device).load(norm).t)
+        parts.append(DsmDepthDataset(cfgs, device).load(norm).t)
+        t = parts[0] if len(parts) == 1 else {k: torch.cat([p[k] for p in parts], 0) for k in parts[0]}
+        out["depth"] = GpuRayBank(t, n_classes=out["rgb"].semantic_n_classes, car_cls_idx=out["rgb"].car_cls_idx, seed=seed + 2)
     for b in out.values():
         b.normalization = norm
     out["rgb"].dataset, out["rgb_test"].dataset = train, test

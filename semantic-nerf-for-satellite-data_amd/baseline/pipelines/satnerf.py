@@ -78,6 +78,19 @@ class SatNeRFConfig(SNeRFConfig):
     t_embedding_vocab: int = 50
     t_embedding_tau: int = 4
     ds_noweights: Union[bool, int] = False
+    # build extension: what feeds the depth branch of a scene loaded from disk -- the bundle-adjustment tie
+    # points (the reference), a DSM GeoTIFF seen through every depth_prior_stride-th pixel's ray (baseline/dataset/
+    # dsm_depth_dataset.py), or both; depth_prior_weight is the constant weight of the prior's rows
+    depth_source: Literal["tie_points", "dsm", "both"] = "tie_points"
+    depth_prior_dsm_fp: str = ""
+    depth_prior_stride: int = 4
+    depth_prior_weight: float = 1.0
+
+    @model_validator(mode="after")
+    def _check_depth_prior(self):
+        from ..dataset.dsm_depth_dataset import prior_settings
+        prior_settings(self)
+        return self
 
 
 class SatNeRFPipeline(BaseRayPipeline):

@@ -7,7 +7,7 @@ reference's un-normalised UTM cloud comes from one more launch (csrc/geo.hip); t
 import numpy as np
 import torch
 
-from .utils.util import lean_inference, sharded_lean_inference, with_depth_mode
+from .utils.util import guided_lean_inference, lean_inference, sharded_lean_inference, with_depth_mode
 
 
 def get_xyz_from_nerf_prediction(rays: torch.Tensor, depth: torch.Tensor) -> torch.Tensor:
@@ -19,7 +19,7 @@ def get_xyz_from_nerf_prediction(rays: torch.Tensor, depth: torch.Tensor) -> tor
 
 @torch.no_grad()
 def extract_pointcloud(cfgs, renderer, models, rays, extras, render_options=None, with_labels=None, sharded=False, geo=None,
-                       with_colors=True, depth_mode="mean"):
+                       with_colors=True, depth_mode="mean", guide=None):
     """One image -> {"xyz_n" (R,3) f64, "colors" (R,3) f32, "depth" (R) f32 [, "labels" (R) i64]}, all on the device.
     `with_colors=False` leaves "colors" out; without labels either, the walk asks for the depth alone and runs as geometry passes
     (eval/utils/util.py: relight_chunks) -- no head launch, the same depth bits, hence the same cloud.
@@ -28,19 +28,29 @@ def extract_pointcloud(cfgs, renderer, models, rays, extras, render_options=None
     inside a data-parallel run).  `sharded=True` is a COLLECTIVE: every rank of the group must call it with the same rays;
     the image is rendered in rank shards and the per-ray results gathered, so every rank returns the whole cloud
     (eval/utils/util.py: sharded_lean_inference).
-    `depth_mode="median"` places every point at its ray's median depth (SNERF_FLAG_DEPTH_MEDIAN) instead of the expected depth."""
+    `depth_mode="median"` places every point at its ray's median depth (SNERF_FLAG_DEPTH_MEDIAN) instead of the expected depth.
+    `guide` (eval/utils/raycast.py DsmGuide): render with guide.n_samples depths in a band round each ray's hit on the guide's DSM
+    (eval/utils/util.py guided_lean_inference) and add "guide_state" (R) u8; not with `sharded` (ValueError).  None (default):
+    every path above as it was."""
+    if guide is not None and sharded:
+        raise ValueError("extract_pointcloud: guide= is a single-device render; pass sharded=False")
     render_options = with_depth_mode(render_options, depth_mode, "extract_pointcloud")
     sem = models["coarse"].spec.n_classes > 0
     if with_labels is None:
         with_labels = sem
     keys = (["rgb_coarse"] if with_colors else []) + ["depth_coarse"] + (["semantic_label_coarse"] if with_labels and sem else [])
     infer = sharded_lean_inference if sharded else lean_inference
-    res = infer(cfgs, renderer, models, rays, extras, keys=keys, render_options=render_options or {})
+    if guide is not None:
+        res = guided_lean_inference(cfgs, renderer, models, rays, extras, guide, keys=keys, render_options=render_options or {})
+    else:
+        res = infer(cfgs, renderer, models, rays, extras, keys=keys, render_options=render_options or {})
     out = {"xyz_n": get_xyz_from_nerf_prediction(rays, res["depth_coarse"]), "depth": res["depth_coarse"]}
     if with_colors:
         out["colors"] = res["rgb_coarse"]
     if "semantic_label_coarse" in res:
         out["labels"] = res["semantic_label_coarse"]
+    if guide is not None:
+        out["guide_state"] = res["guide_state"]
     if geo is not None:
         out["xyz_utm"] = geo.cloud(rays, res["depth_coarse"])[0]
     return out

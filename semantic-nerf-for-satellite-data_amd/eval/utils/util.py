@@ -3,7 +3,7 @@ from collections import defaultdict
 
 import torch
 
-from ...framework.components.rendering import bare_key as _bare, depth_mode_of, n_render_samples
+from ...framework.components.rendering import bare_key as _bare, depth_mode_of, n_render_samples, z_steps_on
 
 _PER_RAY_OPTIONS = ("perturb_rand", "given_z_vals", "importance_rand")   # (N, S) / (N, S') / (N, Ni) tensors a caller may pin for the whole frame
 
@@ -187,6 +187,46 @@ def lean_relight(cfgs, renderer, models, rays, extras, suns, keys=("rgb_coarse",
 
 
 PER_RAY_RESULTS = ("rgb", "depth", "semantic_label", "semantic_logits")   # (N, ...) results: what a frame / point cloud is made of
+
+
+@torch.no_grad()
+def guided_lean_inference(cfgs, renderer, models, rays, extras, guide, keys=("rgb_coarse", "depth_coarse", "semantic_label_coarse"),
+                          render_options={}, show_tqdm=False):
+    """lean_inference with the samples of every ray that meets a DSM placed in a band round the hit, not over the whole
+    [near, far] slab.  `guide` (eval/utils/raycast.py DsmGuide) carries frame, grid, dsm, bias, front_m,
+    back_m and n_samples: the rays are cast on the DSM (raycast.cast_rays), the near / far of the rows that hit are narrowed
+    (raycast.guide_rays), ops.sample_z spreads guide.n_samples depths over every ray's -- narrowed or full -- bounds without jitter,
+    and lean_inference renders the guided rays under {"given_z_vals": z, "perturb": 0}.  A pass costs about in proportion to its
+    samples, so a quarter of the samples is about a quarter of the render.  Rows without a hit (END, OUTSIDE) are rendered over their
+    full bounds with the same guide.n_samples.
+    Only per-ray results may be asked for (PER_RAY_RESULTS and 'depth'): a per-sample key is a KeyError, because the frame buffers
+    take their width from the config, not from the guide.  `given_z_vals` bypasses the proposal pass, so n_importance is not
+    honoured here: the guide takes its place.  render_options may not pin depths or jitter of its own ("given_z_vals",
+    "perturb_rand", "importance_rand": ValueError).  render_options["depth_mode"] = "median" works at the guided width: the median
+    launch takes its sample count from the pass, and its scratch is sized by it (ops.render_pass_into).
+    Returns lean_inference's results plus "guide_state" (n) u8, the cast's state per ray (raycast.TOP ... raycast.BAD)."""
+    from ... import ops
+    from . import raycast
+    for k in keys:
+        if _bare(k) not in _KEY_SHAPES:
+            raise KeyError(f"guided_lean_inference: unknown result '{k}'")
+        if _bare(k) not in PER_RAY_RESULTS:
+            raise KeyError(f"guided_lean_inference: '{k}' is a per-sample result; only per-ray results {PER_RAY_RESULTS} can be asked "
+                           "for (the frame buffers take their width from the config, not from the guide)")
+    for k in _PER_RAY_OPTIONS:
+        if (render_options or {}).get(k) is not None:
+            raise ValueError(f"guided_lean_inference: render_options['{k}'] cannot be pinned: the guide places the depths")
+    S = int(guide.n_samples)
+    if S < 1:
+        raise ValueError(f"guided_lean_inference: guide.n_samples = {guide.n_samples} must be >= 1")
+    cast = raycast.cast_rays(rays, guide.frame, guide.grid, guide.dsm, guide.bias)
+    guided, _ = raycast.guide_rays(rays, cast, guide.front_m, guide.back_m, guide.frame.params.range)
+    opts = dict(render_options) if render_options else {}
+    opts["given_z_vals"] = ops.sample_z(guided[:, :8], z_steps_on(rays.device, S), None)      # (snerf_sample_z reads rows of 8 columns)
+    opts["perturb"] = 0
+    out = lean_inference(cfgs, renderer, models, guided, extras, keys=keys, render_options=opts, show_tqdm=show_tqdm)
+    out["guide_state"] = cast["state"]
+    return out
 
 
 def shard_and_gather(render_rows, n: int, rank: int = None, world: int = None) -> dict:
