@@ -256,8 +256,20 @@ RAYCAST_SIGNATURES = {
     "snerf_raycast.h": {"snerf_dsm_segment_hit": (C.c_int, (C.c_void_p, C.c_void_p, C.c_longlong, C.POINTER(SnerfDsmGrid), C.c_void_p,
                                                             C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, c_stream))},
 }
+# And one more: the entries of include/snerf_fuse.h (tests/test_fuse_cpu.py compares them with it).  quantiles_host is a HOST table
+# (a ctypes array): void*, as suns_host.
+FUSE_SIGNATURES = {
+    "snerf_fuse.h": {
+        "snerf_fuse_count": (C.c_int, (C.c_void_p, C.c_longlong, C.POINTER(SnerfDsmGrid), C.c_int, C.c_double, C.c_double, C.c_void_p,
+                                       C.c_void_p, c_stream)),
+        "snerf_fuse_scatter": (C.c_int, (C.c_void_p, C.c_longlong, C.c_longlong, C.POINTER(SnerfDsmGrid), C.c_int, C.c_double, C.c_double,
+                                         C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, c_stream)),
+        "snerf_fuse_select": (C.c_int, (C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_void_p,
+                                        C.c_void_p, c_stream)),
+    },
+}
 _ALL_SIGNATURES = dict(SIGNATURES)
-for _table in (EXTENSION_SIGNATURES, RAYCAST_SIGNATURES):
+for _table in (EXTENSION_SIGNATURES, RAYCAST_SIGNATURES, FUSE_SIGNATURES):
     for _rows in _table.values():
         assert not set(_rows) & set(_ALL_SIGNATURES)
         _ALL_SIGNATURES.update(_rows)
@@ -270,6 +282,7 @@ SHADOW_UNKNOWN = 255       # include/snerf_hip.h SNERF_SHADOW_UNKNOWN
 ORTHO_MAX_RADIUS = 7       # include/snerf_hip.h SNERF_ORTHO_MAX_RADIUS
 ORTHO_MAX_CLASSES = 255    # include/snerf_hip.h SNERF_ORTHO_MAX_CLASSES
 ORTHO_NO_LABEL = 255       # include/snerf_hip.h SNERF_ORTHO_NO_LABEL
+FUSE_MAX_QUANTILES = 8     # include/snerf_fuse.h SNERF_FUSE_MAX_QUANTILES
 
 # symbol -> (per argument a caller of call() passes: int / float for a scalar slot, None for a pointer slot; whether a trailing
 # stream follows them)

@@ -31,6 +31,20 @@ __device__ __forceinline__ CellWindow cell_window(double x, double y, const Sner
   return w;
 }
 
+// The 64-bit key of a point on this lattice, as snerf_ortho_top (csrc/ortho.hip) and the fuse entries (csrc/fuse.hip) share it:
+// (quantised altitude + 2^31) << 32 | (2^32 - 1 - global index), the quantised altitude rint((z - z0) / q) in [-2^31, 2^31).
+// false (and no key) for an altitude whose quantised value is not finite or out of range.  Ascending keys are ascending
+// altitudes and, at one altitude, descending indices; no key is 0.
+constexpr long long ORTHO_MAX_N = 2147483648LL;          // 2^31
+constexpr long long ORTHO_MAX_INDEX = 4294967295LL;      // 2^32 - 1: index0 + n may not exceed it
+
+__device__ __forceinline__ bool lattice_key(double z, double z0, double q, unsigned long long index, unsigned long long* key) {
+  const double kq = rint((z - z0) / q);
+  if (!(kq >= -2147483648.0 && kq < 2147483648.0)) return false;
+  *key = ((unsigned long long)((long long)kq + 2147483648LL) << 32) | (0xFFFFFFFFull - index);
+  return true;
+}
+
 // the grid of an accumulating entry: res > 0, finite offsets, positive sizes
 static inline bool lattice_grid_ok(const char* who, const SnerfDsmGrid* g) {
   if (g->res > 0.0 && isfinite(g->res) && isfinite(g->xoff) && isfinite(g->yoff) && g->xsize > 0 && g->ysize > 0 && g->out_w > 0 &&

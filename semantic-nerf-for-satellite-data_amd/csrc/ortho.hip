@@ -10,8 +10,6 @@
 
 namespace snerf {
 
-constexpr long long ORTHO_MAX_N = 2147483648LL;          // 2^31
-constexpr long long ORTHO_MAX_INDEX = 4294967295LL;      // 2^32 - 1: index0 + n may not exceed it
 constexpr int ORTHO_THREADS = 256;
 constexpr unsigned ORTHO_MAX_BLOCKS = 4096;
 
@@ -24,12 +22,10 @@ __global__ __launch_bounds__(ORTHO_THREADS) void ortho_top_kernel(const double* 
   unsigned long long bad = 0, reached = 0;
   for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (long long)gridDim.x * blockDim.x) {
     const double x = xyz[3 * p], y = xyz[3 * p + 1], z = xyz[3 * p + 2];
-    const double kq = rint((z - z0) / q);
-    if (!(kq >= -2147483648.0 && kq < 2147483648.0)) { bad++; continue; }
+    unsigned long long key;
+    if (!lattice_key(z, z0, q, index0 + (unsigned long long)p, &key)) { bad++; continue; }
     const CellWindow w = cell_window(x, y, g, r);
     if (w.i0 >= w.i1 || w.j0 >= w.j1) continue;
-    const unsigned long long key = ((unsigned long long)((long long)kq + 2147483648LL) << 32) |
-                                   (0xFFFFFFFFull - (index0 + (unsigned long long)p));
     for (long long lj = w.j0; lj < w.j1; ++lj)
       for (long long li = w.i0; li < w.i1; ++li) atomicMax(&top[(lj - g.joff) * g.out_w + (li - g.ioff)], key);
     reached++;

@@ -9,6 +9,12 @@ Files under `output_dp`/ortho/{split}/:
     top_alt.png/.tif, dsm.png/.tif       the top-surface altitude and the mean DSM: float32 in the .tif (NaN = no data), JET
                                          between the plane's own bounds in the .png (NaN as the colormap treats it: as 0)
     vote_share.png/.tif                  the winning class's share of a cell's votes: float32, BONE in the .png
+  with robust=True (eval/utils/fuse.py) also:
+    median_alt.png/.tif                  the lower median of the views' altitudes in a cell: float32, JET in the .png
+    alt_spread.png/.tif                  the interquartile spread of those altitudes -- where the views agree: float32, BONE
+    offers.png/.tif                      the points that offered themselves to a cell (as float32, the coverage's rule), BONE
+    rgb_median.png/.tif, label_median.png/.tif   the colour and the class of the median point, written as rgb and label_top are
+    fused_eval.json                      with gt=: {"mae": {"dsm", "top_alt", "median_alt"}}, each {"mean", "median"} in metres
 GeoTIFFs carry ModelPixelScale, ModelTiepoint and, with the scene's zone, a GeoKeyDirectory (img_utils.save_geotiff).
 
 export_nadir writes the map rendered from above (eval/utils/ortho.py nadir_products) by the same writers
@@ -136,8 +142,18 @@ def export_ortho(cfgs, renderer, models, images, output_dp, split="test", palett
         planes = [("top_alt", colormaps.COLORMAP_JET), ("dsm", colormaps.COLORMAP_JET)]
         if "vote_share" in prod:
             planes.append(("vote_share", colormaps.COLORMAP_BONE))
+        if "median_alt" in prod:                             # robust=True: the fused quantiles
+            planes += [("median_alt", colormaps.COLORMAP_JET), ("alt_spread", colormaps.COLORMAP_BONE)]
+            _color_plane(fp, "rgb_median", torch.nan_to_num(prod["rgb_median"], nan=0.0), grid, zone_string)
+            if "label_median" in prod:
+                _label_plane(fp, "label_median", prod["label_median"], palette, grid, zone_string)
         for key, cmap in planes:
             _scalar_plane(fp, key, prod[key], cmap, grid, zone_string)
+        if "offers" in prod:
+            _scalar_plane(fp, "offers", prod["offers"].to(torch.float32), colormaps.COLORMAP_BONE, grid, zone_string)
+        if "mae" in prod:
+            with open(fp("fused_eval.json"), "w") as f:
+                json.dump({"mae": prod["mae"]}, f, indent=1)
     return dict(prod, files=files)
 
 

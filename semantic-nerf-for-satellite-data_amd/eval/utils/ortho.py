@@ -17,7 +17,8 @@ Votes -- every point adds 1 to votes[label][cell] over the same window (integer 
 (the lowest class on a tie, 255 for a cell without a vote) and the winner's share of the cell's votes.
 
 ortho_products walks a set of images and returns the fused map; eval/ortho.py writes it (PNG and GeoTIFF).  A splatted map has
-cells no view's point reaches, and its occlusion is "the highest point wins".
+cells no view's point reaches, and its occlusion is "the highest point wins".  With robust=True it adds the per-cell quartiles of
+the views' altitudes (eval/utils/fuse.py): the median surface, its colour and label, and the spread.
 
 nadir_products asks the model instead: one vertical ray per cell of the lattice
 (baseline/components/rays.py nadir_construct, through GeoFrame.to_scene), rendered under a chosen sun -- a DSM without holes, a
@@ -139,7 +140,8 @@ def _flat(img, key):
 
 @torch.no_grad()
 def ortho_products(cfgs, renderer, models, images, geo=None, roi=None, resolution=D.RESOLUTION, radius=0, dsm_radius=1,
-                   sharded=False, grid=None, render_options={}, depth_mode="mean"):
+                   sharded=False, grid=None, render_options={}, depth_mode="mean", robust=False, gt=None, water_mask=None,
+                   ignore_mask=None):
     """The fused map of `images` (dicts with the evaluators' keys: "rays", "extras"[, "dsm": {"geo": GeoFrame}]).
 
     Per image, in the order given: lean_inference (sharded_lean_inference with `sharded`: every rank then holds the whole
@@ -158,8 +160,20 @@ def ortho_products(cfgs, renderer, models, images, geo=None, roi=None, resolutio
     "top_alt": (H, W) f32, "top_index": (H, W) int64 (index into the concatenated rays, -1 where empty), "rgb": (3, H, W) f32
     (NaN where empty)[, "label_top": (H, W) u8, "label_vote": (H, W) u8, "vote_share": (H, W) f32], "n_points", "bad_points"
     (altitudes that are not finite or beyond +-32,768 m: left out of the top surface), "bad_labels" (labels outside the
-    model's classes: no vote), "max_votes"}."""
+    model's classes: no vote), "max_votes"}.
+
+    `robust=True` adds the order statistics of the views' altitudes per cell (eval/utils/fuse.py), on the top
+    surface's `radius`, Z0 and Q: every cloud is made again by one launch for the count walk and once more for the scatter walk
+    (nothing is rendered twice), then "median_alt" (H, W) f32 -- the lower median, an actual point --, "median_index" (H, W) int64,
+    "rgb_median" (3, H, W) f32[, "label_median" (H, W) u8] gathered once per image from the median words as the top surface's are
+    from its words, "alt_q1" / "alt_q3" (H, W) f32, "alt_spread" (H, W) f32 (q3 - q1, exact in the quantised altitudes: where the
+    views agree) and "offers" (H, W) int32 (the points that offered themselves to a cell).  With `gt` (H, W) on the product's lattice
+    (and `water_mask` / `ignore_mask`, as nadir_products takes them; robust only): "mae": {"dsm", "top_alt", "median_alt"}, each
+    {"mean", "median"} of dsm.compute_mae with the same masks.  Without `robust` no fuse entry is called and the result is what
+    it was."""
     from .util import lean_inference, sharded_lean_inference, with_depth_mode
+    if gt is not None and not robust:
+        raise ValueError("ortho_products: gt= scores the fused surfaces and needs robust=True")
     render_options = with_depth_mode(render_options, depth_mode, "ortho_products")
     images = list(images)
     if not images:
@@ -223,6 +237,21 @@ def ortho_products(cfgs, renderer, models, images, geo=None, roi=None, resolutio
             raise OverflowError(f"ortho_products: a cell received {max_votes} votes, its u32 counts could have wrapped")
         res.update(bad_labels=bad_labels, max_votes=max_votes)
     res["bad_points"] = bad_points
+    if robust:
+        from . import fuse as F
+        words, count, _ = F.fuse_walks(lambda: ((f["geo"].cloud(f["rays"], f["depth"])[0], f["index0"]) for f in frames), acc["g"], radius)
+        med = None
+        for f in frames:
+            med = gather(words[1], f["index0"], f["n"], rgb=f["rgb"], labels=f["labels"], out=med)
+        res.update(median_alt=med["alt"], median_index=med["index"], rgb_median=med["rgb"], alt_q1=gather(words[0], 0, 1)["alt"],
+                   alt_q3=gather(words[2], 0, 1)["alt"], alt_spread=F.spread(words[0], words[2]), offers=count)
+        if n_classes:
+            res["label_median"] = med["label"]
+        if gt is not None:
+            res["mae"] = {}
+            for key in ("dsm", "top_alt", "median_alt"):
+                mae = D.compute_mae(res[key], gt, water_mask=water_mask, ignore_mask=ignore_mask)
+                res["mae"][key] = {"mean": mae["mean"], "median": mae["median"]}
     return res
 
 
