@@ -268,8 +268,17 @@ FUSE_SIGNATURES = {
                                         C.c_void_p, c_stream)),
     },
 }
+# And the entries of include/snerf_objects.h (tests/test_objects_cpu.py compares them with it).  member_host and ground_host are HOST
+# tables (ctypes arrays of 256 bytes): void*.
+OBJECTS_SIGNATURES = {
+    "snerf_objects.h": {
+        "snerf_objects_link": (C.c_int, (C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, c_stream)),
+        "snerf_objects_stats": (C.c_int, (C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_int,
+                                          C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, c_stream)),
+    },
+}
 _ALL_SIGNATURES = dict(SIGNATURES)
-for _table in (EXTENSION_SIGNATURES, RAYCAST_SIGNATURES, FUSE_SIGNATURES):
+for _table in (EXTENSION_SIGNATURES, RAYCAST_SIGNATURES, FUSE_SIGNATURES, OBJECTS_SIGNATURES):
     for _rows in _table.values():
         assert not set(_rows) & set(_ALL_SIGNATURES)
         _ALL_SIGNATURES.update(_rows)
@@ -283,6 +292,7 @@ ORTHO_MAX_RADIUS = 7       # include/snerf_hip.h SNERF_ORTHO_MAX_RADIUS
 ORTHO_MAX_CLASSES = 255    # include/snerf_hip.h SNERF_ORTHO_MAX_CLASSES
 ORTHO_NO_LABEL = 255       # include/snerf_hip.h SNERF_ORTHO_NO_LABEL
 FUSE_MAX_QUANTILES = 8     # include/snerf_fuse.h SNERF_FUSE_MAX_QUANTILES
+OBJECTS_ROW_WORDS = 16     # include/snerf_objects.h SNERF_OBJECTS_ROW_WORDS
 
 # symbol -> (per argument a caller of call() passes: int / float for a scalar slot, None for a pointer slot; whether a trailing
 # stream follows them)

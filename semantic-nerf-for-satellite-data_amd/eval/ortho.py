@@ -48,6 +48,14 @@ model's map products on the same grid, scores them against the mosaic.  Files un
     map_eval.json                        with model_products=: PSNR of its colour and, per label plane, the confusion matrix against
                                          the voted labels, accuracy, mIoU and the compared cells
 
+export_objects labels the buildings of any of these maps and measures them (eval/utils/objects.py).  Files under
+`output_dp`/objects/:
+    objects.json                         per object: class, area, centroid, bbox, perimeter, altitudes, ground, height, volume
+    objects_ids.png/.tif                 the object id of every cell (0 = none): float32 in the .tif, a colour per id in the .png
+    objects_height.png/.tif              the height of the cell's object over the ground round it: float32 (NaN off objects), JET
+    reference_objects.json, objects_eval.json   with reference=: the ground truth's objects, and detection precision / recall / F1,
+                                         footprint IoU and the height error of the matched objects
+
 The other exports hand their keyword arguments to their products function, `depth_mode="median"` among them: the altitudes and everything
 built on them are then those of the rays' median depths; at the default every file is what it was."""
 import json
@@ -297,3 +305,64 @@ def export_shadow_check(cfgs, renderer, models, output_dp, zone_string=None, bia
         with open(fp("shadow_check.json"), "w") as f:
             json.dump(doc, f, indent=1)
     return dict(prod, shadow_check=chk, files=files)
+
+
+def id_colors(ids):
+    """(H, W) int32 object ids -> (3, H, W) uint8: every object in a colour taken from its id (three multiplicative hashes, kept
+    off the dark end), the background black"""
+    n = ids.long()
+    rgb = torch.stack([(n * m + a) % 192 + 64 for m, a in ((97, 53), (57, 131), (151, 17))]).to(torch.uint8)
+    return torch.where((n > 0).unsqueeze(0), rgb, torch.zeros_like(rgb)).contiguous()
+
+
+@torch.no_grad()
+def export_objects(products, output_dp, classes=(3,), ground=(0,), label_key=None, alt_key=None, reference=None, zone_string=None,
+                   palette=None, **kwargs):
+    """The objects of a map (eval/utils/objects.py objects), written to `output_dp`/objects/.  `products`: what
+    nadir_products, ortho_products or orthorect.rectify return ("grid" and a label and an altitude plane).  `label_key`: default the
+    first of "label", "label_vote", "label_median", "label_top" present; `alt_key`: the first of "dsm", "median_alt", "top_alt".
+    `classes`: the classes whose components are objects, `ground`: the classes that count as ground round an object -- the defaults
+    (3,) and (0,) are the building and the ground entry of colormaps.DEFAULT_PALETTE's list; a scene with other class ids passes its
+    own.  **kwargs (connectivity, ring, min_area_m2) go to objects().  `reference`: {"label", "alt"} on the same lattice -- for
+    example rectify(lidar_dsm, ...)["label_vote"] with the lidar DSM -- whose objects the map's are scored against (match_objects,
+    object_scores); a lattice mismatch is a ValueError that names both shapes.  `palette` is taken as the other exports take it; no
+    file of this export shows class colours (an object's colour comes from its id), so it is not read.
+    Files: objects.json ({"objects": the table as records, "stats", "parameters"}), objects_ids.tif (float32: ids are exact below
+    2^24, a ValueError beyond) and objects_ids.png (each object in a colour taken from its id), objects_height.tif / .png (the height
+    of the cell's object, NaN off objects; JET); with `reference` also reference_objects.json and objects_eval.json.  Only rank 0
+    writes.  Returns objects()'s result plus "files"[, "reference", "eval"]."""
+    from .utils import objects as OB
+    from .utils.ortho import window_grid
+    label_key = label_key or next((k for k in ("label", "label_vote", "label_median", "label_top") if k in products), None)
+    alt_key = alt_key or next((k for k in ("dsm", "median_alt", "top_alt") if k in products), None)
+    if label_key not in products or alt_key not in products:
+        raise ValueError(f"export_objects: the products hold no label plane ({label_key!r}) or no altitude plane ({alt_key!r})")
+    label, alt, grid = products[label_key], products[alt_key], window_grid(products["grid"])
+    shape = tuple(label.shape)
+    if reference is not None and (tuple(reference["label"].shape) != shape or tuple(reference["alt"].shape) != shape):
+        raise ValueError(f"export_objects: the products lie on a lattice of {tuple(label.shape)} cells, the reference on "
+                         f"{tuple(reference['label'].shape)} (label) / {tuple(reference['alt'].shape)} (alt)")
+    res = OB.objects(label, alt.float(), grid, classes, ground, **kwargs)
+    if res["n"] >= 2 ** 24:
+        raise ValueError(f"export_objects: {res['n']} objects: a float32 GeoTIFF holds ids exactly below 2^24 only")
+    params = dict({"classes": [int(c) for c in classes], "ground": [int(c) for c in ground], "label_key": label_key, "alt_key": alt_key},
+                  **kwargs)
+    if reference is not None:
+        ref = OB.objects(reference["label"], reference["alt"].float(), grid, classes, ground, **kwargs)
+        pairs, inter, union = OB.match_objects(res["ids"], res["n"], ref["ids"], ref["n"])
+        res = dict(res, reference=ref, eval=OB.object_scores(res["table"], ref["table"], pairs, inter, union))
+    zone_string = _zone(zone_string, kwargs)
+    files, fp = _writer(output_dp, "objects")
+    if fp:
+        with open(fp("objects.json"), "w") as f:
+            json.dump({"objects": OB.table_records(res["table"]), "stats": res["stats"], "parameters": params}, f, indent=1)
+        _png(fp("objects_ids.png"), id_colors(res["ids"]))
+        img_utils.save_geotiff(fp("objects_ids.tif"), res["ids"].to(torch.float32), grid, zone_string)
+        _scalar_plane(fp, "objects_height", res["object_height"], colormaps.COLORMAP_JET, grid, zone_string)
+        if reference is not None:
+            with open(fp("reference_objects.json"), "w") as f:
+                json.dump({"objects": OB.table_records(res["reference"]["table"]), "stats": res["reference"]["stats"],
+                           "parameters": params}, f, indent=1)
+            with open(fp("objects_eval.json"), "w") as f:
+                json.dump(res["eval"], f, indent=1)
+    return dict(res, files=files)
