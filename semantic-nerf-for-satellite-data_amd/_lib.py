@@ -277,8 +277,21 @@ OBJECTS_SIGNATURES = {
                                           C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, c_stream)),
     },
 }
+# And the entries of include/snerf_terrain.h (tests/test_terrain_cpu.py compares them with it).  blocked_host is a HOST table (a
+# ctypes array of 256 bytes): void*.  snerf_terrain_workspace_bytes returns a long long, -1 for a refusal.
+TERRAIN_SIGNATURES = {
+    "snerf_terrain.h": {
+        "snerf_terrain_workspace_bytes": (C.c_longlong, (C.c_int, C.c_int)),
+        "snerf_terrain_keys": (C.c_int, (C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, c_stream)),
+        "snerf_terrain_open": (C.c_int, (C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, c_stream)),
+        "snerf_terrain_fill": (C.c_int, (C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_stream)),
+    },
+}
 _ALL_SIGNATURES = dict(SIGNATURES)
-for _table in (EXTENSION_SIGNATURES, RAYCAST_SIGNATURES, FUSE_SIGNATURES, OBJECTS_SIGNATURES):
+for _table in (EXTENSION_SIGNATURES, RAYCAST_SIGNATURES, FUSE_SIGNATURES, OBJECTS_SIGNATURES, TERRAIN_SIGNATURES):
     for _rows in _table.values():
         assert not set(_rows) & set(_ALL_SIGNATURES)
         _ALL_SIGNATURES.update(_rows)
@@ -293,6 +306,9 @@ ORTHO_MAX_CLASSES = 255    # include/snerf_hip.h SNERF_ORTHO_MAX_CLASSES
 ORTHO_NO_LABEL = 255       # include/snerf_hip.h SNERF_ORTHO_NO_LABEL
 FUSE_MAX_QUANTILES = 8     # include/snerf_fuse.h SNERF_FUSE_MAX_QUANTILES
 OBJECTS_ROW_WORDS = 16     # include/snerf_objects.h SNERF_OBJECTS_ROW_WORDS
+TERRAIN_HOLE = -2 ** 31    # include/snerf_terrain.h SNERF_TERRAIN_HOLE
+TERRAIN_MAX_RADIUS = 512   # include/snerf_terrain.h SNERF_TERRAIN_MAX_RADIUS
+TERRAIN_FLAGGED, TERRAIN_BLOCKED, TERRAIN_IS_HOLE = 1, 2, 4     # include/snerf_terrain.h: the bits of a flags byte
 
 # symbol -> (per argument a caller of call() passes: int / float for a scalar slot, None for a pointer slot; whether a trailing
 # stream follows them)

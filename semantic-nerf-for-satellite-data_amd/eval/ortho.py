@@ -56,6 +56,13 @@ export_objects labels the buildings of any of these maps and measures them (eval
     reference_objects.json, objects_eval.json   with reference=: the ground truth's objects, and detection precision / recall / F1,
                                          footprint IoU and the height error of the matched objects
 
+export_terrain puts a bare-earth terrain under any of these maps (eval/utils/terrain.py).  Files under
+`output_dp`/terrain/:
+    dtm.png/.tif, ndsm.png/.tif          the terrain and the height above it: float32 in the .tif (NaN = unreachable), JET in the .png
+    ground.png, reach.png                the ground mask (white = ground) and the distance in cells to the ground a cell was filled from
+    terrain.json                         the schedule, the counts and the parameters
+    terrain_eval.json                    with reference=: DTM / nDSM errors and the ground masks' 2 x 2 table against its terrain
+
 The other exports hand their keyword arguments to their products function, `depth_mode="median"` among them: the altitudes and everything
 built on them are then those of the rays' median depths; at the default every file is what it was."""
 import json
@@ -317,7 +324,7 @@ def id_colors(ids):
 
 @torch.no_grad()
 def export_objects(products, output_dp, classes=(3,), ground=(0,), label_key=None, alt_key=None, reference=None, zone_string=None,
-                   palette=None, **kwargs):
+                   palette=None, dtm=None, **kwargs):
     """The objects of a map (eval/utils/objects.py objects), written to `output_dp`/objects/.  `products`: what
     nadir_products, ortho_products or orthorect.rectify return ("grid" and a label and an altitude plane).  `label_key`: default the
     first of "label", "label_vote", "label_median", "label_top" present; `alt_key`: the first of "dsm", "median_alt", "top_alt".
@@ -326,7 +333,8 @@ def export_objects(products, output_dp, classes=(3,), ground=(0,), label_key=Non
     own.  **kwargs (connectivity, ring, min_area_m2) go to objects().  `reference`: {"label", "alt"} on the same lattice -- for
     example rectify(lidar_dsm, ...)["label_vote"] with the lidar DSM -- whose objects the map's are scored against (match_objects,
     object_scores); a lattice mismatch is a ValueError that names both shapes.  `palette` is taken as the other exports take it; no
-    file of this export shows class colours (an object's colour comes from its id), so it is not read.
+    file of this export shows class colours (an object's colour comes from its id), so it is not read.  `dtm`: a terrain plane on
+    the products' lattice (export_terrain's "dtm"): the map's table gains terrain_alt, height_over_terrain, volume_over_terrain_m3.
     Files: objects.json ({"objects": the table as records, "stats", "parameters"}), objects_ids.tif (float32: ids are exact below
     2^24, a ValueError beyond) and objects_ids.png (each object in a colour taken from its id), objects_height.tif / .png (the height
     of the cell's object, NaN off objects; JET); with `reference` also reference_objects.json and objects_eval.json.  Only rank 0
@@ -342,7 +350,9 @@ def export_objects(products, output_dp, classes=(3,), ground=(0,), label_key=Non
     if reference is not None and (tuple(reference["label"].shape) != shape or tuple(reference["alt"].shape) != shape):
         raise ValueError(f"export_objects: the products lie on a lattice of {tuple(label.shape)} cells, the reference on "
                          f"{tuple(reference['label'].shape)} (label) / {tuple(reference['alt'].shape)} (alt)")
-    res = OB.objects(label, alt.float(), grid, classes, ground, **kwargs)
+    if dtm is not None and tuple(dtm.shape) != shape:
+        raise ValueError(f"export_objects: the products lie on a lattice of {shape} cells, the dtm on {tuple(dtm.shape)}")
+    res = OB.objects(label, alt.float(), grid, classes, ground, dtm=None if dtm is None else dtm.float(), **kwargs)
     if res["n"] >= 2 ** 24:
         raise ValueError(f"export_objects: {res['n']} objects: a float32 GeoTIFF holds ids exactly below 2^24 only")
     params = dict({"classes": [int(c) for c in classes], "ground": [int(c) for c in ground], "label_key": label_key, "alt_key": alt_key},
@@ -364,5 +374,55 @@ def export_objects(products, output_dp, classes=(3,), ground=(0,), label_key=Non
                 json.dump({"objects": OB.table_records(res["reference"]["table"]), "stats": res["reference"]["stats"],
                            "parameters": params}, f, indent=1)
             with open(fp("objects_eval.json"), "w") as f:
+                json.dump(res["eval"], f, indent=1)
+    return dict(res, files=files)
+
+
+@torch.no_grad()
+def export_terrain(products, output_dp, alt_key=None, label_key=None, blocked=(3,), reference=None, zone_string=None, **kwargs):
+    """The bare-earth terrain under a map (eval/utils/terrain.py terrain), written to `output_dp`/terrain/.
+    `products`: what nadir_products, ortho_products or orthorect.rectify return ("grid" and an altitude plane).  `alt_key`: default the
+    first of "dsm", "median_alt", "top_alt" present; `label_key`: default the first of "label", "label_vote", "label_median",
+    "label_top" present -- with a label plane the classes `blocked` can never be ground (the default (3,) is the building entry of
+    colormaps.DEFAULT_PALETTE's list; a scene with other class ids passes its own); without one nothing is blocked.  **kwargs
+    (max_window_m, slope, dh0, dh_max) go to terrain's schedule.  `reference`: {"alt"[, "label"]} on the same lattice -- the lidar DSM,
+    say, with the rectified ground-truth labels -- whose terrain the map's is held to (terrain_agreement); a lattice mismatch is a
+    ValueError that names both shapes.
+    Files: dtm.tif / .png and ndsm.tif / .png (JET), ground.png (white = ground), reach.png (BONE), terrain.json ({"schedule", "stats",
+    "parameters"}); with `reference` also terrain_eval.json.  Only rank 0 writes.  Returns terrain()'s result plus "files"[,
+    "reference", "eval"]."""
+    from .utils import terrain as TR
+    from .utils.ortho import window_grid
+    alt_key = alt_key or next((k for k in ("dsm", "median_alt", "top_alt") if k in products), None)
+    label_key = label_key or next((k for k in ("label", "label_vote", "label_median", "label_top") if k in products), None)
+    if alt_key not in products or (label_key is not None and label_key not in products):
+        raise ValueError(f"export_terrain: the products hold no altitude plane ({alt_key!r}) or no label plane ({label_key!r})")
+    alt, grid = products[alt_key], window_grid(products["grid"])
+    label = products[label_key] if label_key is not None else None
+    shape = tuple(alt.shape)
+    if reference is not None:
+        ref_label = reference.get("label")
+        if tuple(reference["alt"].shape) != shape or (ref_label is not None and tuple(ref_label.shape) != shape):
+            raise ValueError(f"export_terrain: the products lie on a lattice of {shape} cells, the reference on "
+                             f"{tuple(reference['alt'].shape)} (alt)" + ("" if ref_label is None else f" / {tuple(ref_label.shape)} (label)"))
+    used = tuple(blocked) if label is not None else ()
+    res = TR.terrain(alt.float(), grid, label, used, **kwargs)
+    params = dict({"alt_key": alt_key, "label_key": label_key, "blocked": [int(c) for c in used]}, **kwargs)
+    if reference is not None:
+        ref = TR.terrain(reference["alt"].float(), grid, ref_label, tuple(blocked) if ref_label is not None else (), **kwargs)
+        res = dict(res, reference=ref, eval=TR.terrain_agreement(res, ref))
+    zone_string = _zone(zone_string, kwargs)
+    files, fp = _writer(output_dp, "terrain")
+    if fp:
+        _scalar_plane(fp, "dtm", res["dtm"], colormaps.COLORMAP_JET, grid, zone_string)
+        _scalar_plane(fp, "ndsm", res["ndsm"], colormaps.COLORMAP_JET, grid, zone_string)
+        _mask_png(fp("ground.png"), res["ground"].to(torch.uint8))
+        stats = vismaps.plane_minmax(res["reach"].to(torch.float32), vismaps.new_stats(alt.device), "user")
+        _png(fp("reach.png"), vismaps.colormap(res["reach"].to(torch.float32), colormaps.table(colormaps.COLORMAP_BONE, alt.device), stats,
+                                                "user"))
+        with open(fp("terrain.json"), "w") as f:
+            json.dump({"schedule": res["schedule"], "stats": res["stats"], "parameters": params}, f, indent=1)
+        if reference is not None:
+            with open(fp("terrain_eval.json"), "w") as f:
                 json.dump(res["eval"], f, indent=1)
     return dict(res, files=files)

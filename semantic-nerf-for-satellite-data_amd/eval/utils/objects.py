@@ -121,7 +121,7 @@ def _window_origin(grid):
     return float(g.xoff), float(g.yoff), float(g.resolution)
 
 
-def object_table(rows, grid, z0=OR.Z0, q=OR.Q):
+def object_table(rows, grid, z0=OR.Z0, q=OR.Q, terrain_rows=None):
     """per-object columns from the integer words, in fp64 on the host -> a dict of numpy arrays of length K (object n is entry
     n - 1).  `grid`: the lattice of the raster (a DsmGrid, or a _lib.SnerfDsmGrid window: its window offsets are applied).
       class, area_cells, holes (cells without a valid altitude)       int64
@@ -131,7 +131,11 @@ def object_table(rows, grid, z0=OR.Z0, q=OR.Q):
       alt_mean, alt_min, alt_max                                      over the cells with a valid altitude (NaN without one)
       ground_alt, ground_min                                          mean / min over the ring pairs (NaN without one)
       height = alt_mean - ground_alt, height_max = alt_max - ground_alt
-      volume_m3 = (q sum_k + n_valid (z0 - ground_alt)) res^2         the prism over the ground level"""
+      volume_m3 = (q sum_k + n_valid (z0 - ground_alt)) res^2         the prism over the ground level
+    With `terrain_rows` (the words of a second object_rows call over a DTM plane, ring = 0) also
+      terrain_alt                                                     the DTM's mean over the footprint (NaN without a valid cell)
+      height_over_terrain = alt_mean - terrain_alt
+      volume_over_terrain_m3 = n_valid (alt_mean - terrain_alt) res^2 the prism over the terrain under the footprint"""
     r = rows.detach().cpu().numpy() if torch.is_tensor(rows) else np.asarray(rows)
     r = r.view(np.int64).reshape(-1, ROW_WORDS)                # sums are signed; every other word is far below 2^63 where it is used
     xoff, yoff, res = _window_origin(grid)
@@ -148,10 +152,21 @@ def object_table(rows, grid, z0=OR.Z0, q=OR.Q):
         east = xoff + (f[:, 1] / area + 0.5) * res
         north = yoff - (f[:, 2] / area + 0.5) * res
     bbox = np.stack([xoff + f[:, 3] * res, yoff - (f[:, 6] + 1.0) * res, xoff + (f[:, 4] + 1.0) * res, yoff - f[:, 5] * res], 1)
-    return {"class": r[:, 15].copy(), "area_cells": r[:, 0].copy(), "area_m2": area * res * res, "east": east, "north": north, "bbox": bbox,
-            "perimeter_m": f[:, 14] * res, "alt_mean": alt_mean, "alt_min": alt_min, "alt_max": alt_max, "ground_alt": ground,
-            "ground_min": ground_min, "height": alt_mean - ground, "height_max": alt_max - ground,
-            "volume_m3": (q * f[:, 8] + nk * (z0 - ground)) * res * res, "holes": r[:, 0] - r[:, 7]}
+    table = {"class": r[:, 15].copy(), "area_cells": r[:, 0].copy(), "area_m2": area * res * res, "east": east, "north": north, "bbox": bbox,
+             "perimeter_m": f[:, 14] * res, "alt_mean": alt_mean, "alt_min": alt_min, "alt_max": alt_max, "ground_alt": ground,
+             "ground_min": ground_min, "height": alt_mean - ground, "height_max": alt_max - ground,
+             "volume_m3": (q * f[:, 8] + nk * (z0 - ground)) * res * res, "holes": r[:, 0] - r[:, 7]}
+    if terrain_rows is not None:
+        t = terrain_rows.detach().cpu().numpy() if torch.is_tensor(terrain_rows) else np.asarray(terrain_rows)
+        t = t.view(np.int64).reshape(-1, ROW_WORDS)
+        if len(t) != len(r):
+            raise ValueError(f"objects: {len(r)} rows but {len(t)} terrain rows")
+        tf = t.astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            terrain_alt = np.where(t[:, 7] > 0, z0 + q * (tf[:, 8] / tf[:, 7]), nan)
+        table.update(terrain_alt=terrain_alt, height_over_terrain=alt_mean - terrain_alt,
+                     volume_over_terrain_m3=nk * (alt_mean - terrain_alt) * res * res)
+    return table
 
 
 def filter_objects(ids, table, min_area_m2=0.0):
@@ -164,12 +179,15 @@ def filter_objects(ids, table, min_area_m2=0.0):
     return out, {k: np.asarray(v)[keep] for k, v in table.items()}
 
 
-def objects(label, alt, grid, classes, ground, connectivity=4, ring=2, min_area_m2=0.0):
+def objects(label, alt, grid, classes, ground, connectivity=4, ring=2, min_area_m2=0.0, dtm=None):
     """components, object_rows, object_table and filter_objects in one call -> {"ids" (H, W) int32, "n", "table", "object_height"
-    (H, W) f32: the height of the cell's object, NaN off objects, "stats": the 4 words of snerf_objects_stats as Python ints}"""
+    (H, W) f32: the height of the cell's object, NaN off objects, "stats": the 4 words of snerf_objects_stats as Python ints}.
+    `dtm`: a terrain plane ((H, W) f32, eval/utils/terrain.py) -- one further object_rows call at ring = 0 folds it over the
+    footprints and the table gains terrain_alt, height_over_terrain and volume_over_terrain_m3; without it nothing else is launched."""
     ids, K = components(label, classes, connectivity)
     rows, stats = object_rows(ids, K, label, alt, ground, ring)
-    table = object_table(rows, grid)
+    terrain_rows = None if dtm is None else object_rows(ids, K, label, dtm, ground, ring=0)[0]
+    table = object_table(rows, grid, terrain_rows=terrain_rows)
     ids, table = filter_objects(ids, table, min_area_m2)
     height = torch.from_numpy(np.concatenate([[np.nan], table["height"]]).astype(np.float32)).to(ids.device)
     return {"ids": ids, "n": len(table["class"]), "table": table, "object_height": height[ids.long()],
