@@ -290,8 +290,20 @@ TERRAIN_SIGNATURES = {
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_stream)),
     },
 }
+# And the entries of include/snerf_roofs.h (tests/test_roofs_cpu.py compares them with it).  `planes` is a device array of doubles.
+ROOFS_SIGNATURES = {
+    "snerf_roofs.h": {
+        "snerf_roofs_normals": (C.c_int, (C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_int) + (C.c_double,) * 6
+                                + (C.c_void_p,) * 5 + (c_stream,)),
+        "snerf_roofs_link": (C.c_int, (C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, c_stream)),
+        "snerf_roofs_moments": (C.c_int, (C.c_void_p,) * 4 + (C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                              c_stream)),
+        "snerf_roofs_residuals": (C.c_int, (C.c_void_p,) * 3 + (C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_double, C.c_double, C.c_int,
+                                                                C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, c_stream)),
+    },
+}
 _ALL_SIGNATURES = dict(SIGNATURES)
-for _table in (EXTENSION_SIGNATURES, RAYCAST_SIGNATURES, FUSE_SIGNATURES, OBJECTS_SIGNATURES, TERRAIN_SIGNATURES):
+for _table in (EXTENSION_SIGNATURES, RAYCAST_SIGNATURES, FUSE_SIGNATURES, OBJECTS_SIGNATURES, TERRAIN_SIGNATURES, ROOFS_SIGNATURES):
     for _rows in _table.values():
         assert not set(_rows) & set(_ALL_SIGNATURES)
         _ALL_SIGNATURES.update(_rows)
@@ -309,6 +321,12 @@ OBJECTS_ROW_WORDS = 16     # include/snerf_objects.h SNERF_OBJECTS_ROW_WORDS
 TERRAIN_HOLE = -2 ** 31    # include/snerf_terrain.h SNERF_TERRAIN_HOLE
 TERRAIN_MAX_RADIUS = 512   # include/snerf_terrain.h SNERF_TERRAIN_MAX_RADIUS
 TERRAIN_FLAGGED, TERRAIN_BLOCKED, TERRAIN_IS_HOLE = 1, 2, 4     # include/snerf_terrain.h: the bits of a flags byte
+ROOFS_MAX_RADIUS = 4       # include/snerf_roofs.h SNERF_ROOFS_MAX_RADIUS
+ROOFS_MAX_SIDE = 8192      # include/snerf_roofs.h SNERF_ROOFS_MAX_SIDE
+ROOFS_MAX_OBJECTS = 2 ** 27    # include/snerf_roofs.h SNERF_ROOFS_MAX_OBJECTS
+ROOFS_MOMENT_WORDS, ROOFS_RESIDUAL_WORDS = 16, 8               # include/snerf_roofs.h SNERF_ROOFS_*_WORDS
+# include/snerf_roofs.h: the orientation codes (1..8 = the downslope octants N, NE, E, SE, S, SW, W, NW)
+ROOFS_FLAT, ROOFS_STEEP, ROOFS_HOLE, ROOFS_DEGENERATE, ROOFS_NONE = 0, 9, 253, 254, 255
 
 # symbol -> (per argument a caller of call() passes: int / float for a scalar slot, None for a pointer slot; whether a trailing
 # stream follows them)

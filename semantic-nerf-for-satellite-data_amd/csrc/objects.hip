@@ -3,7 +3,7 @@
 // spec is include/snerf_objects.h and DESIGN.md section 5x; the walk is csrc/objects_walk.h, which csrc/objects_walk_main.cpp runs
 // on the host under ThreadSanitizer.  Integer atomics only: every word is independent of the order in which cells arrive.
 #include "lattice.h"
-#include "objects_walk.h"
+#include "link_kernels.h"
 #include "reduce.h"
 #include "../../include/snerf_objects.h"
 
@@ -23,61 +23,13 @@ __device__ __forceinline__ bool in_classes(const ObjClasses& t, unsigned c) {
   return (((c & 128 ? hi : lo) >> (c & 63)) & 1ull) != 0;
 }
 
-// the device side of the walk's memory policy: relaxed, agent scope
-struct DeviceParents {
-  int* parent;
-  __device__ __forceinline__ int load(int c) { return __hip_atomic_load(parent + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-  __device__ __forceinline__ int fetch_min(int c, int v) {
-    return __hip_atomic_fetch_min(parent + c, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+// what links two cells of a class raster (csrc/link_kernels.h: init, merge, flatten): the same class, one of `member_set`
+struct ClassLink {
+  const unsigned char* label;
+  ObjClasses member_set;
+  __device__ __forceinline__ int load(long long c) const { return label[c]; }
+  __device__ __forceinline__ bool member(int l) const { return in_classes(member_set, (unsigned)l); }
 };
-
-// ---- link --------------------------------------------------------------------------------------------------------------------------
-// One thread per cell, consecutive lanes on consecutive cells of a row: a wave's W unions stay in lines it already holds.
-__global__ __launch_bounds__(OBJ_THREADS) void objects_init_kernel(const unsigned char* __restrict__ label, int cells, ObjClasses member,
-                                                                   int* __restrict__ parent, unsigned long long* __restrict__ stats) {
-  unsigned long long members = 0;
-  for (long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x; c < cells; c += (long long)gridDim.x * blockDim.x) {
-    const bool in = in_classes(member, label[c]);
-    parent[c] = in ? (int)c : -1;
-    members += in ? 1 : 0;
-  }
-  members = wave_reduce(members, OpSum());
-  if ((threadIdx.x & 63) == 0 && members) atomicAdd(&stats[1], members);
-}
-
-__global__ __launch_bounds__(OBJ_THREADS) void objects_merge_kernel(const unsigned char* __restrict__ label, int h, int w, ObjClasses member,
-                                                                    int eight, int* parent, unsigned long long* __restrict__ stats) {
-  DeviceParents m = {parent};
-  const long long cells = (long long)h * w;
-  unsigned long long trips = 0;
-  for (long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x; c < cells; c += (long long)gridDim.x * blockDim.x) {
-    const unsigned l = label[c];
-    if (!in_classes(member, l)) continue;
-    const int j = (int)(c / w), i = (int)(c - (long long)j * w);
-    if (i > 0 && label[c - 1] == l) trips += walk_unite(m, (int)c, (int)c - 1);
-    if (j > 0) {
-      const long long n = c - w;
-      if (label[n] == l) trips += walk_unite(m, (int)c, (int)n);
-      if (eight && i > 0 && label[n - 1] == l) trips += walk_unite(m, (int)c, (int)n - 1);
-      if (eight && i + 1 < w && label[n + 1] == l) trips += walk_unite(m, (int)c, (int)n + 1);
-    }
-  }
-  if (trips) atomicAdd(&stats[0], trips);
-}
-
-__global__ __launch_bounds__(OBJ_THREADS) void objects_flatten_kernel(int cells, int* parent, unsigned long long* __restrict__ stats) {
-  DeviceParents m = {parent};
-  unsigned long long trips = 0;
-  for (long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x; c < cells; c += (long long)gridDim.x * blockDim.x) {
-    if (m.load((int)c) < 0) continue;                        // not a member (init's -1)
-    const int root = walk_find(m, (int)c);
-    if (root < 0) { trips++; continue; }
-    // a walk that passes through c meanwhile reads the old ancestor or the root: both lie below c in c's component
-    __hip_atomic_store(parent + c, root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  if (trips) atomicAdd(&stats[0], trips);
-}
 
 // ---- stats -------------------------------------------------------------------------------------------------------------------------
 // rint((alt - z0) / q) as lattice_key quantises; false when it is not in [-2^31, 2^31)
@@ -234,16 +186,8 @@ extern "C" int snerf_objects_link(const unsigned char* label, int h, int w, cons
   }
   ObjClasses member;
   if (!objects_table(who, "member_host", member_host, &member)) return SNERF_ERR_BAD_DESC;
-  const int cells = h * w;
-  const dim3 grid(blocks_for(cells, OBJ_THREADS, OBJ_MAX_BLOCKS)), block(OBJ_THREADS);
-  hipLaunchKernelGGL(objects_init_kernel, grid, block, 0, (hipStream_t)stream, label, cells, member, parent, stats);
-  SNERF_LAUNCH_CHECK();
-  hipLaunchKernelGGL(objects_merge_kernel, grid, block, 0, (hipStream_t)stream, label, h, w, member, connectivity == 8 ? 1 : 0, parent,
-                     stats);
-  SNERF_LAUNCH_CHECK();
-  hipLaunchKernelGGL(objects_flatten_kernel, grid, block, 0, (hipStream_t)stream, cells, parent, stats);
-  SNERF_LAUNCH_CHECK();
-  return SNERF_OK;
+  const ClassLink pred = {label, member};
+  return link_launch(pred, h, w, connectivity, parent, stats, stream);
 }
 
 extern "C" int snerf_objects_stats(const int* ids, const unsigned char* label, const float* alt, int h, int w, long long K,

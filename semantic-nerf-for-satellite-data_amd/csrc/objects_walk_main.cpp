@@ -64,7 +64,7 @@ std::vector<int> flood(const Raster& r, bool eight) {
   return parent;
 }
 
-// the merge step of one cell, as objects_merge_kernel makes it
+// the merge step of one cell, as link_merge_kernel (link_kernels.h) makes it
 int merge_cell(HostParents& m, const Raster& r, bool eight, int c) {
   const unsigned char l = r.label[c];
   if (!member(l)) return 0;

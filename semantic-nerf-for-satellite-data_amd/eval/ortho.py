@@ -63,6 +63,15 @@ export_terrain puts a bare-earth terrain under any of these maps (eval/utils/ter
     terrain.json                         the schedule, the counts and the parameters
     terrain_eval.json                    with reference=: DTM / nDSM errors and the ground masks' 2 x 2 table against its terrain
 
+export_roofs fits roof planes to the buildings export_objects found (eval/utils/roofs.py).  Files under
+`output_dp`/roofs/:
+    pitch.png/.tif, residual.png/.tif    the slope of every building cell in degrees and its distance from its facet's plane in metres:
+                                         float32 in the .tif (NaN off the roofs), JET in the .png
+    aspect.png                           the orientation codes in a fixed palette (ASPECT_PALETTE)
+    facets.tif                           the facet id of every cell (0 = none): int32
+    roofs.json                           the facets and the per-building rows, the parameters and the counts
+    roofs_eval.json                      with reference=: roof types, pitch and normals against the reference's roofs
+
 The other exports hand their keyword arguments to their products function, `depth_mode="median"` among them: the altitudes and everything
 built on them are then those of the rays' median depths; at the default every file is what it was."""
 import json
@@ -424,5 +433,65 @@ def export_terrain(products, output_dp, alt_key=None, label_key=None, blocked=(3
             json.dump({"schedule": res["schedule"], "stats": res["stats"], "parameters": params}, f, indent=1)
         if reference is not None:
             with open(fp("terrain_eval.json"), "w") as f:
+                json.dump(res["eval"], f, indent=1)
+    return dict(res, files=files)
+
+
+# aspect.png: code -> colour.  0 flat grey; 1..8 the downslope octants N, NE, E, SE, S, SW, W, NW round the colour wheel; 9 steep white;
+# 253 (hole) and 254 (degenerate) dark red; everything else (255: not an object cell) black
+ASPECT_PALETTE = {0: (128, 128, 128), 1: (255, 0, 0), 2: (255, 160, 0), 3: (255, 255, 0), 4: (0, 255, 0), 5: (0, 255, 255), 6: (0, 128, 255),
+                  7: (0, 0, 255), 8: (255, 0, 255), 9: (255, 255, 255), 253: (96, 0, 0), 254: (96, 0, 0)}
+
+
+def aspect_colors(code):
+    """(H, W) uint8 orientation codes -> (3, H, W) uint8 through ASPECT_PALETTE"""
+    lut = torch.zeros((256, 3), dtype=torch.uint8)
+    for c, rgb in ASPECT_PALETTE.items():
+        lut[c] = torch.tensor(rgb, dtype=torch.uint8)
+    return lut.to(code.device)[code.long()].permute(2, 0, 1).contiguous()
+
+
+@torch.no_grad()
+def export_roofs(products, objects_result, output_dp, alt_key=None, reference=None, zone_string=None, **kwargs):
+    """The roofs of a map's buildings (eval/utils/roofs.py roofs), written to `output_dp`/roofs/.  `products`: what
+    nadir_products, ortho_products or orthorect.rectify return ("grid" and an altitude plane); `objects_result`: what objects() or
+    export_objects returned for them ("ids", "n", "table").  `alt_key`: default the first of "dsm", "median_alt", "top_alt" present.
+    **kwargs (radius, flat_deg, wall_deg, aspect0_deg, connectivity, min_facet_m2) go to roofs().  `reference`: {"alt", "objects"} on
+    the same lattice -- the lidar DSM, say, and the objects() of the rectified ground-truth labels -- whose roofs the map's are held
+    to over the buildings match_objects pairs (roof_agreement); a lattice mismatch is a ValueError that names both shapes.
+    Files: pitch.tif / .png and residual.tif / .png (JET), aspect.png (ASPECT_PALETTE), facets.tif (int32), roofs.json ({"facets",
+    "buildings", "stats", "parameters"}); with `reference` also roofs_eval.json.  Only rank 0 writes.  Returns roofs()'s result plus
+    "files"[, "reference", "pairs", "eval"]."""
+    from .utils import objects as OB
+    from .utils import roofs as RF
+    from .utils.ortho import window_grid
+    alt_key = alt_key or next((k for k in ("dsm", "median_alt", "top_alt") if k in products), None)
+    if alt_key not in products:
+        raise ValueError(f"export_roofs: the products hold no altitude plane ({alt_key!r})")
+    alt, grid = products[alt_key], window_grid(products["grid"])
+    shape = tuple(alt.shape)
+    if tuple(objects_result["ids"].shape) != shape:
+        raise ValueError(f"export_roofs: the products lie on a lattice of {shape} cells, the objects on {tuple(objects_result['ids'].shape)}")
+    if reference is not None and (tuple(reference["alt"].shape) != shape or tuple(reference["objects"]["ids"].shape) != shape):
+        raise ValueError(f"export_roofs: the products lie on a lattice of {shape} cells, the reference on "
+                         f"{tuple(reference['alt'].shape)} (alt) / {tuple(reference['objects']['ids'].shape)} (objects)")
+    res = RF.roofs(alt.float(), objects_result["ids"], objects_result["n"], grid, objects_result["table"], **kwargs)
+    if reference is not None:
+        ro = reference["objects"]
+        ref = RF.roofs(reference["alt"].float(), ro["ids"], ro["n"], grid, ro["table"], **kwargs)
+        pairs = OB.match_objects(objects_result["ids"], objects_result["n"], ro["ids"], ro["n"])[0]
+        res = dict(res, reference=ref, pairs=pairs, eval=RF.roof_agreement(res, ref, pairs))
+    zone_string = _zone(zone_string, kwargs)
+    files, fp = _writer(output_dp, "roofs")
+    if fp:
+        _scalar_plane(fp, "pitch", res["pitch_deg"], colormaps.COLORMAP_JET, grid, zone_string)
+        _scalar_plane(fp, "residual", res["residual"], colormaps.COLORMAP_JET, grid, zone_string)
+        _png(fp("aspect.png"), aspect_colors(res["code"]))
+        img_utils.save_geotiff(fp("facets.tif"), res["facet_ids"], grid, zone_string)
+        with open(fp("roofs.json"), "w") as f:
+            json.dump({"facets": RF.table_records(res["facets"]), "buildings": RF.table_records(res["buildings"]), "stats": res["stats"],
+                       "parameters": dict({"alt_key": alt_key}, **res["parameters"])}, f, indent=1)
+        if reference is not None:
+            with open(fp("roofs_eval.json"), "w") as f:
                 json.dump(res["eval"], f, indent=1)
     return dict(res, files=files)

@@ -118,7 +118,7 @@ def utm_epsg(zone_string):
 
 
 def save_geotiff(fp, array, grid, zone_string=None):
-    """Write `array` -- (h, w) float32 ("F"), (h, w) uint8 ("L") or (h, w, 3) uint8 ("RGB"); a tensor or an ndarray -- as an
+    """Write `array` -- (h, w) float32 ("F"), (h, w) int32 ("I"), (h, w) uint8 ("L") or (h, w, 3) uint8 ("RGB"); a tensor or an ndarray -- as an
     uncompressed TIFF on `grid` (a DsmGrid: xoff / yoff = the outer corner of the north-west cell): ModelPixelScale =
     (res, res, 0), ModelTiepoint = (0, 0, 0, xoff, yoff, 0) and, with `zone_string`, a GeoKeyDirectory (projected model,
     pixel-is-area, ProjectedCSTypeGeoKey = utm_epsg(zone_string)).  No RPC tags."""
@@ -126,12 +126,14 @@ def save_geotiff(fp, array, grid, zone_string=None):
     a = array.detach().cpu().numpy() if torch.is_tensor(array) else np.asarray(array)
     if a.ndim == 2 and a.dtype == np.float32:
         mode = "F"
+    elif a.ndim == 2 and a.dtype == np.int32:
+        mode = "I"
     elif a.ndim == 2 and a.dtype == np.uint8:
         mode = "L"
     elif a.ndim == 3 and a.shape[2] == 3 and a.dtype == np.uint8:
         mode = "RGB"
     else:
-        raise ValueError(f"save_geotiff: expected (h, w) float32, (h, w) uint8 or (h, w, 3) uint8, got {a.dtype} {a.shape}")
+        raise ValueError(f"save_geotiff: expected (h, w) float32, (h, w) int32, (h, w) uint8 or (h, w, 3) uint8, got {a.dtype} {a.shape}")
     if a.shape[:2] != (int(grid.ysize), int(grid.xsize)):
         raise ValueError(f"save_geotiff: the raster is {a.shape[0]} x {a.shape[1]}, the grid {grid.ysize} x {grid.xsize}")
     res = float(grid.resolution)
