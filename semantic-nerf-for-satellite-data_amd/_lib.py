@@ -302,8 +302,19 @@ ROOFS_SIGNATURES = {
                                                                 C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, c_stream)),
     },
 }
+# And the entries of include/snerf_normals.h (tests/test_normals_cpu.py compares them with it): the density-gradient pass, the size of
+# its scratch buffer (an int return, the size through a size_t*) and its two test hooks.
+NORMALS_SIGNATURES = {
+    "snerf_normals.h": {
+        "snerf_normals_scratch_bytes": (C.c_int, (C.POINTER(SnerfDesc), C.POINTER(C.c_size_t))),
+        "snerf_density_grad": (C.c_int, (C.POINTER(SnerfDesc), C.c_void_p, C.POINTER(SnerfInputs)) + (C.c_void_p,) * 5 + (c_stream,)),
+        "snerf_test_normals_grid": (C.c_int, (C.c_int,)),
+        "snerf_test_normals_dump": (C.c_int, (C.c_void_p, C.c_void_p)),
+    },
+}
 _ALL_SIGNATURES = dict(SIGNATURES)
-for _table in (EXTENSION_SIGNATURES, RAYCAST_SIGNATURES, FUSE_SIGNATURES, OBJECTS_SIGNATURES, TERRAIN_SIGNATURES, ROOFS_SIGNATURES):
+for _table in (EXTENSION_SIGNATURES, RAYCAST_SIGNATURES, FUSE_SIGNATURES, OBJECTS_SIGNATURES, TERRAIN_SIGNATURES, ROOFS_SIGNATURES,
+               NORMALS_SIGNATURES):
     for _rows in _table.values():
         assert not set(_rows) & set(_ALL_SIGNATURES)
         _ALL_SIGNATURES.update(_rows)

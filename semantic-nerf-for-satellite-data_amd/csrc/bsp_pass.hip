@@ -5,6 +5,7 @@
 #include "aux_kernels.h"
 #include "bsp.h"
 #include "composite.h"
+#include "normals.h"
 #include "plan.h"
 
 namespace snerf {
@@ -277,7 +278,7 @@ void take_regions(const Plan& p, RQ& rq, BwdRegions& r, bool embed_only = false)
   r.cs_s3 = cs(H); r.cs_s2 = cs(H);
   if (p.compose_feats) {
     // no d feats tensor, so no cs_fa; of the [W + 32][W] matrix only the 32 sigma rows are a dW launch (same splits as before)
-    r.ld_cs1 = cs_ld(p.h1w); r.cs_fin = cs(p.h1w); r.cs_sun = r.cs_fin + (p.sc ? 0 : p.sun_col);
+    r.ld_cs1 = cs_ld(p.h1w); r.cs_fin = cs(p.h1w); r.cs_sun = r.cs_fin ? r.cs_fin + (p.sc ? 0 : p.sun_col) : nullptr;   // (null: the counting arena)
     r.w_h1 = dw(p.h1w, p.FA, p.FA, false);
     r.nar_sig = nar(); r.w_fs = dw(NARROW, W, W, false, W); r.cs_hl = cs(W);
   } else {
@@ -546,6 +547,83 @@ int backward_bsp(const Plan& p, const float* pk, const SnerfInputs* in, const Sn
                         gp + p.w_h1 + r0 * p.FA, gp + p.b_h1 + r0, gp + p.w_fs, gp + p.b_fs, W, p.FA, p.h1w);
     return bsp::launch_sgemm(tb, 32, st);
   }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// snerf_density_grad (include/snerf_normals.h): coef * d sigma / d xyz per sample and summed per ray.  The backward of a training pass
+// between a cotangent on sigma and the sample positions, as SNERF_FLAG_EMBED_GRAD is the one between the cotangents and t: the composite
+// backward with g_sigmas = coef alone, the planes of d sigma, the dX launches down the trunk with the operands backward_bsp gives
+// them -- no dW launch, no column sums, no reduction, nothing taken from the reduction arena -- and, at every layer that reads the
+// encoding while its dz is live, the encoding-gradient launch of normals.hip.  It writes only what backward_bsp rewrites before it
+// reads (the 32-wide gradients and their planes, dza / dzb, the tile counters), so a snerf_backward on the same workspace afterwards
+// gives its own bits.
+int density_grad_bsp(const Plan& p, const float* pk, const SnerfInputs* in, const float* coef, double* grad_ray, float* grad_sample,
+                     void* workspace, void* scratch, hipStream_t st) {
+  const Ws ws{(char*)workspace};
+  const NormalsScratch ns = normals_scratch(p);
+  double* G = reinterpret_cast<double*>((char*)scratch + ns.o_G);
+  double* wd = reinterpret_cast<double*>((char*)scratch + ns.o_wd);
+  float* part = reinterpret_cast<float*>((char*)scratch + ns.o_part);
+  const int P = p.P, W = p.W;
+  int kcq = 0;     // (the counters are cleared by the composite backward kernel, the first launch of this pass)
+  auto launch_kc = [&](bsp::KcArgs& g) { g.rev = kcq & 1; g.tile_ctr = kcq < KCQ_SLOTS ? ws.i(p.o_kcq) + 16 * kcq++ : nullptr; return bsp::launch_kc(g, st); };
+  auto dact = [&](bsp::KcArgs& g, const PlaneT& h, float w0) {
+    ws.h(g, h, 0);
+    if (p.siren) { g.aux_mode = AUX_SINREC; g.w0 = w0; }
+    else g.aux_mode = AUX_RELU_MASK;
+  };
+  // 0. composite backward: d sigma's pre-activation = coef * softplus'(pre); no other cotangent, no sky slab
+  CompBwdArgs b;
+  CompArgs& c = b.f;
+  c.N = p.N; c.S = p.S; c.H = p.H; c.C = p.C; c.sc = 0; c.sem_sigmoid = p.sem_sigmoid; c.has_sbeta = p.blk_sbeta >= 0;
+  c.z = ws.f(p.o_z); c.sigo = ws.f(p.o_sigo); c.fino = ws.f(p.o_fino); c.suno = ws.f(p.o_suno);
+  narrow_parts(c, p, pk, ws);
+  c.sun_d = in->sun_d; c.sun_stride = in->sun_stride; c.sky = pk + p.sky;
+  b.T = ws.f(p.o_T); b.rgbraw = ws.f(p.o_rgbraw);
+  b.g_sigmas = coef;
+  b.d_sigo = ws.f(p.o_dsig); b.d_fino = ws.f(p.o_dfin); b.d_suno = ws.f(p.o_dsun); b.sky_slab = nullptr;
+  b.zero = ws.u(p.o_kcq); b.zero_n = KCQ_SLOTS * 16;
+  RC(launch_composite_bwd(b, st));
+  // 1. planes of d sigma (the bias sums of the same launch go to scratch and are never read)
+  RC(bsp::launch_colsum32_bsp(ws.f(p.o_dsig), P, part, ws.c(p.pdsig.o), ws.i(p.pdsig.e), p.pl, st));
+  // 2. dz of the last trunk layer from d sigma alone: K = 32 against the sigma rows of the transposed pack, which lie behind the N1
+  //    rows of W_c in a composed plan (api.hip: plan_weights) and behind the W rows of W_f otherwise
+  PlaneT dz_cur = p.dza.view(W), dz_nxt = p.dzb.view(W);
+  {
+    bsp::KcArgs g;
+    ws.a(g, p.pdsig, NARROW);
+    if (p.compose_feats) weights(g, p, pk, p.wj_th1, 0, p.N1);
+    else weights(g, p, pk, p.wj_tfs, 0, W);
+    g.I = P; g.J = W; g.K = NARROW; ws.out(g, dz_cur);
+    dact(g, p.h[p.L - 1], (p.L == 1) ? 30.f : 1.f);
+    RC(launch_kc(g));
+  }
+  // 3. trunk, last layer to first (backward_bsp step 5 without its dW launches); a skip layer's dz is overwritten two launches later,
+  //    so its encoding columns are contracted here, before the launch into the layer below
+  const NormalsDump dump = normals_dump();
+  if (dump.enc) RC(bsp::launch_from_planes(ws.c(p.pe.o), ws.i(p.pe.e), p.pe.ld, 0, P, p.Ep, dump.enc, p.Ep, p.pl, st));
+  int n_enc = 0;
+  for (int i = p.L - 1; i >= 0; --i) {
+    if (i == 0 || ((p.skip_mask >> i) & 1u)) {
+      RC(launch_encgrad_weights(pk + p.w_tr[i], p.k_tr[i], W, p.E, wd, ns.ldw, st));
+      EncGradArgs a;
+      a.dz = ws.c(dz_cur.o); a.Edz = ws.i(dz_cur.e); a.ld_dz = dz_cur.ld;
+      a.pe = ws.c(p.pe.o); a.Epe = ws.i(p.pe.e); a.Ep = p.Ep;
+      a.wd = wd; a.ldw = ns.ldw; a.G = G; a.P = P; a.W = W; a.F = p.F; a.first = n_enc == 0;
+      RC(launch_encgrad(a, st));
+      if (dump.dz) RC(bsp::launch_from_planes(a.dz, a.Edz, a.ld_dz, 0, P, W, dump.dz + (size_t)n_enc * P * W, W, p.pl, st));
+      ++n_enc;
+    }
+    if (i == 0) break;
+    bsp::KcArgs g;
+    ws.a(g, dz_cur, W); weights(g, p, pk, p.wj_tt[i]);
+    g.I = P; g.J = W; g.K = W; ws.out(g, dz_nxt);
+    dact(g, p.h[i - 1], (i - 1 == 0) ? 30.f : 1.f);
+    RC(launch_kc(g));
+    const PlaneT sw = dz_cur; dz_cur = dz_nxt; dz_nxt = sw;
+  }
+  // 4. per ray
+  return launch_ray_fold3(G, p.N, p.S, grad_ray, grad_sample, st);
 }
 
 }  // namespace snerf

@@ -186,7 +186,8 @@ def export_nadir(cfgs, renderer, models, output_dp, palette=None, zone_string=No
     """nadir_products(cfgs, renderer, models, **kwargs), written to `output_dp`/nadir/.  `palette`: (K, 3) uint8, default
     colormaps.DEFAULT_PALETTE.  `zone_string`: the GeoTIFFs' UTM zone, default the zone of the GeoFrame in use.  Every rank
     computes the products (with sharded=True each renders its share of the lattice); only rank 0 writes.  Returns the products
-    plus "files": {name: path}."""
+    plus "files": {name: path}.  With normals=True (nadir_products) also normal.png -- RGB = 0.5 + 0.5 (east, north, up), a cell
+    without a normal black --, normal_up.tif (the up component) and normals.json (the agreement with the DSM's own raster normals)."""
     prod = nadir_products(cfgs, renderer, models, **kwargs)
     zone_string = _zone(zone_string, kwargs)
     grid = prod["grid"]
@@ -198,6 +199,12 @@ def export_nadir(cfgs, renderer, models, output_dp, palette=None, zone_string=No
             _label_plane(fp, "label", prod["label"], palette, grid, zone_string)
         for key, cmap in (("dsm", colormaps.COLORMAP_JET), ("sun", colormaps.COLORMAP_BONE), ("beta", colormaps.COLORMAP_BONE)):
             _scalar_plane(fp, key, prod[key], cmap, grid, zone_string)
+        if "normal" in prod:
+            _png(fp("normal.png"), to_uint8_image(torch.nan_to_num(0.5 + 0.5 * prod["normal"], nan=0.0).clamp(0.0, 1.0)))
+            img_utils.save_geotiff(fp("normal_up.tif"), prod["normal"][2].contiguous(), grid, zone_string)
+            with open(fp("normals.json"), "w") as f:
+                json.dump({"agreement_with_dsm_normals": prod["normal_agreement"], "frame": "east / north / up at the scene centre",
+                           "encoding": "normal.png: RGB = 0.5 + 0.5 n; normal_up.tif: the up component"}, f, indent=1)
     return dict(prod, files=files)
 
 

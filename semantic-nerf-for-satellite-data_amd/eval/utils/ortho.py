@@ -380,7 +380,7 @@ def _nadir_walk(who, cfgs, renderer, models, suns, geo, grid, roi, min_alt, max_
 @torch.no_grad()
 def nadir_products(cfgs, renderer, models, geo=None, grid=None, roi=None, min_alt=None, max_alt=None, sun_elevation=None,
                    sun_azimuth=None, t=0, render_options={}, sharded=False, gt=None, water_mask=None, ignore_mask=None,
-                   dataset=None, depth_mode="mean"):
+                   dataset=None, depth_mode="mean", normals=False):
     """The map of the lattice rendered from above: one vertical ray per cell (rays.nadir_construct between `max_alt` and
     `min_alt` metres, through `geo`, a GeoFrame), extras of the sun at (`sun_elevation`, `sun_azimuth`) degrees and the
     embedding index `t`.  The grid: `grid` (a DsmGrid, or a window of one from dsm.grid_struct), else the ROI grid of `roi`
@@ -398,13 +398,41 @@ def nadir_products(cfgs, renderer, models, geo=None, grid=None, roi=None, min_al
     (a model with classes; 255 for a label beyond 254)], "rays": the (H W, 8) nadir rays, "planimetric_error": the largest
     |east / north of the cloud - cell centre| in metres (the self-check of the ray construction), "scene_bounds": GeoBounds of
     the lattice's scene x / y (to_scene's stats)[, "mae": {"mean", "median"} of dsm.compute_mae(dsm, gt, water_mask,
-    ignore_mask), with `gt` (H, W)]}."""
+    ignore_mask), with `gt` (H, W)]}.
+    `normals=True` (single-device: a ValueError with `sharded`) adds the normals of the density field along the same rays, by a
+    second walk (normals.ray_normals, on the stratified depths of `render_options`): "normal" (3, H, W) f32, east / north / up, NaN
+    where the field has no gradient; "normal_angle" (H, W) f32, the angle in degrees to the raster normal of "dsm" itself
+    (roofs.normals over the whole raster, radius 1); "normal_agreement": normals.normal_agreement's figures plus "bad", the NaN
+    normals -- a consistency measure between the field and its own surface that needs no lidar.  False (default): nothing new runs
+    and every product is what it was."""
     from .util import with_depth_mode
+    if normals and sharded:
+        raise ValueError("nadir_products: normals=True is a single-device walk; pass sharded=False")
     out = _nadir_walk("nadir_products", cfgs, renderer, models, [(sun_elevation, sun_azimuth)], geo, grid, roi, min_alt, max_alt, t,
                       with_depth_mode(render_options, depth_mode, "nadir_products"), sharded, gt, water_mask, ignore_mask, dataset)
+    if normals:
+        out.update(_nadir_normals(cfgs, renderer, models, out, geo if geo is not None else dataset.geo, t, render_options))
     del out["suns"]
     out["rgb"], out["sun"] = out["rgb"][0], out["sun"][0]
     return out
+
+
+def _nadir_normals(cfgs, renderer, models, prod, geo, t, render_options):
+    """the normals products of nadir_products from its walk's products `prod` (rays, dsm, grid, suns)"""
+    from ...baseline.components import rays as R
+    from . import normals as NM
+    from . import roofs as RF
+    from . import terrain as TR
+    rays, dsm = prod["rays"], prod["dsm"]
+    h, w = dsm.shape
+    el, az = prod["suns"][0]
+    opts = {k: v for k, v in (render_options or {}).items() if k != "depth_mode"}
+    res = NM.ray_normals(cfgs, renderer, models, rays, R.nadir_extras(el, az, t, rays.shape[0], rays.device), opts)
+    normal = NM.to_enu(geo, res["normal_n"]).t().contiguous().reshape(3, h, w)
+    key, _, _ = TR.keys(dsm.contiguous())
+    slope_e, slope_n, _, _, _ = RF.normals(key, torch.ones((h, w), dtype=torch.int32, device=dsm.device), 1, float(prod["grid"].resolution), radius=1)
+    angle, stats = NM.normal_agreement(normal, slope_e, slope_n)
+    return {"normal": normal, "normal_angle": torch.from_numpy(angle).to(torch.float32).to(dsm.device), "normal_agreement": dict(stats, bad=res["bad"])}
 
 
 def sweep_suns(suns, dataset=None, who="nadir_sun_sweep"):

@@ -775,3 +775,64 @@ def ray_distortion(weights: torch.Tensor, z_vals: torch.Tensor, rays: torch.Tens
     values = _empty((N,), dtype=torch.float64, device=weights.device) if per_ray else None
     _lib.call("snerf_ray_distortion", weights.detach(), z_vals.detach(), rays.detach(), rays.shape[1], N, S, d_weights, values, acc)
     return (d_weights, acc, values) if per_ray else (d_weights, acc)
+
+
+_NORMALS_SCRATCH: dict = {}      # (device index, stream id) -> the scratch tensor of density_grad_into, grown as needed
+
+
+@torch.no_grad()
+def density_grad_into(spec: ModelSpec, params: dict, pin: PassInputs, t: torch.Tensor, t_s: torch.Tensor | None = None,
+                      coef: torch.Tensor | None = None, out: dict | None = None, want_samples: bool = False,
+                      packed: torch.Tensor | None = None) -> dict:
+    """coef * d sigma / d xyz of one ray batch -- snerf_density_grad (include/snerf_normals.h): a training forward
+    on a leased training workspace, then the backward between a cotangent on sigma and the sample positions alone.  `coef` (N, S) fp32
+    weighs the samples; None = the pass's own compositing weights, so that -grad / |grad| is the ray's surface normal.  Returns
+    {"grad": (N, 3) fp64, the sum over a ray's samples in normalised scene coordinates; "weights" (N, S); "depth" (N); with
+    `want_samples` also "grad_samples" (N, S, 3) fp32}.  `out` may carry preallocated contiguous tensors under those keys (and
+    "z_vals" (N, S)), which are then written in place.  The main pass only; the default arithmetic only.  Launches on the current
+    stream, no synchronisation."""
+    if t is None:
+        raise ValueError("density_grad_into: t (N, tau) is required")
+    _check_dev(t, "t")
+    if coef is not None:
+        _check_dev(coef, "coef")
+    N, dev = t.shape[0], t.device
+    S, d, nbytes, tc, tsc, launch = _forward_setup(spec, pin, t, t_s, _lib.FLAG_TRAIN)
+    out = dict(out) if out is not None else {}
+    shapes = {"grad": ((N, 3), torch.float64), "weights": ((N, S), torch.float32), "depth": ((N,), torch.float32),
+              "grad_samples": ((N, S, 3), torch.float32), "z_vals": ((N, S), torch.float32)}
+    for k, v in out.items():
+        if k not in shapes:
+            raise KeyError(f"density_grad_into: '{k}' is not a result of this pass (have {sorted(shapes)})")
+        if not v.is_cuda:
+            raise RuntimeError(f"snerf_amd: out['{k}'] must live on the GPU (the HIP path has no CPU fallback)")
+        if tuple(v.shape) != shapes[k][0] or v.dtype != shapes[k][1] or not v.is_contiguous():
+            raise ValueError(f"density_grad_into: out['{k}'] must be a contiguous {shapes[k][0]} {shapes[k][1]} tensor, got {tuple(v.shape)} {v.dtype}")
+    for k in ("grad", "weights", "depth") + (("grad_samples",) if want_samples else ()):
+        if k not in out:
+            out[k] = _empty(shapes[k][0], dtype=shapes[k][1], device=dev)
+    if coef is not None and (tuple(coef.shape) != (N, S) or not coef.is_contiguous()):
+        raise ValueError(f"density_grad_into: coef must be a contiguous (N, S) = {(N, S)} tensor, got {tuple(coef.shape)}")
+    if packed is None:
+        packed = pack_params(spec, params)
+    n_scratch = _lib.C.c_size_t(0)
+    _lib.check(_lib._invoke("snerf_normals_scratch_bytes", (d, n_scratch), None), "snerf_normals_scratch_bytes")
+    with torch.cuda.device(dev):
+        key = (dev.index if dev.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(dev).cuda_stream)
+        scratch = _NORMALS_SCRATCH.get(key)
+        if scratch is None or scratch.numel() < n_scratch.value:
+            scratch = _NORMALS_SCRATCH[key] = _empty(n_scratch.value, dtype=torch.uint8, device=dev)
+        lease = lease_workspace(dev, nbytes)
+    so = _lib.SnerfOutputs()
+    so.weights, so.depth = out["weights"].data_ptr(), out["depth"].data_ptr()
+    if "z_vals" in out:
+        so.z_vals = out["z_vals"].data_ptr()
+    try:
+        launch(packed, so, lease.t)
+        _lib.call("snerf_density_grad", d, packed, pin.struct(tc, tsc), coef if coef is not None else out["weights"], out["grad"],
+                  out.get("grad_samples") if want_samples else None, lease.t, scratch)
+    finally:
+        lease.release()
+    if not want_samples:
+        out.pop("grad_samples", None)
+    return out
