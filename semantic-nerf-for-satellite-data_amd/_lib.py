@@ -302,6 +302,16 @@ ROOFS_SIGNATURES = {
                                                                 C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, c_stream)),
     },
 }
+# And the entries of include/snerf_solar.h (tests/test_solar_cpu.py compares them with it).  `dirs_host` and `suns_host` are host tables.
+SOLAR_SIGNATURES = {
+    "snerf_solar.h": {
+        "snerf_solar_horizon": (C.c_int, (C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p,
+                                          c_stream)),
+        "snerf_solar_svf": (C.c_int, (C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, c_stream)),
+        "snerf_solar_irradiate": (C.c_int, (C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                            C.c_void_p, c_stream)),
+    },
+}
 # And the entries of include/snerf_normals.h (tests/test_normals_cpu.py compares them with it): the density-gradient pass, the size of
 # its scratch buffer (an int return, the size through a size_t*) and its two test hooks.
 NORMALS_SIGNATURES = {
@@ -314,7 +324,7 @@ NORMALS_SIGNATURES = {
 }
 _ALL_SIGNATURES = dict(SIGNATURES)
 for _table in (EXTENSION_SIGNATURES, RAYCAST_SIGNATURES, FUSE_SIGNATURES, OBJECTS_SIGNATURES, TERRAIN_SIGNATURES, ROOFS_SIGNATURES,
-               NORMALS_SIGNATURES):
+               SOLAR_SIGNATURES, NORMALS_SIGNATURES):
     for _rows in _table.values():
         assert not set(_rows) & set(_ALL_SIGNATURES)
         _ALL_SIGNATURES.update(_rows)
@@ -338,6 +348,9 @@ ROOFS_MAX_OBJECTS = 2 ** 27    # include/snerf_roofs.h SNERF_ROOFS_MAX_OBJECTS
 ROOFS_MOMENT_WORDS, ROOFS_RESIDUAL_WORDS = 16, 8               # include/snerf_roofs.h SNERF_ROOFS_*_WORDS
 # include/snerf_roofs.h: the orientation codes (1..8 = the downslope octants N, NE, E, SE, S, SW, W, NW)
 ROOFS_FLAT, ROOFS_STEEP, ROOFS_HOLE, ROOFS_DEGENERATE, ROOFS_NONE = 0, 9, 253, 254, 255
+SOLAR_MAX_DIRS = 64        # include/snerf_solar.h SNERF_SOLAR_MAX_DIRS
+SOLAR_MAX_SECTORS = 720    # include/snerf_solar.h SNERF_SOLAR_MAX_SECTORS
+SOLAR_MAX_SUNS = 64        # include/snerf_solar.h SNERF_SOLAR_MAX_SUNS
 
 # symbol -> (per argument a caller of call() passes: int / float for a scalar slot, None for a pointer slot; whether a trailing
 # stream follows them)

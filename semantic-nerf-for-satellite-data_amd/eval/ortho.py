@@ -72,6 +72,13 @@ export_roofs fits roof planes to the buildings export_objects found (eval/utils/
     roofs.json                           the facets and the per-building rows, the parameters and the counts
     roofs_eval.json                      with reference=: roof types, pitch and normals against the reference's roofs
 
+export_solar measures the solar potential of any of these maps (eval/utils/solar.py).  Files under
+`output_dp`/solar/:
+    svf.png/.tif, sun_hours.png/.tif     the sky-view factor and the hours of direct sun per year: float32 in the .tif (NaN = a hole),
+                                         BONE / JET in the .png
+    insolation.png/.tif                  the global irradiation in kWh per m^2 of surface and year: float32 in the .tif, JET in the .png
+    solar.json                           the parameters, the sun count and the per-facet and per-building tables
+
 The other exports hand their keyword arguments to their products function, `depth_mode="median"` among them: the altitudes and everything
 built on them are then those of the rays' median depths; at the default every file is what it was."""
 import json
@@ -502,3 +509,56 @@ def export_roofs(products, objects_result, output_dp, alt_key=None, reference=No
             with open(fp("roofs_eval.json"), "w") as f:
                 json.dump(res["eval"], f, indent=1)
     return dict(res, files=files)
+
+
+@torch.no_grad()
+def export_solar(products, output_dp, roofs_result=None, objects_result=None, geo=None, lat_deg=None, lon_deg=None, alt_key=None,
+                 zone_string=None, **kwargs):
+    """The solar potential of a map (eval/utils/solar.py solar), written to `output_dp`/solar/.  `products`: what
+    nadir_products, ortho_products or orthorect.rectify return ("grid" and an altitude plane); `alt_key`: default the first of "dsm",
+    "median_alt", "top_alt" present.  `roofs_result`: what roofs() or export_roofs returned for them -- its slopes tilt the building
+    cells (every other cell is horizontal) and its facets get a table; `objects_result`: what objects() or export_objects returned
+    ("ids", "n") -- the buildings get a table.  The site's latitude and longitude: `lat_deg` / `lon_deg`, else those of the grid's
+    centre through `geo`.to_scene(centre, want_lla=True) (a GeoFrame).  **kwargs (year, step_minutes, day_step, min_elevation_deg, D,
+    bias, max_dist_m, suns, hours, dni, dhi, clear_sky_options) go to solar(); min_kwh_m2 to solar_table().
+    Files: svf.tif / .png (BONE), sun_hours.tif / .png and insolation.tif / .png (JET), solar.json ({"parameters", "n_suns",
+    "annual_dhi_kwh", "facets", "buildings"}).  Only rank 0 writes.  Returns solar()'s result plus "files", "facets" and "buildings"
+    (solar_table's columns, None without the ids)."""
+    from .utils import solar as SO
+    from .utils.ortho import window_grid
+    from .utils.roofs import table_records
+    alt_key = alt_key or next((k for k in ("dsm", "median_alt", "top_alt") if k in products), None)
+    if alt_key not in products:
+        raise ValueError(f"export_solar: the products hold no altitude plane ({alt_key!r})")
+    alt, grid = products[alt_key], window_grid(products["grid"])
+    shape = tuple(alt.shape)
+    for name, plane in (("roofs", None if roofs_result is None else roofs_result["slope_e"]),
+                        ("objects", None if objects_result is None else objects_result["ids"])):
+        if plane is not None and tuple(plane.shape) != shape:
+            raise ValueError(f"export_solar: the products lie on a lattice of {shape} cells, the {name} on {tuple(plane.shape)}")
+    if lat_deg is None or lon_deg is None:
+        if geo is None:
+            raise ValueError("export_solar: the site needs lat_deg and lon_deg, or a geo= frame to take them from")
+        centre = torch.tensor([[grid.xoff + 0.5 * grid.xsize * grid.resolution, grid.yoff - 0.5 * grid.ysize * grid.resolution, 0.0]],
+                              dtype=torch.float64, device=alt.device)
+        lla = geo.to_scene(centre, want_lla=True)[1][0].tolist()
+        lat_deg, lon_deg = lla[0] if lat_deg is None else lat_deg, lla[1] if lon_deg is None else lon_deg
+    table_kw = {k: kwargs.pop(k) for k in ("min_kwh_m2",) if k in kwargs}
+    slopes = (None, None) if roofs_result is None else (roofs_result["slope_e"], roofs_result["slope_n"])
+    res = SO.solar(alt.float(), grid, lat_deg, lon_deg, *slopes, **kwargs)
+    facets = buildings = None
+    if roofs_result is not None:
+        facets = SO.solar_table(res, roofs_result["facet_ids"], roofs_result["n_facets"], grid.resolution, **table_kw)
+    if objects_result is not None:
+        buildings = SO.solar_table(res, objects_result["ids"], objects_result["n"], grid.resolution, **table_kw)
+    zone_string = _zone(zone_string, kwargs, geo)
+    files, fp = _writer(output_dp, "solar")
+    if fp:
+        _scalar_plane(fp, "svf", res["svf"], colormaps.COLORMAP_BONE, grid, zone_string)
+        _scalar_plane(fp, "sun_hours", res["sun_hours"].float(), colormaps.COLORMAP_JET, grid, zone_string)
+        _scalar_plane(fp, "insolation", res["global_kwh"].float(), colormaps.COLORMAP_JET, grid, zone_string)
+        with open(fp("solar.json"), "w") as f:
+            json.dump({"parameters": dict({"alt_key": alt_key}, **dict(res["parameters"], **table_kw)), "n_suns": res["n_suns"],
+                       "annual_dhi_kwh": res["annual_dhi_kwh"], "facets": None if facets is None else table_records(facets),
+                       "buildings": None if buildings is None else table_records(buildings)}, f, indent=1)
+    return dict(res, files=files, facets=facets, buildings=buildings)

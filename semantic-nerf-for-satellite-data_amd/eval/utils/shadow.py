@@ -17,8 +17,9 @@ the lidar DSM.  eval/ortho.py export_shadow_check writes the masks and the figur
 `bias` (metres) lifts the start of every march: 0.0 is the exact-spec value, and on a noisy learned DSM a cell's own neighbours
 rise above it by the noise and shadow it at low suns.  What bias a learned DSM needs is UNMEASURED; it stays a parameter.
 
-Out of scope: soft shadows and penumbrae, sub-cell interpolation of the height field, sun positions from dates, a max-mip
-acceleration.  The occlusion of a satellite's view direction is cast_rows under a view row (eval/utils/orthorect.py visibility)."""
+The suns of a date and place come from eval/utils/solar.py sun_position, whose (elevation, azimuth) pairs are a `suns` list; a year
+of suns is cheaper through that module's horizon planes than through one march per sun.
+Out of scope: soft shadows and penumbrae, sub-cell interpolation of the height field, a max-mip acceleration.  The occlusion of a satellite's view direction is cast_rows under a view row (eval/utils/orthorect.py visibility)."""
 import ctypes as C
 import math
 
