@@ -7,7 +7,7 @@
  * SnerfDsmGrid and the limits.  Same conventions: plain pointers + sizes, device pointers unless stated, `stream` is a hipStream_t,
  * 0 = SNERF_OK, a message for every other return through snerf_last_error(); no entry allocates or synchronises with the host, and
  * none launches anything for n == 0.  snerf_version() stays 6.
- * The Python binding is the table _lib.FUSE_SIGNATURES (tests/test_fuse_cpu.py compares it with this file).
+ * The Python binding is this header's group of rows in _lib.HEADER_SIGNATURES (tests/test_fuse_cpu.py compares it with this file).
  *
  * An order statistic cannot be folded with one atomic per cell: it needs the cell's list.  Three entries build the lists and read
  * them: count the offers per cell, (the caller's exclusive prefix sums turn the counts into the segments of one key buffer,)

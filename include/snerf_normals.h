@@ -8,7 +8,7 @@
  * Same conventions: plain pointers + sizes, device pointers unless stated, `stream` is a hipStream_t, 0 = SNERF_OK, a message for
  * every other return through snerf_last_error(); no entry allocates or synchronises with the host.  snerf_version() stays 6 and no
  * size snerf_workspace_bytes reports changes: what the pass needs beyond a training workspace lives in a scratch buffer of its own.
- * The Python binding is the table _lib.NORMALS_SIGNATURES (tests/test_normals_cpu.py compares it with this file). */
+ * The Python binding is this header's group of rows in _lib.HEADER_SIGNATURES (tests/test_normals_cpu.py compares it with this file). */
 #ifndef SNERF_NORMALS_H
 #define SNERF_NORMALS_H
 

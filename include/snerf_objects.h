@@ -7,7 +7,7 @@
  * conventions: plain pointers + sizes, device pointers unless stated, `stream` is a hipStream_t, 0 = SNERF_OK, a message for every
  * other return through snerf_last_error(); no entry allocates or synchronises with the host, and none launches anything for an
  * empty problem.  snerf_version() stays 6.
- * The Python binding is the table _lib.OBJECTS_SIGNATURES (tests/test_objects_cpu.py compares it with this file).
+ * The Python binding is this header's group of rows in _lib.HEADER_SIGNATURES (tests/test_objects_cpu.py compares it with this file).
  *
  * A raster is (h, w), row 0 the north edge, cell c = j * w + i (row j, column i); h * w < 2^31.  A class table is a HOST array of
  * 256 bytes, entry c non-zero = class c is in the set; it goes to the kernel by value.  Class 255 (SNERF_ORTHO_NO_LABEL) is in no

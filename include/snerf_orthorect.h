@@ -6,7 +6,7 @@
  * of its own, which includes it for the error codes, SnerfDsmGrid, SnerfRpc and the limits.  Same conventions: plain pointers +
  * sizes, device pointers unless stated, `stream` is a hipStream_t, 0 = SNERF_OK, a message for every other return through
  * snerf_last_error().  snerf_version() stays 6.
- * The Python binding is the table _lib.EXTENSION_SIGNATURES (tests/test_orthorect_cpu.py compares it with this file). */
+ * The Python binding is this header's group of rows in _lib.HEADER_SIGNATURES (tests/test_orthorect_cpu.py compares it with this file). */
 #ifndef SNERF_ORTHORECT_H
 #define SNERF_ORTHORECT_H
 

@@ -6,7 +6,7 @@
  * declared in a header of its own (as include/snerf_orthorect.h), which includes it for the error codes and SnerfDsmGrid.  Same
  * conventions: plain pointers + sizes, device pointers unless stated, `stream` is a hipStream_t, 0 = SNERF_OK, a message for every
  * other return through snerf_last_error().  snerf_version() stays 6.
- * The Python binding is the table _lib.RAYCAST_SIGNATURES (tests/test_raycast_cpu.py compares it with this file). */
+ * The Python binding is this header's group of rows in _lib.HEADER_SIGNATURES (tests/test_raycast_cpu.py compares it with this file). */
 #ifndef SNERF_RAYCAST_H
 #define SNERF_RAYCAST_H
 

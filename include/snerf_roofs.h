@@ -8,7 +8,7 @@
  * conventions: plain pointers + sizes, device pointers unless stated, `stream` is a hipStream_t, 0 = SNERF_OK, a message for every
  * other return through snerf_last_error(); no entry allocates or synchronises with the host, and none launches anything for an
  * empty problem.  snerf_version() stays 6.
- * The Python binding is the table _lib.ROOFS_SIGNATURES (tests/test_roofs_cpu.py compares it with this file).
+ * The Python binding is this header's group of rows in _lib.HEADER_SIGNATURES (tests/test_roofs_cpu.py compares it with this file).
  *
  * A raster is (h, w), row 0 the north edge, cell c = j * w + i (row j, column i); here h and w are at most SNERF_ROOFS_MAX_SIDE
  * (8192), which the sum bounds below rely on.  `key` is the int32 plane of snerf_terrain_keys (include/snerf_terrain.h):

@@ -7,7 +7,7 @@
  * declared in a header of its own (as include/snerf_roofs.h), which includes it for the error codes.  Same conventions: plain
  * pointers + sizes, device pointers unless stated, `stream` is a hipStream_t, 0 = SNERF_OK, a message for every other return through
  * snerf_last_error(); no entry allocates, copies or synchronises with the host.  snerf_version() stays 6.
- * The Python binding is the table _lib.SOLAR_SIGNATURES (tests/test_solar_cpu.py compares it with this file).
+ * The Python binding is this header's group of rows in _lib.HEADER_SIGNATURES (tests/test_solar_cpu.py compares it with this file).
  *
  * A raster is (h, w), row 0 the north edge, cell c = j * w + i (row j, column i), h * w < 2^31.  The kernels do fp64 + - * /,
  * comparisons and integer work only, one IEEE operation at a time (none contracted): the host evaluates every transcendental and no

@@ -8,7 +8,7 @@
  * conventions: plain pointers + sizes, device pointers unless stated, `stream` is a hipStream_t, 0 = SNERF_OK, a message for every
  * other return through snerf_last_error(); no entry allocates or synchronises with the host, and none launches anything for an
  * empty problem.  snerf_version() stays 6.
- * The Python binding is the table _lib.TERRAIN_SIGNATURES (tests/test_terrain_cpu.py compares it with this file).
+ * The Python binding is this header's group of rows in _lib.HEADER_SIGNATURES (tests/test_terrain_cpu.py compares it with this file).
  *
  * A raster is (h, w), row 0 the north edge, cell c = j * w + i (row j, column i); h * w < 2^31.
  * An altitude becomes a key k = rint((alt - z0) / q) in fp64, as the lattice's keys quantise.  A key is valid in the OPEN range

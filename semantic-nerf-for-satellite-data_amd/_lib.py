@@ -243,22 +243,17 @@ def _signatures():
 SIGNATURES = _signatures()
 EXPORTED_SYMBOLS = tuple(SIGNATURES)
 
-# Entries declared OUTSIDE include/snerf_hip.h, whose list of symbols is frozen at ABI 6: header -> rows in that header's order
-# (tests/test_orthorect_cpu.py compares them with the header as tests/test_abi_cpu.py does for the table above).  lib() and call()
-# serve both tables alike.  The SnerfRectImage table goes as void* twice: the host copy (a ctypes array), the device copy (a tensor).
-EXTENSION_SIGNATURES = {
+# Entries declared OUTSIDE include/snerf_hip.h, whose list of symbols is frozen at ABI 6: header -> rows in that header's order, the
+# headers in the order they were added (tests/abi_header.py compares each group with its header as tests/test_abi_cpu.py does for
+# the table above, and freezes the symbols of every group).  lib() and call() serve both tables alike.  A new map entry adds its
+# header's group here.
+HEADER_SIGNATURES = {
+    # the SnerfRectImage table goes as void* twice: the host copy (a ctypes array), the device copy (a tensor)
     "snerf_orthorect.h": {"snerf_orthorectify": (C.c_int, (C.c_void_p, C.POINTER(SnerfDsmGrid), C.c_double, C.c_int, C.c_void_p, C.c_void_p,
                                                           C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int) + (C.c_void_p,) * 9 + (c_stream,))},
-}
-# A further table of the same kind (tests/test_orthorect_cpu.py pins the one above to its single header): the entries of
-# include/snerf_raycast.h (tests/test_raycast_cpu.py compares them with it).
-RAYCAST_SIGNATURES = {
     "snerf_raycast.h": {"snerf_dsm_segment_hit": (C.c_int, (C.c_void_p, C.c_void_p, C.c_longlong, C.POINTER(SnerfDsmGrid), C.c_void_p,
                                                             C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, c_stream))},
-}
-# And one more: the entries of include/snerf_fuse.h (tests/test_fuse_cpu.py compares them with it).  quantiles_host is a HOST table
-# (a ctypes array): void*, as suns_host.
-FUSE_SIGNATURES = {
+    # quantiles_host is a HOST table (a ctypes array): void*, as suns_host
     "snerf_fuse.h": {
         "snerf_fuse_count": (C.c_int, (C.c_void_p, C.c_longlong, C.POINTER(SnerfDsmGrid), C.c_int, C.c_double, C.c_double, C.c_void_p,
                                        C.c_void_p, c_stream)),
@@ -267,19 +262,14 @@ FUSE_SIGNATURES = {
         "snerf_fuse_select": (C.c_int, (C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_void_p,
                                         C.c_void_p, c_stream)),
     },
-}
-# And the entries of include/snerf_objects.h (tests/test_objects_cpu.py compares them with it).  member_host and ground_host are HOST
-# tables (ctypes arrays of 256 bytes): void*.
-OBJECTS_SIGNATURES = {
+    # member_host and ground_host are HOST tables (ctypes arrays of 256 bytes): void*
     "snerf_objects.h": {
         "snerf_objects_link": (C.c_int, (C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, c_stream)),
         "snerf_objects_stats": (C.c_int, (C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_int,
                                           C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, c_stream)),
     },
-}
-# And the entries of include/snerf_terrain.h (tests/test_terrain_cpu.py compares them with it).  blocked_host is a HOST table (a
-# ctypes array of 256 bytes): void*.  snerf_terrain_workspace_bytes returns a long long, -1 for a refusal.
-TERRAIN_SIGNATURES = {
+    # blocked_host is a HOST table (a ctypes array of 256 bytes): void*.  snerf_terrain_workspace_bytes returns a long long, -1 for a
+    # refusal
     "snerf_terrain.h": {
         "snerf_terrain_workspace_bytes": (C.c_longlong, (C.c_int, C.c_int)),
         "snerf_terrain_keys": (C.c_int, (C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_void_p,
@@ -289,9 +279,7 @@ TERRAIN_SIGNATURES = {
         "snerf_terrain_fill": (C.c_int, (C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_stream)),
     },
-}
-# And the entries of include/snerf_roofs.h (tests/test_roofs_cpu.py compares them with it).  `planes` is a device array of doubles.
-ROOFS_SIGNATURES = {
+    # `planes` is a device array of doubles
     "snerf_roofs.h": {
         "snerf_roofs_normals": (C.c_int, (C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_int) + (C.c_double,) * 6
                                 + (C.c_void_p,) * 5 + (c_stream,)),
@@ -301,9 +289,7 @@ ROOFS_SIGNATURES = {
         "snerf_roofs_residuals": (C.c_int, (C.c_void_p,) * 3 + (C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_double, C.c_double, C.c_int,
                                                                 C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, c_stream)),
     },
-}
-# And the entries of include/snerf_solar.h (tests/test_solar_cpu.py compares them with it).  `dirs_host` and `suns_host` are host tables.
-SOLAR_SIGNATURES = {
+    # `dirs_host` and `suns_host` are host tables
     "snerf_solar.h": {
         "snerf_solar_horizon": (C.c_int, (C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p,
                                           c_stream)),
@@ -311,10 +297,7 @@ SOLAR_SIGNATURES = {
         "snerf_solar_irradiate": (C.c_int, (C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                             C.c_void_p, c_stream)),
     },
-}
-# And the entries of include/snerf_normals.h (tests/test_normals_cpu.py compares them with it): the density-gradient pass, the size of
-# its scratch buffer (an int return, the size through a size_t*) and its two test hooks.
-NORMALS_SIGNATURES = {
+    # the density-gradient pass, the size of its scratch buffer (an int return, the size through a size_t*) and its two test hooks
     "snerf_normals.h": {
         "snerf_normals_scratch_bytes": (C.c_int, (C.POINTER(SnerfDesc), C.POINTER(C.c_size_t))),
         "snerf_density_grad": (C.c_int, (C.POINTER(SnerfDesc), C.c_void_p, C.POINTER(SnerfInputs)) + (C.c_void_p,) * 5 + (c_stream,)),
@@ -323,11 +306,9 @@ NORMALS_SIGNATURES = {
     },
 }
 _ALL_SIGNATURES = dict(SIGNATURES)
-for _table in (EXTENSION_SIGNATURES, RAYCAST_SIGNATURES, FUSE_SIGNATURES, OBJECTS_SIGNATURES, TERRAIN_SIGNATURES, ROOFS_SIGNATURES,
-               SOLAR_SIGNATURES, NORMALS_SIGNATURES):
-    for _rows in _table.values():
-        assert not set(_rows) & set(_ALL_SIGNATURES)
-        _ALL_SIGNATURES.update(_rows)
+for _rows in HEADER_SIGNATURES.values():
+    assert not set(_rows) & set(_ALL_SIGNATURES)
+    _ALL_SIGNATURES.update(_rows)
 
 HIT_TOP, HIT_WALL, HIT_START, HIT_END, HIT_OUTSIDE, HIT_BAD = range(6)     # include/snerf_raycast.h SNERF_HIT_*
 

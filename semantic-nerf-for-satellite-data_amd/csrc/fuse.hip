@@ -175,7 +175,7 @@ __global__ __launch_bounds__(FUSE_WAVE) void fuse_select_kernel(const unsigned l
 static int fuse_walk_check(const char* who, const double* xyz, long long n, const SnerfDsmGrid* grid, int radius, double z0, double q,
                            const void* slots, const unsigned long long* stats) {
   if (!grid || !slots || !stats || (n > 0 && !xyz)) { set_error("%s: null pointer", who); return SNERF_ERR_NULL; }
-  if (n < 0 || n > ORTHO_MAX_N) { set_error("%s: n must lie in [0, 2^31] (n = %lld)", who, n); return SNERF_ERR_BAD_DESC; }
+  if (n < 0 || n > LATTICE_MAX_POINTS) { set_error("%s: n must lie in [0, 2^31] (n = %lld)", who, n); return SNERF_ERR_BAD_DESC; }
   if (radius < 0 || radius > SNERF_ORTHO_MAX_RADIUS) {
     set_error("%s: radius must lie in [0, %d] (radius = %d)", who, SNERF_ORTHO_MAX_RADIUS, radius);
     return SNERF_ERR_BAD_DESC;

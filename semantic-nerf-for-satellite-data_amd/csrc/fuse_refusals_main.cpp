@@ -2,9 +2,6 @@
 #include "refusals_main.h"
 #include "../../include/snerf_fuse.h"
 
-static const char* g_prefix = nullptr;
-static void expect(const char* what, int rc, int want, const char* needle) { expect(what, rc, want, needle, g_prefix); }
-
 static SnerfDsmGrid grid_of(double res, int xsize, int ysize, int ioff, int joff, int out_w, int out_h) {
   SnerfDsmGrid g = {1000.0, 2000.0, res, xsize, ysize, ioff, joff, out_w, out_h};
   return g;

@@ -1,8 +1,6 @@
 // The refusal paths of snerf_geo_cloud / snerf_geo_points (geo.hip geo_launch): see refusals_main.h.
 #include "refusals_main.h"
 
-static void expect(const char* what, int rc, int want, const char* needle) { expect(what, rc, want, needle, nullptr); }
-
 int main() {
   what_width = 52;
   // never dereferenced: every call is refused before a launch

@@ -35,7 +35,8 @@ __device__ __forceinline__ CellWindow cell_window(double x, double y, const Sner
 // (quantised altitude + 2^31) << 32 | (2^32 - 1 - global index), the quantised altitude rint((z - z0) / q) in [-2^31, 2^31).
 // false (and no key) for an altitude whose quantised value is not finite or out of range.  Ascending keys are ascending
 // altitudes and, at one altitude, descending indices; no key is 0.
-constexpr long long ORTHO_MAX_N = 2147483648LL;          // 2^31
+constexpr long long LATTICE_MAX_CELLS = 1LL << 31;       // a raster or a window has FEWER cells: a cell index is an int32
+constexpr long long LATTICE_MAX_POINTS = LATTICE_MAX_CELLS;   // a call takes AT MOST as many points or segments (n in [0, 2^31])
 constexpr long long ORTHO_MAX_INDEX = 4294967295LL;      // 2^32 - 1: index0 + n may not exceed it
 
 __device__ __forceinline__ bool lattice_key(double z, double z0, double q, unsigned long long index, unsigned long long* key) {
@@ -58,6 +59,36 @@ static inline bool lattice_grid_ok(const char* who, const SnerfDsmGrid* g) {
 static inline bool lattice_window_fits_int32(const char* who, const SnerfDsmGrid* g) {
   if ((long long)g->ioff + g->out_w <= 2147483647LL && (long long)g->joff + g->out_h <= 2147483647LL) return true;
   set_error("%s: the output window reaches beyond int32 cell indices", who);
+  return false;
+}
+
+// a window whose cells are counted in an int32
+static inline bool lattice_window_cells_ok(const char* who, const SnerfDsmGrid* g) {
+  if ((long long)g->out_h * g->out_w < LATTICE_MAX_CELLS) return true;
+  set_error("%s: a window of %d x %d cells: out_h * out_w < 2^31 required", who, g->out_h, g->out_w);
+  return false;
+}
+
+// a raster of h x w cells that are counted in an int32
+static inline bool lattice_cells_ok(const char* who, int h, int w) {
+  if (h < 1 || w < 1) { set_error("%s: h and w must be >= 1 (h = %d, w = %d)", who, h, w); return false; }
+  if ((long long)h * w >= LATTICE_MAX_CELLS) { set_error("%s: h * w must be below 2^31 (h = %d, w = %d)", who, h, w); return false; }
+  return true;
+}
+
+// Row k of a host table (`what` names a row: "sun", "direction"): its n values are finite, and the dim (2 or 3) of them from
+// row[at] on form a unit vector to 1e-9.  The other fields of a row have rules of their own, checked by the entry.
+static inline bool unit_row_ok(const char* who, const char* what, int k, const double* row, int n, int at, int dim) {
+  for (int c = 0; c < n; ++c)
+    if (!isfinite(row[c])) { set_error("%s: %s %d is not finite", who, what, k); return false; }
+  const double* u = row + at;
+  if (dim == 2) {
+    if (fabs(u[0] * u[0] + u[1] * u[1] - 1.0) <= 1e-9) return true;
+    set_error("%s: %s %d: (ux, uy) = (%.17g, %.17g) is not a unit vector", who, what, k, u[0], u[1]);
+  } else {
+    if (fabs(u[0] * u[0] + u[1] * u[1] + u[2] * u[2] - 1.0) <= 1e-9) return true;
+    set_error("%s: %s %d: (east, north, up) = (%.17g, %.17g, %.17g) is not a unit vector", who, what, k, u[0], u[1], u[2]);
+  }
   return false;
 }
 

@@ -156,12 +156,6 @@ __global__ __launch_bounds__(OBJ_THREADS) void objects_stats_kernel(const int* _
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------
-static bool objects_sizes_ok(const char* who, int h, int w) {
-  if (h < 1 || w < 1) { set_error("%s: h and w must be >= 1 (h = %d, w = %d)", who, h, w); return false; }
-  if ((long long)h * w >= 2147483648LL) { set_error("%s: h * w must be below 2^31 (h = %d, w = %d)", who, h, w); return false; }
-  return true;
-}
-
 static bool objects_table(const char* who, const char* what, const unsigned char* table_host, ObjClasses* out) {
   if (table_host[255]) { set_error("%s: %s[255] is set: class 255 means no label and is in no set", who, what); return false; }
   ObjClasses t = {{0, 0, 0, 0}};
@@ -179,7 +173,7 @@ extern "C" int snerf_objects_link(const unsigned char* label, int h, int w, cons
                                   int* parent, unsigned long long* stats, void* stream) {
   const char* who = "snerf_objects_link";
   if (!label || !member_host || !parent || !stats) { set_error("%s: null pointer", who); return SNERF_ERR_NULL; }
-  if (!objects_sizes_ok(who, h, w)) return SNERF_ERR_BAD_DESC;
+  if (!lattice_cells_ok(who, h, w)) return SNERF_ERR_BAD_DESC;
   if (connectivity != 4 && connectivity != 8) {
     set_error("%s: connectivity must be 4 or 8 (connectivity = %d)", who, connectivity);
     return SNERF_ERR_BAD_DESC;
@@ -195,8 +189,8 @@ extern "C" int snerf_objects_stats(const int* ids, const unsigned char* label, c
                                    unsigned long long* rows, unsigned long long* stats, void* stream) {
   const char* who = "snerf_objects_stats";
   if (!ids || !label || !alt || !ground_host || !stats || (K > 0 && !rows)) { set_error("%s: null pointer", who); return SNERF_ERR_NULL; }
-  if (!objects_sizes_ok(who, h, w)) return SNERF_ERR_BAD_DESC;
-  if (K < 0 || K >= 2147483648LL) { set_error("%s: K must lie in [0, 2^31) (K = %lld)", who, K); return SNERF_ERR_BAD_DESC; }
+  if (!lattice_cells_ok(who, h, w)) return SNERF_ERR_BAD_DESC;
+  if (K < 0 || K >= LATTICE_MAX_CELLS) { set_error("%s: K must lie in [0, 2^31) (K = %lld)", who, K); return SNERF_ERR_BAD_DESC; }
   if (ring < 0 || ring > SNERF_ORTHO_MAX_RADIUS) {
     set_error("%s: ring must lie in [0, %d] (ring = %d)", who, SNERF_ORTHO_MAX_RADIUS, ring);
     return SNERF_ERR_BAD_DESC;

@@ -2,9 +2,6 @@
 #include "refusals_main.h"
 #include "../../include/snerf_objects.h"
 
-static const char* g_prefix = nullptr;
-static void expect(const char* what, int rc, int want, const char* needle) { expect(what, rc, want, needle, g_prefix); }
-
 int main() {
   // never dereferenced as device memory: every call is refused before a launch
   static unsigned char label[12], classes[256], with_255[256];

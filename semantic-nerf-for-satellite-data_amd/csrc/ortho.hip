@@ -122,7 +122,7 @@ using namespace snerf;
 extern "C" int snerf_ortho_top(const double* xyz, long long n, long long index0, const SnerfDsmGrid* grid, int radius, double z0,
                                double q, unsigned long long* top, unsigned long long* stats, void* stream) {
   if (!grid || !top || !stats || (n > 0 && !xyz)) { set_error("snerf_ortho_top: null pointer"); return SNERF_ERR_NULL; }
-  if (n < 0 || n > ORTHO_MAX_N) { set_error("snerf_ortho_top: n must lie in [0, 2^31]"); return SNERF_ERR_BAD_DESC; }
+  if (n < 0 || n > LATTICE_MAX_POINTS) { set_error("snerf_ortho_top: n must lie in [0, 2^31]"); return SNERF_ERR_BAD_DESC; }
   if (index0 < 0 || index0 > ORTHO_MAX_INDEX || index0 + n > ORTHO_MAX_INDEX) {
     set_error("snerf_ortho_top: index0 >= 0 and index0 + n <= 2^32 - 1 required (index0 = %lld, n = %lld)", index0, n);
     return SNERF_ERR_BAD_DESC;
@@ -144,7 +144,7 @@ extern "C" int snerf_ortho_gather(const unsigned long long* top, long long cells
   if (!rgb != !rgb_out || !labels != !label_out || !scalar != !scalar_out) {
     set_error("snerf_ortho_gather: a payload and its output are given together or not at all"); return SNERF_ERR_NULL; }
   if (cells < 1 || cells > (1LL << 62)) { set_error("snerf_ortho_gather: cells must be >= 1"); return SNERF_ERR_BAD_DESC; }
-  if (n < 0 || n > ORTHO_MAX_N) { set_error("snerf_ortho_gather: n must lie in [0, 2^31]"); return SNERF_ERR_BAD_DESC; }
+  if (n < 0 || n > LATTICE_MAX_POINTS) { set_error("snerf_ortho_gather: n must lie in [0, 2^31]"); return SNERF_ERR_BAD_DESC; }
   if (index0 < 0 || index0 > ORTHO_MAX_INDEX || index0 + n > ORTHO_MAX_INDEX) {
     set_error("snerf_ortho_gather: index0 >= 0 and index0 + n <= 2^32 - 1 required (index0 = %lld, n = %lld)", index0, n);
     return SNERF_ERR_BAD_DESC;
@@ -160,7 +160,7 @@ extern "C" int snerf_ortho_gather(const unsigned long long* top, long long cells
 extern "C" int snerf_ortho_votes(const double* xyz, const long long* labels, long long n, const SnerfDsmGrid* grid, int radius,
                                  int n_classes, unsigned* votes, unsigned long long* stats, void* stream) {
   if (!grid || !votes || !stats || (n > 0 && (!xyz || !labels))) { set_error("snerf_ortho_votes: null pointer"); return SNERF_ERR_NULL; }
-  if (n < 0 || n > ORTHO_MAX_N) { set_error("snerf_ortho_votes: n must lie in [0, 2^31]"); return SNERF_ERR_BAD_DESC; }
+  if (n < 0 || n > LATTICE_MAX_POINTS) { set_error("snerf_ortho_votes: n must lie in [0, 2^31]"); return SNERF_ERR_BAD_DESC; }
   if (radius < 0 || radius > SNERF_ORTHO_MAX_RADIUS) { set_error("snerf_ortho_votes: radius must lie in [0, %d]", SNERF_ORTHO_MAX_RADIUS); return SNERF_ERR_BAD_DESC; }
   if (n_classes < 1 || n_classes > SNERF_ORTHO_MAX_CLASSES) { set_error("snerf_ortho_votes: n_classes must lie in [1, %d]", SNERF_ORTHO_MAX_CLASSES); return SNERF_ERR_BAD_DESC; }
   if (!lattice_grid_ok("snerf_ortho_votes", grid) || !lattice_window_fits_int32("snerf_ortho_votes", grid)) return SNERF_ERR_BAD_DESC;

@@ -25,7 +25,6 @@ namespace snerf {
 constexpr int RECT_THREADS = 256;
 constexpr int RECT_WAVES = RECT_THREADS / 64;
 constexpr unsigned RECT_MAX_BLOCKS = 8192;             // workgroups (they stride over the cells)
-constexpr long long RECT_MAX_CELLS = 2147483648LL;     // 2^31, snerf_shadow_cast's bound: the visibility planes are its output
 
 static_assert(sizeof(SnerfRectImage) == 1384, "snerf_amd/_lib.py mirrors this layout");
 static_assert(SNERF_RECT_MAX_IMAGES == SNERF_SHADOW_MAX_SUNS, "one cast call makes one call's visibility planes");
@@ -152,10 +151,7 @@ extern "C" int snerf_orthorectify(const float* dsm, const SnerfDsmGrid* grid, do
   if (!dsm || !grid || !images_host || !images_dev || !rgbs || !sum || !count || !stats) { set_error("%s: null pointer", who); return SNERF_ERR_NULL; }
   if ((labels == nullptr) != (votes == nullptr)) { set_error("%s: labels and votes go together (one of them is null)", who); return SNERF_ERR_NULL; }
   if (!lattice_grid_ok(who, grid) || !lattice_window_fits_int32(who, grid)) return SNERF_ERR_BAD_DESC;
-  if ((long long)grid->out_h * grid->out_w >= RECT_MAX_CELLS) {
-    set_error("%s: a window of %d x %d cells: out_h * out_w < 2^31 required", who, grid->out_h, grid->out_w);
-    return SNERF_ERR_BAD_DESC;
-  }
+  if (!lattice_window_cells_ok(who, grid)) return SNERF_ERR_BAD_DESC;
   if (n_images < 1 || n_images > SNERF_RECT_MAX_IMAGES) {
     set_error("%s: n_images = %d outside [1, %d]", who, n_images, SNERF_RECT_MAX_IMAGES);
     return SNERF_ERR_BAD_DESC;

@@ -4,8 +4,6 @@
 
 #include <climits>
 
-static void expect(const char* what, int rc, int want, const char* needle) { expect(what, rc, want, needle, "snerf_orthorectify: "); }
-
 // never dereferenced as device memory: every call is refused before a launch
 static float dsm[12], rgbs[3 * 40], rgb_out[2 * 3 * 12];
 static unsigned char labels[40], visible[2 * 12], label_out[2 * 12], state_out[2 * 12];
@@ -40,6 +38,7 @@ static int call(const Args& a) {
 }
 
 int main() {
+  g_prefix = "snerf_orthorectify: ";
   what_width = 52;
   for (int k = 0; k <= SNERF_RECT_MAX_IMAGES; ++k) {
     SnerfRectImage& im = images[k];

@@ -17,8 +17,6 @@ namespace snerf {
 
 constexpr int RAYCAST_THREADS = 256;
 constexpr unsigned RAYCAST_MAX_BLOCKS = 65536;         // segments beyond it are strided over
-constexpr long long RAYCAST_MAX_CELLS = 2147483648LL;  // 2^31
-constexpr long long RAYCAST_MAX_N = 2147483648LL;      // 2^31
 
 // one axis of the slab clip of step 3; false: the segment misses the window on this axis
 __device__ __forceinline__ bool clip_axis(double c0, double dc, double size, double& t0, double& t1) {
@@ -121,12 +119,9 @@ extern "C" int snerf_dsm_segment_hit(const double* p0, const double* p1, long lo
                                      double bias, double* s_out, unsigned char* state_out, int* cell_out, void* stream) {
   const char* who = "snerf_dsm_segment_hit";
   if (!p0 || !p1 || !grid || !dsm || !s_out || !state_out) { set_error("%s: null pointer", who); return SNERF_ERR_NULL; }
-  if (n < 0 || n > RAYCAST_MAX_N) { set_error("%s: n = %lld outside [0, 2^31]", who, n); return SNERF_ERR_BAD_DESC; }
+  if (n < 0 || n > LATTICE_MAX_POINTS) { set_error("%s: n = %lld outside [0, 2^31]", who, n); return SNERF_ERR_BAD_DESC; }
   if (!lattice_grid_ok(who, grid) || !lattice_window_fits_int32(who, grid)) return SNERF_ERR_BAD_DESC;
-  if ((long long)grid->out_h * grid->out_w >= RAYCAST_MAX_CELLS) {
-    set_error("%s: a window of %d x %d cells: out_h * out_w < 2^31 required", who, grid->out_h, grid->out_w);
-    return SNERF_ERR_BAD_DESC;
-  }
+  if (!lattice_window_cells_ok(who, grid)) return SNERF_ERR_BAD_DESC;
   if (!__builtin_isfinite(bias)) { set_error("%s: bias must be finite", who); return SNERF_ERR_BAD_DESC; }
   if (n == 0) return SNERF_OK;
   hipLaunchKernelGGL(dsm_segment_hit_kernel, dim3(blocks_for(n, RAYCAST_THREADS, RAYCAST_MAX_BLOCKS)), dim3(RAYCAST_THREADS), 0,

@@ -2,14 +2,13 @@
 #include "refusals_main.h"
 #include "../../include/snerf_raycast.h"
 
-static void expect(const char* what, int rc, int want, const char* needle) { expect(what, rc, want, needle, "snerf_dsm_segment_hit: "); }
-
 static SnerfDsmGrid grid_of(double res, int xsize, int ysize, int ioff, int joff, int out_w, int out_h) {
   SnerfDsmGrid g = {1000.0, 2000.0, res, xsize, ysize, ioff, joff, out_w, out_h};
   return g;
 }
 
 int main() {
+  g_prefix = "snerf_dsm_segment_hit: ";
   // never dereferenced as device memory: every call is refused before a launch
   static double p0[6], p1[6], s[2];
   static float dsm[12];

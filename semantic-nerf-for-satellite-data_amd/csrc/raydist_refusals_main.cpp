@@ -1,9 +1,8 @@
 // The refusal paths of snerf_ray_distortion (raydist.hip): see refusals_main.h.
 #include "refusals_main.h"
 
-static void expect(const char* what, int rc, int want, const char* needle) { expect(what, rc, want, needle, "snerf_ray_distortion: "); }
-
 int main() {
+  g_prefix = "snerf_ray_distortion: ";
   // never dereferenced as device memory: every call is refused before a launch
   static float w[12], z[12], rays[16], dw[12];
   static double per_ray[2];

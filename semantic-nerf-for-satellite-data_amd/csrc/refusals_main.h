@@ -34,6 +34,10 @@ static void expect(const char* what, int rc, int want, const char* needle, const
   g_error[0] = 0;
 }
 
+// the same under the prefix in force: a program sets g_prefix to "snerf_X: " before the cases of entry X, and to NULL for accepted calls
+static const char* g_prefix = nullptr;
+static void expect(const char* what, int rc, int want, const char* needle) { expect(what, rc, want, needle, g_prefix); }
+
 // the verdict line and the program's exit status
 static int verdict(const char* name) {
   printf("%s refusals: %s\n", name, failures ? "FAILED" : "ok");

@@ -1,9 +1,8 @@
 // The refusal paths of snerf_resample_z (resample.hip): see refusals_main.h.
 #include "refusals_main.h"
 
-static void expect(const char* what, int rc, int want, const char* needle) { expect(what, rc, want, needle, "snerf_resample_z: "); }
-
 int main() {
+  g_prefix = "snerf_resample_z: ";
   // never dereferenced as device memory: every call is refused before a launch
   static float z[12], w[12], u[8], out[20], fine[8];
 

@@ -3,9 +3,6 @@
 #include "refusals_main.h"
 #include "../../include/snerf_roofs.h"
 
-static const char* g_prefix = nullptr;
-static void expect(const char* what, int rc, int want, const char* needle) { expect(what, rc, want, needle, g_prefix); }
-
 int main() {
   // never dereferenced as device memory: every call is refused before a launch
   static int key[12], ids[12], tag[12], parent[12], fids[12], root[12];

@@ -1,16 +1,14 @@
 // Cast shadows on the DSM lattice: the shadow a height field casts under a sun (one Amanatides-Woo march per cell and sun), and
 // the agreement of a learned shadow map with the cast mask (integer counts and quantised integer sums).  The spec is
 // the cast-shadow section of include/snerf_hip.h and DESIGN.md section 5o.
-//   - the march is fp64, evaluated operation by operation (no fused multiply-adds in this file), and uses only + - * /,
-//     comparisons and integer work: the host evaluates every transcendental, so tests/shadow_numpy.py reproduces it bit for bit.
-//     Plain operators under `fp contract(off)`, NOT __dadd_rn / __dmul_rn: those are header inlines compiled under the build's
-//     default contraction, their operations keep that licence when inlined here, and `h0 + rise * t` written with them came out
-//     as one v_fma_f64;
-//   - a workgroup is one 16 x 16 tile of cells under ONE sun: the sun's row is wave-uniform and comes from the kernel arguments,
-//     and the parallel rays of a tile read neighbouring cells of the height field (which lives in L2: 4 MB at 1024 x 1024);
+//   - the march is the walk of dsm_march.h (fp64, operation by operation, no fused multiply-add anywhere in this file: see the note
+//     there), so tests/shadow_numpy.py reproduces it bit for bit; a workgroup is one 16 x 16 tile of cells under ONE sun, whose
+//     height field lives in L2 (4 MB at 1024 x 1024);
 //   - the agreement words are folded per wave with shuffles, then one 64-bit integer atomic add per wave and word: exact and
 //     independent of the launch order.
 // No allocation, no copy and no host synchronisation; both entries run on the caller's stream.
+#include "dsm_march.h"
+#include "lattice.h"
 #include "reduce.h"
 #include "../../include/snerf_hip.h"
 
@@ -22,7 +20,6 @@ constexpr int SHADOW_TILE = 16;
 constexpr int SHADOW_THREADS = SHADOW_TILE * SHADOW_TILE;
 constexpr unsigned SHADOW_MAX_BLOCKS = 65536;          // tiles beyond it are strided over (a tile's marches differ in length)
 constexpr unsigned SHADOW_AGREE_MAX_BLOCKS = 4096;     // per sun
-constexpr long long SHADOW_MAX_CELLS = 2147483648LL;   // 2^31
 
 // the checked rows of a call, by value in the kernel arguments
 struct ShadowSuns {
@@ -34,15 +31,11 @@ __global__ __launch_bounds__(SHADOW_THREADS) void shadow_cast_kernel(const float
                                                                      long long tiles_per_sun, long long n_tiles, ShadowSuns suns,
                                                                      double bias, double z_top, unsigned char* __restrict__ lit_out,
                                                                      float* __restrict__ dist_out) {
-  const int tx = threadIdx.x & (SHADOW_TILE - 1), ty = threadIdx.x / SHADOW_TILE;
-  const int max_steps = h + w + 2;                     // h * w < 2^31: no overflow
   for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const int k = (int)(tile / tiles_per_sun);
-    const long long r = tile - k * tiles_per_sun;
-    const long long i0 = (r % tiles_x) * SHADOW_TILE + tx, j0 = (r / tiles_x) * SHADOW_TILE + ty;
-    if (i0 >= w || j0 >= h) continue;
-    const long long cell = j0 * w + i0, o = ((long long)k * h + j0) * w + i0;
-    const double ux = suns.row[k][0], uy = suns.row[k][1], rise = suns.row[k][2];
+    int k, i0, j0;
+    if (!march_tile_cell<SHADOW_TILE, SHADOW_TILE>(tile, tiles_x, tiles_per_sun, h, w, &k, &i0, &j0)) continue;
+    const long long cell = (long long)j0 * w + i0, o = ((long long)k * h + j0) * w + i0;
+    const double rise = suns.row[k][2];
     const double start = (double)dsm[cell];
     unsigned char lit = 1;
     float dist = __builtin_nanf("");
@@ -50,28 +43,13 @@ __global__ __launch_bounds__(SHADOW_THREADS) void shadow_cast_kernel(const float
       lit = SNERF_SHADOW_UNKNOWN;
     } else {
       const double h0 = start + bias;
-      const int stepx = ux > 0.0 ? 1 : -1, stepy = uy > 0.0 ? 1 : -1;
-      const double inf = __builtin_inf();
-      const double tdx = ux == 0.0 ? inf : 1.0 / fabs(ux), tdy = uy == 0.0 ? inf : 1.0 / fabs(uy);
-      double tmx = 0.5 * tdx, tmy = 0.5 * tdy;
-      int i = (int)i0, j = (int)j0;
-      for (int s = 0; s < max_steps; ++s) {
-        double t;
-        if (tmx <= tmy) {
-          t = tmx;
-          i += stepx;
-          tmx = tmx + tdx;
-        } else {
-          t = tmy;
-          j += stepy;
-          tmy = tmy + tdy;
-        }
-        if (i < 0 || i >= w || j < 0 || j >= h) break;                       // a. left the window: lit
-        const double hr = h0 + rise * t;                                      // two roundings (see the note above)
+      DsmMarch m(h, w, i0, j0, suns.row[k][0], suns.row[k][1]);
+      while (m.next()) {                                                     // a. left the window: lit
+        const double hr = h0 + rise * m.t;                                    // two roundings
         if (hr > z_top) break;                                               // b. above everything: lit
-        if ((double)dsm[(long long)j * w + i] > hr) {                        // c. blocked (false for a NaN cell)
+        if ((double)dsm[(long long)m.j * w + m.i] > hr) {                    // c. blocked (false for a NaN cell)
           lit = 0;
-          dist = (float)t;
+          dist = (float)m.t;
           break;
         }
       }
@@ -118,10 +96,7 @@ using namespace snerf;
 extern "C" int snerf_shadow_cast(const float* dsm, int h, int w, const double* suns_host, int n_suns, double bias, double z_top,
                                  unsigned char* lit_out, float* dist_out, void* stream) {
   if (!dsm || !suns_host || !lit_out) { set_error("snerf_shadow_cast: null pointer"); return SNERF_ERR_NULL; }
-  if (h < 1 || w < 1 || (long long)h * w >= SHADOW_MAX_CELLS) {
-    set_error("snerf_shadow_cast: h, w >= 1 and h * w < 2^31 required (h = %d, w = %d)", h, w);
-    return SNERF_ERR_BAD_DESC;
-  }
+  if (!lattice_cells_ok("snerf_shadow_cast", h, w)) return SNERF_ERR_BAD_DESC;
   if (n_suns < 1 || n_suns > SNERF_SHADOW_MAX_SUNS) {
     set_error("snerf_shadow_cast: n_suns = %d outside [1, %d]", n_suns, SNERF_SHADOW_MAX_SUNS);
     return SNERF_ERR_BAD_DESC;
@@ -130,24 +105,17 @@ extern "C" int snerf_shadow_cast(const float* dsm, int h, int w, const double* s
   if (z_top != z_top) { set_error("snerf_shadow_cast: z_top is NaN"); return SNERF_ERR_BAD_DESC; }
   ShadowSuns suns = {};
   for (int k = 0; k < n_suns; ++k) {
-    const double ux = suns_host[3 * k], uy = suns_host[3 * k + 1], rise = suns_host[3 * k + 2];
-    if (!__builtin_isfinite(ux) || !__builtin_isfinite(uy) || !__builtin_isfinite(rise)) {
-      set_error("snerf_shadow_cast: sun %d is not finite", k);
-      return SNERF_ERR_BAD_DESC;
-    }
-    if (!(fabs(ux * ux + uy * uy - 1.0) <= 1e-9)) {
-      set_error("snerf_shadow_cast: sun %d: (ux, uy) = (%.17g, %.17g) is not a unit vector", k, ux, uy);
-      return SNERF_ERR_BAD_DESC;
-    }
+    const double* r = suns_host + 3 * k;
+    if (!unit_row_ok("snerf_shadow_cast", "sun", k, r, 3, 0, 2)) return SNERF_ERR_BAD_DESC;
+    const double ux = r[0], uy = r[1], rise = r[2];
     if (!(rise > 0.0)) { set_error("snerf_shadow_cast: sun %d: rise = %.17g must be > 0", k, rise); return SNERF_ERR_BAD_DESC; }
     suns.row[k][0] = ux;
     suns.row[k][1] = uy;
     suns.row[k][2] = rise;
   }
-  const int tiles_x = (w + SHADOW_TILE - 1) / SHADOW_TILE, tiles_y = (h + SHADOW_TILE - 1) / SHADOW_TILE;
-  const long long tiles_per_sun = (long long)tiles_x * tiles_y, n_tiles = tiles_per_sun * n_suns;
-  hipLaunchKernelGGL(shadow_cast_kernel, dim3(blocks_for(n_tiles, 1, SHADOW_MAX_BLOCKS)), dim3(SHADOW_THREADS), 0, (hipStream_t)stream,
-                     dsm, h, w, tiles_x, tiles_per_sun, n_tiles, suns, bias, z_top, lit_out, dist_out);
+  const MarchTiles m = march_tiles(h, w, SHADOW_TILE, SHADOW_TILE, n_suns);
+  hipLaunchKernelGGL(shadow_cast_kernel, dim3(blocks_for(m.n_tiles, 1, SHADOW_MAX_BLOCKS)), dim3(SHADOW_THREADS), 0, (hipStream_t)stream,
+                     dsm, h, w, m.tiles_x, m.tiles_per_plane, m.n_tiles, suns, bias, z_top, lit_out, dist_out);
   SNERF_LAUNCH_CHECK();
   return SNERF_OK;
 }

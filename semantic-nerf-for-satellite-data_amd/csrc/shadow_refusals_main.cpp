@@ -1,8 +1,6 @@
 // The refusal paths of snerf_shadow_cast / snerf_shadow_agreement (shadow.hip): see refusals_main.h.
 #include "refusals_main.h"
 
-static void expect(const char* what, int rc, int want, const char* needle) { expect(what, rc, want, needle, nullptr); }
-
 int main() {
   // never dereferenced as device memory: every call is refused before a launch
   static float dsm[12], sun[12], dist[12];

@@ -2,15 +2,15 @@
 // the sky-view factor from those planes, and a table of suns tested against them (direct irradiation and lit counts).  The spec is
 // include/snerf_solar.h and DESIGN.md section 5zb.
 //   - fp64, evaluated operation by operation (no fused multiply-adds in this file), only + - * /, comparisons and integer work: the
-//     host evaluates every transcendental, so tests/solar_numpy.py reproduces every word bit for bit.  Plain operators under
-//     `fp contract(off)`, not __dadd_rn and friends: see the note at the top of shadow.hip;
-//   - the horizon's march is the walk of shadow_cast_kernel (shadow.hip).  A workgroup is one 64 x 4 tile of cells under ONE
-//     direction: the direction is wave-uniform and comes from the kernel arguments, a wave is 64 neighbouring cells of a row, so the
-//     parallel marches read neighbouring addresses of the height field;
+//     host evaluates every transcendental, so tests/solar_numpy.py reproduces every word bit for bit (see the note in dsm_march.h);
+//   - the horizon's march is the walk of dsm_march.h.  A workgroup is one 64 x 4 tile of cells under ONE direction: a wave is 64
+//     neighbouring cells of a row, so the parallel marches read neighbouring addresses of the height field;
 //   - the slope of a step is a division; a step skips it when a product proves that the quotient cannot exceed the best so far, and
 //     a march ends when the same product proves that of every altitude up to z_top.  Neither changes a bit (solar_cannot_exceed);
 //   - svf and irradiate are one thread per cell over planes read sector by sector: every load is coalesced.
 // No allocation, no copy and no host synchronisation; every entry runs on the caller's stream.
+#include "dsm_march.h"
+#include "lattice.h"
 #include "reduce.h"
 #include "../../include/snerf_solar.h"
 
@@ -22,7 +22,6 @@ constexpr int SOLAR_TILE_X = 64, SOLAR_TILE_Y = 4;
 constexpr int SOLAR_THREADS = SOLAR_TILE_X * SOLAR_TILE_Y;
 constexpr unsigned SOLAR_MAX_BLOCKS = 65536;           // tiles beyond it are strided over (a tile's marches differ in length)
 constexpr unsigned SOLAR_CELL_MAX_BLOCKS = 16384;      // svf, irradiate: cells beyond it are strided over
-constexpr long long SOLAR_MAX_CELLS = 2147483648LL;    // 2^31
 
 // the checked rows of a call, by value in the kernel arguments
 struct SolarDirs {
@@ -46,16 +45,10 @@ __global__ __launch_bounds__(SOLAR_THREADS) void solar_horizon_kernel(const floa
                                                                       long long tiles_per_dir, long long n_tiles, SolarDirs dirs,
                                                                       double bias, double z_top, double max_dist,
                                                                       float* __restrict__ horizon_out) {
-  const int tx = threadIdx.x & (SOLAR_TILE_X - 1), ty = threadIdx.x / SOLAR_TILE_X;
-  const int max_steps = h + w + 2;                     // h * w < 2^31: no overflow
-  const double inf = __builtin_inf();
   for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const int k = (int)(tile / tiles_per_dir);
-    const long long r = tile - k * tiles_per_dir;
-    const long long i0 = (r % tiles_x) * SOLAR_TILE_X + tx, j0 = (r / tiles_x) * SOLAR_TILE_Y + ty;
-    if (i0 >= w || j0 >= h) continue;
-    const long long cell = j0 * w + i0, o = ((long long)k * h + j0) * w + i0;
-    const double ux = dirs.row[k][0], uy = dirs.row[k][1];
+    int k, i0, j0;
+    if (!march_tile_cell<SOLAR_TILE_X, SOLAR_TILE_Y>(tile, tiles_x, tiles_per_dir, h, w, &k, &i0, &j0)) continue;
+    const long long cell = (long long)j0 * w + i0, o = ((long long)k * h + j0) * w + i0;
     const double start = (double)dsm[cell];
     if (start != start) {
       horizon_out[o] = __builtin_nanf("");
@@ -63,27 +56,14 @@ __global__ __launch_bounds__(SOLAR_THREADS) void solar_horizon_kernel(const floa
     }
     const double h0 = start + bias;
     const double top = z_top - h0;                     // no altitude <= z_top gives a larger numerator (rounding is monotone)
-    const int stepx = ux > 0.0 ? 1 : -1, stepy = uy > 0.0 ? 1 : -1;
-    const double tdx = ux == 0.0 ? inf : 1.0 / fabs(ux), tdy = uy == 0.0 ? inf : 1.0 / fabs(uy);
-    double tmx = 0.5 * tdx, tmy = 0.5 * tdy;
-    double best = -inf;
-    int i = (int)i0, j = (int)j0;
-    for (int s = 0; s < max_steps; ++s) {
-      double t;
-      if (tmx <= tmy) {
-        t = tmx;
-        i += stepx;
-        tmx = tmx + tdx;
-      } else {
-        t = tmy;
-        j += stepy;
-        tmy = tmy + tdy;
-      }
-      if (i < 0 || i >= w || j < 0 || j >= h) break;                         // a. left the window
+    double best = -__builtin_inf();
+    DsmMarch m(h, w, i0, j0, dirs.row[k][0], dirs.row[k][1]);
+    while (m.next()) {                                                       // a. left the window
+      const double t = m.t;
       if (t > max_dist) break;                                               // b. beyond the search distance
       const double p = best * t;                                             // -inf until something was tested: both tests then fail
       if (top >= 0.0 && solar_cannot_exceed(top, p, best)) break;            // nothing from here on can raise best (t only grows)
-      const double num = (double)dsm[(long long)j * w + i] - h0;
+      const double num = (double)dsm[(long long)m.j * w + m.i] - h0;
       if (solar_cannot_exceed(num, p, best)) continue;
       const double sl = num / t;                                             // c. false for a NaN cell
       if (sl > best) best = sl;
@@ -138,12 +118,6 @@ __global__ __launch_bounds__(256) void solar_irradiate_kernel(const float* __res
   }
 }
 
-static bool solar_sizes_ok(const char* who, int h, int w) {
-  if (h >= 1 && w >= 1 && (long long)h * w < SOLAR_MAX_CELLS) return true;
-  set_error("%s: h, w >= 1 and h * w < 2^31 required (h = %d, w = %d)", who, h, w);
-  return false;
-}
-
 }  // namespace snerf
 
 using namespace snerf;
@@ -151,7 +125,7 @@ using namespace snerf;
 extern "C" int snerf_solar_horizon(const float* dsm, int h, int w, const double* dirs_host, int n_dirs, double bias, double z_top,
                                    double max_dist, float* horizon_out, void* stream) {
   if (!dsm || !dirs_host || !horizon_out) { set_error("snerf_solar_horizon: null pointer"); return SNERF_ERR_NULL; }
-  if (!solar_sizes_ok("snerf_solar_horizon", h, w)) return SNERF_ERR_BAD_DESC;
+  if (!lattice_cells_ok("snerf_solar_horizon", h, w)) return SNERF_ERR_BAD_DESC;
   if (n_dirs < 1 || n_dirs > SNERF_SOLAR_MAX_DIRS) {
     set_error("snerf_solar_horizon: n_dirs = %d outside [1, %d]", n_dirs, SNERF_SOLAR_MAX_DIRS);
     return SNERF_ERR_BAD_DESC;
@@ -161,29 +135,21 @@ extern "C" int snerf_solar_horizon(const float* dsm, int h, int w, const double*
   if (!(max_dist > 0.0)) { set_error("snerf_solar_horizon: max_dist = %.17g must be > 0 (+inf: no bound)", max_dist); return SNERF_ERR_BAD_DESC; }
   SolarDirs dirs = {};
   for (int k = 0; k < n_dirs; ++k) {
-    const double ux = dirs_host[2 * k], uy = dirs_host[2 * k + 1];
-    if (!__builtin_isfinite(ux) || !__builtin_isfinite(uy)) {
-      set_error("snerf_solar_horizon: direction %d is not finite", k);
-      return SNERF_ERR_BAD_DESC;
-    }
-    if (!(fabs(ux * ux + uy * uy - 1.0) <= 1e-9)) {
-      set_error("snerf_solar_horizon: direction %d: (ux, uy) = (%.17g, %.17g) is not a unit vector", k, ux, uy);
-      return SNERF_ERR_BAD_DESC;
-    }
-    dirs.row[k][0] = ux;
-    dirs.row[k][1] = uy;
+    const double* r = dirs_host + 2 * k;
+    if (!unit_row_ok("snerf_solar_horizon", "direction", k, r, 2, 0, 2)) return SNERF_ERR_BAD_DESC;
+    dirs.row[k][0] = r[0];
+    dirs.row[k][1] = r[1];
   }
-  const int tiles_x = (w + SOLAR_TILE_X - 1) / SOLAR_TILE_X, tiles_y = (h + SOLAR_TILE_Y - 1) / SOLAR_TILE_Y;
-  const long long tiles_per_dir = (long long)tiles_x * tiles_y, n_tiles = tiles_per_dir * n_dirs;
-  hipLaunchKernelGGL(solar_horizon_kernel, dim3(blocks_for(n_tiles, 1, SOLAR_MAX_BLOCKS)), dim3(SOLAR_THREADS), 0, (hipStream_t)stream,
-                     dsm, h, w, tiles_x, tiles_per_dir, n_tiles, dirs, bias, z_top, max_dist, horizon_out);
+  const MarchTiles m = march_tiles(h, w, SOLAR_TILE_X, SOLAR_TILE_Y, n_dirs);
+  hipLaunchKernelGGL(solar_horizon_kernel, dim3(blocks_for(m.n_tiles, 1, SOLAR_MAX_BLOCKS)), dim3(SOLAR_THREADS), 0, (hipStream_t)stream,
+                     dsm, h, w, m.tiles_x, m.tiles_per_plane, m.n_tiles, dirs, bias, z_top, max_dist, horizon_out);
   SNERF_LAUNCH_CHECK();
   return SNERF_OK;
 }
 
 extern "C" int snerf_solar_svf(const float* horizon, int n_dirs, int h, int w, double res, float* svf_out, void* stream) {
   if (!horizon || !svf_out) { set_error("snerf_solar_svf: null pointer"); return SNERF_ERR_NULL; }
-  if (!solar_sizes_ok("snerf_solar_svf", h, w)) return SNERF_ERR_BAD_DESC;
+  if (!lattice_cells_ok("snerf_solar_svf", h, w)) return SNERF_ERR_BAD_DESC;
   if (n_dirs < 1 || n_dirs > SNERF_SOLAR_MAX_SECTORS) {
     set_error("snerf_solar_svf: n_dirs = %d outside [1, %d]", n_dirs, SNERF_SOLAR_MAX_SECTORS);
     return SNERF_ERR_BAD_DESC;
@@ -203,7 +169,7 @@ extern "C" int snerf_solar_irradiate(const float* horizon, int n_dirs, int h, in
     set_error("snerf_solar_irradiate: slope_e and slope_n are both null or both set");
     return SNERF_ERR_NULL;
   }
-  if (!solar_sizes_ok("snerf_solar_irradiate", h, w)) return SNERF_ERR_BAD_DESC;
+  if (!lattice_cells_ok("snerf_solar_irradiate", h, w)) return SNERF_ERR_BAD_DESC;
   if (n_dirs < 1 || n_dirs > SNERF_SOLAR_MAX_SECTORS) {
     set_error("snerf_solar_irradiate: n_dirs = %d outside [1, %d]", n_dirs, SNERF_SOLAR_MAX_SECTORS);
     return SNERF_ERR_BAD_DESC;
@@ -215,18 +181,13 @@ extern "C" int snerf_solar_irradiate(const float* horizon, int n_dirs, int h, in
   SolarSuns suns = {};
   for (int k = 0; k < n_suns; ++k) {
     const double* r = suns_host + 7 * k;
-    for (int c = 0; c < 7; ++c)
-      if (!__builtin_isfinite(r[c])) { set_error("snerf_solar_irradiate: sun %d is not finite", k); return SNERF_ERR_BAD_DESC; }
+    if (!unit_row_ok("snerf_solar_irradiate", "sun", k, r, 7, 3, 3)) return SNERF_ERR_BAD_DESC;
     if (!(r[0] >= 0.0 && r[0] < (double)n_dirs) || r[0] != (double)(int)r[0]) {
       set_error("snerf_solar_irradiate: sun %d: sector = %.17g is no integer of [0, %d)", k, r[0], n_dirs);
       return SNERF_ERR_BAD_DESC;
     }
     if (!(r[1] >= 0.0 && r[1] < 1.0)) { set_error("snerf_solar_irradiate: sun %d: frac = %.17g outside [0, 1)", k, r[1]); return SNERF_ERR_BAD_DESC; }
     if (!(r[2] > 0.0)) { set_error("snerf_solar_irradiate: sun %d: rise = %.17g must be > 0", k, r[2]); return SNERF_ERR_BAD_DESC; }
-    if (!(fabs(r[3] * r[3] + r[4] * r[4] + r[5] * r[5] - 1.0) <= 1e-9)) {
-      set_error("snerf_solar_irradiate: sun %d: (east, north, up) = (%.17g, %.17g, %.17g) is not a unit vector", k, r[3], r[4], r[5]);
-      return SNERF_ERR_BAD_DESC;
-    }
     if (!(r[5] > 0.0)) { set_error("snerf_solar_irradiate: sun %d: up = %.17g must be > 0", k, r[5]); return SNERF_ERR_BAD_DESC; }
     if (!(r[6] >= 0.0)) { set_error("snerf_solar_irradiate: sun %d: weight = %.17g must be >= 0", k, r[6]); return SNERF_ERR_BAD_DESC; }
     for (int c = 0; c < 7; ++c) suns.row[k][c] = r[c];

@@ -2,9 +2,6 @@
 #include "refusals_main.h"
 #include "../../include/snerf_solar.h"
 
-static const char* g_prefix = nullptr;
-static void expect(const char* what, int rc, int want, const char* needle) { expect(what, rc, want, needle, g_prefix); }
-
 int main() {
   // never dereferenced as device memory: every call is refused before a launch.  The rows ARE read: they are host tables.
   static float dsm[12], horizon[24], svf[12], slope_e[12], slope_n[12];

@@ -368,12 +368,6 @@ __global__ __launch_bounds__(TER_THREADS) void terrain_fill_combine_kernel(const
 // ---- host side ---------------------------------------------------------------------------------------------------------------------
 constexpr unsigned TER_MAX_BLOCKS = 65536;               // cells beyond it are taken in a grid-stride
 
-static bool terrain_sizes_ok(const char* who, int h, int w) {
-  if (h < 1 || w < 1) { set_error("%s: h and w must be >= 1 (h = %d, w = %d)", who, h, w); return false; }
-  if ((long long)h * w >= 2147483648LL) { set_error("%s: h * w must be below 2^31 (h = %d, w = %d)", who, h, w); return false; }
-  return true;
-}
-
 // the four passes' launch shapes: every count below fits 32 bits for h * w < 2^31 (a group or a block holds at least 3 cells)
 struct TerPassShape {
   int nb, chunks, groups;            // rows: blocks per wave, steps per wave, waves per row
@@ -403,7 +397,7 @@ static TerPassShape terrain_pass_shape(int h, int w, int radius) {
 using namespace snerf;
 
 extern "C" long long snerf_terrain_workspace_bytes(int h, int w) {
-  if (!terrain_sizes_ok("snerf_terrain_workspace_bytes", h, w)) return -1;
+  if (!lattice_cells_ok("snerf_terrain_workspace_bytes", h, w)) return -1;
   return 16LL * h * w;
 }
 
@@ -416,7 +410,7 @@ extern "C" int snerf_terrain_keys(const float* alt, const unsigned char* label, 
               blocked_host ? "given" : "null");
     return SNERF_ERR_NULL;
   }
-  if (!terrain_sizes_ok(who, h, w)) return SNERF_ERR_BAD_DESC;
+  if (!lattice_cells_ok(who, h, w)) return SNERF_ERR_BAD_DESC;
   if (!quant_ok(who, z0, q)) return SNERF_ERR_BAD_DESC;
   TerClasses blocked = {{0, 0, 0, 0}};
   if (blocked_host) {
@@ -438,7 +432,7 @@ extern "C" int snerf_terrain_open(const int* key_in, int h, int w, int radius, l
                                   void* ws, unsigned long long* stats, void* stream) {
   const char* who = "snerf_terrain_open";
   if (!key_in || !key_out || !ws || !stats) { set_error("%s: null pointer", who); return SNERF_ERR_NULL; }
-  if (!terrain_sizes_ok(who, h, w)) return SNERF_ERR_BAD_DESC;
+  if (!lattice_cells_ok(who, h, w)) return SNERF_ERR_BAD_DESC;
   if (radius < 1 || radius > SNERF_TERRAIN_MAX_RADIUS) {
     set_error("%s: radius must lie in [1, %d] (radius = %d)", who, SNERF_TERRAIN_MAX_RADIUS, radius);
     return SNERF_ERR_BAD_DESC;
@@ -477,7 +471,7 @@ extern "C" int snerf_terrain_fill(const int* key, const unsigned char* flags, co
                                   float* dtm, float* ndsm, int* reach, void* ws, unsigned long long* stats, void* stream) {
   const char* who = "snerf_terrain_fill";
   if (!key || !flags || !alt || !dtm || !ndsm || !ws || !stats) { set_error("%s: null pointer", who); return SNERF_ERR_NULL; }
-  if (!terrain_sizes_ok(who, h, w)) return SNERF_ERR_BAD_DESC;
+  if (!lattice_cells_ok(who, h, w)) return SNERF_ERR_BAD_DESC;
   if (!quant_ok(who, z0, q)) return SNERF_ERR_BAD_DESC;
   const long long cells = (long long)h * w;
   int* west = (int*)ws;

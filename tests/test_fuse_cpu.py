@@ -1,5 +1,5 @@
 """CPU-side checks of the fused altitude quantiles (include/snerf_fuse.h, csrc/fuse.hip, eval/utils/fuse.py):
-the new header's prototypes and constant against the binding (_lib.FUSE_SIGNATURES), the rank rule and the restatement
+the new header's prototypes and constant against the binding (_lib.HEADER_SIGNATURES), the rank rule and the restatement
 (tests/fuse_numpy.py, the oracle of tests/test_gpu_fuse.py) against numpy's own quantile and against its plain-loop form, the
 floater case as exact values, and every refusal of the three entries through the binding (none reaches a launch)."""
 import ctypes as C
@@ -19,7 +19,6 @@ from tests import ortho_numpy as R
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "snerf_fuse.h")
 DUMMY = 4096        # a non-null address no refusal path dereferences
-SYMBOLS = ["snerf_fuse_count", "snerf_fuse_scatter", "snerf_fuse_select"]
 NAMES = {
     "snerf_fuse_count": ["xyz", "n", "grid", "radius", "z0", "q", "count", "stats", "stream"],
     "snerf_fuse_scatter": ["xyz", "n", "index0", "grid", "radius", "z0", "q", "offsets", "capacity", "cursor", "keys", "stats", "stream"],
@@ -28,37 +27,11 @@ NAMES = {
 
 
 def test_the_new_header_matches_its_binding_rows():
-    """include/snerf_fuse.h against _lib.FUSE_SIGNATURES["snerf_fuse.h"], as tests/test_raycast_cpu.py compares its header: every
-    prototype has a row and the reverse, in the header's order; return type, parameter count and, per parameter, class, width and
-    signedness; the stream marker exactly where the parameter is called `stream`; the library exports the symbols and lib() /
-    call() know them.  The main header, the main table, the other extension tables and the ABI version are untouched."""
-    from tests.test_abi_cpu import _c_type, _table_type
+    """include/snerf_fuse.h against its rows of _lib.HEADER_SIGNATURES (tests/abi_header.py), then the constants; the main header, the
+    main table, the other headers' rows and the ABI version are untouched"""
+    from tests.abi_header import check_header
+    check_header("snerf_fuse.h", NAMES)
     text = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    src = re.sub(r"^\s*#.*$", "", src, flags=re.M)
-    protos = {}
-    for ret, name, params in re.findall(r"([\w \*]+?)\b(snerf_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", src):
-        protos[name] = (_c_type(ret), [(_c_type(t), n) for t, n in (re.fullmatch(r"\s*(.*?)(\w+)\s*", p).groups() for p in params.split(","))])
-    assert list(_lib.FUSE_SIGNATURES) == ["snerf_fuse.h"]
-    rows = _lib.FUSE_SIGNATURES["snerf_fuse.h"]
-    assert list(rows) == list(protos) == SYMBOLS
-    for symbol in SYMBOLS:
-        ret, params = protos[symbol]
-        restype, argtypes = rows[symbol]
-        assert _table_type(restype) == ret == ("int", 4, True) and len(argtypes) == len(params)
-        assert [n for _, n in params] == NAMES[symbol]
-        for k, (t, (want, pname)) in enumerate(zip(argtypes, params)):
-            got = _table_type(t)
-            assert got == want or (want[0] == "pointer" and got == ("pointer", None)), (symbol, k, pname, t, want)
-            assert (t is _lib.c_stream) == (pname == "stream"), (symbol, k, pname)
-        fn = getattr(_lib.lib(), symbol)
-        assert fn.restype is restype and tuple(fn.argtypes) == tuple(argtypes) and symbol in _lib._PLANS
-        assert symbol not in _lib.SIGNATURES and symbol not in _lib.EXPORTED_SYMBOLS
-        assert symbol not in _lib.EXTENSION_SIGNATURES["snerf_orthorect.h"] and symbol not in _lib.RAYCAST_SIGNATURES["snerf_raycast.h"]
-    assert list(_lib.EXTENSION_SIGNATURES) == ["snerf_orthorect.h"] and list(_lib.RAYCAST_SIGNATURES) == ["snerf_raycast.h"]
-    main = open(os.path.join(ROOT, "include", "snerf_hip.h")).read()
-    assert "snerf_fuse" not in main and "SNERF_FUSE_" not in main and '#include "snerf_hip.h"' in text
-    assert _lib.lib().snerf_version() == _lib.ABI_VERSION == 6
     assert int(re.search(r"#define SNERF_FUSE_MAX_QUANTILES (\d+)", text).group(1)) == _lib.FUSE_MAX_QUANTILES == F.MAX_QUANTILES == 8
     assert F.QUARTILES == N.QUARTILES == ((1, 4), (1, 2), (3, 4))
 

@@ -20,10 +20,8 @@ from snerf_amd.eval.utils import normals as NM          # the feature under test
 from tests import normals_numpy as NN
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "snerf_normals.h")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 DUMMY = 4096        # a non-null, 256-byte aligned address no refusal path dereferences
-SYMBOLS = ["snerf_normals_scratch_bytes", "snerf_density_grad", "snerf_test_normals_grid", "snerf_test_normals_dump"]
 NAMES = {
     "snerf_normals_scratch_bytes": ["desc", "bytes"],
     "snerf_density_grad": ["desc", "packed_params", "inputs", "coef", "grad_ray", "grad_sample", "workspace", "scratch", "stream"],
@@ -154,33 +152,9 @@ def test_scratch_size_and_the_cpu_refusal_of_ops():
 
 # ---- header and ABI -------------------------------------------------------------------------------------------------------------------------
 def test_the_new_header_matches_its_binding_rows():
-    from tests.test_abi_cpu import _c_type, _table_type
-    text = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    src = re.sub(r"^\s*#.*$", "", src, flags=re.M)
-    protos = {}
-    for ret, name, params in re.findall(r"([\w \*]+?)\b(snerf_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", src):
-        protos[name] = (_c_type(ret), [(_c_type(t), n) for t, n in (re.fullmatch(r"\s*(.*?)(\w+)\s*", p).groups() for p in params.split(","))])
-    assert list(_lib.NORMALS_SIGNATURES) == ["snerf_normals.h"]
-    rows = _lib.NORMALS_SIGNATURES["snerf_normals.h"]
-    assert list(rows) == list(protos) == SYMBOLS
-    for symbol in SYMBOLS:
-        ret, params = protos[symbol]
-        restype, argtypes = rows[symbol]
-        assert _table_type(restype) == ret == ("int", 4, True) and len(argtypes) == len(params)
-        assert [n for _, n in params] == NAMES[symbol]
-        for k, (t, (want, pname)) in enumerate(zip(argtypes, params)):
-            got = _table_type(t)
-            assert got == want or (want[0] == "pointer" and got[0] == "pointer"), (symbol, k, pname, t, want)
-            assert (t is _lib.c_stream) == (pname == "stream"), (symbol, k, pname)
-        fn = getattr(_lib.lib(), symbol)
-        assert fn.restype is restype and tuple(fn.argtypes) == tuple(argtypes) and symbol in _lib._PLANS
-        assert symbol not in _lib.SIGNATURES and symbol not in _lib.EXPORTED_SYMBOLS
-        for other in (_lib.EXTENSION_SIGNATURES, _lib.RAYCAST_SIGNATURES, _lib.FUSE_SIGNATURES, _lib.OBJECTS_SIGNATURES, _lib.TERRAIN_SIGNATURES,
-                      _lib.ROOFS_SIGNATURES):
-            assert all(symbol not in table for table in other.values())
-    assert '#include "snerf_hip.h"' in text
-    assert _lib.lib().snerf_version() == _lib.ABI_VERSION == 6
+    """include/snerf_normals.h (the pass, its scratch size and the two test hooks) against its rows of _lib.HEADER_SIGNATURES"""
+    from tests.abi_header import check_header
+    check_header("snerf_normals.h", NAMES)
 
 
 def test_the_main_header_is_what_it_was():

@@ -1,5 +1,5 @@
 """CPU-side checks of the objects on the map (include/snerf_objects.h, csrc/objects.hip, eval/utils/objects.py):
-the new header's prototypes and constant against the binding (_lib.OBJECTS_SIGNATURES), the restatement's labelling
+the new header's prototypes and constant against the binding (_lib.HEADER_SIGNATURES), the restatement's labelling
 (tests/objects_numpy.py, the oracle of tests/test_gpu_objects.py) against scipy.ndimage.label, the table arithmetic on hand-made
 rows, the matching and the scores on CPU tensors, and every refusal of the two entries through the binding (none reaches a launch)."""
 import ctypes as C
@@ -19,7 +19,6 @@ from tests import objects_numpy as N
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "snerf_objects.h")
 DUMMY = 4096        # a non-null address no refusal path dereferences
-SYMBOLS = ["snerf_objects_link", "snerf_objects_stats"]
 NAMES = {
     "snerf_objects_link": ["label", "h", "w", "member_host", "connectivity", "parent", "stats", "stream"],
     "snerf_objects_stats": ["ids", "label", "alt", "h", "w", "K", "ground_host", "ring", "z0", "q", "row0", "row1", "rows", "stats",
@@ -28,37 +27,11 @@ NAMES = {
 
 
 def test_the_new_header_matches_its_binding_rows():
-    """include/snerf_objects.h against _lib.OBJECTS_SIGNATURES["snerf_objects.h"], as tests/test_fuse_cpu.py compares its header:
-    every prototype has a row and the reverse, in the header's order; return type, parameter count and, per parameter, class, width
-    and signedness; the stream marker exactly where the parameter is called `stream`; the library exports the symbols and lib() /
-    call() know them.  The main header, the main table, the other extension tables and the ABI version are untouched."""
-    from tests.test_abi_cpu import _c_type, _table_type
+    """include/snerf_objects.h against its rows of _lib.HEADER_SIGNATURES (tests/abi_header.py), then the constants; the main header, the
+    main table, the other headers' rows and the ABI version are untouched"""
+    from tests.abi_header import check_header
+    check_header("snerf_objects.h", NAMES)
     text = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    src = re.sub(r"^\s*#.*$", "", src, flags=re.M)
-    protos = {}
-    for ret, name, params in re.findall(r"([\w \*]+?)\b(snerf_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", src):
-        protos[name] = (_c_type(ret), [(_c_type(t), n) for t, n in (re.fullmatch(r"\s*(.*?)(\w+)\s*", p).groups() for p in params.split(","))])
-    assert list(_lib.OBJECTS_SIGNATURES) == ["snerf_objects.h"]
-    rows = _lib.OBJECTS_SIGNATURES["snerf_objects.h"]
-    assert list(rows) == list(protos) == SYMBOLS
-    for symbol in SYMBOLS:
-        ret, params = protos[symbol]
-        restype, argtypes = rows[symbol]
-        assert _table_type(restype) == ret == ("int", 4, True) and len(argtypes) == len(params)
-        assert [n for _, n in params] == NAMES[symbol]
-        for k, (t, (want, pname)) in enumerate(zip(argtypes, params)):
-            got = _table_type(t)
-            assert got == want or (want[0] == "pointer" and got == ("pointer", None)), (symbol, k, pname, t, want)
-            assert (t is _lib.c_stream) == (pname == "stream"), (symbol, k, pname)
-        fn = getattr(_lib.lib(), symbol)
-        assert fn.restype is restype and tuple(fn.argtypes) == tuple(argtypes) and symbol in _lib._PLANS
-        assert symbol not in _lib.SIGNATURES and symbol not in _lib.EXPORTED_SYMBOLS
-        for other in (_lib.EXTENSION_SIGNATURES, _lib.RAYCAST_SIGNATURES, _lib.FUSE_SIGNATURES):
-            assert all(symbol not in table for table in other.values())
-    main = open(os.path.join(ROOT, "include", "snerf_hip.h")).read()
-    assert "snerf_objects" not in main and "SNERF_OBJECTS_" not in main and '#include "snerf_hip.h"' in text
-    assert _lib.lib().snerf_version() == _lib.ABI_VERSION == 6
     assert int(re.search(r"#define SNERF_OBJECTS_ROW_WORDS (\d+)", text).group(1)) == _lib.OBJECTS_ROW_WORDS == OB.ROW_WORDS == N.ROW_WORDS == 16
     assert OB.MAX_RING == _lib.ORTHO_MAX_RADIUS == 7 and OB.NO_LABEL == N.NO_LABEL == 255
     # the initial row words of the header's table, in the host layer (int64 holding the u64) and in the restatement

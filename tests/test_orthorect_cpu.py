@@ -1,5 +1,5 @@
 """CPU-side checks of the orthorectifier (include/snerf_orthorect.h, csrc/orthorect.hip, eval/utils/orthorect.py):
-the extension header's prototype, constants and struct layout against the binding (_lib.EXTENSION_SIGNATURES), the refusals of the
+the extension header's prototype, constants and struct layout against the binding (_lib.HEADER_SIGNATURES), the refusals of the
 entry through the binding (none reaches a launch) and of the Python layer, map_agreement (plain torch: it runs on CPU tensors), and the numpy restatement
 (tests/orthorect_numpy.py, the oracle of tests/test_gpu_orthorect.py) on the fixture scene: the five images of
 tests/golden/scene_small on a 2 m lattice over their corners, the DSM a plane with one 30 m block."""
@@ -20,6 +20,8 @@ from tests import shadow_numpy as SN
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "snerf_orthorect.h")
 DUMMY = 4096        # a non-null address no refusal path dereferences
+NAMES = {"snerf_orthorectify": ["dsm", "grid", "lon0", "south", "images_host", "images_dev", "n_images", "rgbs", "labels", "n_rows", "n_classes",
+                                "visible", "sum", "count", "votes", "col_row", "rgb_out", "label_out", "state_out", "stats", "stream"]}
 
 
 def test_header_constants_and_layout_match_the_binding():
@@ -35,32 +37,11 @@ def test_header_constants_and_layout_match_the_binding():
 
 
 def test_extension_header_matches_its_binding_row():
-    """include/snerf_orthorect.h against _lib.EXTENSION_SIGNATURES["snerf_orthorect.h"], as tests/test_abi_cpu.py compares the main
-    header with the main table: every prototype has a row and the reverse, in the header's order; return type, parameter count and,
-    per parameter, class, width and signedness; the stream marker exactly where the parameter is called `stream`; the library exports
-    the symbol and lib() / call() know it.  The main header, the main table and the ABI version are untouched."""
-    from tests.test_abi_cpu import _c_type, _table_type
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    src = re.sub(r"^\s*#.*$", "", src, flags=re.M)
-    src = re.sub(r"typedef struct \w+ \{.*?\} \w+;", "", src, flags=re.S)
-    protos = {}
-    for ret, name, params in re.findall(r"([\w \*]+?)\b(snerf_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", src):
-        protos[name] = (_c_type(ret), [(_c_type(t), n) for t, n in (re.fullmatch(r"\s*(.*?)(\w+)\s*", p).groups() for p in params.split(","))])
-    assert list(_lib.EXTENSION_SIGNATURES) == ["snerf_orthorect.h"]
-    rows = _lib.EXTENSION_SIGNATURES["snerf_orthorect.h"]
-    assert list(rows) == list(protos) == ["snerf_orthorectify"]
-    for name, (ret, params) in protos.items():
-        restype, argtypes = rows[name]
-        assert _table_type(restype) == ret and len(argtypes) == len(params) == 21, name
-        for k, (t, (want, pname)) in enumerate(zip(argtypes, params)):
-            got = _table_type(t)
-            assert got == want or (want[0] == "pointer" and got == ("pointer", None)), (name, k, pname, t, want)
-            assert (t is _lib.c_stream) == (pname == "stream"), (name, k, pname)
-        fn = getattr(_lib.lib(), name)
-        assert fn.restype is restype and tuple(fn.argtypes) == tuple(argtypes) and name in _lib._PLANS
-        assert name not in _lib.SIGNATURES and name not in _lib.EXPORTED_SYMBOLS
-    main = open(os.path.join(ROOT, "include", "snerf_hip.h")).read()
-    assert "snerf_orthorectify" not in main and "SnerfRectImage" not in main and '#include "snerf_hip.h"' in open(HEADER).read()
+    """include/snerf_orthorect.h against its rows of _lib.HEADER_SIGNATURES (tests/abi_header.py); the main header, the main table,
+    the other headers' rows and the ABI version are untouched"""
+    from tests.abi_header import check_header
+    check_header("snerf_orthorect.h", NAMES)
+    assert len(NAMES["snerf_orthorectify"]) == 21
 
 
 @pytest.fixture(scope="module")

@@ -1,5 +1,5 @@
 """CPU-side checks of the DSM ray cast (include/snerf_raycast.h, csrc/raycast.hip, eval/utils/raycast.py, baseline/dataset/
-dsm_depth_dataset.py): the new header's prototype and constants against the binding (_lib.RAYCAST_SIGNATURES),
+dsm_depth_dataset.py): the new header's prototype and constants against the binding (_lib.HEADER_SIGNATURES),
 the refusals of the entry through the binding (none reaches a launch), of the Python layer and of the new config fields, the numpy
 restatement (tests/raycast_numpy.py, the oracle of tests/test_gpu_raycast.py) against an independent dense oracle, guide_rays on
 hand-made rows, and the host logic of DsmDepthDataset on the fixture scene."""
@@ -35,33 +35,10 @@ def test_header_constants_match_the_binding_and_the_restatement():
 
 
 def test_the_new_header_matches_its_binding_row():
-    """include/snerf_raycast.h against _lib.RAYCAST_SIGNATURES["snerf_raycast.h"], as tests/test_orthorect_cpu.py compares its header:
-    every prototype has a row and the reverse, in the header's order; return type, parameter count and, per parameter, class, width
-    and signedness; the stream marker exactly where the parameter is called `stream`; the library exports the symbol and lib() /
-    call() know it.  The main header, the main table, the extension table and the ABI version are untouched."""
-    from tests.test_abi_cpu import _c_type, _table_type
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    src = re.sub(r"^\s*#.*$", "", src, flags=re.M)
-    protos = {}
-    for ret, name, params in re.findall(r"([\w \*]+?)\b(snerf_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", src):
-        protos[name] = (_c_type(ret), [(_c_type(t), n) for t, n in (re.fullmatch(r"\s*(.*?)(\w+)\s*", p).groups() for p in params.split(","))])
-    assert list(_lib.RAYCAST_SIGNATURES) == ["snerf_raycast.h"]
-    rows = _lib.RAYCAST_SIGNATURES["snerf_raycast.h"]
-    assert list(rows) == list(protos) == [SYMBOL]
-    ret, params = protos[SYMBOL]
-    restype, argtypes = rows[SYMBOL]
-    assert _table_type(restype) == ret and len(argtypes) == len(params) == 10
-    assert [n for _, n in params] == ["p0", "p1", "n", "grid", "dsm", "bias", "s_out", "state_out", "cell_out", "stream"]
-    for k, (t, (want, pname)) in enumerate(zip(argtypes, params)):
-        got = _table_type(t)
-        assert got == want or (want[0] == "pointer" and got == ("pointer", None)), (k, pname, t, want)
-        assert (t is _lib.c_stream) == (pname == "stream"), (k, pname)
-    fn = getattr(_lib.lib(), SYMBOL)
-    assert fn.restype is restype and tuple(fn.argtypes) == tuple(argtypes) and SYMBOL in _lib._PLANS
-    assert SYMBOL not in _lib.SIGNATURES and SYMBOL not in _lib.EXPORTED_SYMBOLS
-    assert list(_lib.EXTENSION_SIGNATURES) == ["snerf_orthorect.h"] and SYMBOL not in _lib.EXTENSION_SIGNATURES["snerf_orthorect.h"]
-    main = open(os.path.join(ROOT, "include", "snerf_hip.h")).read()
-    assert SYMBOL not in main and "SNERF_HIT_" not in main and '#include "snerf_hip.h"' in open(HEADER).read()
+    """include/snerf_raycast.h against its rows of _lib.HEADER_SIGNATURES (tests/abi_header.py); the main header, the main table,
+    the other headers' rows and the ABI version are untouched"""
+    from tests.abi_header import check_header
+    check_header("snerf_raycast.h", {SYMBOL: ["p0", "p1", "n", "grid", "dsm", "bias", "s_out", "state_out", "cell_out", "stream"]})
 
 
 # ---- refusals of the entry ----------------------------------------------------------------------------------------------------------

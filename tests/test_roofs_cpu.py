@@ -1,5 +1,5 @@
 """CPU-side checks of the roof planes (include/snerf_roofs.h, csrc/roofs.hip, eval/utils/roofs.py): the new
-header's prototypes and constants against the binding (_lib.ROOFS_SIGNATURES), the restatement (tests/roofs_numpy.py, the oracle of
+header's prototypes and constants against the binding (_lib.HEADER_SIGNATURES), the restatement (tests/roofs_numpy.py, the oracle of
 tests/test_gpu_roofs.py) against numpy.linalg.lstsq, exact integer planes and scipy.ndimage.label, the host tables on hand-made words,
 the synthetic town's exact facts, and every refusal of the four entries through the binding (none reaches a launch)."""
 import math
@@ -18,7 +18,6 @@ from tests import roofs_numpy as N
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "snerf_roofs.h")
 DUMMY = 4096        # a non-null address no refusal path dereferences
-SYMBOLS = ["snerf_roofs_normals", "snerf_roofs_link", "snerf_roofs_moments", "snerf_roofs_residuals"]
 NAMES = {
     "snerf_roofs_normals": ["key", "ids", "h", "w", "K", "radius", "q", "res", "cos0", "sin0", "tan2_flat", "tan2_wall", "slope_e", "slope_n",
                             "code", "tag", "stats", "stream"],
@@ -29,44 +28,11 @@ NAMES = {
 
 
 def test_the_new_header_matches_its_binding_rows():
-    """include/snerf_roofs.h against _lib.ROOFS_SIGNATURES["snerf_roofs.h"], as tests/test_terrain_cpu.py compares its header: every
-    prototype has a row and the reverse, in the header's order; return type, parameter count and, per parameter, class, width and
-    signedness; the stream marker exactly where the parameter is called `stream`; the library exports the symbols and lib() / call()
-    know them.  The main header, the main table, the other extension tables and the ABI version are untouched."""
-    from tests.test_abi_cpu import _c_type, _table_type
+    """include/snerf_roofs.h against its rows of _lib.HEADER_SIGNATURES (tests/abi_header.py), then the constants; the main header, the
+    main table, the other headers' rows and the ABI version are untouched"""
+    from tests.abi_header import check_header
+    check_header("snerf_roofs.h", NAMES)
     text = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    src = re.sub(r"^\s*#.*$", "", src, flags=re.M)
-    protos = {}
-    for ret, name, params in re.findall(r"([\w \*]+?)\b(snerf_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", src):
-        protos[name] = (_c_type(ret), [(_c_type(t), n) for t, n in (re.fullmatch(r"\s*(.*?)(\w+)\s*", p).groups() for p in params.split(","))])
-    assert list(_lib.ROOFS_SIGNATURES) == ["snerf_roofs.h"]
-    rows = _lib.ROOFS_SIGNATURES["snerf_roofs.h"]
-    assert list(rows) == list(protos) == SYMBOLS
-    for symbol in SYMBOLS:
-        ret, params = protos[symbol]
-        restype, argtypes = rows[symbol]
-        assert _table_type(restype) == ret == ("int", 4, True) and len(argtypes) == len(params)
-        assert [n for _, n in params] == NAMES[symbol]
-        for k, (t, (want, pname)) in enumerate(zip(argtypes, params)):
-            got = _table_type(t)
-            assert got == want or (want[0] == "pointer" and got == ("pointer", None)), (symbol, k, pname, t, want)
-            assert (t is _lib.c_stream) == (pname == "stream"), (symbol, k, pname)
-        fn = getattr(_lib.lib(), symbol)
-        assert fn.restype is restype and tuple(fn.argtypes) == tuple(argtypes) and symbol in _lib._PLANS
-        assert symbol not in _lib.SIGNATURES and symbol not in _lib.EXPORTED_SYMBOLS
-        for other in (_lib.EXTENSION_SIGNATURES, _lib.RAYCAST_SIGNATURES, _lib.FUSE_SIGNATURES, _lib.OBJECTS_SIGNATURES, _lib.TERRAIN_SIGNATURES):
-            assert all(symbol not in table for table in other.values())
-    main = open(os.path.join(ROOT, "include", "snerf_hip.h")).read()
-    assert "snerf_roofs" not in main and "SNERF_ROOFS_" not in main and '#include "snerf_hip.h"' in text
-    assert _lib.lib().snerf_version() == _lib.ABI_VERSION == 6
-    # the other tables are what they were
-    assert list(_lib.EXTENSION_SIGNATURES["snerf_orthorect.h"]) == ["snerf_orthorectify"]
-    assert list(_lib.RAYCAST_SIGNATURES["snerf_raycast.h"]) == ["snerf_dsm_segment_hit"]
-    assert list(_lib.FUSE_SIGNATURES["snerf_fuse.h"]) == ["snerf_fuse_count", "snerf_fuse_scatter", "snerf_fuse_select"]
-    assert list(_lib.OBJECTS_SIGNATURES["snerf_objects.h"]) == ["snerf_objects_link", "snerf_objects_stats"]
-    assert list(_lib.TERRAIN_SIGNATURES["snerf_terrain.h"]) == ["snerf_terrain_workspace_bytes", "snerf_terrain_keys", "snerf_terrain_open",
-                                                                "snerf_terrain_fill"]
     consts = {k: int(v) for k, v in re.findall(r"#define (SNERF_ROOFS_\w+) (\d+)", text)}
     assert consts["SNERF_ROOFS_MAX_RADIUS"] == _lib.ROOFS_MAX_RADIUS == RF.MAX_RADIUS == N.MAX_RADIUS == 4
     assert consts["SNERF_ROOFS_MAX_SIDE"] == _lib.ROOFS_MAX_SIDE == RF.MAX_SIDE == 8192

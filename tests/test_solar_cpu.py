@@ -1,5 +1,5 @@
 """CPU-side checks of the solar potential (include/snerf_solar.h, csrc/solar.hip, eval/utils/solar.py): the new
-header's prototypes and constants against the binding (_lib.SOLAR_SIGNATURES), every refusal of the three entries through the binding
+header's prototypes and constants against the binding (_lib.HEADER_SIGNATURES), every refusal of the three entries through the binding
 (none reaches a launch), the restatement (tests/solar_numpy.py, the oracle of tests/test_gpu_solar.py) against a brute-force
 formulation, an analytic wall and the restated cast shadows, sun_position against astronomy, and the host tables on hand-made input."""
 import ctypes as C
@@ -21,7 +21,6 @@ from tests.test_gpu_shadow import _make_dsm
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "snerf_solar.h")
 DUMMY = 4096        # a non-null address no refusal path dereferences
-SYMBOLS = ["snerf_solar_horizon", "snerf_solar_svf", "snerf_solar_irradiate"]
 NAMES = {
     "snerf_solar_horizon": ["dsm", "h", "w", "dirs_host", "n_dirs", "bias", "z_top", "max_dist", "horizon_out", "stream"],
     "snerf_solar_svf": ["horizon", "n_dirs", "h", "w", "res", "svf_out", "stream"],
@@ -31,36 +30,11 @@ S2 = math.sqrt(0.5)
 
 
 def test_the_new_header_matches_its_binding_rows():
-    """include/snerf_solar.h against _lib.SOLAR_SIGNATURES["snerf_solar.h"], as tests/test_roofs_cpu.py compares its header: order,
-    types, the stream marker, the constants; the main header, the other tables and the ABI version are untouched"""
-    from tests.test_abi_cpu import _c_type, _table_type
+    """include/snerf_solar.h against its rows of _lib.HEADER_SIGNATURES (tests/abi_header.py), then the constants; the main header, the
+    main table, the other headers' rows and the ABI version are untouched"""
+    from tests.abi_header import check_header
+    check_header("snerf_solar.h", NAMES)
     text = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    src = re.sub(r"^\s*#.*$", "", src, flags=re.M)
-    protos = {}
-    for ret, name, params in re.findall(r"([\w \*]+?)\b(snerf_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", src):
-        protos[name] = (_c_type(ret), [(_c_type(t), n) for t, n in (re.fullmatch(r"\s*(.*?)(\w+)\s*", p).groups() for p in params.split(","))])
-    assert list(_lib.SOLAR_SIGNATURES) == ["snerf_solar.h"]
-    rows = _lib.SOLAR_SIGNATURES["snerf_solar.h"]
-    assert list(rows) == list(protos) == SYMBOLS
-    for symbol in SYMBOLS:
-        ret, params = protos[symbol]
-        restype, argtypes = rows[symbol]
-        assert _table_type(restype) == ret == ("int", 4, True) and len(argtypes) == len(params)
-        assert [n for _, n in params] == NAMES[symbol]
-        for k, (t, (want, pname)) in enumerate(zip(argtypes, params)):
-            got = _table_type(t)
-            assert got == want or (want[0] == "pointer" and got == ("pointer", None)), (symbol, k, pname, t, want)
-            assert (t is _lib.c_stream) == (pname == "stream"), (symbol, k, pname)
-        fn = getattr(_lib.lib(), symbol)
-        assert fn.restype is restype and tuple(fn.argtypes) == tuple(argtypes) and symbol in _lib._PLANS
-        assert symbol not in _lib.SIGNATURES and symbol not in _lib.EXPORTED_SYMBOLS
-        for other in (_lib.EXTENSION_SIGNATURES, _lib.RAYCAST_SIGNATURES, _lib.FUSE_SIGNATURES, _lib.OBJECTS_SIGNATURES, _lib.TERRAIN_SIGNATURES,
-                      _lib.ROOFS_SIGNATURES, _lib.NORMALS_SIGNATURES):
-            assert all(symbol not in table for table in other.values())
-    main = open(os.path.join(ROOT, "include", "snerf_hip.h")).read()
-    assert "snerf_solar" not in main and "SNERF_SOLAR_" not in main and '#include "snerf_hip.h"' in text
-    assert _lib.lib().snerf_version() == _lib.ABI_VERSION == 6
     consts = {k: int(v) for k, v in re.findall(r"#define (SNERF_SOLAR_\w+) (\d+)", text)}
     assert consts == {"SNERF_SOLAR_MAX_DIRS": 64, "SNERF_SOLAR_MAX_SECTORS": 720, "SNERF_SOLAR_MAX_SUNS": 64}
     assert (_lib.SOLAR_MAX_DIRS, _lib.SOLAR_MAX_SECTORS, _lib.SOLAR_MAX_SUNS) == (SO.MAX_DIRS, SO.MAX_SECTORS, SO.MAX_SUNS) == \

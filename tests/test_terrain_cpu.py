@@ -1,5 +1,5 @@
 """CPU-side checks of the bare-earth terrain (include/snerf_terrain.h, csrc/terrain.hip, eval/utils/terrain.py):
-the new header's prototypes and constants against the binding (_lib.TERRAIN_SIGNATURES), the restatement's opening
+the new header's prototypes and constants against the binding (_lib.HEADER_SIGNATURES), the restatement's opening
 (tests/terrain_numpy.py, the oracle of tests/test_gpu_terrain.py) against scipy.ndimage and against a brute-force loop, the schedule
 on hand-computed values, the synthetic town's exact properties, terrain_agreement on hand-made tensors, the objects' tables without a
 DTM, and every refusal of the four entries through the binding (none reaches a launch)."""
@@ -21,7 +21,6 @@ from tests import terrain_numpy as N
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "snerf_terrain.h")
 DUMMY = 4096        # a non-null address no refusal path dereferences
-SYMBOLS = ["snerf_terrain_workspace_bytes", "snerf_terrain_keys", "snerf_terrain_open", "snerf_terrain_fill"]
 NAMES = {
     "snerf_terrain_workspace_bytes": ["h", "w"],
     "snerf_terrain_keys": ["alt", "label", "h", "w", "blocked_host", "z0", "q", "key", "flags", "stats", "stream"],
@@ -31,43 +30,11 @@ NAMES = {
 
 
 def test_the_new_header_matches_its_binding_rows():
-    """include/snerf_terrain.h against _lib.TERRAIN_SIGNATURES["snerf_terrain.h"], as tests/test_objects_cpu.py compares its header:
-    every prototype has a row and the reverse, in the header's order; return type, parameter count and, per parameter, class, width
-    and signedness; the stream marker exactly where the parameter is called `stream`; the library exports the symbols and lib() /
-    call() know them.  The main header, the main table, the other extension tables and the ABI version are untouched."""
-    from tests.test_abi_cpu import _c_type, _table_type
+    """include/snerf_terrain.h against its rows of _lib.HEADER_SIGNATURES (tests/abi_header.py), then the constants; the main header, the
+    main table, the other headers' rows and the ABI version are untouched"""
+    from tests.abi_header import check_header
+    check_header("snerf_terrain.h", NAMES, returns={"snerf_terrain_workspace_bytes": ("int", 8, True)})
     text = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    src = re.sub(r"^\s*#.*$", "", src, flags=re.M)
-    protos = {}
-    for ret, name, params in re.findall(r"([\w \*]+?)\b(snerf_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", src):
-        protos[name] = (_c_type(ret), [(_c_type(t), n) for t, n in (re.fullmatch(r"\s*(.*?)(\w+)\s*", p).groups() for p in params.split(","))])
-    assert list(_lib.TERRAIN_SIGNATURES) == ["snerf_terrain.h"]
-    rows = _lib.TERRAIN_SIGNATURES["snerf_terrain.h"]
-    assert list(rows) == list(protos) == SYMBOLS
-    for symbol in SYMBOLS:
-        ret, params = protos[symbol]
-        restype, argtypes = rows[symbol]
-        want_ret = ("int", 8, True) if symbol == "snerf_terrain_workspace_bytes" else ("int", 4, True)
-        assert _table_type(restype) == ret == want_ret and len(argtypes) == len(params)
-        assert [n for _, n in params] == NAMES[symbol]
-        for k, (t, (want, pname)) in enumerate(zip(argtypes, params)):
-            got = _table_type(t)
-            assert got == want or (want[0] == "pointer" and got == ("pointer", None)), (symbol, k, pname, t, want)
-            assert (t is _lib.c_stream) == (pname == "stream"), (symbol, k, pname)
-        fn = getattr(_lib.lib(), symbol)
-        assert fn.restype is restype and tuple(fn.argtypes) == tuple(argtypes) and symbol in _lib._PLANS
-        assert symbol not in _lib.SIGNATURES and symbol not in _lib.EXPORTED_SYMBOLS
-        for other in (_lib.EXTENSION_SIGNATURES, _lib.RAYCAST_SIGNATURES, _lib.FUSE_SIGNATURES, _lib.OBJECTS_SIGNATURES):
-            assert all(symbol not in table for table in other.values())
-    main = open(os.path.join(ROOT, "include", "snerf_hip.h")).read()
-    assert "snerf_terrain" not in main and "SNERF_TERRAIN_" not in main and '#include "snerf_hip.h"' in text
-    assert _lib.lib().snerf_version() == _lib.ABI_VERSION == 6
-    # the other tables are what they were
-    assert list(_lib.EXTENSION_SIGNATURES["snerf_orthorect.h"]) == ["snerf_orthorectify"]
-    assert list(_lib.RAYCAST_SIGNATURES["snerf_raycast.h"]) == ["snerf_dsm_segment_hit"]
-    assert list(_lib.FUSE_SIGNATURES["snerf_fuse.h"]) == ["snerf_fuse_count", "snerf_fuse_scatter", "snerf_fuse_select"]
-    assert list(_lib.OBJECTS_SIGNATURES["snerf_objects.h"]) == ["snerf_objects_link", "snerf_objects_stats"]
     consts = {k: v for k, v in re.findall(r"#define (SNERF_TERRAIN_\w+) (\(?-?[\d \-]+\)?)", text)}
     assert eval(consts["SNERF_TERRAIN_HOLE"]) == _lib.TERRAIN_HOLE == TR.HOLE == N.HOLE == -2 ** 31
     assert int(consts["SNERF_TERRAIN_MAX_RADIUS"]) == _lib.TERRAIN_MAX_RADIUS == TR.MAX_RADIUS == 512

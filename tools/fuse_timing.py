@@ -13,7 +13,6 @@ only route to the same rasters without these kernels: the device-to-host copy of
 import argparse
 import json
 import os
-import statistics
 import sys
 import time
 
@@ -24,7 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from _timing import window_ms  # noqa: E402
+from _timing import wall_ms, window_ms  # noqa: E402
 from snerf_amd import _lib  # noqa: E402
 from snerf_amd.baseline.components.normalization import StandardNormalization  # noqa: E402
 from snerf_amd.eval.utils import dsm as D  # noqa: E402
@@ -32,18 +31,6 @@ from snerf_amd.eval.utils import fuse as F  # noqa: E402
 from snerf_amd.framework.components.coordinate_systems import GeoFrame  # noqa: E402
 
 KEYS = ("X_scale", "X_offset", "Y_scale", "Y_offset", "Z_scale", "Z_offset")
-
-
-def wall_ms(fn, reps):
-    fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ts.append((time.perf_counter() - t0) * 1e3)
-    return statistics.median(ts)
 
 
 def main():

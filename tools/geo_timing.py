@@ -7,9 +7,7 @@ median of --reps calls after a warm-up call, as one JSON line."""
 import argparse
 import json
 import os
-import statistics
 import sys
-import time
 
 import numpy as np
 import torch
@@ -17,22 +15,11 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from tools._timing import wall_ms  # noqa: E402
 from snerf_amd.baseline.components.normalization import StandardNormalization  # noqa: E402
 from snerf_amd.framework.components.coordinate_systems import GeoFrame  # noqa: E402
 
 KEYS = ("X_scale", "X_offset", "Y_scale", "Y_offset", "Z_scale", "Z_offset")
-
-
-def wall_ms(fn, reps):
-    fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ts.append((time.perf_counter() - t0) * 1e3)
-    return statistics.median(ts)
 
 
 def main():

@@ -13,7 +13,6 @@ scipy is installed (the per-object reductions would come on top of it)."""
 import argparse
 import json
 import os
-import statistics
 import sys
 import time
 
@@ -24,16 +23,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from _timing import window_ms as _window_ms  # noqa: E402
+from _timing import wall_ms, warm_window_ms as window_ms  # noqa: E402
 from snerf_amd import _lib  # noqa: E402
 from snerf_amd.eval.utils import dsm as D  # noqa: E402
 from snerf_amd.eval.utils import objects as OB  # noqa: E402
 from snerf_amd.eval.utils import ortho as OR  # noqa: E402
-
-
-def window_ms(fn, reps):
-    fn()                                                   # a warm-up call outside the window
-    return _window_ms(fn, reps)
 
 
 def town(side, seed=0):
@@ -51,18 +45,6 @@ def town(side, seed=0):
             label[j0 + 68:j0 + 70, i0 + 4:i0 + 8] = 4
             alt[j0 + 68:j0 + 70, i0 + 4:i0 + 8] += 1.5
     return label, alt
-
-
-def wall_ms(fn, reps):
-    fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ts.append((time.perf_counter() - t0) * 1e3)
-    return statistics.median(ts)
 
 
 def main():

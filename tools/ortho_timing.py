@@ -10,7 +10,6 @@ route to the same arrays without these kernels: the device-to-host copy of cloud
 import argparse
 import json
 import os
-import statistics
 import sys
 import time
 
@@ -20,6 +19,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from tools._timing import wall_ms  # noqa: E402
 from snerf_amd.baseline.components.normalization import StandardNormalization  # noqa: E402
 from snerf_amd.eval.utils import dsm as D  # noqa: E402
 from snerf_amd.eval.utils import ortho as OR  # noqa: E402
@@ -27,18 +27,6 @@ from snerf_amd.framework.components.coordinate_systems import GeoFrame  # noqa: 
 
 KEYS = ("X_scale", "X_offset", "Y_scale", "Y_offset", "Z_scale", "Z_offset")
 N_CLASSES = 5
-
-
-def wall_ms(fn, reps):
-    fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ts.append((time.perf_counter() - t0) * 1e3)
-    return statistics.median(ts)
 
 
 def main():

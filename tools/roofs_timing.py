@@ -12,7 +12,6 @@ import argparse
 import json
 import math
 import os
-import statistics
 import sys
 import time
 
@@ -23,7 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from _timing import window_ms as _window_ms  # noqa: E402
+from _timing import wall_ms, warm_window_ms as window_ms  # noqa: E402
 from snerf_amd import _lib  # noqa: E402
 from snerf_amd.eval.utils import dsm as D  # noqa: E402
 from snerf_amd.eval.utils import objects as OB  # noqa: E402
@@ -33,23 +32,6 @@ from snerf_amd.eval.utils import terrain as TR  # noqa: E402
 
 RADII = (1, 4)
 RES = 0.5
-
-
-def window_ms(fn, reps):
-    fn()                                                   # a warm-up call outside the window
-    return _window_ms(fn, reps)
-
-
-def wall_ms(fn, reps):
-    fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ts.append((time.perf_counter() - t0) * 1e3)
-    return statistics.median(ts)
 
 
 def tan2(deg):

@@ -26,17 +26,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from _timing import window_ms as _window_ms  # noqa: E402
+from _timing import warm_window_ms as window_ms  # noqa: E402
 from roofs_timing import RES, town  # noqa: E402
 from snerf_amd.eval.utils import shadow as S  # noqa: E402
 from snerf_amd.eval.utils import solar as SO  # noqa: E402
 
 LAT, LON, YEAR = 30.3, -81.7, 2021
-
-
-def window_ms(fn, reps):
-    fn()                                                   # a warm-up call outside the window
-    return _window_ms(fn, reps)
 
 
 def main():
