@@ -124,6 +124,27 @@ def test_dsm_abi_rejects_bad_arguments():
     assert L.snerf_dsm_shift_diff(P, P, 8, 8, 0, 0, 0.0, P, P, P, P, 8, None) == 2
 
 
+def test_ncc_search_abi_limits():
+    from snerf_amd import _lib
+    L = _lib.lib()
+    P = C.c_void_p(16)                                       # never dereferenced: every call below fails its checks
+    lim = 1 << 20
+    need = L.snerf_dsm_workspace_bytes(65, 33, 5)
+    assert need == 6 * 3 * 121 * 8 and L.snerf_dsm_workspace_bytes(40, 8200, 2) == 514 * 3 * 25 * 8 and L.snerf_dsm_workspace_bytes(1, 1, 0) == 2 * 1024 * 8
+    # a centre of +-2^20 passes the argument checks: the refusal is the next check's, the workspace one byte short
+    for cx, cy in ((lim, 0), (-lim, 0), (0, lim), (0, -lim), (lim, -lim)):
+        assert L.snerf_dsm_ncc_search(P, P, 0, 65, 33, cx, cy, 5, P, P, need - 1, None) == 2
+        assert b"workspace" in L.snerf_last_error()
+    for cx, cy in ((lim + 1, 0), (-lim - 1, 0), (0, lim + 1), (0, -lim - 1)):
+        assert L.snerf_dsm_ncc_search(P, P, 0, 65, 33, cx, cy, 5, P, P, need, None) == 1
+        assert b"centre" in L.snerf_last_error()
+    assert L.snerf_dsm_ncc_search(P, P, 0, 65, 33, 0, 0, 8, P, P, 1 << 30, None) == 1
+    assert b"radius" in L.snerf_last_error()
+    for h, w, r in ((65, 33, 5), (40, 8200, 2), (1, 1, 0)):
+        n = L.snerf_dsm_workspace_bytes(h, w, r)
+        assert L.snerf_dsm_ncc_search(P, P, 1, h, w, 0, 0, r, P, P, n - 1, None) == 2
+
+
 def test_no_vgpr_hazards_in_dsm_kernels(tmp_path):
     """tools/check_vgpr_hazards.py over csrc/dsm.hip compiled as the product build compiles it"""
     if not os.path.exists(HIPCC):
