@@ -149,6 +149,11 @@ RECT_MAX_IMAGES = 64       # include/snerf_orthorect.h SNERF_RECT_MAX_IMAGES
 RECT_SEEN, RECT_HOLE, RECT_OUTSIDE, RECT_HIDDEN = 0, 1, 2, 3     # include/snerf_orthorect.h SNERF_RECT_*
 
 
+class SnerfWarpMap(C.Structure):
+    """include/snerf_warp.h: the destination lattice in the source's cell coordinates"""
+    _fields_ = [(n, C.c_double) for n in ("off_x", "step_x", "off_y", "step_y")] + [(n, C.c_int) for n in ("src_w", "src_h", "dst_w", "dst_h")]
+
+
 class SnerfGeoParams(C.Structure):
     _fields_ = [("centre", C.c_double * 3), ("range", C.c_double), ("lon0", C.c_double), ("south", C.c_int), ("direction", C.c_int)]
 
@@ -245,8 +250,8 @@ EXPORTED_SYMBOLS = tuple(SIGNATURES)
 
 # Entries declared OUTSIDE include/snerf_hip.h, whose list of symbols is frozen at ABI 6: header -> rows in that header's order, the
 # headers in the order they were added (tests/abi_header.py compares each group with its header as tests/test_abi_cpu.py does for
-# the table above, and freezes the symbols of every group).  lib() and call() serve both tables alike.  A new map entry adds its
-# header's group here.
+# the table above, and freezes the symbols of every group).  lib() and call() serve both tables alike.  The groups are frozen there: a
+# newer header's group goes into ADDED_HEADER_SIGNATURES below.
 HEADER_SIGNATURES = {
     # the SnerfRectImage table goes as void* twice: the host copy (a ctypes array), the device copy (a tensor)
     "snerf_orthorect.h": {"snerf_orthorectify": (C.c_int, (C.c_void_p, C.POINTER(SnerfDsmGrid), C.c_double, C.c_int, C.c_void_p, C.c_void_p,
@@ -305,8 +310,16 @@ HEADER_SIGNATURES = {
         "snerf_test_normals_dump": (C.c_int, (C.c_void_p, C.c_void_p)),
     },
 }
+# The headers added after tests/abi_header.py froze the table above: the same shape, merged the same way, each group compared with its
+# header by its own test (include/snerf_warp.h: tests/test_warp_cpu.py).  A newer header adds its group here.
+ADDED_HEADER_SIGNATURES = {
+    "snerf_warp.h": {
+        "snerf_warp_planes": (C.c_int, (C.c_void_p, C.c_int, C.POINTER(SnerfWarpMap), C.c_int, C.c_double, C.c_void_p, C.c_void_p, c_stream)),
+        "snerf_warp_labels": (C.c_int, (C.c_void_p, C.POINTER(SnerfWarpMap), C.c_int, C.c_void_p, C.c_void_p, c_stream)),
+    },
+}
 _ALL_SIGNATURES = dict(SIGNATURES)
-for _rows in HEADER_SIGNATURES.values():
+for _rows in list(HEADER_SIGNATURES.values()) + list(ADDED_HEADER_SIGNATURES.values()):
     assert not set(_rows) & set(_ALL_SIGNATURES)
     _ALL_SIGNATURES.update(_rows)
 
@@ -332,6 +345,9 @@ ROOFS_FLAT, ROOFS_STEEP, ROOFS_HOLE, ROOFS_DEGENERATE, ROOFS_NONE = 0, 9, 253, 2
 SOLAR_MAX_DIRS = 64        # include/snerf_solar.h SNERF_SOLAR_MAX_DIRS
 SOLAR_MAX_SECTORS = 720    # include/snerf_solar.h SNERF_SOLAR_MAX_SECTORS
 SOLAR_MAX_SUNS = 64        # include/snerf_solar.h SNERF_SOLAR_MAX_SUNS
+WARP_NEAREST, WARP_BILINEAR, WARP_AVERAGE, WARP_MIN, WARP_MAX, WARP_MODE = range(6)      # include/snerf_warp.h SNERF_WARP_*: the methods
+WARP_MAX_STEP = 64         # include/snerf_warp.h SNERF_WARP_MAX_STEP
+WARP_MAX_PLANES = 16       # include/snerf_warp.h SNERF_WARP_MAX_PLANES
 
 # symbol -> (per argument a caller of call() passes: int / float for a scalar slot, None for a pointer slot; whether a trailing
 # stream follows them)

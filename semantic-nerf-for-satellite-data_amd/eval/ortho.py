@@ -345,9 +345,23 @@ def id_colors(ids):
     return torch.where((n > 0).unsqueeze(0), rgb, torch.zeros_like(rgb)).contiguous()
 
 
+def _reference_on(grid, reference, reference_grid, resample):
+    """`reference` ({"alt"[, "label"]}) as the exports compare it: itself without `reference_grid`; with one, its planes warped from
+    that lattice onto `grid` -- "alt" by `resample` (None: the default by the steps), "label" by the label default"""
+    if reference is None or reference_grid is None:
+        return reference
+    from .utils import warp as W
+    out = dict(reference)
+    src = W.lattice_of(reference_grid, reference["alt"].shape)
+    out["alt"] = W.warp(reference["alt"], src, grid, resample)
+    if reference.get("label") is not None:
+        out["label"] = W.warp(reference["label"], src, grid)
+    return out
+
+
 @torch.no_grad()
 def export_objects(products, output_dp, classes=(3,), ground=(0,), label_key=None, alt_key=None, reference=None, zone_string=None,
-                   palette=None, dtm=None, **kwargs):
+                   palette=None, dtm=None, reference_grid=None, reference_resample=None, **kwargs):
     """The objects of a map (eval/utils/objects.py objects), written to `output_dp`/objects/.  `products`: what
     nadir_products, ortho_products or orthorect.rectify return ("grid" and a label and an altitude plane).  `label_key`: default the
     first of "label", "label_vote", "label_median", "label_top" present; `alt_key`: the first of "dsm", "median_alt", "top_alt".
@@ -358,6 +372,9 @@ def export_objects(products, output_dp, classes=(3,), ground=(0,), label_key=Non
     object_scores); a lattice mismatch is a ValueError that names both shapes.  `palette` is taken as the other exports take it; no
     file of this export shows class colours (an object's colour comes from its id), so it is not read.  `dtm`: a terrain plane on
     the products' lattice (export_terrain's "dtm"): the map's table gains terrain_alt, height_over_terrain, volume_over_terrain_m3.
+    `reference_grid`: the lattice of `reference` (a DsmGrid or a geotransform) when it is not the products' -- its planes are first
+    warped onto the products' lattice (eval/utils/warp.py; DESIGN.md section 5zd), "alt" by `reference_resample` (a method name;
+    default bilinear / average by the steps), "label" by the label default; without it the shapes must agree, as before.
     Files: objects.json ({"objects": the table as records, "stats", "parameters"}), objects_ids.tif (float32: ids are exact below
     2^24, a ValueError beyond) and objects_ids.png (each object in a colour taken from its id), objects_height.tif / .png (the height
     of the cell's object, NaN off objects; JET); with `reference` also reference_objects.json and objects_eval.json.  Only rank 0
@@ -370,6 +387,7 @@ def export_objects(products, output_dp, classes=(3,), ground=(0,), label_key=Non
         raise ValueError(f"export_objects: the products hold no label plane ({label_key!r}) or no altitude plane ({alt_key!r})")
     label, alt, grid = products[label_key], products[alt_key], window_grid(products["grid"])
     shape = tuple(label.shape)
+    reference = _reference_on(grid, reference, reference_grid, reference_resample)
     if reference is not None and (tuple(reference["label"].shape) != shape or tuple(reference["alt"].shape) != shape):
         raise ValueError(f"export_objects: the products lie on a lattice of {tuple(label.shape)} cells, the reference on "
                          f"{tuple(reference['label'].shape)} (label) / {tuple(reference['alt'].shape)} (alt)")
@@ -402,7 +420,8 @@ def export_objects(products, output_dp, classes=(3,), ground=(0,), label_key=Non
 
 
 @torch.no_grad()
-def export_terrain(products, output_dp, alt_key=None, label_key=None, blocked=(3,), reference=None, zone_string=None, **kwargs):
+def export_terrain(products, output_dp, alt_key=None, label_key=None, blocked=(3,), reference=None, zone_string=None, reference_grid=None,
+                   reference_resample=None, **kwargs):
     """The bare-earth terrain under a map (eval/utils/terrain.py terrain), written to `output_dp`/terrain/.
     `products`: what nadir_products, ortho_products or orthorect.rectify return ("grid" and an altitude plane).  `alt_key`: default the
     first of "dsm", "median_alt", "top_alt" present; `label_key`: default the first of "label", "label_vote", "label_median",
@@ -410,7 +429,8 @@ def export_terrain(products, output_dp, alt_key=None, label_key=None, blocked=(3
     colormaps.DEFAULT_PALETTE's list; a scene with other class ids passes its own); without one nothing is blocked.  **kwargs
     (max_window_m, slope, dh0, dh_max) go to terrain's schedule.  `reference`: {"alt"[, "label"]} on the same lattice -- the lidar DSM,
     say, with the rectified ground-truth labels -- whose terrain the map's is held to (terrain_agreement); a lattice mismatch is a
-    ValueError that names both shapes.
+    ValueError that names both shapes.  `reference_grid`, `reference_resample`: as export_objects takes them -- a reference on a
+    lattice of its own is first warped onto the products'.
     Files: dtm.tif / .png and ndsm.tif / .png (JET), ground.png (white = ground), reach.png (BONE), terrain.json ({"schedule", "stats",
     "parameters"}); with `reference` also terrain_eval.json.  Only rank 0 writes.  Returns terrain()'s result plus "files"[,
     "reference", "eval"]."""
@@ -423,6 +443,7 @@ def export_terrain(products, output_dp, alt_key=None, label_key=None, blocked=(3
     alt, grid = products[alt_key], window_grid(products["grid"])
     label = products[label_key] if label_key is not None else None
     shape = tuple(alt.shape)
+    reference = _reference_on(grid, reference, reference_grid, reference_resample)
     if reference is not None:
         ref_label = reference.get("label")
         if tuple(reference["alt"].shape) != shape or (ref_label is not None and tuple(ref_label.shape) != shape):

@@ -21,7 +21,8 @@ MAE -- compute_dsm_and_mae_from_latlon -> compute_mae (dsm.py:112-266).  The ref
 crops it to the ROI; here the ROI is rasterised directly with the cell indices of the bounds lattice shifted by the integer
 ROI offset, which equals "bounds grid, then crop" bit for bit (points outside the ROI still feed its edge cells, cells outside
 the bounds grid receive nothing).  DIVERGENCE: an ROI corner off that lattice (by more than 1e-6 res) or an ROI resolution
-other than the DSM's raises ValueError where gdal would resample.  ROI cells beyond the cloud are NaN.  The prediction is set
+other than the DSM's raises ValueError where gdal would resample (a cloud is rasterised on the lattice asked for, never resampled; a
+ground-truth RASTER on another lattice is warped by eval/utils/warp.py when the loader is given resample=).  ROI cells beyond the cloud are NaN.  The prediction is set
 to NaN where the water mask is 9 or the ignore mask is non-zero, BEFORE registration (dsm.py:205-224).  Registration is
 dsmr.compute_shift(gt, pred, scaling=False) + apply_shift on the RAW cropped ground truth (compute_shift reads the gdal crop
 from disk, dsm.py:236); the difference uses the ground truth with values below -500 set to 0 (not NaN, dsm.py:229-231).
@@ -49,8 +50,8 @@ east/north/up frame as before, optionally through a caller's `to_world(xyz_n) ->
 
 Out of scope: writing error GeoTIFFs (arrays out; eval/ortho.py writes the DSM of a fused map as a GeoTIFF, the ground truth is
 READ by framework/util/img_utils.py); training in
-the UTM coordinate system; resampling an off-lattice ground truth or ROI (ValueError); the Norway / Svalbard UTM zone
-exceptions.  SSIM is eval/utils/metrics.py; eval/eval_nerf.py reports PSNR, SSIM and this MAE per image."""
+the UTM coordinate system; the Norway / Svalbard UTM zone exceptions.  An off-lattice ROI of create_dsm raises ValueError; an off-lattice
+ground truth raises unless resample= is given (framework/util/img_utils.py, eval/utils/warp.py mae_between).  SSIM is eval/utils/metrics.py; eval/eval_nerf.py reports PSNR, SSIM and this MAE per image."""
 import math
 from collections import namedtuple
 

@@ -6,7 +6,8 @@ is read from the GeoTIFF tags ModelPixelScale (33550) and ModelTiepoint (33922) 
 (xoff, yoff, size, resolution) and the water (class 9) or ignore mask.  Cropping to the ROI replaces the reference's
 gdal.Translate(projWin=...): an integer-offset crop when the raster lies on the ROI's lattice; a raster without the tags must
 already have the ROI's shape.  DIVERGENCE: anything else (another resolution, a corner off the lattice by more than 1e-6 cells,
-an ROI reaching beyond the raster) raises ValueError where gdal would resample or pad.
+an ROI reaching beyond the raster) raises ValueError where gdal would resample or pad -- unless `resample=` is given: the raster is
+then warped onto the ROI's lattice on the device (eval/utils/warp.py), cells it does not cover NaN / 255.
 
 save_geotiff writes a north-up raster on a DsmGrid with the same two tags and, given the scene's UTM zone, a GeoKeyDirectory
 (34735) naming the projected CRS (EPSG 326zz north / 327zz south).  The reference writes its DSMs with rasterio; neither
@@ -68,8 +69,13 @@ def load_dsm_geotiff(fp):
     return a, (tie[3] - tie[0] * scale[0], tie[4] + tie[1] * scale[1], scale[0], scale[1])
 
 
-def crop_to_roi(raster, geotransform, roi_meta, what="DSM"):
-    """the (size, size) window of `raster` that the ROI (xoff, yoff, size, resolution; yoff = the SOUTH edge) covers"""
+def crop_to_roi(raster, geotransform, roi_meta, what="DSM", resample=None, device=None):
+    """the (size, size) window of `raster` that the ROI (xoff, yoff, size, resolution; yoff = the SOUTH edge) covers.
+    `resample` (default None: anything off the ROI's lattice raises, as before): True or a method name of eval/utils/warp.py -- a raster
+    at another resolution, off the ROI's lattice or not containing the ROI is warped onto it on `device` (default "cuda") and comes
+    back as a host array; True takes the default method (bilinear / nearest onto a lattice as fine or finer, average / mode
+    otherwise), a uint8 raster always the label default.  ROI cells the raster does not cover are NaN (255 in a uint8 raster).  A raster
+    on the ROI's lattice that contains the ROI is cropped as without `resample`: its bits are kept."""
     xoff, yoff, size, res = [float(v) for v in np.asarray(roi_meta, np.float64).reshape(-1)[:4]]
     n = int(size)
     if geotransform is None:
@@ -77,22 +83,33 @@ def crop_to_roi(raster, geotransform, roi_meta, what="DSM"):
             raise ValueError(f"{what} raster of shape {raster.shape} carries no georeference and is not the ROI's {n} x {n}")
         return raster
     x0, y0, sx, sy = geotransform
+    i = j = 0
+    refusal = None
     if abs(sx - res) > 1e-9 * res or abs(sy - res) > 1e-9 * res:
-        raise ValueError(f"{what} raster resolution ({sx}, {sy}) != ROI resolution {res}: resampling is not supported")
-    fi, fj = (xoff - x0) / res, (y0 - (yoff + n * res)) / res
-    i, j = round(fi), round(fj)
-    if abs(fi - i) > 1e-6 or abs(fj - j) > 1e-6:
-        raise ValueError(f"{what} raster origin ({x0}, {y0}) is off the ROI lattice ({xoff} + k {res}, {yoff} + k {res}): "
-                         "resampling is not supported")
-    if i < 0 or j < 0 or i + n > raster.shape[1] or j + n > raster.shape[0]:
-        raise ValueError(f"the ROI ({n} x {n} cells from column {i}, row {j}) reaches beyond the {what} raster {raster.shape}")
+        refusal = f"{what} raster resolution ({sx}, {sy}) != ROI resolution {res}: resampling is not supported"
+    else:
+        fi, fj = (xoff - x0) / res, (y0 - (yoff + n * res)) / res
+        i, j = round(fi), round(fj)
+        if abs(fi - i) > 1e-6 or abs(fj - j) > 1e-6:
+            refusal = (f"{what} raster origin ({x0}, {y0}) is off the ROI lattice ({xoff} + k {res}, {yoff} + k {res}): "
+                       "resampling is not supported")
+        elif i < 0 or j < 0 or i + n > raster.shape[1] or j + n > raster.shape[0]:
+            refusal = f"the ROI ({n} x {n} cells from column {i}, row {j}) reaches beyond the {what} raster {raster.shape}"
+    if refusal is not None and resample:
+        from ...eval.utils import warp as W
+        method = None if resample is True or raster.dtype == np.uint8 else resample
+        src = torch.from_numpy(np.ascontiguousarray(raster)).to(device or "cuda")
+        return W.warp(src, W.lattice_of(geotransform, raster.shape), W.Lattice(xoff, yoff + n * res, res, res, n, n), method).cpu().numpy()
+    if refusal is not None:
+        raise ValueError(refusal)
     return raster[j:j + n, i:i + n]
 
 
-def load_dsm_ground_truth(dsm_tif_fp, dsm_txt_fp, dsm_cls_fp=None, ignore_mask_fp=None):
+def load_dsm_ground_truth(dsm_tif_fp, dsm_txt_fp, dsm_cls_fp=None, ignore_mask_fp=None, resample=None, device=None):
     """{"gt": (n, n) f32, "roi": (4,) f64, "water_mask" | "ignore_mask": (n, n) u8} as CPU tensors.  Exactly one mask is used, as
     eval/utils/dsm.py:124-129,199-219 of the reference: the ignore mask when the scene names one, else the water mask (the CLS
-    raster; class 9 is water) when its file exists."""
+    raster; class 9 is water) when its file exists.  `resample`, `device`: as crop_to_roi takes them (the method name serves the DSM,
+    a mask takes the label default); without them a raster off the ROI's lattice raises."""
     import os
     roi = np.loadtxt(dsm_txt_fp, dtype=np.float64).reshape(-1)
     if roi.size < 4:
@@ -100,11 +117,14 @@ def load_dsm_ground_truth(dsm_tif_fp, dsm_txt_fp, dsm_cls_fp=None, ignore_mask_f
     gt, gtf = load_dsm_geotiff(dsm_tif_fp)
     if gt.dtype != np.float32:
         raise ValueError(f"DSM GeoTIFF {dsm_tif_fp!r}: expected a float32 raster, got {gt.dtype}")
-    out = {"gt": torch.from_numpy(np.ascontiguousarray(crop_to_roi(gt, gtf, roi))), "roi": torch.from_numpy(roi[:4].copy())}
+    out = {"gt": torch.from_numpy(np.ascontiguousarray(crop_to_roi(gt, gtf, roi, resample=resample, device=device))),
+           "roi": torch.from_numpy(roi[:4].copy())}
     key, fp = ("ignore_mask", ignore_mask_fp) if ignore_mask_fp else ("water_mask", dsm_cls_fp)
     if fp and os.path.isfile(fp):
         m, mtf = load_dsm_geotiff(fp)
-        out[key] = torch.from_numpy(np.ascontiguousarray(crop_to_roi(m, mtf, roi, what=key)).astype(np.uint8))
+        if resample:
+            m = m.astype(np.uint8)
+        out[key] = torch.from_numpy(np.ascontiguousarray(crop_to_roi(m, mtf, roi, what=key, resample=resample, device=device)).astype(np.uint8))
     return out
 
 
