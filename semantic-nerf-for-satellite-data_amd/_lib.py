@@ -311,15 +311,30 @@ HEADER_SIGNATURES = {
     },
 }
 # The headers added after tests/abi_header.py froze the table above: the same shape, merged the same way, each group compared with its
-# header by its own test (include/snerf_warp.h: tests/test_warp_cpu.py).  A newer header adds its group here.
+# header by its own test (include/snerf_warp.h: tests/test_warp_cpu.py).  That test pins this table's headers too, so it is frozen
+# as well: a newer header's group goes into LATER_HEADER_SIGNATURES below.
 ADDED_HEADER_SIGNATURES = {
     "snerf_warp.h": {
         "snerf_warp_planes": (C.c_int, (C.c_void_p, C.c_int, C.POINTER(SnerfWarpMap), C.c_int, C.c_double, C.c_void_p, C.c_void_p, c_stream)),
         "snerf_warp_labels": (C.c_int, (C.c_void_p, C.POINTER(SnerfWarpMap), C.c_int, C.c_void_p, C.c_void_p, c_stream)),
     },
 }
+# The headers added after that: the same shape, merged the same way, each group compared with its header by its own test
+# (include/snerf_outline.h: tests/test_outline_cpu.py, which pins the symbols of a group and not the list of headers).  A newer
+# header adds its group here.  snerf_outline_workspace_bytes returns a long long, -1 for a refusal.
+LATER_HEADER_SIGNATURES = {
+    "snerf_outline.h": {
+        "snerf_outline_sides": (C.c_int, (C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, c_stream)),
+        "snerf_outline_link": (C.c_int, (C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_longlong, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, c_stream)),
+        "snerf_outline_workspace_bytes": (C.c_longlong, (C.c_longlong,)),
+        "snerf_outline_rank": (C.c_int, (C.c_void_p, C.c_void_p, C.c_longlong) + (C.c_void_p,) * 5 + (C.c_longlong, C.c_void_p, c_stream)),
+        "snerf_outline_emit": (C.c_int, (C.c_void_p,) * 7 + (C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_longlong) + (C.c_void_p,) * 3
+                               + (c_stream,)),
+    },
+}
 _ALL_SIGNATURES = dict(SIGNATURES)
-for _rows in list(HEADER_SIGNATURES.values()) + list(ADDED_HEADER_SIGNATURES.values()):
+for _rows in list(HEADER_SIGNATURES.values()) + list(ADDED_HEADER_SIGNATURES.values()) + list(LATER_HEADER_SIGNATURES.values()):
     assert not set(_rows) & set(_ALL_SIGNATURES)
     _ALL_SIGNATURES.update(_rows)
 
@@ -348,6 +363,9 @@ SOLAR_MAX_SUNS = 64        # include/snerf_solar.h SNERF_SOLAR_MAX_SUNS
 WARP_NEAREST, WARP_BILINEAR, WARP_AVERAGE, WARP_MIN, WARP_MAX, WARP_MODE = range(6)      # include/snerf_warp.h SNERF_WARP_*: the methods
 WARP_MAX_STEP = 64         # include/snerf_warp.h SNERF_WARP_MAX_STEP
 WARP_MAX_PLANES = 16       # include/snerf_warp.h SNERF_WARP_MAX_PLANES
+OUTLINE_ROW_WORDS = 8      # include/snerf_outline.h SNERF_OUTLINE_ROW_WORDS
+OUTLINE_MAX_CELLS = 2 ** 29    # include/snerf_outline.h SNERF_OUTLINE_MAX_CELLS
+OUTLINE_CORNER = 1         # include/snerf_outline.h SNERF_OUTLINE_CORNER: bit 0 of an edge's flags; bits 1-2 hold its side
 
 # symbol -> (per argument a caller of call() passes: int / float for a scalar slot, None for a pointer slot; whether a trailing
 # stream follows them)

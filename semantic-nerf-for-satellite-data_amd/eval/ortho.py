@@ -55,6 +55,8 @@ export_objects labels the buildings of any of these maps and measures them (eval
     objects_height.png/.tif              the height of the cell's object over the ground round it: float32 (NaN off objects), JET
     reference_objects.json, objects_eval.json   with reference=: the ground truth's objects, and detection precision / recall / F1,
                                          footprint IoU and the height error of the matched objects
+    footprints.geojson                   with polygons=True: the objects' outlines as polygons in map coordinates, traced on the device
+                                         (eval/utils/outline.py), the records of objects.json as properties
 
 export_terrain puts a bare-earth terrain under any of these maps (eval/utils/terrain.py).  Files under
 `output_dp`/terrain/:
@@ -71,6 +73,7 @@ export_roofs fits roof planes to the buildings export_objects found (eval/utils/
     facets.tif                           the facet id of every cell (0 = none): int32
     roofs.json                           the facets and the per-building rows, the parameters and the counts
     roofs_eval.json                      with reference=: roof types, pitch and normals against the reference's roofs
+    facets.geojson                       with polygons=True: the kept facets' outlines as polygons, the facet records as properties
 
 export_solar measures the solar potential of any of these maps (eval/utils/solar.py).  Files under
 `output_dp`/solar/:
@@ -361,7 +364,7 @@ def _reference_on(grid, reference, reference_grid, resample):
 
 @torch.no_grad()
 def export_objects(products, output_dp, classes=(3,), ground=(0,), label_key=None, alt_key=None, reference=None, zone_string=None,
-                   palette=None, dtm=None, reference_grid=None, reference_resample=None, **kwargs):
+                   palette=None, dtm=None, reference_grid=None, reference_resample=None, polygons=False, simplify_m=0.0, **kwargs):
     """The objects of a map (eval/utils/objects.py objects), written to `output_dp`/objects/.  `products`: what
     nadir_products, ortho_products or orthorect.rectify return ("grid" and a label and an altitude plane).  `label_key`: default the
     first of "label", "label_vote", "label_median", "label_top" present; `alt_key`: the first of "dsm", "median_alt", "top_alt".
@@ -375,6 +378,10 @@ def export_objects(products, output_dp, classes=(3,), ground=(0,), label_key=Non
     `reference_grid`: the lattice of `reference` (a DsmGrid or a geotransform) when it is not the products' -- its planes are first
     warped onto the products' lattice (eval/utils/warp.py; DESIGN.md section 5zd), "alt" by `reference_resample` (a method name;
     default bilinear / average by the steps), "label" by the label default; without it the shapes must agree, as before.
+    `polygons`: also trace the objects' outlines on the device (eval/utils/outline.py) and write
+    footprints.geojson -- one Polygon per object in map coordinates, its properties the object's record of objects.json; `simplify_m`:
+    the Douglas-Peucker tolerance in metres (0 = every corner of the raster outline).  Without `polygons` nothing more is launched or
+    written.
     Files: objects.json ({"objects": the table as records, "stats", "parameters"}), objects_ids.tif (float32: ids are exact below
     2^24, a ValueError beyond) and objects_ids.png (each object in a colour taken from its id), objects_height.tif / .png (the height
     of the cell's object, NaN off objects; JET); with `reference` also reference_objects.json and objects_eval.json.  Only rank 0
@@ -403,8 +410,18 @@ def export_objects(products, output_dp, classes=(3,), ground=(0,), label_key=Non
         pairs, inter, union = OB.match_objects(res["ids"], res["n"], ref["ids"], ref["n"])
         res = dict(res, reference=ref, eval=OB.object_scores(res["table"], ref["table"], pairs, inter, union))
     zone_string = _zone(zone_string, kwargs)
+    if polygons:
+        import inspect
+        from .utils import outline as OL
+        # the connectivity the ids were labelled with: the caller's, else the default of objects() itself
+        connectivity = kwargs.get("connectivity", inspect.signature(OB.objects).parameters["connectivity"].default)
+        doc, outline = OL.footprints(res["ids"], res["n"], grid, connectivity, simplify_m, zone_string, OB.table_records(res["table"]))
+        res = dict(res, footprints=doc, outline_stats=outline["stats"])
     files, fp = _writer(output_dp, "objects")
     if fp:
+        if polygons:
+            with open(fp("footprints.geojson"), "w") as f:
+                json.dump(res["footprints"], f)
         with open(fp("objects.json"), "w") as f:
             json.dump({"objects": OB.table_records(res["table"]), "stats": res["stats"], "parameters": params}, f, indent=1)
         _png(fp("objects_ids.png"), id_colors(res["ids"]))
@@ -494,12 +511,17 @@ def export_roofs(products, objects_result, output_dp, alt_key=None, reference=No
     **kwargs (radius, flat_deg, wall_deg, aspect0_deg, connectivity, min_facet_m2) go to roofs().  `reference`: {"alt", "objects"} on
     the same lattice -- the lidar DSM, say, and the objects() of the rectified ground-truth labels -- whose roofs the map's are held
     to over the buildings match_objects pairs (roof_agreement); a lattice mismatch is a ValueError that names both shapes.
+    Two keywords are taken out of **kwargs before roofs() sees them (the named parameters are pinned by tests/test_roofs_cpu.py):
+    `polygons` (default False) and `simplify_m` (default 0.0), as export_objects takes them -- facets.geojson holds one Polygon per
+    kept facet, its properties the facet's record of roofs.json; the facets are simplified one by one, so neighbours may part by up
+    to the tolerance.  Without `polygons` nothing more is launched or written.
     Files: pitch.tif / .png and residual.tif / .png (JET), aspect.png (ASPECT_PALETTE), facets.tif (int32), roofs.json ({"facets",
     "buildings", "stats", "parameters"}); with `reference` also roofs_eval.json.  Only rank 0 writes.  Returns roofs()'s result plus
     "files"[, "reference", "pairs", "eval"]."""
     from .utils import objects as OB
     from .utils import roofs as RF
     from .utils.ortho import window_grid
+    polygons, simplify_m = bool(kwargs.pop("polygons", False)), kwargs.pop("simplify_m", 0.0)
     alt_key = alt_key or next((k for k in ("dsm", "median_alt", "top_alt") if k in products), None)
     if alt_key not in products:
         raise ValueError(f"export_roofs: the products hold no altitude plane ({alt_key!r})")
@@ -517,8 +539,16 @@ def export_roofs(products, objects_result, output_dp, alt_key=None, reference=No
         pairs = OB.match_objects(objects_result["ids"], objects_result["n"], ro["ids"], ro["n"])[0]
         res = dict(res, reference=ref, pairs=pairs, eval=RF.roof_agreement(res, ref, pairs))
     zone_string = _zone(zone_string, kwargs)
+    if polygons:
+        from .utils import outline as OL
+        doc, outline = OL.footprints(res["facet_ids"], res["n_facets"], grid, res["parameters"]["connectivity"], simplify_m, zone_string,
+                                     RF.table_records(res["facets"]))
+        res = dict(res, footprints=doc, outline_stats=outline["stats"])
     files, fp = _writer(output_dp, "roofs")
     if fp:
+        if polygons:
+            with open(fp("facets.geojson"), "w") as f:
+                json.dump(res["footprints"], f)
         _scalar_plane(fp, "pitch", res["pitch_deg"], colormaps.COLORMAP_JET, grid, zone_string)
         _scalar_plane(fp, "residual", res["residual"], colormaps.COLORMAP_JET, grid, zone_string)
         _png(fp("aspect.png"), aspect_colors(res["code"]))
