@@ -332,6 +332,15 @@ LATER_HEADER_SIGNATURES = {
         "snerf_outline_emit": (C.c_int, (C.c_void_p,) * 7 + (C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_longlong) + (C.c_void_p,) * 3
                                + (c_stream,)),
     },
+    # facet growth and the arcs of a partition (tests/test_rooflines_cpu.py compares the group with its header)
+    "snerf_rooflines.h": {
+        "snerf_roofs_grow": (C.c_int, (C.c_void_p,) * 5 + (C.c_int, C.c_int, C.c_longlong, C.c_double, C.c_longlong, C.c_int) + (C.c_void_p,) * 3
+                             + (c_stream,)),
+        "snerf_arcs_first": (C.c_int, (C.c_void_p,) * 4 + (C.c_int, C.c_int, C.c_longlong, C.c_longlong) + (C.c_void_p,) * 3 + (c_stream,)),
+        "snerf_arcs_mark": (C.c_int, (C.c_void_p,) * 12 + (C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_longlong) + (C.c_void_p,) * 7
+                            + (c_stream,)),
+        "snerf_arcs_fold": (C.c_int, (C.c_void_p,) * 16 + (C.c_int, C.c_int) + (C.c_longlong,) * 4 + (C.c_void_p,) * 3 + (c_stream,)),
+    },
 }
 _ALL_SIGNATURES = dict(SIGNATURES)
 for _rows in list(HEADER_SIGNATURES.values()) + list(ADDED_HEADER_SIGNATURES.values()) + list(LATER_HEADER_SIGNATURES.values()):
@@ -366,6 +375,9 @@ WARP_MAX_PLANES = 16       # include/snerf_warp.h SNERF_WARP_MAX_PLANES
 OUTLINE_ROW_WORDS = 8      # include/snerf_outline.h SNERF_OUTLINE_ROW_WORDS
 OUTLINE_MAX_CELLS = 2 ** 29    # include/snerf_outline.h SNERF_OUTLINE_MAX_CELLS
 OUTLINE_CORNER = 1         # include/snerf_outline.h SNERF_OUTLINE_CORNER: bit 0 of an edge's flags; bits 1-2 hold its side
+ARCS_ROW_WORDS = 12        # include/snerf_rooflines.h SNERF_ARCS_ROW_WORDS
+ARCS_NO_FIRST = 2 ** 31 - 1    # include/snerf_rooflines.h SNERF_ARCS_NO_FIRST: the initial word of a ring's first break
+GROW_MAX_ROUNDS = 64       # include/snerf_rooflines.h SNERF_GROW_MAX_ROUNDS: the rounds of one snerf_roofs_grow call
 
 # symbol -> (per argument a caller of call() passes: int / float for a scalar slot, None for a pointer slot; whether a trailing
 # stream follows them)

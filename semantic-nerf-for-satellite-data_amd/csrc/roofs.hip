@@ -7,6 +7,7 @@
 #include "lattice.h"
 #include "link_kernels.h"
 #include "reduce.h"
+#include "roof_plane.h"
 #include "../../include/snerf_roofs.h"
 #include "../../include/snerf_terrain.h"
 
@@ -24,9 +25,6 @@ constexpr int ROOF_TILE_WAVES = ROOF_TILE_THREADS / 64;
 constexpr int ROOF_THREADS = 256;            // the per-facet folds: one thread per cell of the band
 constexpr unsigned ROOF_MAX_BLOCKS = 65536;
 constexpr long long ROOF_DK_LIMIT = 1LL << 24;
-constexpr long long ROOF_RQ_LIMIT = 1LL << 18;
-
-__device__ __forceinline__ bool roof_valid(int k) { return k != INT_MIN && k != INT_MAX; }
 
 // ---- normals -----------------------------------------------------------------------------------------------------------------------
 // A workgroup of 64 x 8 threads takes a 64 x 8 tile.  It stages (key, id) pairs of the tile and its halo of R cells in LDS, a hole
@@ -273,13 +271,10 @@ __global__ __launch_bounds__(ROOF_THREADS) void roofs_residuals_kernel(const int
       const double* p = planes + (long long)(r.fid - 1) * 3;
       const double gamma = p[0], alpha = p[1], beta = p[2];
       if (r.keyed && isfinite(gamma) && isfinite(alpha) && isfinite(beta)) {
-        const double pred = (gamma + (alpha * (double)r.di)) + (beta * (double)r.dj);
-        const double e = (double)r.dk - pred;
-        out = (float)(q * e);
-        const double t = rint(e / unit);
-        if (!(t < 262144.0)) { rq = ROOF_RQ_LIMIT; clamped = 1; }
-        else if (t < -262144.0) { rq = -ROOF_RQ_LIMIT; clamped = 1; }
-        else rq = (long long)t;
+        const RoofMisfit m = roof_misfit(gamma, alpha, beta, r.di, r.dj, r.dk, unit);      // roof_plane.h: shared with the growth
+        out = (float)(q * m.e);
+        rq = m.rq;
+        clamped = m.clamped;
         id = r.fid;
         with++;
       } else {

@@ -503,6 +503,40 @@ def aspect_colors(code):
     return lut.to(code.device)[code.long()].permute(2, 0, 1).contiguous()
 
 
+def _roof_arcs(res, alt, ids, grid, zone_string, roofs_kwargs, want_lines, want_polygons, simplify_m, grow_m, step_m, level_deg):
+    """what export_roofs adds for `lines` and for `polygons` with `shared`: the grown facet raster, its arcs, the roof lines and the
+    polygons with shared borders -> the keys to merge into roofs()'s result"""
+    from fractions import Fraction
+    from .utils import arcs as AR
+    from .utils import outline as OL
+    from .utils import roofs as RF
+    from .utils import terrain as TR
+    from .utils.ortho import Q, Z0
+    z0, q = roofs_kwargs.get("z0", Z0), roofs_kwargs.get("q", Q)
+    key, _, _ = TR.keys(alt, z0=z0, q=q)
+    grown, grown_cells, rounds = RF.grow(res["facet_ids"], ids, key, res["facets"], grow_m=grow_m, q=q)
+    arcs = AR.arcs(grown, res["n_facets"], res["parameters"]["connectivity"], key=key)
+    out = {"facet_ids_grown": grown, "grown_cells": grown_cells, "grow_rounds": rounds, "arc_stats": arcs["stats"]}
+    cells = Fraction(simplify_m) / Fraction(float(grid.resolution))
+    if want_lines:
+        records = RF.lines(arcs, res["facets"], grid, step_m=step_m, level_deg=level_deg, simplify_cells=cells, z0=z0, q=q)
+        doc = {"type": "FeatureCollection",
+               "features": [{"type": "Feature", "id": k + 1, "properties": {name: v for name, v in rec.items() if name != "coordinates"},
+                             "geometry": {"type": "LineString", "coordinates": rec["coordinates"]}} for k, rec in enumerate(records)]}
+        if zone_string is not None:
+            doc["crs"] = {"type": "name", "properties": {"name": f"urn:ogc:def:crs:EPSG::{img_utils.utm_epsg(zone_string)}"}}
+        K = len(res["buildings"]["facets"])
+        counts = {kind: sum(1 for rec in records if rec["kind"] == kind) for kind in RF.LINE_KINDS}
+        summary = {"buildings": RF.table_records(RF.line_table(records, K)), "counts": counts, "rounds": rounds,
+                   "grown_cells": [int(v) for v in grown_cells], "arcs": arcs["stats"],
+                   "parameters": {"grow_m": grow_m, "step_m": step_m, "level_deg": level_deg, "simplify_m": float(simplify_m)}}
+        out.update(lines=records, lines_geojson=doc, lines_summary=summary)
+    if want_polygons:
+        polys = OL.simplify_shared(arcs, cells)
+        out.update(footprints=OL.geojson(polys, grid, zone_string, RF.table_records(res["facets"])), outline_stats=arcs["rings"]["stats"])
+    return out
+
+
 @torch.no_grad()
 def export_roofs(products, objects_result, output_dp, alt_key=None, reference=None, zone_string=None, **kwargs):
     """The roofs of a map's buildings (eval/utils/roofs.py roofs), written to `output_dp`/roofs/.  `products`: what
@@ -515,6 +549,13 @@ def export_roofs(products, objects_result, output_dp, alt_key=None, reference=No
     `polygons` (default False) and `simplify_m` (default 0.0), as export_objects takes them -- facets.geojson holds one Polygon per
     kept facet, its properties the facet's record of roofs.json; the facets are simplified one by one, so neighbours may part by up
     to the tolerance.  Without `polygons` nothing more is launched or written.
+    Five more are taken out the same way: `lines` (default False), `shared` (default False), `grow_m` (0.25), `step_m` (1.0) and
+    `level_deg` (5.0).  With `lines` the kept facets are grown over the dropped cells of their buildings (roofs.grow), the arcs of the
+    grown raster are traced (eval/utils/arcs.py) and classified (roofs.lines): lines.geojson holds one 3-D
+    LineString per roof line with its record as properties, lines.json {"buildings": roofs.line_table, "parameters", "counts",
+    "rounds", "grown_cells", "arcs"}, facets_grown.tif the grown ids.  With `polygons` and `shared`, facets.geojson comes from
+    outline.simplify_shared on the grown raster: neighbouring facets share their borders.  Without them nothing more is launched or
+    written.
     Files: pitch.tif / .png and residual.tif / .png (JET), aspect.png (ASPECT_PALETTE), facets.tif (int32), roofs.json ({"facets",
     "buildings", "stats", "parameters"}); with `reference` also roofs_eval.json.  Only rank 0 writes.  Returns roofs()'s result plus
     "files"[, "reference", "pairs", "eval"]."""
@@ -522,6 +563,8 @@ def export_roofs(products, objects_result, output_dp, alt_key=None, reference=No
     from .utils import roofs as RF
     from .utils.ortho import window_grid
     polygons, simplify_m = bool(kwargs.pop("polygons", False)), kwargs.pop("simplify_m", 0.0)
+    lines, shared = bool(kwargs.pop("lines", False)), bool(kwargs.pop("shared", False))
+    grow_m, step_m, level_deg = kwargs.pop("grow_m", 0.25), kwargs.pop("step_m", 1.0), kwargs.pop("level_deg", 5.0)
     alt_key = alt_key or next((k for k in ("dsm", "median_alt", "top_alt") if k in products), None)
     if alt_key not in products:
         raise ValueError(f"export_roofs: the products hold no altitude plane ({alt_key!r})")
@@ -539,7 +582,10 @@ def export_roofs(products, objects_result, output_dp, alt_key=None, reference=No
         pairs = OB.match_objects(objects_result["ids"], objects_result["n"], ro["ids"], ro["n"])[0]
         res = dict(res, reference=ref, pairs=pairs, eval=RF.roof_agreement(res, ref, pairs))
     zone_string = _zone(zone_string, kwargs)
-    if polygons:
+    if lines or (polygons and shared):
+        res = dict(res, **_roof_arcs(res, alt.float(), objects_result["ids"], grid, zone_string, kwargs, lines, polygons and shared, simplify_m,
+                                     grow_m, step_m, level_deg))
+    if polygons and not shared:
         from .utils import outline as OL
         doc, outline = OL.footprints(res["facet_ids"], res["n_facets"], grid, res["parameters"]["connectivity"], simplify_m, zone_string,
                                      RF.table_records(res["facets"]))
@@ -549,6 +595,12 @@ def export_roofs(products, objects_result, output_dp, alt_key=None, reference=No
         if polygons:
             with open(fp("facets.geojson"), "w") as f:
                 json.dump(res["footprints"], f)
+        if lines:
+            with open(fp("lines.geojson"), "w") as f:
+                json.dump(res["lines_geojson"], f)
+            with open(fp("lines.json"), "w") as f:
+                json.dump(res["lines_summary"], f, indent=1)
+            img_utils.save_geotiff(fp("facets_grown.tif"), res["facet_ids_grown"], grid, zone_string)
         _scalar_plane(fp, "pitch", res["pitch_deg"], colormaps.COLORMAP_JET, grid, zone_string)
         _scalar_plane(fp, "residual", res["residual"], colormaps.COLORMAP_JET, grid, zone_string)
         _png(fp("aspect.png"), aspect_colors(res["code"]))

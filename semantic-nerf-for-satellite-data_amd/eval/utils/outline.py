@@ -12,6 +12,7 @@ section 5ze), the stages are the kernels of csrc/outline.hip, torch is plumbing.
   rings        the four in one call;
   polygons     per object its outer ring (positive area) followed by its holes;
   simplify     Douglas-Peucker per ring, exact in integers, on the host;
+  simplify_shared  the same per ARC (eval/utils/arcs.py): a border two objects share is simplified once, so neighbours stay gap-free;
   to_map       lattice vertices -> (east, north);
   geojson      a FeatureCollection, one Polygon per object.
 
@@ -226,9 +227,14 @@ def _dist2(p, a, b):
 
 def _simplify_ring(ring, t2):
     pts = [(int(x), int(y)) for x, y in ring]
-    n = len(pts)
-    if n < 3:
+    if len(pts) < 3:
         return ring
+    return np.array([pts[k] for k in _ring_keep(pts, t2)], np.int64).reshape(-1, 2)
+
+
+def _ring_keep(pts, t2):
+    """the ordinals of the vertices that simplify keeps of a ring of at least 3 lattice points, ascending"""
+    n = len(pts)
     far = max(range(n), key=lambda k: ((pts[k][0] - pts[0][0]) ** 2 + (pts[k][1] - pts[0][1]) ** 2, -k))
     closed = pts + [pts[0]]
     keep = {0, far}
@@ -241,7 +247,22 @@ def _simplify_ring(ring, t2):
         if d2 > t2:
             keep.add(-k)
             stack += [(a, -k), (-k, b)]
-    return np.array([pts[k] for k in sorted(keep)], np.int64).reshape(-1, 2)
+    return sorted(keep)
+
+
+def _open_keep(pts, t2):
+    """the same for an open polyline whose two endpoints stay"""
+    keep = {0, len(pts) - 1}
+    stack = [(0, len(pts) - 1)]
+    while stack:
+        a, b = stack.pop()
+        if b - a < 2:
+            continue
+        d2, k = max(((_dist2(pts[k], pts[a], pts[b]), -k) for k in range(a + 1, b)))
+        if d2 > t2:
+            keep.add(-k)
+            stack += [(a, -k), (-k, b)]
+    return sorted(keep)
 
 
 def simplify(polygons, tolerance_cells):
@@ -262,6 +283,105 @@ def simplify(polygons, tolerance_cells):
         holes = [_simplify_ring(r, t * t) for r in ring_list[1:]]
         out[n] = [outer if len(outer) >= 3 else ring_list[0]] + [r for r in holes if len(r) >= 3]
     return out
+
+
+def _area2(pts):
+    return sum(x0 * y1 - x1 * y0 for (x0, y0), (x1, y1) in zip(pts, pts[1:] + pts[:1]))
+
+
+def arc_points(arcs, a):
+    """the vertices of arc `a` of arcs.arcs()'s result as a list of (x, y) Python ints"""
+    start = arcs["arc_start"]
+    return [(int(x), int(y)) for x, y in arcs["vertices"][int(start[a]):int(start[a + 1])]]
+
+
+def simplify_shared(arcs, tolerance_cells):
+    """Gap-free Douglas-Peucker: `arcs` is what arcs.arcs() returns for an id raster -> {id: [outer ring, hole, ...]} in the format of
+    polygons().  Every OWNER open arc is simplified once, with the distance of simplify() and both endpoints (nodes) fixed; a closed arc
+    goes through the ring rule of simplify(); an arc that is no owner takes its twin's result, reversed: a border two ids share is one
+    polyline in both polygons, so neighbours neither part nor overlap.  A ring is the concatenation of its arcs.  Where a region comes
+    out with an outer ring of fewer than 3 vertices or of non-positive doubled area, all the arcs of its rings (and their twins) are put
+    back unsimplified and the rings are assembled again, until no region is in that state: at most as many passes as there are arcs.  A
+    hole left with fewer than 3 vertices is dropped.  With a tolerance above 0 the nodes stay vertices of the rings, also where the
+    ring runs straight through them: every segment of a polygon then has its reverse in the neighbour's.  tolerance_cells = 0 returns
+    what polygons(rings()) returns, vertex for vertex: the rings without the nodes that are no corners, from the ring's start."""
+    t = Fraction(tolerance_cells)
+    if t < 0:
+        raise ValueError(f"outline.simplify_shared: tolerance_cells = {tolerance_cells!r} is negative")
+    t2 = t * t
+    A = len(arcs["right"])
+    closed, owner, twin, edges = (np.asarray(arcs[k]).tolist() for k in ("closed", "owner", "twin", "edges"))
+    full = [arc_points(arcs, a) for a in range(A)]
+    frozen = [t == 0] * A
+
+    def keep_of():
+        keep = [None] * A
+        for a in range(A):
+            if owner[a] or twin[a] < 0:
+                n = len(full[a])
+                if frozen[a] or n < 3:
+                    keep[a] = list(range(n))
+                else:
+                    keep[a] = _ring_keep(full[a], t2) if closed[a] else _open_keep(full[a], t2)
+        for a in range(A):
+            if keep[a] is None:
+                b = twin[a]
+                if closed[a]:
+                    kept = {full[b][k] for k in keep[b]}
+                    keep[a] = [k for k, v in enumerate(full[a]) if v in kept]
+                else:
+                    if len(full[a]) != len(full[b]):
+                        raise ValueError(f"outline.simplify_shared: arc {a} and its twin {b} differ in their vertices")
+                    keep[a] = sorted(len(full[a]) - 1 - k for k in keep[b])
+        return keep
+
+    def ring_of(r, keep):
+        pts, dist, d0 = [], [], 0
+        for a in arcs["ring_arcs"][r].tolist():
+            P = full[a]
+            cum = [0]
+            for (x0, y0), (x1, y1) in zip(P, P[1:]):
+                cum.append(cum[-1] + abs(x1 - x0) + abs(y1 - y0))
+            idx = keep[a] if closed[a] else keep[a][:-1]
+            pts += [P[k] for k in idx]
+            dist += [d0 + cum[k] for k in idx]
+            d0 += edges[a]
+        if t == 0:
+            n = len(pts)
+            corner = [(pts[k][0] - pts[k - 1][0]) * (pts[(k + 1) % n][1] - pts[k][1])
+                      != (pts[k][1] - pts[k - 1][1]) * (pts[(k + 1) % n][0] - pts[k][0]) for k in range(n)]
+            pts, dist = [v for v, c in zip(pts, corner) if c], [d for d, c in zip(dist, corner) if c]
+        L = int(arcs["ring_edges"][r])
+        offset = (L - int(arcs["ring_first"][r])) % L
+        turn = next((k for k, d in enumerate(dist) if d >= offset), 0)
+        return pts[turn:] + pts[:turn]
+
+    rings = arcs["rings"]
+    obj, area2 = np.asarray(rings["ring_object"]).tolist(), np.asarray(rings["ring_area2"]).tolist()
+    R = len(obj)
+    for _ in range(A + 1):
+        keep = keep_of()
+        out = [ring_of(r, keep) for r in range(R)]
+        bad = {obj[r] for r in range(R) if area2[r] > 0 and (len(out[r]) < 3 or _area2(out[r]) <= 0)}
+        thaw = [a for r in range(R) if obj[r] in bad for a in arcs["ring_arcs"][r].tolist() if not frozen[a]]
+        if not thaw:
+            break
+        for a in thaw:
+            frozen[a] = True
+            if twin[a] >= 0:
+                frozen[twin[a]] = True
+    outer, holes = {}, {}
+    for r in range(R):
+        ring = np.array(out[r], np.int64).reshape(-1, 2)
+        if area2[r] > 0:
+            outer.setdefault(obj[r], []).append(ring)
+        elif len(ring) >= 3:
+            holes.setdefault(obj[r], []).append(ring)
+    for n in sorted(outer):
+        if len(outer[n]) != 1:
+            raise ValueError(f"outline.simplify_shared: object {n} has {len(outer[n])} rings of positive area: the ids are not the "
+                             "components of this connectivity")
+    return {n: outer[n] + holes.get(n, []) for n in sorted(outer)}
 
 
 def to_map(polygons, grid):

@@ -16,6 +16,9 @@ section 5z), the stages are the kernels of csrc/roofs.hip, torch is plumbing.  T
   roof_table     per building: facets, flat and pitched shares, the dominant facet's pitch and azimuth, rms, eave and ridge height and
                  a roof type by a rule whose thresholds are keyword parameters;
   roofs          all of the above in one call;
+  grow           snerf_roofs_grow: the kept facets grown over the dropped cells of their buildings, so that neighbours touch;
+  lines          the arcs of the grown facets (eval/utils/arcs.py) as ridge, hip, valley, step, eave, top and rake lines with heights;
+  line_table     per building the summed line lengths per kind;
   roof_agreement two maps' roofs over the buildings match_objects pairs (torch, any device).
 
 Everything a kernel writes is integer or fp64 arithmetic fixed operation by operation: the planes are bit-reproducible.  The defaults
@@ -353,6 +356,174 @@ def roofs(alt, ids, K, grid, objects_table, radius=1, flat_deg=5.0, wall_deg=60.
                       "folded": m[0], "left_out": m[1], "residual_cells": r[0], "without_residual": r[1]},
             "parameters": {"radius": int(radius), "flat_deg": flat_deg, "wall_deg": wall_deg, "aspect0_deg": aspect0_deg,
                            "connectivity": connectivity, "min_facet_m2": min_facet_m2}}
+
+
+# ---- roof lines ---------------------------------------------------------------------------------------------------------------------------
+GROW_BATCH = 8                                                  # rounds queued between two reads of the counters
+LINE_KINDS = ("ridge", "hip", "valley", "crease", "step", "enclosed", "eave", "top", "rake", "flat_edge")
+
+
+def grow(fids, ids, key, table, grow_m=0.25, q=OR.Q, unit=UNIT, max_rounds=None):
+    """snerf_roofs_grow: the kept facets (`fids`, `table`: what filter_facets returns) grown over the cells of their buildings that
+    carry no facet -- the hip lines and steps the facet filter dropped -- so that neighbouring facets touch -> (grown (H, W) int32,
+    grown_cells (F) int64 numpy: the cells every facet gained, rounds: how many rounds assigned a cell).  In a round a building cell
+    without a facet takes, among the facets of its N, E, S, W neighbours in the same building, the one whose plane it misses by the least,
+    if that is at most `grow_m` metres (in steps of q unit); the rounds are Jacobi steps, GROW_BATCH of them are queued between two reads
+    of the counters, and the growth stops after a batch whose last round assigned nothing, or at `max_rounds` (default H + W) rounds.  A
+    facet only gains cells next to itself: it stays one component.  grow_m is a parameter, not a claim."""
+    fids = _raster(fids, torch.int32, "fids")
+    h, w = fids.shape
+    _sizes(h, w)
+    ids = _raster(ids, torch.int32, "ids", fids.shape)
+    key = _raster(key, torch.int32, "key", fids.shape)
+    F = _count(len(table["object"]), "F")
+    if not (grow_m >= 0.0 and math.isfinite(grow_m) and q > 0.0 and math.isfinite(q) and unit > 0.0 and math.isfinite(unit)):
+        raise ValueError(f"roofs: grow_m >= 0, q > 0 and unit > 0, all finite, required, got {grow_m!r}, {q!r}, {unit!r}")
+    limit = h + w if max_rounds is None else int(max_rounds)
+    if limit < 1:
+        raise ValueError(f"roofs: max_rounds = {max_rounds!r} is below 1")
+    dev = fids.device
+    planes = torch.from_numpy(np.ascontiguousarray(np.asarray(table["plane"], np.float64).reshape(F, 3))).to(dev)
+    root = torch.from_numpy(np.asarray(table["root"]).astype(np.int32).reshape(F)).to(dev)
+    max_rq = int(math.floor(grow_m / (q * unit)))
+    cur, a, b = fids, torch.empty_like(fids), torch.empty_like(fids)
+    counts = []
+    while len(counts) < limit:
+        n = min(GROW_BATCH, limit - len(counts))
+        stats = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        _lib.call("snerf_roofs_grow", cur, ids, key, root, planes, h, w, F, unit, max_rq, n, a, b, stats, exc=ValueError)
+        # the batch's result lies in the buffer its last round wrote; the next batch reads it and writes the other one first
+        cur, a, b = (a, b, a) if n & 1 else (b, a, b)
+        s = [int(v) for v in stats.cpu()]
+        if s[n]:
+            raise RuntimeError(f"roofs.grow: {s[n]} guard trip(s): a facet id outside [0, {F}] or a facet root outside the raster")
+        counts += s[:n]
+        if s[n - 1] == 0:
+            break
+    grown = cur.clone()
+    gained = (torch.bincount(grown.reshape(-1).long(), minlength=F + 1) - torch.bincount(fids.reshape(-1).long(), minlength=F + 1))[1:F + 1]
+    return grown, gained.cpu().numpy().astype(np.int64), max([r + 1 for r, c in enumerate(counts) if c], default=0)
+
+
+def _line(kind, obj, right, left, xyz, step=None, height=None):
+    xyz = np.asarray(xyz, np.float64).reshape(-1, 3)
+    seg = np.diff(xyz, axis=0)
+    length = float(np.hypot(seg[:, 0], seg[:, 1]).sum())
+    pitch = math.degrees(math.atan2(abs(float(xyz[-1, 2] - xyz[0, 2])), length)) if length > 0.0 else 0.0
+    return {"kind": kind, "object": int(obj), "facet_right": int(right), "facet_left": int(left),
+            "coordinates": [[float(e), float(n), float(z)] for e, n, z in xyz], "length_m": length, "pitch_deg": pitch,
+            "step_m": None if step is None else float(step), "height_m": None if height is None else float(height)}
+
+
+def lines(arcs, facets, grid, step_m=1.0, level_deg=5.0, simplify_cells=0, z0=OR.Z0, q=OR.Q):
+    """The roof lines of a facet raster, on the host: `arcs` is what arcs.arcs() returns for the (grown) facet ids, `facets` the kept
+    facets' table (with "alt": facet_table needs `root_key`), `grid` the raster's lattice -> a list of records {"kind", "object",
+    "facet_right", "facet_left", "coordinates": [[east, north, z], ...], "length_m" (in plan), "pitch_deg" (of the line itself, end to
+    end), "step_m", "height_m"}.  Every arc is taken once, from its owner.  The raster is north-up and an arc runs with its own facet R
+    on its right: in (east, north), with the unit tangent t, the left normal is nl = (-t_n, t_e); s = (slope_e, slope_n) of a facet.
+    INTERIOR arc (R and the facet on the left, L, belong to one building): t is the chord from the first to the last vertex; a zero
+    chord, or a closed arc, is "enclosed".  d = the mean over the vertices of z_R - z_L; |d| > step_m is a "step" (step_m = |d|, z from
+    the higher plane).  Else, with a = s_R . nl and b = -s_L . nl, the rise per metre of either facet towards the line, and tol =
+    tan(level_deg): a, b > tol is a "ridge" when |(s_R + s_L) / 2 . t| <= tol and a "hip" otherwise; a, b < -tol a "valley"; anything
+    else a "crease"; z = (z_R + z_L) / 2.
+    OUTER arc (nothing on the left, or another building): simplified by `simplify_cells` (outline's distance; nodes stay), then segment
+    by segment with o = s_R . nl, the rise going outward: o < -tol "eave", o > tol "top", else "flat_edge" on a flat facet (code 0) and
+    "rake" on a pitched one; consecutive segments of one kind are one line; z from R's plane; height_m = the line's mean z minus the
+    mean altitude of the cells across, where the arcs carry key sums.
+    step_m, level_deg and simplify_cells are parameters, not claims."""
+    from fractions import Fraction
+    from . import outline as OL
+    g = OR.window_grid(grid)
+    xoff, yoff, res = float(g.xoff), float(g.yoff), float(g.resolution)
+    tol = math.tan(math.radians(level_deg))
+    obj, code = np.asarray(facets["object"], np.int64), np.asarray(facets["code"], np.int64)
+    se, sn, alt = (np.asarray(facets[k], np.float64) for k in ("slope_e", "slope_n", "alt"))
+    ce, cn = np.asarray(facets["east"], np.float64) - xoff, yoff - np.asarray(facets["north"], np.float64)
+    if not np.isfinite(alt).all():
+        raise ValueError("roofs.lines: the facet table carries no altitudes (facet_table needs root_key)")
+    t2 = Fraction(simplify_cells) ** 2
+
+    def plane(f, xy):
+        """the altitude of facet f's plane at lattice vertices"""
+        k = f - 1
+        return alt[k] + se[k] * (xy[:, 0] * res - ce[k]) - sn[k] * (xy[:, 1] * res - cn[k])
+
+    def to_xyz(xy, z):
+        return np.stack([xoff + xy[:, 0] * res, yoff - xy[:, 1] * res, z], 1)
+
+    out = []
+    for a in np.flatnonzero(np.asarray(arcs["owner"])).tolist():
+        R, L = int(arcs["right"][a]), int(arcs["left"][a])
+        pts = OL.arc_points(arcs, a)
+        closed = bool(arcs["closed"][a])
+        if L > 0 and obj[L - 1] == obj[R - 1]:
+            xy = np.array(pts, np.float64).reshape(-1, 2)
+            if closed:
+                xy = np.concatenate([xy, xy[:1]])
+            zr, zl = plane(R, xy), plane(L, xy)
+            chord = np.array([(xy[-1, 0] - xy[0, 0]) * res, -(xy[-1, 1] - xy[0, 1]) * res])
+            norm = float(np.hypot(*chord))
+            d = float(np.mean(zr - zl))
+            if closed or norm == 0.0:
+                out.append(_line("enclosed", obj[R - 1], R, L, to_xyz(xy, 0.5 * (zr + zl))))
+            elif abs(d) > step_m:
+                out.append(_line("step", obj[R - 1], R, L, to_xyz(xy, zr if d > 0.0 else zl), step=abs(d)))
+            else:
+                t = chord / norm
+                nl = np.array([-t[1], t[0]])
+                sa, sb = se[R - 1] * nl[0] + sn[R - 1] * nl[1], -(se[L - 1] * nl[0] + sn[L - 1] * nl[1])
+                along = 0.5 * ((se[R - 1] + se[L - 1]) * t[0] + (sn[R - 1] + sn[L - 1]) * t[1])
+                if sa > tol and sb > tol:
+                    kind = "ridge" if abs(along) <= tol else "hip"
+                elif sa < -tol and sb < -tol:
+                    kind = "valley"
+                else:
+                    kind = "crease"
+                out.append(_line(kind, obj[R - 1], R, L, to_xyz(xy, 0.5 * (zr + zl))))
+            continue
+        if t2 > 0 and len(pts) >= 3:
+            pts = [pts[k] for k in (OL._ring_keep(pts, t2) if closed else OL._open_keep(pts, t2))]
+        xy = np.array(pts, np.float64).reshape(-1, 2)
+        if closed:
+            xy = np.concatenate([xy, xy[:1]])
+        xyz = to_xyz(xy, plane(R, xy))
+        kinds = []
+        for k in range(len(xy) - 1):
+            te, tn = (xy[k + 1, 0] - xy[k, 0]) * res, -(xy[k + 1, 1] - xy[k, 1]) * res
+            norm = math.hypot(te, tn)
+            o = (se[R - 1] * -tn + sn[R - 1] * te) / norm if norm > 0.0 else 0.0
+            kinds.append("eave" if o < -tol else "top" if o > tol else "flat_edge" if code[R - 1] == FLAT else "rake")
+        runs = []                                               # [kind, first segment, one past the last]
+        for k, kind in enumerate(kinds):
+            if runs and runs[-1][0] == kind:
+                runs[-1][2] = k + 1
+            else:
+                runs.append([kind, k, k + 1])
+        ground = None
+        if int(arcs["key_edges"][a]) > 0:
+            ground = z0 + q * (float(arcs["key_sum_left"][a]) / float(arcs["key_edges"][a]))
+        if closed and len(runs) > 1 and runs[0][0] == runs[-1][0]:          # a closed arc's first and last run meet at its start
+            kind, lo, hi = runs.pop()
+            first_run = runs.pop(0)
+            joined = np.concatenate([xyz[lo:hi + 1], xyz[1:first_run[2] + 1]])
+            out.append(_line(kind, obj[R - 1], R, L, joined, height=None if ground is None else float(joined[:, 2].mean()) - ground))
+        for kind, lo, hi in runs:
+            part = xyz[lo:hi + 1]
+            out.append(_line(kind, obj[R - 1], R, L, part, height=None if ground is None else float(part[:, 2].mean()) - ground))
+    return out
+
+
+def line_table(lines, K):
+    """per building (entry n - 1 = object n) the summed plan lengths of its lines per kind -> {"lines": (K) int64, kind: (K) f64 for every
+    kind of LINE_KINDS}"""
+    out = {"lines": np.zeros(K, np.int64)}
+    out.update({kind: np.zeros(K, np.float64) for kind in LINE_KINDS})
+    for rec in lines:
+        n = int(rec["object"])
+        if 1 <= n <= K:
+            out["lines"][n - 1] += 1
+            out[rec["kind"]][n - 1] += rec["length_m"]
+    return out
 
 
 def roof_agreement(res, ref, pairs):
